@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- headline metric of BASELINE.json on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config {2,4}] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config {2,4}] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-alt]]
+
+A plain run sets up, warms up, times K steps, writes the last step's waveform if --dump-outputs is given, and prints the
+line: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step), config.  --full adds what the headline
+does not need: HIP events around the conv / activation launches of every 8th timed step and the two roofline objects
+built from them, the other conv form's side measurement (alt_conv_form), the CPU baseline, and for N > 1 the scatter /
+gather check after the timed region.
+
+--dump-outputs DIR: after the timed steps, the waveform of the last one (what generate_from_device hands its caller)
+as DIR/waveform.npy, float32 [clips, 480000]; where that exceeds 60 MB, a fixed seeded sample of its rows, whose
+indices go to DIR/waveform_rows.npy (float64).  Under a multi-rank clip-sharded run every rank writes its own clips
+(waveform_rank<r>.npy).  Weights, clips and prior noise are seeded: the same arguments give the same inputs.
 
 A "step" is one pass of FlowHighSR.generate() over one batch of synthetic clips whose low-rate
 input and prior noise are already resident in HBM (device resampler -> log-mel -> `time_step`
@@ -10,8 +22,8 @@ vector-field evaluations -> BigVGAN -> STFT post-processing), ending with the 48
 --config 2 (default): BASELINE.json configs[1] on every GPU (B = 1, one 10 s clip, 12 -> 48 kHz, time_step = 1
     euler, transformer 2 x 16 x 64, SYNTH-CFG BigVGAN-48k-256band; random-init weights, synthetic audio).
     For N > 1 every rank runs that workload on its own clips (independent clips, no data-path collective:
-    weak scaling); after the timed region the clips of all ranks go once through the RCCL scatter / gather path
-    (flowhigh_amd.parallel.generate_sharded) and rank 0 checks the result against its own runs.
+    weak scaling); with --full, after the timed region the clips of all ranks go once through the RCCL scatter / gather
+    path (flowhigh_amd.parallel.generate_sharded) and rank 0 checks the result against its own runs.
 --config 4: BASELINE.json configs[3]: 32 N clips of 10 s, 8 -> 48 kHz, euler x 1, live on rank 0; a step is
     scatter (RCCL P2P over xGMI) -> generate on every rank -> gather on rank 0 (256 clips over 8 GPUs).
 
@@ -40,7 +52,8 @@ PEAK_HBM_GBS = 8000.0
 SECS, STEPS_ODE, METHOD = 10.0, 1, "euler"
 CONFIGS = {2: dict(sr_in=12000, per_gpu=1, sharded=False, name="BASELINE configs[1]"),
            4: dict(sr_in=8000, per_gpu=32, sharded=True, name="BASELINE configs[3]")}
-EVENT_EVERY = 8          # HIP events bracket the conv / activation launches of every 8th timed step
+EVENT_EVERY = 8          # --full: HIP events bracket the conv / activation launches of every 8th timed step
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: at most this much waveform (with the row indices: under 64 MB)
 
 
 def cpu_baseline(sd, cfg, sr_in):
@@ -149,6 +162,102 @@ def alt_form(form, sd, cfg, dev, sr_in, x, z, out_main, B, n_frames, steps):
             "note": f"the same workload with conv_form='{form}' (FlowHighSR.from_local(..., conv_form=); INTEGRATION.md section 1); not the headline"}
 
 
+def roofline(voc, conv_ev, act_ev, timed_steps, B, n_frames):
+    """--full: the line's `roofline` (the dominant conv kernel family on its matrix instructions) and `roofline_hbm` (the
+    activation launches against HBM bandwidth) from the HIP events of the sampled timed steps."""
+    plan = voc.plan(B, n_frames)
+    conv_ms = sum(a.elapsed_time(b) for a, b in conv_ev)          # conv launches of the sampled timed steps
+    act_ms = sum(a.elapsed_time(b) for a, b in act_ev)
+    n_conv, n_act = len(conv_ev), len(act_ev)
+    conv_s, act_s = conv_ms / 1e3 / max(n_conv, 1), act_ms / 1e3 / max(n_act, 1)
+    # FLOPs the matrix cores execute per launch (Winograd F(5,4): 1.6 ceil(k/4), F(4,3): 1.5 ceil(k/3) instead of k MACs per output) and the
+    # direct-form ("algorithmic") FLOPs of the same convs (SURVEY.md 8d: 2 622.6 MFLOP per frame)
+    exec_per_launch = plan["conv_executed_flops"] * timed_steps / max(n_conv, 1)
+    alg_per_launch = voc.conv_flops_per_frame() * n_frames * B * timed_steps / max(n_conv, 1)
+    executed = exec_per_launch / conv_s / 1e12 if conv_s > 0 else 0.0
+    alg_equiv = alg_per_launch / conv_s / 1e12 if conv_s > 0 else 0.0
+    act_bytes_per_launch = plan["act_bytes"] * timed_steps / max(n_act, 1)
+    act_gbs = act_bytes_per_launch / act_s / 1e9 if act_s > 0 else 0.0
+
+    fams = family_split(conv_ev, plan["conv_launches"], timed_steps)
+    dom = next(iter(fams)) if fams else None
+    from tools.make_traffic_json import source_fingerprint
+    fp_now = source_fingerprint(ROOT)
+    stale = {}
+
+    def pmc(name):          # (the PMC passes are per batch size: profiles/<name>.json at B = 1, <name>_B<n>.json otherwise)
+        f = ROOT / "profiles" / (name if B == 1 else name.replace(".json", f"_B{B}.json"))
+        if not f.exists():
+            stale[name] = "no PMC file for this batch size"
+            return None
+        rec = json.loads(f.read_text())
+        if rec.get("source_fingerprint") != fp_now:
+            # the kernels or the launch planner changed since the PMC passes: the committed bytes describe other launches
+            stale[name] = (f"profiles/{f.name} was measured on other kernel / planner sources (fingerprint "
+                           f"{rec.get('source_fingerprint')}, now {fp_now}): re-run tools/profile_round.sh")
+            return None
+        return rec.get("bytes_per_launch")
+    rl = {"bound": "mfma",
+          # the dominant kernel family of the step (most conv time; by_family has all of them)
+          "kernel": KERNEL_BY_FAMILY[dom],
+          "achieved": fams[dom]["matrix_tflops"], "peak": fams[dom]["peak"], "unit": "TFLOP/s",
+          "frac": fams[dom]["frac"],
+          "launches_per_step": fams[dom]["launches_per_step"],
+          "avg_launch_us": round(fams[dom]["ms_per_step"] * 1e3 / max(fams[dom]["launches_per_step"], 1), 2),
+          "traffic": pmc("conv_hbm_bytes_per_launch.json"),
+          "traffic_source": "profiles/conv_hbm_bytes_per_launch.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
+                            "passes of an earlier run of this command (tools/profile_round.sh), NOT measured "
+                            f"by this run; bytes per conv launch (all families) at B = {B}; null when that file was "
+                            "measured on other kernel / planner sources (traffic_stale says so)",
+          "note": "achieved = FLOPs the dominant family issues to ITS matrix instructions (Winograd F(5,4): 1.6 ceil(k/4) MACs per "
+                  "output and channel pair instead of k; bf16 x 6: six bf16 MFMA FLOPs per such fp32-equivalent FLOP, against the "
+                  "dense bf16 peak) / HIP-event time of that family's launches, measured live in this run; by_family: every "
+                  "conv kernel family the same way; all_conv: every conv launch together in fp32-equivalent executed FLOPs "
+                  "against the fp32 MFMA peak (the line's `frac` until round 5), algorithmic_equiv = direct-form FLOPs of the "
+                  "same convs (SURVEY.md 8d) / the same time",
+          "by_family": fams,
+          "all_conv": {"executed_fp32_equiv_tflops": round(executed, 2), "peak_fp32_mfma": PEAK_FP32_MFMA_TFLOPS,
+                       "frac_of_fp32_mfma_peak": round(executed / PEAK_FP32_MFMA_TFLOPS, 4),
+                       "algorithmic_equiv": round(alg_equiv, 2),
+                       "algorithmic_equiv_frac": round(alg_equiv / PEAK_FP32_MFMA_TFLOPS, 4),
+                       "launches_per_step": n_conv // max(timed_steps, 1),
+                       "avg_launch_us": round(conv_s * 1e6, 2),
+                       "executed_gflop_per_launch": round(exec_per_launch / 1e9, 3),
+                       "algorithmic_gflop_per_launch": round(alg_per_launch / 1e9, 3)},
+          "conv_ms_per_step": round(conv_ms / max(timed_steps, 1), 3)}
+    rh = {"bound": "hbm",
+          "kernel": "act1d_strip_kernel (all Activation1d launches: up2x -> Snake(Beta) -> down2x)",
+          "achieved": round(act_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+          "frac": round(act_gbs / PEAK_HBM_GBS, 4),
+          "traffic": pmc("act_hbm_bytes_per_launch.json"),
+          "traffic_source": "profiles/act_hbm_bytes_per_launch.json (rocprofv3 --pmc passes of an earlier "
+                            "run, as above)",
+          "note": "achieved = algorithmic bytes (each site reads and writes its [B, C, L] tensor once: "
+                  "8 B per sample) / HIP-event time of the activation launches",
+          "launches_per_step": n_act // max(timed_steps, 1),
+          "avg_launch_us": round(act_s * 1e6, 2),
+          "algorithmic_mb_per_launch": round(act_bytes_per_launch / 1e6, 2),
+          "act_ms_per_step": round(act_ms / max(timed_steps, 1), 3)}
+    for obj, name in ((rl, "conv_hbm_bytes_per_launch.json"), (rh, "act_hbm_bytes_per_launch.json")):
+        if name in stale:
+            obj["traffic_stale"] = stale[name]
+    return rl, rh
+
+
+def dump_outputs(out, dir_, tag, budget):
+    """--dump-outputs: the waveform [clips, samples] as <dir_>/waveform<tag>.npy in float32; past `budget` bytes a fixed seeded
+    sample of its rows (sorted), their indices in <dir_>/waveform_rows<tag>.npy (float64)."""
+    import numpy as np
+    dir_.mkdir(parents=True, exist_ok=True)
+    wav = out.detach().float().cpu().numpy()
+    if wav.nbytes > budget:
+        keep = max(1, budget // (wav.shape[1] * 4))
+        rows = np.sort(np.random.default_rng(0).choice(wav.shape[0], size=keep, replace=False))
+        np.save(dir_ / f"waveform_rows{tag}.npy", rows.astype(np.float64))
+        wav = wav[rows]
+    np.save(dir_ / f"waveform{tag}.npy", wav)
+
+
 def visible_gpus():
     """GPUs of this node counted WITHOUT the HIP runtime: the kfd topology nodes that have SIMDs (CPUs have none),
     cut by *_VISIBLE_DEVICES.  None when the topology is not readable (the ranks then find out themselves)."""
@@ -192,11 +301,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=None, help="clips per GPU (default: 1 for --config 2, 32 for --config 4)")
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip the side measurement of the other conv form (fp32-MFMA Winograd next to a bf16 x 6 headline, or the reverse)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline (HIP events in the timed steps), the other conv form, the CPU baseline and the multi-GPU scatter / gather check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's waveform to DIR/waveform.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the side measurement of the other conv form (fp32-MFMA Winograd next to a bf16 x 6 headline, or the reverse)")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("FH_BENCH_GRAPH", "0")),
                     help="1: a step replays the HIP graph of generate_from_device (same launches, one enqueue)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -294,13 +408,13 @@ def main():
         for _ in range(2):
             out = step()
     voc = model.flowhigh.vocoder
-    # HIP events (on the launch stream = torch's current stream) around every conv and every Activation1d launch
+    # --full: HIP events (on the launch stream = torch's current stream) around every conv and every Activation1d launch
     # of every 8th timed step: an event pair costs ~6 us of stream time, sampling keeps that under 0.5 %
     conv_ev, act_ev, timed_steps = [], [], 0
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        sampled = i % EVENT_EVERY == 0
+        sampled = args.full and i % EVENT_EVERY == 0
         voc.conv_timing = conv_ev if sampled else None
         voc.act_timing = act_ev if sampled else None
         timed_steps += sampled
@@ -311,46 +425,17 @@ def main():
     if not conf["sharded"] or rank == 0:
         rows = world * B if conf["sharded"] else B
         assert tuple(out.shape) == (rows, t48) and bool(torch.isfinite(out).all())
+        if args.dump_outputs:
+            # several clip-sharded ranks: each writes its own clips, within an equal share of the budget
+            tag = "" if conf["sharded"] or world == 1 else f"_rank{rank}"
+            dump_outputs(out, Path(args.dump_outputs), tag, DUMP_BYTES if conf["sharded"] else DUMP_BYTES // world)
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- roofline of the dominant kernels ---------------------------------------------------------------------------
-    plan = voc.plan(B, n_frames)
-    conv_ms = sum(a.elapsed_time(b) for a, b in conv_ev)          # conv launches of the sampled timed steps
-    act_ms = sum(a.elapsed_time(b) for a, b in act_ev)
-    n_conv, n_act = len(conv_ev), len(act_ev)
-    conv_s, act_s = conv_ms / 1e3 / max(n_conv, 1), act_ms / 1e3 / max(n_act, 1)
-    # FLOPs the matrix cores execute per launch (Winograd F(5,4): 1.6 ceil(k/4), F(4,3): 1.5 ceil(k/3) instead of k MACs per output) and the
-    # direct-form ("algorithmic") FLOPs of the same convs (2 622.6 MFLOP per frame)
-    exec_per_launch = plan["conv_executed_flops"] * timed_steps / max(n_conv, 1)
-    alg_per_launch = voc.conv_flops_per_frame() * n_frames * B * timed_steps / max(n_conv, 1)
-    executed = exec_per_launch / conv_s / 1e12 if conv_s > 0 else 0.0
-    alg_equiv = alg_per_launch / conv_s / 1e12 if conv_s > 0 else 0.0
-    act_bytes_per_launch = plan["act_bytes"] * timed_steps / max(n_act, 1)
-    act_gbs = act_bytes_per_launch / act_s / 1e9 if act_s > 0 else 0.0
-
-    fams = family_split(conv_ev, plan["conv_launches"], timed_steps)
-    dom = next(iter(fams)) if fams else None
     line = None
     if rank == 0:
-        from tools.make_traffic_json import source_fingerprint
-        fp_now = source_fingerprint(ROOT)
-        stale = {}
-
-        def pmc(name):          # (the PMC passes are per batch size: profiles/<name>.json at B = 1, <name>_B<n>.json otherwise)
-            f = ROOT / "profiles" / (name if B == 1 else name.replace(".json", f"_B{B}.json"))
-            if not f.exists():
-                stale[name] = "no PMC file for this batch size"
-                return None
-            rec = json.loads(f.read_text())
-            if rec.get("source_fingerprint") != fp_now:
-                # the kernels or the launch planner changed since the PMC passes: the committed bytes describe other launches
-                stale[name] = (f"profiles/{f.name} was measured on other kernel / planner sources (fingerprint "
-                               f"{rec.get('source_fingerprint')}, now {fp_now}): re-run tools/profile_round.sh")
-                return None
-            return rec.get("bytes_per_launch")
         metric = "48 kHz audio-seconds/sec (real-time factor), 12→48 kHz, 10 s clips, 1/2/4/8 MI355X"
         if args.config == 4:
             metric = "48 kHz audio-seconds/sec (real-time factor), 8→48 kHz, 10 s clips, clips scattered from / gathered on rank 0"
@@ -378,63 +463,21 @@ def main():
                        # calibration launches), and what packing it from the state dict took on this host (once, rank 0)
                        "load_s": round(load_s, 3), "pack_s": round(pack_s, 2), "blob_mib": round(blob_mib, 1),
                        "sharded_check": None},
-            "roofline": {"bound": "mfma",
-                         # the dominant kernel family of the step (most conv time; by_family has all of them)
-                         "kernel": KERNEL_BY_FAMILY[dom],
-                         "achieved": fams[dom]["matrix_tflops"], "peak": fams[dom]["peak"], "unit": "TFLOP/s",
-                         "frac": fams[dom]["frac"],
-                         "launches_per_step": fams[dom]["launches_per_step"],
-                         "avg_launch_us": round(fams[dom]["ms_per_step"] * 1e3 / max(fams[dom]["launches_per_step"], 1), 2),
-                         "traffic": pmc("conv_hbm_bytes_per_launch.json"),
-                         "traffic_source": "profiles/conv_hbm_bytes_per_launch.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
-                                           "passes of an earlier run of this command (tools/profile_round.sh), NOT measured "
-                                           f"by this run; bytes per conv launch (all families) at B = {B}; null when that file was "
-                                           "measured on other kernel / planner sources (traffic_stale says so)",
-                         "note": "achieved = FLOPs the dominant family issues to ITS matrix instructions (Winograd F(5,4): 1.6 ceil(k/4) MACs per "
-                                 "output and channel pair instead of k; bf16 x 6: six bf16 MFMA FLOPs per such fp32-equivalent FLOP, against the "
-                                 "dense bf16 peak) / HIP-event time of that family's launches, measured live in this run; by_family: every "
-                                 "conv kernel family the same way; all_conv: every conv launch together in fp32-equivalent executed FLOPs "
-                                 "against the fp32 MFMA peak (the line's `frac` until round 5), algorithmic_equiv = direct-form FLOPs of the "
-                                 "same convs (SURVEY.md 8d) / the same time",
-                         "by_family": fams,
-                         "all_conv": {"executed_fp32_equiv_tflops": round(executed, 2), "peak_fp32_mfma": PEAK_FP32_MFMA_TFLOPS,
-                                      "frac_of_fp32_mfma_peak": round(executed / PEAK_FP32_MFMA_TFLOPS, 4),
-                                      "algorithmic_equiv": round(alg_equiv, 2),
-                                      "algorithmic_equiv_frac": round(alg_equiv / PEAK_FP32_MFMA_TFLOPS, 4),
-                                      "launches_per_step": n_conv // max(timed_steps, 1),
-                                      "avg_launch_us": round(conv_s * 1e6, 2),
-                                      "executed_gflop_per_launch": round(exec_per_launch / 1e9, 3),
-                                      "algorithmic_gflop_per_launch": round(alg_per_launch / 1e9, 3)},
-                         "conv_ms_per_step": round(conv_ms / max(timed_steps, 1), 3)},
-            "roofline_hbm": {"bound": "hbm",
-                             "kernel": "act1d_strip_kernel (all Activation1d launches: up2x -> Snake(Beta) -> down2x)",
-                             "achieved": round(act_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                             "frac": round(act_gbs / PEAK_HBM_GBS, 4),
-                             "traffic": pmc("act_hbm_bytes_per_launch.json"),
-                             "traffic_source": "profiles/act_hbm_bytes_per_launch.json (rocprofv3 --pmc passes of an earlier "
-                                               "run, as above)",
-                             "note": "achieved = algorithmic bytes (each site reads and writes its [B, C, L] tensor once: "
-                                     "8 B per sample) / HIP-event time of the activation launches",
-                             "launches_per_step": n_act // max(timed_steps, 1),
-                             "avg_launch_us": round(act_s * 1e6, 2),
-                             "algorithmic_mb_per_launch": round(act_bytes_per_launch / 1e6, 2),
-                             "act_ms_per_step": round(act_ms / max(timed_steps, 1), 3)},
         }
-        for key, name in (("roofline", "conv_hbm_bytes_per_launch.json"), ("roofline_hbm", "act_hbm_bytes_per_launch.json")):
-            if name in stale:
-                line[key]["traffic_stale"] = stale[name]
-        if not args.no_alt and world == 1 and args.config == 2:
-            other = "winograd" if form == "bf16x6" else "bf16x6"
-            line["alt_conv_form"] = alt_form(other, sd, cfg, dev, sr_in, x, z, out, B, n_frames, max(10, args.steps // 2))
-        if not args.no_cpu_baseline and world == 1 and args.config == 2:
-            line["cpu_baseline"] = cpu_baseline(sd, cfg, sr_in)
-        else:
-            line["cpu_baseline"] = None
-    # ---- the scatter / gather path against rank-0-only runs (outside the timed region, after the line is built) ------
+        if args.full:
+            line["roofline"], line["roofline_hbm"] = roofline(voc, conv_ev, act_ev, timed_steps, B, n_frames)
+            if not args.no_alt and world == 1 and args.config == 2:
+                other = "winograd" if form == "bf16x6" else "bf16x6"
+                line["alt_conv_form"] = alt_form(other, sd, cfg, dev, sr_in, x, z, out, B, n_frames, max(10, args.steps // 2))
+            if not args.no_cpu_baseline and world == 1 and args.config == 2:
+                line["cpu_baseline"] = cpu_baseline(sd, cfg, sr_in)
+            else:
+                line["cpu_baseline"] = None
+    # ---- --full: the scatter / gather path against rank-0-only runs (outside the timed region, after the line is built) -----
     # A watchdog on every rank: should the P2P exchange not finish, rank 0 still prints the measured line (without
     # the check) and every rank exits NON-ZERO, instead of leaving the launcher waiting or reporting success.
     rc = 0
-    if dist is not None:
+    if dist is not None and args.full:
         import threading
         printed = threading.Lock()           # exactly one JSON line, whoever gets there first
 

@@ -125,12 +125,43 @@ def run_ops():
     print("ops: kaiser taps", taps.tolist()[:6], "pp_cr", cr)
 
 
+# tests/test_reference_pin.py: (cfg name, sr_in, ode method, steps), weights seed 11, clip seed 11 of 0.23 s, prior seed 4242
+PIN_CASES = [("ALT_CFG", 12000, "euler", 2), ("TINY_CFG", 24000, "midpoint", 1),
+             ("ODD_CFG", 16000, "midpoint", 1), ("NK5_AMP2_CFG", 8000, "euler", 1)]
+
+
+def pin_key(cfgname, sr_in, method, steps):
+    return f"out_{cfgname}_{sr_in}_{method}_{steps}"
+
+
+def run_pin():
+    """pin.npz: the reference's generate() waveform on the PIN_CASES (its own prior draw, torch.manual_seed(4242)), and
+    the names and shapes of the reference model's state dict built from synth.TINY_CFG seed 0."""
+    arrays = {}
+    for cfgname, sr_in, method, steps in PIN_CASES:
+        cfg = getattr(synth, cfgname)
+        d = tempfile.mkdtemp(prefix="fh_pin_")
+        synth.write_checkpoint_dir(d, cfg, seed=11)
+        model = ref_shim.build_reference_model(d, method)
+        audio = synth.lowres_clip(11, 0.23, sr_in)
+        torch.manual_seed(4242)
+        arrays[pin_key(cfgname, sr_in, method, steps)] = model.generate(audio, sr_in, 48000, steps).numpy()
+    d = tempfile.mkdtemp(prefix="fh_pin_")
+    synth.write_checkpoint_dir(d, synth.TINY_CFG, seed=0)
+    ref_sd = ref_shim.build_reference_model(d, "euler").state_dict()
+    arrays["tiny_state_dict_shapes"] = json.dumps({k: list(v.shape) for k, v in ref_sd.items()})
+    np.savez_compressed(OUT / "pin.npz", **arrays)
+    print("pin:", ", ".join(f"{k} {v.shape}" for k, v in arrays.items() if k.startswith("out_")))
+
+
 if __name__ == "__main__":
     OUT.mkdir(parents=True, exist_ok=True)
     with torch.no_grad():
-        only = sys.argv[1:]                      # optional: names of the cases to (re)generate
+        only = sys.argv[1:]                      # optional: names of the cases to (re)generate ("pin": pin.npz)
         for name, args in CASES.items():
             if not only or name in only:
                 run_case(name, *args)
         if not only:
             run_ops()
+        if not only or "pin" in only:
+            run_pin()

@@ -576,10 +576,10 @@ def test_named_conv_form_batch_ragged_and_chunked_invariants_bitwise(form):
     assert torch.equal(voc.forward_chunked(mel, 48), voc.forward(mel))
 
 
-@pytest.mark.parametrize("args,workload", [(["--steps", "9", "--warmup", "1", "--no-cpu-baseline"], "configs[1]"),
-                                           (["--config", "4", "--batch", "2", "--steps", "2", "--warmup", "1"], "configs[3]")])
+@pytest.mark.parametrize("args,workload", [(["--full", "--steps", "9", "--warmup", "1", "--no-cpu-baseline"], "configs[1]"),
+                                           (["--full", "--config", "4", "--batch", "2", "--steps", "2", "--warmup", "1"], "configs[3]")])
 def test_bench_prints_one_contract_line(args, workload):
-    """bench.py on the GPU box: exactly one JSON line with the driver's keys, both roofline objects measured live
+    """bench.py --full on the GPU box: exactly one JSON line with the driver's keys, both roofline objects measured live
     (HIP events) and self-consistent, and -- for the default workload -- the opt-in bf16 x 6 side measurement with its
     distance from the fp32 form."""
     import json
@@ -612,6 +612,31 @@ def test_bench_prints_one_contract_line(args, workload):
     if "--config" not in args:
         alt = line["alt_conv_form"]
         assert alt["conv_form"] != form and alt["max_abs_diff_vs_headline_waveform"] <= 5e-5 and alt["value"] > 0
+
+
+def test_plain_bench_times_its_steps_and_dumps_the_waveform(tmp_path):
+    """bench.py without --full: the headline keys only (no roofline, side measurements or CPU baseline), `steps` timed
+    steps, and with --dump-outputs the last step's waveform as float32 [clips, 480000]."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       cwd=root, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    for k in ("roofline", "roofline_hbm", "alt_conv_form", "cpu_baseline"):
+        assert k not in line, k
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["higher_is_better"] is True
+    assert abs(line["value"] - 10.0 / (line["ms_per_step"] / 1e3)) / line["value"] < 0.02
+    assert sorted(f.name for f in tmp_path.iterdir()) == ["waveform.npy"]
+    wav = np.load(tmp_path / "waveform.npy")
+    assert wav.dtype == np.float32 and wav.shape == (1, 480000) and np.isfinite(wav).all() and np.abs(wav).max() > 0
 
 
 # ------------------------------------------------------------------------------------------
@@ -706,8 +731,8 @@ def test_bench_under_torchrun_one_rank_initialises_rccl_and_checks_the_sharded_p
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-           "--master-port", "29611", str(root / "bench.py"), "--gpus", "1", "--config", "4", "--batch", "2", "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline", "--no-alt"]
+           "--master-port", "29611", str(root / "bench.py"), "--full", "--gpus", "1", "--config", "4", "--batch", "2",
+           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-alt"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

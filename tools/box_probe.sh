@@ -12,5 +12,5 @@ if [ -f tools/abl/trace2.so ]; then       # in-kernel shader clock of a conv lau
 fi
 python tools/conv_layers.py 1 1000 2>/dev/null | tail -1
 python tools/act_bench.py 2>/dev/null | sed -n 3,4p
-python bench.py --no-cpu-baseline --no-alt 2>/dev/null | python -c "
+python bench.py --full --no-cpu-baseline --no-alt 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('bench',d['value'],'audio-s/s',d['ms_per_step'],'ms  conv frac',d['roofline']['frac'],' act frac',d['roofline_hbm']['frac'])"
