@@ -130,17 +130,24 @@ def pack_amp_weight(w, channels=None):
     return torch.cat(parts, dim=-1).contiguous()
 
 
+def split_pieces(x):
+    """fp32 tensor -> its three bf16 pieces (h, m, l), x = h + m + l exactly: h = bf16(x), m = bf16(x - h), l = bf16(x - h - m)
+    (round to nearest even; the subtractions are exact in fp32).  The one host split of every bf16 x 6 weight packer."""
+    x = x.float()
+    h = x.to(torch.bfloat16)
+    r = x - h.float()
+    m = r.to(torch.bfloat16)
+    l = (r - m.float()).to(torch.bfloat16)
+    return h, m, l
+
+
 def pack_gemm_bf_weight(w):
     """Linear weight [n_pad, K] (n_pad % 64 == 0, K % 32 == 0; rows past N zero) -> the bf16 x 6 GEMM's weights (gemm_bf.hip,
     fh_gemm_bf16x6_f32): float32 container of bf16 bit patterns [n_pad / 64][K / 32][piece h, m, l][k-octet][64 rows][8 bf16]."""
     n_pad, k = w.shape
     if n_pad % 64 or k % 32:
         raise ValueError(f"bf16 x 6 GEMM weight: [{n_pad}, {k}] (rows a multiple of 64, K of 32)")
-    w = w.float()
-    h = w.to(torch.bfloat16)
-    r = w - h.float()
-    m = r.to(torch.bfloat16)
-    l = (r - m.float()).to(torch.bfloat16)
+    h, m, l = split_pieces(w)
     p = torch.stack([h, m, l], dim=0).view(3, n_pad // 64, 64, k // 32, 4, 8)           # [piece, granule, row, stage, octet, e]
     return p.permute(1, 3, 0, 4, 2, 5).contiguous().view(torch.int16).reshape(-1).view(torch.float32)
 
@@ -179,22 +186,14 @@ def pack_narrow_bf_weight(w, channels=None):
         full[:, :k * og] = blk
         # [na, n, kb, lg, e] -> [kb, na, lane = 16 lg + n, e]
         full = full.view(ma, 16, nb, 4, 8).permute(2, 0, 3, 1, 4).reshape(nb, ma, 64, 8)
-        h = full.to(torch.bfloat16)
-        r = full - h.float()
-        m = r.to(torch.bfloat16)
-        l = (r - m.float()).to(torch.bfloat16)
+        h, m, l = split_pieces(full)
         parts.append(torch.stack([h, m, l], dim=2).contiguous().view(torch.int16).reshape(-1))      # [kb, na, piece, lane, 8]
     return torch.cat(parts).contiguous().view(torch.float32)
 
 
 def split_bf3(u):
-    """fp32 tensor [..., 16] -> int16 tensor [..., 3, 16] of bf16 bit patterns: x = h + m + l with h = bf16(x),
-    m = bf16(x - h), l = bf16(x - h - m) (round to nearest even; the subtractions are exact in fp32)."""
-    u = u.float()
-    h = u.to(torch.bfloat16)
-    r = u - h.float()
-    m = r.to(torch.bfloat16)
-    l = (r - m.float()).to(torch.bfloat16)
+    """fp32 tensor [..., 16] -> int16 tensor [..., 3, 16] of bf16 bit patterns: the pieces h, m, l of split_pieces."""
+    h, m, l = split_pieces(u)
     return torch.stack([h, m, l], dim=-2).contiguous().view(torch.int16)
 
 

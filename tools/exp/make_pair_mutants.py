@@ -1,0 +1,124 @@
+"""Mutants of the four bf16 x 6 kernels (results wrong on purpose): does the suite notice a lost piece pair or a wrong device split?
+    python tools/exp/make_pair_mutants.py [name ...]     ->  tools/abl/pairs/<name>.so  (sources: tools/exp/abl_pairs/<name>/)
+    python tools/exp/run_pair_mutants.py                 ->  profiles/r07_bf16x6_pair_mutants.txt
+Per kernel (gemm = gemm_bf.hip, narrow = narrow_bf.hip, w43 = conv_wino.hip's BF path, w54 = conv_wino54_kernel.h <BF>):
+  <kernel>_pair_<ab>   the MFMA of pair (activation piece a, weight piece b) gets a zero activation operand (hh hm mh hl lh mm)
+  <kernel>_split_l0    the device split writes l = 0
+  <kernel>_split_trunc the device split truncates to bf16 instead of rounding to nearest even
+An operand is zeroed, no instruction deleted: addressing and register allocation stay the product's.  Built with build.py's flags
+for the file (-fno-slp-vectorize where the product has it) against the product's other objects (flowhigh_amd/build/, run
+`python -m flowhigh_amd.build` first); a mutant whose kernels need scratch beyond build.MAX_SCRATCH_BYTES is rejected, as the
+product build rejects such a kernel."""
+import subprocess
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[2]
+sys.path.insert(0, str(ROOT))
+from flowhigh_amd import build as B         # noqa: E402
+
+CSRC = ROOT / "flowhigh_amd" / "csrc"
+SRC_DIR = ROOT / "tools" / "exp" / "abl_pairs"
+LIB_DIR = ROOT / "tools" / "abl" / "pairs"
+PAIRS = ["hh", "hm", "mh", "hl", "lh", "mm"]        # (activation piece, weight piece)
+TRUNC = "{{ return (__float_as_uint(a) >> 16) | (__float_as_uint(b) & 0xffff0000u); }}"
+
+
+def one(text, old, new):
+    assert text.count(old) == 1, old
+    return text.replace(old, new)
+
+
+def gemm(kind, arg):
+    t = (CSRC / "gemm_bf.hip").read_text()
+    if kind == "pair":                   # table order: (l h) (h l) (m m) (m h) (h m) (h h) as (A piece, W piece)
+        pp = ["lh", "hl", "mm", "mh", "hm", "hh"].index(arg)
+        return {"gemm_bf.hip": one(t, "__builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mt][pa[pp]], b[nt][pb[pp]]",
+                                   f"__builtin_amdgcn_mfma_f32_32x32x16_bf16(pp == {pp} ? __builtin_bit_cast(gb_bf16x8, "
+                                   "(u32x4){0u, 0u, 0u, 0u}) : a[mt][pa[pp]], b[nt][pb[pp]]")}
+    if arg == "l0":
+        return {"gemm_bf.hip": one(t, "l[i] = gb_pack(ra - gb_lo(m[i]), rb - gb_hi(m[i]));", "l[i] = 0u;")}
+    return {"gemm_bf.hip": one(t, "{\n  const gb_bf16x2 v = {(__bf16)a, (__bf16)b};\n  return __builtin_bit_cast(unsigned, v);\n}",
+                               TRUNC.format())}
+
+
+def narrow(kind, arg):
+    t = (CSRC / "narrow_bf.hip").read_text()
+    if kind == "pair":                   # table order as gemm_bf.hip, (sample piece, weight piece)
+        pp = ["lh", "hl", "mm", "mh", "hm", "hh"].index(arg)
+        return {"narrow_bf.hip": one(t, "__builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][pa[pp]],",
+                                     f"__builtin_amdgcn_mfma_f32_16x16x32_bf16(pp == {pp} ? __builtin_bit_cast(nb_bf16x8, "
+                                     "(u32x4){0u, 0u, 0u, 0u}) : a[i][pa[pp]],")}
+    if arg == "l0":
+        return {"narrow_bf.hip": one(t, "l[i] = nb_pack(ra - nb_lo(m[i]), rb - nb_hi(m[i]));", "l[i] = 0u;")}
+    return {"narrow_bf.hip": one(t, "{              // v_cvt_pk_bf16_f32 (round to nearest even)\n"
+                                    "  const nb_bf16x2 v = {(__bf16)a, (__bf16)b};\n  return __builtin_bit_cast(unsigned, v);\n}",
+                                 TRUNC.format())}
+
+
+def w43(kind, arg):
+    t = (CSRC / "conv_wino.hip").read_text()
+    if kind == "pair":                   # six written-out MFMAs (weight piece, activation piece)
+        w_, a_ = arg[1], arg[0]
+        old = f"__builtin_amdgcn_mfma_f32_32x32x16_bf16(a{w_}, b{a_}, t, 0, 0, 0);"
+        # (a zero the compiler cannot see, made in a vector register by an empty asm: with a constant zero it re-schedules this
+        # loop and the 64 x 512 and 128 x 256 tiles spill)
+        new = ("{ unsigned z = 0u; asm volatile(\"\" : \"+v\"(z)); "
+               f"t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a{w_}, __builtin_bit_cast(bf16x8, (u32x4){{z, z, z, z}}), t, 0, 0, 0); }}")
+        return {"conv_wino.hip": one(t, "t = " + old, new)}
+    if arg == "l0":                      # (0 * x: not folded, the register use stays the product's)
+        return {"conv_wino.hip": one(t, "lp[i] = pack_bf16(sa, sb);", "lp[i] = pack_bf16(0.f * sa, 0.f * sb);")}
+    return {"conv_wino.hip": one(t, "{          // v_cvt_pk_bf16_f32\n  const bf16x2 v = {(__bf16)a, (__bf16)b};\n"
+                                    "  return __builtin_bit_cast(unsigned, v);\n}", TRUNC.format())}
+
+
+def w54(kind, arg):
+    t = (CSRC / "conv_wino54_kernel.h").read_text()
+    if kind == "pair":                   # table order (W piece, activation piece): (h h) (h m) (h l) (m h) (m m) (l h)
+        pp = ["hh", "mh", "lh", "hm", "mm", "hl"].index(arg)
+        t = one(t, "pb[pp] == 0 ? bh : pb[pp] == 1 ? bm : bl, acc[mt][nt], 0, 0, 0);",
+                f"pp == {pp} ? __builtin_bit_cast(v_bf16x8, (u32x4){{0u, 0u, 0u, 0u}}) : pb[pp] == 0 ? bh : pb[pp] == 1 ? bm : bl, "
+                "acc[mt][nt], 0, 0, 0);")
+    elif arg == "l0":
+        t = one(t, "lp[i] = v_pack_bf16(sa, sb);", "lp[i] = 0u;")
+    else:
+        t = one(t, "{        // v_cvt_pk_bf16_f32\n  const v_bf16x2 v = {(__bf16)a, (__bf16)b};\n  return __builtin_bit_cast(unsigned, v);\n}",
+                TRUNC.format())
+    return {"conv_wino54_kernel.h": t, "conv_wino54_bf.hip": (CSRC / "conv_wino54_bf.hip").read_text()}
+
+
+KERNELS = {"gemm": (gemm, "gemm_bf.hip"), "narrow": (narrow, "narrow_bf.hip"), "w43": (w43, "conv_wino.hip"),
+           "w54": (w54, "conv_wino54_bf.hip")}
+MUTANTS = [(f"{k}_pair_{p}", k, "pair", p) for k in KERNELS for p in PAIRS] + \
+          [(f"{k}_split_{s}", k, "split", s) for k in KERNELS for s in ("l0", "trunc")]
+
+
+def build(name, kernel, kind, arg):
+    make, src = KERNELS[kernel]
+    files = make(kind, arg)
+    d = SRC_DIR / name
+    d.mkdir(parents=True, exist_ok=True)
+    for f, text in files.items():
+        (d / f).write_text(text)
+    obj = d / (src + ".o")
+    cmd = [B.os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), *B.FLAGS, *B.EXTRA_FLAGS.get(src, []), *B.RESOURCE_FLAGS,
+           f"-I{CSRC}", "-c", str(d / src), "-o", str(obj)]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    if p.returncode:
+        raise RuntimeError(f"{name}: hipcc failed\n{p.stderr[-3000:]}")
+    spills = {k: r["ScratchSize"] for k, r in B.parse_resource_remarks(p.stderr).items() if r.get("ScratchSize", 0) > B.MAX_SCRATCH_BYTES}
+    if spills:
+        raise RuntimeError(f"{name}: rejected, kernels spill: {spills}")
+    others = [str(ROOT / "flowhigh_amd" / "build" / (s + ".o")) for s in B.SOURCES if s != src]
+    LIB_DIR.mkdir(parents=True, exist_ok=True)
+    subprocess.check_call([cmd[0], "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(LIB_DIR / f"{name}.so"), *others, str(obj)])
+    obj.unlink()
+    return LIB_DIR / f"{name}.so"
+
+
+if __name__ == "__main__":
+    from concurrent.futures import ThreadPoolExecutor
+    want = [m for m in MUTANTS if not sys.argv[1:] or m[0] in sys.argv[1:]]
+    with ThreadPoolExecutor(8) as ex:
+        for m, f in zip(want, [ex.submit(build, *m) for m in want]):
+            print(f.result().relative_to(ROOT), flush=True)
