@@ -34,6 +34,7 @@
 //     every thread applies A^T, bias, residuals and the scale, and stores 4 outputs.
 // MFMA work per output: 1.5 ceil(k/3) instead of k multiply-adds per channel pair (k = 3 / 7 / 11:
 // 2.0x / 1.56x / 1.83x fewer matrix-core cycles).
+#include "bf16x6.h"
 #include "fh_common.h"
 
 #include <stdlib.h>
@@ -43,43 +44,14 @@
 namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 // ---- fp32 operands as three bf16 pieces (BF = true kernels) ---------------------------------------------------------
-// x = h + m + l with h = bf16(x), m = bf16(x - h), l = bf16(x - h - m) (round to nearest even; the two
-// subtractions are exact in fp32): 3 x 8 significant bits.  A product a b is summed over the six leading piece
-// pairs (hh, hm, mh, mm, hl, lh) by six v_mfma_f32_32x32x16_bf16 per 16-channel k-block into the SAME fp32
-// accumulator; the dropped pairs (ml, lm, ll) are <= 2^-24 |a b|, below the rounding of the fp32 accumulation itself
-// (tools/micro/bf16x6.hip: a 32 x 32 x 1024 product against float64: 4.17e-7 of sum |a b| for this form, 4.19e-7 for
-// v_mfma_f32_32x32x2_f32).  6 bf16 MFMAs of 32 cycles replace 8 fp32 MFMAs of 64: 0.375 of the matrix-pipe cycles.
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {          // v_cvt_pk_bf16_f32
-  const bf16x2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(unsigned, v);
-}
-// Everything that runs beside the bf16 MFMAs is written one result per lane, and this file's BF instantiations are compiled
-// with -fno-slp-vectorize (conv_wino_bf.hip): at plain -O3 the SLP vectoriser re-packs adjacent scalar subtractions / FMAs into
+// The split and the pairs are bf16x6.h's: six v_mfma_f32_32x32x16_bf16 per 16-channel k-block, small terms first.  6 bf16
+// MFMAs of 32 cycles replace 8 fp32 MFMAs of 64: 0.375 of the matrix-pipe cycles.
+// Everything that runs beside the bf16 MFMAs is written one result per lane, and this file is compiled with
+// -fno-slp-vectorize (build.py): at plain -O3 the SLP vectoriser re-packs adjacent scalar subtractions / FMAs into
 // v_pk_add_f32 / v_pk_fma_f32, which share the matrix cores' fp32 lanes -- each costs 11-13 cycles of a 32-cycle bf16 MFMA gap,
 // a plain instruction issues in the MFMA's shadow (MI355X_MICROARCH.md, "price of one filler beside MFMAs").
-__device__ __forceinline__ float bf_lo(unsigned p) {                       // the low bf16 of a pair as a float
-  return __uint_as_float(__builtin_amdgcn_perm(0u, p, 0x01000c0cu));
-}
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-  unsigned hp[4], mp[4], lp[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = v[2 * i], b = v[2 * i + 1];
-    hp[i] = pack_bf16(a, b);
-    // (low half -> float by v_perm_b32: from `hp << 16` the combiner makes a SECOND v_cvt_pk of (a, 0) and then the shift)
-    const float ra = a - bf_lo(hp[i]), rb = b - __uint_as_float(hp[i] & 0xffff0000u);
-    mp[i] = pack_bf16(ra, rb);
-    const float sa = ra - bf_lo(mp[i]), sb = rb - __uint_as_float(mp[i] & 0xffff0000u);
-    lp[i] = pack_bf16(sa, sb);
-  }
-  h = __builtin_bit_cast(bf16x8, (u32x4){hp[0], hp[1], hp[2], hp[3]});
-  m = __builtin_bit_cast(bf16x8, (u32x4){mp[0], mp[1], mp[2], mp[3]});
-  l = __builtin_bit_cast(bf16x8, (u32x4){lp[0], lp[1], lp[2], lp[3]});
-}
 constexpr int W_A3 = 24;             // floats (96 bytes) per output row and 16-channel chunk of the 3-piece weights
 
 constexpr int W_CK = 16;             // input channels per chunk
@@ -150,7 +122,7 @@ __device__ __forceinline__ WSeg load_wseg(const fh_wino_seg* S) {
 // 8-byte LDS stores; needs contiguous, 16-byte aligned rows: phase-major tensors, or dilation 1 and len % 4 == 0.
 // BF: the transformed weights are stored as three bf16 pieces, [C_in/16][tap group][6][C_out_pad][3][16] (96 bytes per
 // row and chunk: lane (row, half) reads its 8 channels of each piece as one 16-byte load), the B fragments are
-// split in registers, and a 16-channel k-block is six v_mfma_f32_32x32x16_bf16 (see split8 above).  The lane <->
+// split in registers, and a 16-channel k-block is six v_mfma_f32_32x32x16_bf16 (bf16x6.h).  The lane <->
 // channel assignment is the one of the fp32 form: lane half h owns channels 8 h .. 8 h + 7 of the chunk.
 // launch constants the block -> work mapping divides by (fh_common.h: fh_fastdiv); rect_*: the xcd_ranges mapping
 struct WDivs {
@@ -478,7 +450,7 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
                 const int j = 3 * g + sh + o[r];
                 x[r] = *reinterpret_cast<const f32x2*>(xsb + ((j & 3) * W_P + (j >> 2)) * 2 + kp * W_RP2 + 128 * nt);
               }
-              // (one result per lane on purpose, see split8; same bits as the packed form of the fp32 kernel: every element
+              // (one result per lane on purpose, top of the file; same bits as the packed form of the fp32 kernel: every element
               // is one fma chain)
 #pragma unroll
               for (int e = 0; e < 2; ++e) {
@@ -487,19 +459,17 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
                 v[2 * kp + e] = __builtin_fmaf(bc2, qq, pp);
               }
             }
-            bf16x8 bh, bm, bl;
-            split8(v, bh, bm, bl);
+            u32x4 bp[3];                           // the B pieces h, m, l
+            bf16x6_split(v, bp[0], bp[1], bp[2]);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
-              const bf16x8 ah = __builtin_bit_cast(bf16x8, a3[mt][0]), am = __builtin_bit_cast(bf16x8, a3[mt][1]),
-                           al = __builtin_bit_cast(bf16x8, a3[mt][2]);
-              f32x16 t = acc[mt][nt];              // small terms first
-              t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, t, 0, 0, 0);
-              t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, t, 0, 0, 0);
-              t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, t, 0, 0, 0);
-              t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, t, 0, 0, 0);
-              t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, t, 0, 0, 0);
-              t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, t, 0, 0, 0);
+              f32x16 t = acc[mt][nt];
+#pragma unroll
+              for (int pp = 0; pp < 6; ++pp) {
+                const Bf16x6Pair s = kBf16x6SmallFirst[pp];          // (weight piece, B piece)
+                t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a3[mt][s.a]), __builtin_bit_cast(bf16x8, bp[s.b]),
+                                                            t, 0, 0, 0);
+              }
               acc[mt][nt] = t;
             }
           }

@@ -32,6 +32,7 @@
 //     each), the 5-sample tiles are re-laid row-major in LDS and leave as aligned 16-byte vectors with bias, residuals
 //     and scale applied.
 #pragma once
+#include "bf16x6.h"
 #include "fh_common.h"
 
 #include <type_traits>
@@ -39,14 +40,11 @@
 namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 v_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 v_bf16x2 __attribute__((ext_vector_type(2)));
 
 // ---- BF = true: the same contraction on the BF16 matrix cores, fp32-grade (round 6) --------------------------------------------
-// Every fp32 operand is split EXACTLY into three bf16 pieces, x = h + m + l (h = bf16(x), m = bf16(x - h), l = bf16(x - h - m),
-// round to nearest even, both subtractions exact in fp32), and a 16-channel k-block is six v_mfma_f32_32x32x16_bf16 over the piece
-// pairs (h h), (h m), (h l), (m h), (m m), (l h) into the same fp32 accumulator: 6 x 32 matrix-pipe cycles against 8 x 64 of the
-// fp32 form; the dropped pairs are <= 2^-24 |a b| (conv_wino.hip, tools/micro/bf16x6.hip).  The weights arrive pre-split
+// Every fp32 operand is split exactly into three bf16 pieces, and a 16-channel k-block is six v_mfma_f32_32x32x16_bf16 over the
+// piece pairs into the same fp32 accumulator, in the order of kBf16x6AMajor (bf16x6.h: the split, the pairs and their error
+// bound): 6 x 32 matrix-pipe cycles against 8 x 64 of the fp32 form.  The weights arrive pre-split
 // (packing.split_bf3 of pack_wino54_weight: [cin/16][tap group][8][cout_pad][3 pieces][16] bf16 = 96 bytes per row and chunk), the
 // B operands are transformed exactly as in the fp32 form (same fma chain per element: same V bits) and split in registers.
 // Everything beside the MFMAs is written one result per lane and this form's instantiations are compiled with
@@ -54,28 +52,6 @@ typedef __bf16 v_bf16x2 __attribute__((ext_vector_type(2)));
 // (MI355X_MICROARCH.md, "price of one filler beside MFMAs"), plain ones issue in its shadow.  What the loop's shape is worth was
 // measured on a stand-alone model of it first (tools/micro/bf54.hip, profiles/r06_bf16x6_coissue.txt).
 constexpr int V_A3 = 24;             // floats (96 bytes) per output row and 16-channel chunk of the three-piece weights
-__device__ __forceinline__ unsigned v_pack_bf16(float a, float b) {        // v_cvt_pk_bf16_f32
-  const v_bf16x2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float v_bf_lo(unsigned p) {                     // the low bf16 of a pair as a float (v_perm_b32: from
-  return __uint_as_float(__builtin_amdgcn_perm(0u, p, 0x01000c0cu));       // `p << 16` the combiner derives a second v_cvt_pk)
-}
-__device__ __forceinline__ void v_split8(const float (&v)[8], v_bf16x8& h, v_bf16x8& m, v_bf16x8& l) {
-  unsigned hp[4], mp[4], lp[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = v[2 * i], b = v[2 * i + 1];
-    hp[i] = v_pack_bf16(a, b);
-    const float ra = a - v_bf_lo(hp[i]), rb = b - __uint_as_float(hp[i] & 0xffff0000u);
-    mp[i] = v_pack_bf16(ra, rb);
-    const float sa = ra - v_bf_lo(mp[i]), sb = rb - __uint_as_float(mp[i] & 0xffff0000u);
-    lp[i] = v_pack_bf16(sa, sb);
-  }
-  h = __builtin_bit_cast(v_bf16x8, (u32x4){hp[0], hp[1], hp[2], hp[3]});
-  m = __builtin_bit_cast(v_bf16x8, (u32x4){mp[0], mp[1], mp[2], mp[3]});
-  l = __builtin_bit_cast(v_bf16x8, (u32x4){lp[0], lp[1], lp[2], lp[3]});
-}
 
 constexpr int V_CK = 16;             // input channels per chunk
 constexpr int V_THREADS = 512;       // 8 waves = 8 transform points
@@ -466,23 +442,24 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
                 v[2 * kp + e] = t;
               }
             }
-            v_bf16x8 bh, bm, bl;
-            v_split8(v, bh, bm, bl);
-            // (piece pairs outermost, row tiles inside: MT independent accumulators between two MFMAs on the same one.  The
-            // weights' pieces are used in the order h h h m m l, and each is requested for the NEXT tap group as soon as the group's
-            // second column is through with it -- h three pairs, m one pair ahead of the end of the MFMAs, and in the order the next
-            // group needs them: one register set, yet most of the L2 round trip runs under this group's matrix work)
+            u32x4 bp[3];                                 // the B pieces h, m, l
+            bf16x6_split(v, bp[0], bp[1], bp[2]);
+            // (piece pairs outermost, row tiles inside: MT independent accumulators between two MFMAs on the same one.  In
+            // kBf16x6AMajor the weights' pieces are used in the order h h h m m l, and each is requested for the NEXT tap group right
+            // behind its last use in the group's second column (bf16x6_last_use) -- h three pairs, m one pair ahead of the end of the
+            // MFMAs, and in the order the next group needs them: one register set, yet most of the L2 round trip runs under this
+            // group's matrix work)
             const bool same_chunk = g + 1 < GC;
             const int nc = same_chunk ? c : c + 1, ng = same_chunk ? g + 1 : 0;
             const bool nv = same_chunk || has_next;
 #pragma unroll
             for (int pp = 0; pp < 6; ++pp) {
-              constexpr int pa[6] = {0, 0, 0, 1, 1, 2}, pb[6] = {0, 1, 2, 0, 1, 0};      // (h h) (h m) (h l) (m h) (m m) (l h)
+              const Bf16x6Pair s = kBf16x6AMajor[pp];                  // (weight piece, B piece)
 #pragma unroll
               for (int mt = 0; mt < MT; ++mt)
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v_bf16x8, a3[mt][pa[pp]]),
-                                                                      pb[pp] == 0 ? bh : pb[pp] == 1 ? bm : bl, acc[mt][nt], 0, 0, 0);
-              if (nt == 1 && (pp == 2 || pp == 4 || pp == 5)) load_a3(S, nc, ng, nv, pp == 2 ? 1 : pp == 4 ? 2 : 4);
+                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a3[mt][s.a]),
+                                                                      __builtin_bit_cast(bf16x8, bp[s.b]), acc[mt][nt], 0, 0, 0);
+              if (nt == 1 && pp == bf16x6_last_use(kBf16x6AMajor, s.a)) load_a3(S, nc, ng, nv, 1 << s.a);
             }
           }
         }

@@ -1,6 +1,6 @@
 // GEMM in the bf16 x 6 form:  C[M, N] = epilogue(A[M, K] * W[N, K]^T) with fp32 in / out / accumulate and every product as six
-// v_mfma_f32_32x32x16_bf16 over exact three-piece splits (x = h + m + l, h = bf16(x), m = bf16(x - h), l = bf16(x - h - m); the pairs
-// h h, h m, m h, h l, l h, m m; dropped terms <= 2^-24 |a b|): the transformer's linears of a conv_form = 'bf16x6' model.
+// v_mfma_f32_32x32x16_bf16 over exact three-piece splits (bf16x6.h, small terms first): the transformer's linears of a
+// conv_form = 'bf16x6' model.
 //
 // Replaces the same nn.Linear call sites as gemm_mfma.hip (/root/reference/src/flowhigh/models/flow.py:239,261; attend.py:170-171,
 // 176,189; transformer.py:98-104) -- same epilogues (bias, alpha, residual; GEGLU pairs), same tile variants and block order.
@@ -12,32 +12,13 @@
 // global loads of stage i + 1 are in registers before the MFMAs of stage i; LDS single-buffered, two barriers per stage.
 // W in memory: [64-row granule][k stage][piece][k-octet][64 rows][8 bf16] (12 KB per granule and stage: a stage's W tile is a
 // straight copy of 1-2 granules).
+#include "bf16x6.h"
 #include "fh_common.h"
 
 namespace {
 
-typedef __bf16 gb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 gb_bf16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int GB_BK = 32;
 constexpr int GB_GRAN = 3 * 4 * 64;        // 16-byte units of one (64-row granule, k stage) of packed W
-
-__device__ __forceinline__ unsigned gb_pack(float a, float b) {
-  const gb_bf16x2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float gb_lo(unsigned p) { return __uint_as_float(__builtin_amdgcn_perm(0u, p, 0x01000c0cu)); }
-__device__ __forceinline__ float gb_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ void gb_split8(const f32x4& v0, const f32x4& v1, u32x4& h, u32x4& m, u32x4& l) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = i < 2 ? v0[2 * i] : v1[2 * i - 4], b = i < 2 ? v0[2 * i + 1] : v1[2 * i - 3];
-    h[i] = gb_pack(a, b);
-    const float ra = a - gb_lo(h[i]), rb = b - gb_hi(h[i]);
-    m[i] = gb_pack(ra, rb);
-    l[i] = gb_pack(ra - gb_lo(m[i]), rb - gb_hi(m[i]));
-  }
-}
 
 __device__ __forceinline__ float gb_epi_pair(float first, float second, int mode) {
   if (mode == FH_EPI_GEGLU) return gelu_erf(second) * first;
@@ -104,8 +85,10 @@ __global__ __launch_bounds__(256) void gemm_bf_kernel(const float* __restrict__ 
 #pragma unroll
     for (int i = 0; i < AIT; ++i) {
       const int item = tid + 256 * i, row = item >> 2, ko = item & 3;
+      const f32x4 &v0 = areg[i][0], &v1 = areg[i][1];
+      const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
       u32x4 h, m, l;
-      gb_split8(areg[i][0], areg[i][1], h, m, l);
+      bf16x6_split(v, h, m, l);
       As[(0 * 4 + ko) * AP + row] = h;
       As[(1 * 4 + ko) * AP + row] = m;
       As[(2 * 4 + ko) * AP + row] = l;
@@ -125,23 +108,22 @@ __global__ __launch_bounds__(256) void gemm_bf_kernel(const float* __restrict__ 
     if (ks + 1 < kstages) gload(ks + 1);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      gb_bf16x8 a[MT][3], b[NT][3];
+      bf16x8 a[MT][3], b[NT][3];
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) a[mt][p] = __builtin_bit_cast(gb_bf16x8, As[(p * 4 + 2 * q + lh) * AP + (wm * MT + mt) * 32 + l31]);
+        for (int mt = 0; mt < MT; ++mt) a[mt][p] = __builtin_bit_cast(bf16x8, As[(p * 4 + 2 * q + lh) * AP + (wm * MT + mt) * 32 + l31]);
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) b[nt][p] = __builtin_bit_cast(gb_bf16x8, Ws[(p * 4 + 2 * q + lh) * BN + (wn * NT + nt) * 32 + l31]);
+        for (int nt = 0; nt < NT; ++nt) b[nt][p] = __builtin_bit_cast(bf16x8, Ws[(p * 4 + 2 * q + lh) * BN + (wn * NT + nt) * 32 + l31]);
       }
-      // piece pairs (A piece, W piece), small terms first: (l h) (h l) (m m) (m h) (h m) (h h)
 #pragma unroll
       for (int pp = 0; pp < 6; ++pp) {
-        constexpr int pa[6] = {2, 0, 1, 1, 0, 0}, pb[6] = {0, 2, 1, 0, 1, 0};
+        const Bf16x6Pair s = kBf16x6SmallFirst[pp];                  // (A piece, W piece)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
           for (int nt = 0; nt < NT; ++nt)
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mt][pa[pp]], b[nt][pb[pp]], acc[mt][nt], 0, 0, 0);
+            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mt][s.a], b[nt][s.b], acc[mt][nt], 0, 0, 0);
       }
     }
   }

@@ -9,8 +9,8 @@
 // re-interleave than its matrix work is worth (amp_fused.hip: 3.7 vector + 3.8 scalar instructions per MFMA, matrix pipe 0.38-0.48
 // busy), and a bf16 x 6 Winograd loop would have to split every transformed value (8 points x channels x tap groups).  The direct
 // form splits every input sample ONCE, when it enters LDS, and its K loop is ds_read_b128 + MFMA with no vector arithmetic:
-//   * x = h + m + l, h = bf16(x), m = bf16(x - h), l = bf16(x - h - m) (exact); a product a b is the six MFMAs h h, h m, m h, h l,
-//     l h, m m with fp32 accumulation (dropped terms <= 2^-24 |a b|), weights split on the host (packing.pack_narrow_bf_weight);
+//   * a product a b is the six piece-pair MFMAs of bf16x6.h, small terms first, with fp32 accumulation; samples split on the device
+//     (bf16x6_split), weights on the host (packing.pack_narrow_bf_weight);
 //   * block = 4 waves = 256 outputs of every channel; wave = 4 M tiles of 16 outputs x ceil(C / 16) N tiles of 16 channels
 //     (M = time: a lane's 4 accumulator registers are 4 consecutive samples of one channel, stored as one 16-byte vector with bias,
 //     residuals and scale straight from the registers: no staging, no barrier in the epilogue);
@@ -22,12 +22,10 @@
 //     set is 18-110 KB per conv, the same for every block of the launch, and no wave waits for another inside the K loop.
 // A sample's arithmetic depends on its absolute position only (fixed K order), so a clip gives the same bits alone, in a batch, in
 // a ragged launch and in time chunks.
+#include "bf16x6.h"
 #include "fh_common.h"
 
 namespace {
-
-typedef __bf16 nb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 nb_bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int NB_THREADS = 256;              // 4 waves
 constexpr int NB_NM = 4;                     // M tiles (16 outputs) per wave
@@ -36,25 +34,6 @@ constexpr int NB_NSP = NB_OUT + 64;          // samples (16-byte units) per (pie
 constexpr int NB_OG = 3;                     // octets (8 channels) per slab
 constexpr int NB_PLANE = NB_OG * NB_NSP;     // units of a piece plane
 constexpr int NB_MAX_D = 6;                  // (taps: at most 11, center at most 5 -- NB_NSP; checked where the descriptors are made)
-
-__device__ __forceinline__ unsigned nb_pack(float a, float b) {              // v_cvt_pk_bf16_f32 (round to nearest even)
-  const nb_bf16x2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float nb_lo(unsigned p) { return __uint_as_float(__builtin_amdgcn_perm(0u, p, 0x01000c0cu)); }
-__device__ __forceinline__ float nb_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-
-// 8 values -> three 16-byte pieces (8 bf16 each)
-__device__ __forceinline__ void nb_split8(const float (&v)[8], u32x4& h, u32x4& m, u32x4& l) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = v[2 * i], b = v[2 * i + 1];
-    h[i] = nb_pack(a, b);
-    const float ra = a - nb_lo(h[i]), rb = b - nb_hi(h[i]);
-    m[i] = nb_pack(ra, rb);
-    l[i] = nb_pack(ra - nb_lo(m[i]), rb - nb_hi(m[i]));
-  }
-}
 
 // MA: N tiles (16 output channels each).  VEC: every row of every group is 16-byte aligned (len % 4 == 0).
 template <int MA, bool VEC>
@@ -143,7 +122,7 @@ void narrow_bf_kernel(const fh_amp_group* __restrict__ groups, const fh_amp_tile
 #pragma unroll
               for (int c = 0; c < 8; ++c) v[c] = __uint_as_float(xq[c][e]);
               u32x4 h, m, l;
-              nb_split8(v, h, m, l);
+              bf16x6_split(v, h, m, l);
               dst[e] = h;
               dst[NB_PLANE + e] = m;
               dst[2 * NB_PLANE + e] = l;
@@ -158,7 +137,7 @@ void narrow_bf_kernel(const fh_amp_group* __restrict__ groups, const fh_amp_tile
             for (int c = 0; c < 8; ++c)
               v[c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, in ? (unsigned)((8 * (ob + o) + c) * len + t) * 4u : 0x80000000u, 0, 0));
             u32x4 h, m, l;
-            nb_split8(v, h, m, l);
+            bf16x6_split(v, h, m, l);
             u32x4* const dst = slab + o * NB_NSP + s;
             dst[0] = h;
             dst[NB_PLANE] = m;
@@ -182,20 +161,19 @@ void narrow_bf_kernel(const fh_amp_group* __restrict__ groups, const fh_amp_tile
           const u32x4* const ap = slab + o * NB_NSP + (Ha - H) + tap * d + wv * (16 * NB_NM) + li;
 #pragma unroll
           for (int mp = 0; mp < NB_NM; mp += 2) {
-            nb_bf16x8 a[2][3];
+            bf16x8 a[2][3];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-              for (int p = 0; p < 3; ++p) a[i][p] = __builtin_bit_cast(nb_bf16x8, ap[(mp + i) * 16 + p * NB_PLANE]);
-            // piece pairs (sample piece, weight piece), small terms first: (l h) (h l) (m m) (m h) (h m) (h h)
+              for (int p = 0; p < 3; ++p) a[i][p] = __builtin_bit_cast(bf16x8, ap[(mp + i) * 16 + p * NB_PLANE]);
 #pragma unroll
             for (int pp = 0; pp < 6; ++pp) {
-              constexpr int pa[6] = {2, 0, 1, 1, 0, 0}, pb[6] = {0, 2, 1, 0, 1, 0};
+              const Bf16x6Pair s = kBf16x6SmallFirst[pp];            // (sample piece, weight piece)
 #pragma unroll
               for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int na = 0; na < MA; ++na)
-                  acc[mp + i][na] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][pa[pp]], __builtin_bit_cast(nb_bf16x8, bw[set][na][pb[pp]]),
+                  acc[mp + i][na] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][s.a], __builtin_bit_cast(bf16x8, bw[set][na][s.b]),
                                                                            acc[mp + i][na], 0, 0, 0);
             }
           }

@@ -1,8 +1,8 @@
 """The bf16 x 6 property, by construction: every fp32 operand is split exactly into h + m + l (round to nearest even) and every
-product is the sum of the six piece-pair MFMAs h h, h m, m h, h l, l h, m m.  The four kernels that implement it each have their
-own device split and pair selection (gemm_bf.hip, narrow_bf.hip, conv_wino.hip's BF path, conv_wino54_kernel.h <BF>), and their
-random-input tests sit at tolerances a lost small pair (2^-16 .. 2^-18 of a product) lands right on.  Here every output is one
-exact product chain, so each test asserts equality:
+product is the sum of the six piece-pair MFMAs h h, h m, m h, h l, l h, m m.  The four kernels that implement it share one device
+split and two pair schedules (bf16x6.h) but each feeds them its own way (gemm_bf.hip, narrow_bf.hip, conv_wino.hip's BF path,
+conv_wino54_kernel.h <BF>), and their random-input tests sit at tolerances a lost small pair (2^-16 .. 2^-18 of a product) lands
+right on.  Here every output is one exact product chain, so each test asserts equality:
 
   * the weights' three piece planes are written by the test with ONE slot filled (the others zero).  With an activation
     a = a_h + a_m + a_l the kept pairs make the result sum a v (slot h: pairs h h, m h, l h), sum (a_h + a_m) v (slot m: h m, m m)

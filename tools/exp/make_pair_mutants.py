@@ -5,6 +5,7 @@ Per kernel (gemm = gemm_bf.hip, narrow = narrow_bf.hip, w43 = conv_wino.hip's BF
   <kernel>_pair_<ab>   the MFMA of pair (activation piece a, weight piece b) gets a zero activation operand (hh hm mh hl lh mm)
   <kernel>_split_l0    the device split writes l = 0
   <kernel>_split_trunc the device split truncates to bf16 instead of rounding to nearest even
+The split mutants edit a copy of the shared bf16x6.h next to the kernel's source: only that kernel is built against it.
 An operand is zeroed, no instruction deleted: addressing and register allocation stay the product's.  Built with build.py's flags
 for the file (-fno-slp-vectorize where the product has it) against the product's other objects (flowhigh_amd/build/, run
 `python -m flowhigh_amd.build` first); a mutant whose kernels need scratch beyond build.MAX_SCRATCH_BYTES is rejected, as the
@@ -21,7 +22,7 @@ CSRC = ROOT / "flowhigh_amd" / "csrc"
 SRC_DIR = ROOT / "tools" / "exp" / "abl_pairs"
 LIB_DIR = ROOT / "tools" / "abl" / "pairs"
 PAIRS = ["hh", "hm", "mh", "hl", "lh", "mm"]        # (activation piece, weight piece)
-TRUNC = "{{ return (__float_as_uint(a) >> 16) | (__float_as_uint(b) & 0xffff0000u); }}"
+TRUNC = "  return (__float_as_uint(a) >> 16) | (__float_as_uint(b) & 0xffff0000u);\n"
 
 
 def one(text, old, new):
@@ -29,62 +30,61 @@ def one(text, old, new):
     return text.replace(old, new)
 
 
+def split(arg, l_zero="0u"):
+    """bf16x6.h with its split mutated: l = l_zero, or a truncating pack"""
+    t = (CSRC / "bf16x6.h").read_text()
+    if arg == "l0":
+        return {"bf16x6.h": one(t, "lp[i] = bf16_pack(ra - bf16_lo(mp[i]), rb - bf16_hi(mp[i]));", f"lp[i] = {l_zero};")}
+    return {"bf16x6.h": one(t, "  const bf16x2 v = {(__bf16)a, (__bf16)b};\n  return __builtin_bit_cast(unsigned, v);\n", TRUNC)}
+
+
+ZERO = "__builtin_bit_cast(bf16x8, (u32x4){0u, 0u, 0u, 0u})"
+
+
 def gemm(kind, arg):
     t = (CSRC / "gemm_bf.hip").read_text()
-    if kind == "pair":                   # table order: (l h) (h l) (m m) (m h) (h m) (h h) as (A piece, W piece)
-        pp = ["lh", "hl", "mm", "mh", "hm", "hh"].index(arg)
-        return {"gemm_bf.hip": one(t, "__builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mt][pa[pp]], b[nt][pb[pp]]",
-                                   f"__builtin_amdgcn_mfma_f32_32x32x16_bf16(pp == {pp} ? __builtin_bit_cast(gb_bf16x8, "
-                                   "(u32x4){0u, 0u, 0u, 0u}) : a[mt][pa[pp]], b[nt][pb[pp]]")}
-    if arg == "l0":
-        return {"gemm_bf.hip": one(t, "l[i] = gb_pack(ra - gb_lo(m[i]), rb - gb_hi(m[i]));", "l[i] = 0u;")}
-    return {"gemm_bf.hip": one(t, "{\n  const gb_bf16x2 v = {(__bf16)a, (__bf16)b};\n  return __builtin_bit_cast(unsigned, v);\n}",
-                               TRUNC.format())}
+    if kind == "split":
+        return {"gemm_bf.hip": t, **split(arg)}
+    # schedule kBf16x6SmallFirst: (l h) (h l) (m m) (m h) (h m) (h h) as (A piece, W piece)
+    pp = ["lh", "hl", "mm", "mh", "hm", "hh"].index(arg)
+    return {"gemm_bf.hip": one(t, "__builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mt][s.a], b[nt][s.b]",
+                               f"__builtin_amdgcn_mfma_f32_32x32x16_bf16(pp == {pp} ? {ZERO} : a[mt][s.a], b[nt][s.b]")}
 
 
 def narrow(kind, arg):
     t = (CSRC / "narrow_bf.hip").read_text()
-    if kind == "pair":                   # table order as gemm_bf.hip, (sample piece, weight piece)
-        pp = ["lh", "hl", "mm", "mh", "hm", "hh"].index(arg)
-        return {"narrow_bf.hip": one(t, "__builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][pa[pp]],",
-                                     f"__builtin_amdgcn_mfma_f32_16x16x32_bf16(pp == {pp} ? __builtin_bit_cast(nb_bf16x8, "
-                                     "(u32x4){0u, 0u, 0u, 0u}) : a[i][pa[pp]],")}
-    if arg == "l0":
-        return {"narrow_bf.hip": one(t, "l[i] = nb_pack(ra - nb_lo(m[i]), rb - nb_hi(m[i]));", "l[i] = 0u;")}
-    return {"narrow_bf.hip": one(t, "{              // v_cvt_pk_bf16_f32 (round to nearest even)\n"
-                                    "  const nb_bf16x2 v = {(__bf16)a, (__bf16)b};\n  return __builtin_bit_cast(unsigned, v);\n}",
-                                 TRUNC.format())}
+    if kind == "split":
+        return {"narrow_bf.hip": t, **split(arg)}
+    pp = ["lh", "hl", "mm", "mh", "hm", "hh"].index(arg)          # as gemm_bf.hip, (sample piece, weight piece)
+    return {"narrow_bf.hip": one(t, "__builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][s.a],",
+                                 f"__builtin_amdgcn_mfma_f32_16x16x32_bf16(pp == {pp} ? {ZERO} : a[i][s.a],")}
 
 
 def w43(kind, arg):
     t = (CSRC / "conv_wino.hip").read_text()
-    if kind == "pair":                   # six written-out MFMAs (weight piece, activation piece)
-        w_, a_ = arg[1], arg[0]
-        old = f"__builtin_amdgcn_mfma_f32_32x32x16_bf16(a{w_}, b{a_}, t, 0, 0, 0);"
-        # (a zero the compiler cannot see, made in a vector register by an empty asm: with a constant zero it re-schedules this
-        # loop and the 64 x 512 and 128 x 256 tiles spill)
-        new = ("{ unsigned z = 0u; asm volatile(\"\" : \"+v\"(z)); "
-               f"t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a{w_}, __builtin_bit_cast(bf16x8, (u32x4){{z, z, z, z}}), t, 0, 0, 0); }}")
-        return {"conv_wino.hip": one(t, "t = " + old, new)}
-    if arg == "l0":                      # (0 * x: not folded, the register use stays the product's)
-        return {"conv_wino.hip": one(t, "lp[i] = pack_bf16(sa, sb);", "lp[i] = pack_bf16(0.f * sa, 0.f * sb);")}
-    return {"conv_wino.hip": one(t, "{          // v_cvt_pk_bf16_f32\n  const bf16x2 v = {(__bf16)a, (__bf16)b};\n"
-                                    "  return __builtin_bit_cast(unsigned, v);\n}", TRUNC.format())}
+    if kind == "split":                  # (l = 0 * x: not folded, the register use stays the product's)
+        return {"conv_wino.hip": t, **split(arg, "bf16_pack(0.f * (ra - bf16_lo(mp[i])), 0.f * (rb - bf16_hi(mp[i])))")}
+    # schedule kBf16x6SmallFirst as (weight piece, activation piece)
+    pp = ["lh", "hl", "mm", "mh", "hm", "hh"].index(arg[1] + arg[0])
+    # (a zero the compiler cannot see, made in a vector register by an empty asm: with a constant zero it re-schedules this
+    # loop and the 64 x 512 and 128 x 256 tiles spill)
+    old = "t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a3[mt][s.a]), __builtin_bit_cast(bf16x8, bp[s.b]),"
+    new = (f"unsigned z = 0u;\n                if (pp == {pp}) asm volatile(\"\" : \"+v\"(z));\n"
+           "                t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a3[mt][s.a]), "
+           f"pp == {pp} ? __builtin_bit_cast(bf16x8, (u32x4){{z, z, z, z}}) : __builtin_bit_cast(bf16x8, bp[s.b]),")
+    return {"conv_wino.hip": one(t, old, new)}
 
 
 def w54(kind, arg):
     t = (CSRC / "conv_wino54_kernel.h").read_text()
-    if kind == "pair":                   # table order (W piece, activation piece): (h h) (h m) (h l) (m h) (m m) (l h)
-        pp = ["hh", "mh", "lh", "hm", "mm", "hl"].index(arg)
-        t = one(t, "pb[pp] == 0 ? bh : pb[pp] == 1 ? bm : bl, acc[mt][nt], 0, 0, 0);",
-                f"pp == {pp} ? __builtin_bit_cast(v_bf16x8, (u32x4){{0u, 0u, 0u, 0u}}) : pb[pp] == 0 ? bh : pb[pp] == 1 ? bm : bl, "
-                "acc[mt][nt], 0, 0, 0);")
-    elif arg == "l0":
-        t = one(t, "lp[i] = v_pack_bf16(sa, sb);", "lp[i] = 0u;")
-    else:
-        t = one(t, "{        // v_cvt_pk_bf16_f32\n  const v_bf16x2 v = {(__bf16)a, (__bf16)b};\n  return __builtin_bit_cast(unsigned, v);\n}",
-                TRUNC.format())
-    return {"conv_wino54_kernel.h": t, "conv_wino54_bf.hip": (CSRC / "conv_wino54_bf.hip").read_text()}
+    files = {"conv_wino54_bf.hip": (CSRC / "conv_wino54_bf.hip").read_text()}
+    if kind == "split":                  # (the kernel header next to the mutated bf16x6.h: its quoted include finds that one)
+        return {**files, "conv_wino54_kernel.h": t, **split(arg)}
+    # schedule kBf16x6AMajor (W piece, activation piece): (h h) (h m) (h l) (m h) (m m) (l h)
+    pp = ["hh", "mh", "lh", "hm", "mm", "hl"].index(arg)
+    t = one(t, "__builtin_bit_cast(bf16x8, bp[s.b]), acc[mt][nt], 0, 0, 0);",
+            f"pp == {pp} ? {ZERO} : __builtin_bit_cast(bf16x8, bp[s.b]), acc[mt][nt], 0, 0, 0);")
+    return {**files, "conv_wino54_kernel.h": t}
 
 
 KERNELS = {"gemm": (gemm, "gemm_bf.hip"), "narrow": (narrow, "narrow_bf.hip"), "w43": (w43, "conv_wino.hip"),
