@@ -9,12 +9,13 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "lib" / "libflowhigh_hip.so"
 SOURCES = ["api_common.hip", "conv_mfma.hip", "conv_wino.hip", "conv_wino54.hip", "conv_wino54_bf.hip", "amp_fused.hip", "narrow_bf.hip", "act1d.hip", "gemm_mfma.hip", "gemm_bf.hip", "flow_ops.hip",
-           "attention.hip", "frontend.hip", "fft.hip"]
+           "attention.hip", "attention_bf.hip", "frontend.hip", "fft.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-source extra flags.  The bf16 x 6 kernels keep everything beside their MFMAs one result per lane: the SLP vectoriser
 # would re-pack it into v_pk_*_f32, which stall a bf16 MFMA (conv_wino54_kernel.h)
 # (conv_wino.hip as a whole: its bf16 x 6 instantiations need it for the same reason, and without it the 128 x 256 one spills)
-EXTRA_FLAGS = {"conv_wino54_bf.hip": ["-fno-slp-vectorize"], "conv_wino.hip": ["-fno-slp-vectorize"]}
+# (attention_bf.hip: the softmax beside its bf16 MFMAs; 2-3 % at the large shapes, same bits)
+EXTRA_FLAGS = {"conv_wino54_bf.hip": ["-fno-slp-vectorize"], "conv_wino.hip": ["-fno-slp-vectorize"], "attention_bf.hip": ["-fno-slp-vectorize"]}
 # every kernel's resources are read from the compiler's remarks: a kernel that spills more than a few registers fails the build.
 # The conv kernels fill every register they are given; a variant that spills a hundred (it happened three times in round 6: the
 # scheduler hoisting the next tile column's work until the file is full) runs its K loop through scratch.  (Round 6 also found
@@ -22,7 +23,7 @@ EXTRA_FLAGS = {"conv_wino54_bf.hip": ["-fno-slp-vectorize"], "conv_wino.hip": ["
 # fixed at the source, conv_wino.hip: prefetch_a; the limit here is about speed.)
 RESOURCE_FLAGS = ["-Rpass-analysis=kernel-resource-usage"]
 MAX_SCRATCH_BYTES = 16          # per lane: up to 4 spilled registers (prologue / epilogue values) are tolerated and reported
-HEADERS = ["fh_common.h", "bf16x6.h", "conv_wino54_kernel.h"]
+HEADERS = ["fh_common.h", "bf16x6.h", "conv_wino54_kernel.h", "attention_softmax.h"]
 
 
 def _deps():

@@ -1,0 +1,299 @@
+// Streaming-softmax attention with both products in the bf16 x 6 form (dim_head = 64): attn_form = 'bf16x6'.
+//
+// Replaces the same call site as attention.hip: Attend.forward of the reference, models/attend.py:102-139
+//   sim = einsum(q, k) * scale ; attn = softmax(sim) ; out = einsum(attn, v)
+// fp32 in / out / accumulate; S^T = K Q^T and O^T = V^T P^T are six v_mfma_f32_32x32x16_bf16 per k-step over exact three-piece
+// splits (bf16x6.h), pair order kBf16x6SmallFirst with the pair read as (K piece, Q piece) and (V piece, P piece).
+//
+// Everything beside the two products is attention.hip's: 32-key tiles, two interleaved online-softmax streams per query row
+// merged by merge_streams (attention_softmax.h), base-2 exponent, the masking of the last tile, the SPLIT = 1 / 2 kernel shapes
+// and the rule that picks one.  Where both products are exact in both forms the two kernels give the same bits.
+//
+// Every operand is split once:
+//   K   by the block that stages the tile, on the way into LDS: 16-byte units of 8 consecutive d, [piece][tile][d-octet][key];
+//       A operand of S^T (row = key, k = d), read with ds_read_b128 (gemm_bf.hip's layout).
+//   V   likewise, and transposed while staged: a staging item is 4 consecutive keys of one d, so a split yields the two packed
+//       words of half a fragment; units [piece][tile][k-step s][lane half h][d], element j = key 16 s + 8 (j >> 2) + 4 h + (j & 3)
+//       of the tile, which is the k order of the S^T accumulator.  A operand of O^T (row = d, k = key), ds_read_b128.
+//   Q   once per wave into 48 registers: B operand of S^T for the whole kernel.
+//   P   in the S^T accumulator the lane's query is the column, so registers 8 s .. 8 s + 7 are the B fragment of k-step s of
+//       O^T with no lane movement: split in registers, the only split arithmetic inside the loop.
+// LDS: K 3 x 2 x 8 x 34 + V 3 x 2 x 4 x 64 units = 50 688 bytes per block.
+#include <math.h>
+
+#include "attention_softmax.h"
+#include "bf16x6.h"
+#include "fh_common.h"
+
+namespace {
+
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int KPB = 34;                    // pitch (units) of a (piece, tile, d-octet) plane of K: a staging pass's 16 lanes are 2 keys x
+                                           // 8 d-octets, 2 mod 16 puts them in 16 different bank groups
+constexpr int K_UNITS = 3 * 2 * 8 * KPB;
+constexpr int V_UNITS = 3 * 2 * 4 * 64;
+
+__device__ __forceinline__ bf16x8 as_bf(const u32x4& v) { return __builtin_bit_cast(bf16x8, v); }
+
+template <int WAVES, int SPLIT>
+__global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2))) void attention_bf_kernel(const float* __restrict__ qkv,
+                                                               float* __restrict__ out, int n, int heads,
+                                                               float scale, const int* __restrict__ seg) {
+  constexpr int NT = 64 * WAVES;           // threads
+  constexpr int NKI = 512 / NT;            // (key, d-octet) items of K staged per thread and iteration (64 keys)
+  constexpr int NVI = 1024 / NT;           // (4 keys, d) items of V
+  static_assert(NVI % 2 == 0, "V items are split in pairs");
+  __shared__ __attribute__((aligned(16))) u32x4 smem[K_UNITS + V_UNITS];
+  u32x4* const Ks = smem;
+  u32x4* const Vs = smem + K_UNITS;
+  const int b = blockIdx.z, h = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int inner = heads * 64;
+  const size_t ld = (size_t)3 * inner;
+  // ragged batch (fh_attention_bf16x6_seg_f32): clip b is rows [seg[2b], seg[2b] + seg[2b+1]) of the token-major tensors;
+  // its keys are its own rows only (the reference's key mask, attend.py:127-128, for clips packed without padding)
+  size_t row0 = (size_t)b * n;
+  if (seg) {
+    row0 = (size_t)__builtin_amdgcn_readfirstlane(seg[2 * b]);
+    n = __builtin_amdgcn_readfirstlane(seg[2 * b + 1]);
+    if ((int)blockIdx.x * (32 * WAVES / SPLIT) >= n) return;        // (block-uniform: before any barrier)
+  }
+  const float* base = qkv + row0 * ld + h * 64;
+  const int qt = wave / SPLIT, sp = wave % SPLIT;      // query tile of the block, stream of this wave (SPLIT = 2)
+  const int q0 = blockIdx.x * (32 * WAVES / SPLIT) + qt * 32;
+  const int qi = q0 + l31;
+
+  // Q pieces: element j of qp[piece][ks] = piece of Q[qi][16 ks + 8 lh + j]
+  u32x4 qp[3][4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
+    if (qi < n) {
+      const float* p = base + (size_t)qi * ld + 16 * ks + 8 * lh;
+      v0 = *reinterpret_cast<const f32x4*>(p);
+      v1 = *reinterpret_cast<const f32x4*>(p + 4);
+    }
+    const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+    bf16x6_split(v, qp[0][ks], qp[1][ks], qp[2][ks]);
+  }
+
+  constexpr int NS = 3 - SPLIT;            // streams this wave runs: 2 (SPLIT = 1) or 1 (SPLIT = 2)
+  Stream st[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { st[i].o0[r] = 0.f; st[i].o1[r] = 0.f; }
+    st[i].m = -INFINITY;
+    st[i].l = 0.f;
+  }
+
+  // one 32-key tile (tile t of the staged 64 keys) into one stream
+  auto tile = [&](Stream& S, int k0, int t) {
+    // S^T tile
+    f32x16 s;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      bf16x8 kf[3];
+#pragma unroll
+      for (int p = 0; p < 3; ++p) kf[p] = as_bf(Ks[((p * 2 + t) * 8 + 2 * ks + lh) * KPB + l31]);
+#pragma unroll
+      for (int pp = 0; pp < 6; ++pp) {
+        const Bf16x6Pair c = kBf16x6SmallFirst[pp];                  // (K piece, Q piece)
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[c.a], as_bf(qp[c.b][ks]), s, 0, 0, 0);
+      }
+    }
+    // online softmax for this lane's query, in base 2, exactly as attention.hip's; key of reg r = k0 + (r&3) + 8 (r>>2) + 4 lh
+    float mx = -INFINITY;
+    if (k0 + 32 <= n) {                              // (whole tile: no key mask -- wave-uniform)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        s[r] = __fmul_rn(s[r], scale);
+        mx = fmaxf(mx, s[r]);
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const float v = key < n ? __fmul_rn(s[r], scale) : -INFINITY;
+        s[r] = v;
+        mx = fmaxf(mx, v);
+      }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(S.m, mx);            // finite: every tile has >= 1 valid key
+    const float corr = __builtin_amdgcn_exp2f(S.m - m_new);        // exp2(-inf) = 0 on the first tile
+    float psum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float p = __builtin_amdgcn_exp2f(s[r] - m_new);
+      s[r] = p;
+      psum += p;
+    }
+    psum += __shfl_xor(psum, 32, 64);
+    S.l = __fmaf_rn(S.l, corr, psum);
+    S.m = m_new;
+    if (__builtin_amdgcn_ballot_w64(corr != 1.f) != 0ull) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { S.o0[r] *= corr; S.o1[r] *= corr; }
+    }
+    // O^T += V^T P^T: registers 8 s2 .. 8 s2 + 7 are k-step s2 of the B operand
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      const float pv[8] = {s[8 * s2], s[8 * s2 + 1], s[8 * s2 + 2], s[8 * s2 + 3], s[8 * s2 + 4], s[8 * s2 + 5], s[8 * s2 + 6], s[8 * s2 + 7]};
+      u32x4 pq[3];
+      bf16x6_split(pv, pq[0], pq[1], pq[2]);
+      bf16x8 v0[3], v1[3];
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        const u32x4* plane = Vs + ((p * 2 + t) * 4 + 2 * s2 + lh) * 64;
+        v0[p] = as_bf(plane[l31]);
+        v1[p] = as_bf(plane[32 + l31]);
+      }
+#pragma unroll
+      for (int pp = 0; pp < 6; ++pp) {
+        const Bf16x6Pair c = kBf16x6SmallFirst[pp];                  // (V piece, P piece)
+        S.o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v0[c.a], as_bf(pq[c.b]), S.o0, 0, 0, 0);
+        S.o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v1[c.a], as_bf(pq[c.b]), S.o1, 0, 0, 0);
+      }
+    }
+  };
+
+  // K / V of the next 64 keys go global -> registers one iteration ahead, registers -> split -> LDS at the top of their own
+  // iteration.  K item: key = item >> 3, d-octet = item & 7 (2 float4).  V item: d = item & 63, keys 4 (item >> 6) .. + 3 (4 floats;
+  // a wave's 64 lanes read one row's 256 bytes per load).
+  f32x4 kreg[NKI][2];
+  float vreg[NVI][4];
+  auto load_kv = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < NKI; ++i) {
+      const int item = tid + NT * i, key = item >> 3, oct = item & 7;
+      f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = a;
+      if (k0 + key < n) {
+        const float* rowp = base + (size_t)(k0 + key) * ld + inner + 8 * oct;
+        a = *reinterpret_cast<const f32x4*>(rowp);
+        c = *reinterpret_cast<const f32x4*>(rowp + 4);
+      }
+      kreg[i][0] = a;
+      kreg[i][1] = c;
+    }
+#pragma unroll
+    for (int i = 0; i < NVI; ++i) {
+      const int item = tid + NT * i, d = item & 63, key = 4 * (item >> 6);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        vreg[i][e] = k0 + key + e < n ? base[(size_t)(k0 + key + e) * ld + 2 * inner + d] : 0.f;
+    }
+  };
+  auto store_kv = [&]() {
+#pragma unroll
+    for (int i = 0; i < NKI; ++i) {
+      const int item = tid + NT * i, key = item >> 3, oct = item & 7;
+      const f32x4 &a = kreg[i][0], &c = kreg[i][1];
+      const float v[8] = {a[0], a[1], a[2], a[3], c[0], c[1], c[2], c[3]};
+      u32x4 pc[3];
+      bf16x6_split(v, pc[0], pc[1], pc[2]);
+#pragma unroll
+      for (int p = 0; p < 3; ++p) Ks[((p * 2 + (key >> 5)) * 8 + oct) * KPB + (key & 31)] = pc[p];
+    }
+#pragma unroll
+    for (int i = 0; i < NVI; i += 2) {
+      const float v[8] = {vreg[i][0], vreg[i][1], vreg[i][2], vreg[i][3], vreg[i + 1][0], vreg[i + 1][1], vreg[i + 1][2], vreg[i + 1][3]};
+      u32x4 pc[3];
+      bf16x6_split(v, pc[0], pc[1], pc[2]);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        // key-quad kq of the 64 keys -> tile kq >> 3, k-step (kq >> 2) & 1, 8-byte half (kq >> 1) & 1, lane half kq & 1
+        const int item = tid + NT * (i + j), d = item & 63, kq = item >> 6;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+          u32x2* unit = reinterpret_cast<u32x2*>(Vs + ((p * 2 + (kq >> 3)) * 4 + 2 * ((kq >> 2) & 1) + (kq & 1)) * 64 + d);
+          unit[(kq >> 1) & 1] = (u32x2){pc[p][2 * j], pc[p][2 * j + 1]};
+        }
+      }
+    }
+  };
+  load_kv(0);
+  for (int kb = 0; kb < n; kb += 64) {
+    __syncthreads();
+    store_kv();
+    __syncthreads();
+    if (kb + 64 < n) load_kv(kb + 64);
+    if constexpr (SPLIT == 2) {
+      const int k0 = kb + 32 * sp;               // this wave's key tile of the iteration
+      if (k0 < n) tile(st[0], k0, sp);           // (wave-uniform; the barriers are outside)
+    } else {
+      tile(st[0], kb, 0);
+      if (kb + 32 < n) tile(st[1], kb + 32, 1);
+    }
+  }
+
+  if constexpr (SPLIT == 2) {      // stream 1 -> the sp == 0 wave (through the K / V tiles' LDS)
+    __syncthreads();
+    float* X = reinterpret_cast<float*>(smem) + qt * (34 * 64);              // per query tile: 32 O values + m + l per lane
+    static_assert((WAVES / SPLIT) * 34 * 64 <= 4 * (K_UNITS + V_UNITS), "exchange area");
+    if (sp == 1) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { X[r * 64 + lane] = st[0].o0[r]; X[(16 + r) * 64 + lane] = st[0].o1[r]; }
+      X[32 * 64 + lane] = st[0].m;
+      X[33 * 64 + lane] = st[0].l;
+    }
+    __syncthreads();
+    if (sp != 0) return;
+    float b0[16], b1[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { b0[r] = X[r * 64 + lane]; b1[r] = X[(16 + r) * 64 + lane]; }
+    merge_streams(st[0], b0, b1, X[32 * 64 + lane], X[33 * 64 + lane]);
+  } else {
+    float b0[16], b1[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { b0[r] = st[NS - 1].o0[r]; b1[r] = st[NS - 1].o1[r]; }
+    merge_streams(st[0], b0, b1, st[NS - 1].m, st[NS - 1].l);
+  }
+  if (qi < n) {
+    const float inv = 1.f / st[0].l;
+    float* orow = out + (row0 + qi) * inner + h * 64;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      // regs 4g..4g+3 -> d = 8 g + 4 lh + (0..3)
+      f32x4 a = {st[0].o0[4 * g] * inv, st[0].o0[4 * g + 1] * inv, st[0].o0[4 * g + 2] * inv, st[0].o0[4 * g + 3] * inv};
+      f32x4 c = {st[0].o1[4 * g] * inv, st[0].o1[4 * g + 1] * inv, st[0].o1[4 * g + 2] * inv, st[0].o1[4 * g + 3] * inv};
+      *reinterpret_cast<f32x4*>(orow + 8 * g + 4 * lh) = a;
+      *reinterpret_cast<f32x4*>(orow + 32 + 8 * g + 4 * lh) = c;
+    }
+  }
+}
+
+int launch_attention_bf(const float* qkv, float* out, const int* seg, int batch, int n, int heads, float scale, void* stream) {
+  scale *= 1.44269504088896340736f;        // the kernel's softmax runs in base 2: exp(x) = exp2(x log2(e))
+  if ((long long)fh_cdiv(n, 128) * heads * batch >= 512) {         // (attention.hip's rule)
+    dim3 grid(fh_cdiv(n, 128), heads, batch);
+    hipLaunchKernelGGL((attention_bf_kernel<4, 1>), grid, dim3(256), 0, (hipStream_t)stream, qkv, out, n, heads, scale, seg);
+  } else {
+    dim3 grid(fh_cdiv(n, 64), heads, batch);
+    hipLaunchKernelGGL((attention_bf_kernel<4, 2>), grid, dim3(256), 0, (hipStream_t)stream, qkv, out, n, heads, scale, seg);
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int fh_attention_bf16x6_f32(const float* qkv, float* out, int batch, int n, int heads, float scale, void* stream) {
+  FH_CHECK_ARG(qkv && out && batch > 0 && n > 0 && heads > 0, "fh_attention_bf16x6_f32: bad args");
+  FH_CHECK_ARG((((uintptr_t)qkv | (uintptr_t)out) & 15) == 0, "fh_attention_bf16x6_f32: qkv / out must be 16-byte aligned");
+  launch_attention_bf(qkv, out, nullptr, batch, n, heads, scale, stream);
+  FH_CHECK_LAUNCH("fh_attention_bf16x6_f32");
+  return FH_OK;
+}
+
+extern "C" int fh_attention_bf16x6_seg_f32(const float* qkv, float* out, const int* seg, int n_seg, int max_n, int heads,
+                                           float scale, void* stream) {
+  FH_CHECK_ARG(qkv && out && seg && n_seg > 0 && max_n > 0 && heads > 0, "fh_attention_bf16x6_seg_f32: bad args");
+  FH_CHECK_ARG((((uintptr_t)qkv | (uintptr_t)out) & 15) == 0, "fh_attention_bf16x6_seg_f32: qkv / out must be 16-byte aligned");
+  launch_attention_bf(qkv, out, seg, n_seg, max_n, heads, scale, stream);
+  FH_CHECK_LAUNCH("fh_attention_bf16x6_seg_f32");
+  return FH_OK;
+}

@@ -52,7 +52,7 @@ def pack_geglu(w, b):
 
 
 class FlowNet:
-    def __init__(self, sd, device, depth=2, heads=16, dim_head=64, store=None, bf=False):
+    def __init__(self, sd, device, depth=2, heads=16, dim_head=64, store=None, bf=False, attn_form="f32"):
         if dim_head != 64:
             raise NotImplementedError("dim_head must be 64")
         self.device = hip.norm_device(device)
@@ -65,6 +65,12 @@ class FlowNet:
         # bf: the linears run in the bf16 x 6 form (gemm_bf.hip: six bf16 MFMAs per product over exact three-piece splits,
         # fp32-grade; the model's conv_form = 'bf16x6'): their weights are stored split (6 bytes per weight)
         self.bf = bool(bf)
+        # attn_form: 'f32' (attention.hip) | 'bf16x6' (attention_bf.hip: the two products of attention in the same six-MFMA form,
+        # the softmax unchanged).  The entry pair is picked here, once; a missing entry is an error at the first forward.
+        from .planner import resolve_attn_form
+        self.attn_form = resolve_attn_form(attn_form)
+        self._attn, self._attn_seg = (("fh_attention_bf16x6_f32", "fh_attention_bf16x6_seg_f32") if self.attn_form == "bf16x6"
+                                      else ("fh_attention_f32", "fh_attention_seg_f32"))
         if getattr(W, "form", None) is not None and (W.form == "bf16x6") != self.bf:
             # (a blob holds the linears in ONE form: asking it for the other would fail on the first missing key)
             raise ValueError(f"the weight blob was packed for conv_form={W.form!r}: its linears are "
@@ -227,14 +233,13 @@ class FlowNet:
                 hip.check(L.fh_qknorm_rope_f32(qkv.data_ptr(), lay["gq"].data_ptr(), lay["gk"].data_ptr(),
                                                ws["cos"].data_ptr(), ws["sin"].data_ptr(), batch, n, self.heads, st),
                           "fh_qknorm_rope_f32")
-                hip.check(L.fh_attention_f32(qkv.data_ptr(), att.data_ptr(), batch, n, self.heads, 10.0, st),
-                          "fh_attention_f32")
+                hip.check(getattr(L, self._attn)(qkv.data_ptr(), att.data_ptr(), batch, n, self.heads, 10.0, st), self._attn)
             else:
                 hip.check(L.fh_qknorm_rope_seg_f32(qkv.data_ptr(), lay["gq"].data_ptr(), lay["gk"].data_ptr(),
                                                    ws["cos"].data_ptr(), ws["sin"].data_ptr(), seg, n_seg, max_n,
                                                    self.heads, st), "fh_qknorm_rope_seg_f32")
-                hip.check(L.fh_attention_seg_f32(qkv.data_ptr(), att.data_ptr(), seg, n_seg, max_n, self.heads, 10.0, st),
-                          "fh_attention_seg_f32")
+                hip.check(getattr(L, self._attn_seg)(qkv.data_ptr(), att.data_ptr(), seg, n_seg, max_n, self.heads, 10.0, st),
+                          self._attn_seg)
             self.gemm(att, lay["w_out"], other, M, D, D, R=cur)
             cur, other = other, cur
             hip.check(L.fh_rmsnorm_f32(cur.data_ptr(), g2.data_ptr(), b2.data_ptr(), a.data_ptr(), M, D, st),

@@ -20,7 +20,7 @@ CONV_MAX_TAPS = 16
 CONV_MAX_SEG = 3
 CONV_MAX_HALO = 64
 
-ABI_VERSION = 5            # FH_ABI_VERSION of include/flowhigh_hip.h
+ABI_VERSION = 6            # FH_ABI_VERSION of include/flowhigh_hip.h
 EPI_LINEAR, EPI_GEGLU, EPI_MAG, EPI_LOGCLAMP = 0, 1, 2, 3
 
 
@@ -112,6 +112,7 @@ _SIGS = {
     "fh_sizeof_sum_job": [],
     "fh_sum_multi_f32": [_P, _I, C.c_longlong, _P],
     "fh_attention_seg_f32": [_P, _P, _P, _I, _I, _I, _F, _P],
+    "fh_attention_bf16x6_seg_f32": [_P, _P, _P, _I, _I, _I, _F, _P],
     "fh_dwconv_gelu_res_seg_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "fh_qknorm_rope_seg_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "fh_gemm_f32": [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _F, _I, _P],
@@ -122,6 +123,7 @@ _SIGS = {
     "fh_rmsnorm_f32": [_P, _P, _P, _P, _I, _I, _P],
     "fh_qknorm_rope_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "fh_attention_f32": [_P, _P, _I, _I, _I, _F, _P],
+    "fh_attention_bf16x6_f32": [_P, _P, _I, _I, _I, _F, _P],
     "fh_rfft2048_f32": [_P, _P, _P, _I, _I, _P],
     "fh_irfft2048_f32": [_P, _P, _P, _I, _P],
     "fh_frame_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

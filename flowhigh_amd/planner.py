@@ -68,6 +68,23 @@ def resolve_conv_form(conv_form=None, bf16x6=None):
     return (DEFAULT_CONV_FORM, True) if form == "auto" else (form, False)
 
 
+# ---- which arithmetic form the transformer's attention runs in: a constructor keyword, independent of conv_form (it touches no
+# weight, so it is no part of a weight blob's format tag) --------------------------------------------------------------------
+#   'f32'     both products on the fp32 matrix instructions (attention.hip): the default
+#   'bf16x6'  both products as six bf16 MFMAs over exact three-piece splits, the softmax unchanged (attention_bf.hip)
+ATTN_FORMS = ("f32", "bf16x6")
+DEFAULT_ATTN_FORM = "f32"
+
+
+def resolve_attn_form(attn_form=None):
+    """-> 'f32' or 'bf16x6'.  None = the default ('f32'); a keyword only, no environment switch."""
+    if attn_form is None:
+        return DEFAULT_ATTN_FORM
+    if attn_form not in ATTN_FORMS:
+        raise ValueError(f"attn_form must be one of {ATTN_FORMS} ('f32' or 'bf16x6'), got {attn_form!r}")
+    return attn_form
+
+
 def _wino_on(form):
     """Winograd kernels allowed?  form None: the environment (FH_WINO=0 / FH_CONV_FORM=direct switch them off)."""
     return (resolve_conv_form()[0] if form is None else form) != "direct"

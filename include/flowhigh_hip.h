@@ -27,7 +27,7 @@ extern "C" {
 #define FH_E_ARG (-1)     /* bad argument / unsupported shape */
 #define FH_E_LAUNCH (-2)  /* HIP launch error */
 
-#define FH_ABI_VERSION 5
+#define FH_ABI_VERSION 6
 
 int fh_abi_version(void);
 const char* fh_last_error(void);
@@ -430,6 +430,10 @@ int fh_qknorm_rope_f32(float* qkv, const float* gq, const float* gk, const float
  * qkv as above (q | k | v along the feature axis), out [B*n, heads*64].  dim_head 64. */
 int fh_attention_f32(const float* qkv, float* out, int batch, int n, int heads, float scale,
                      void* stream);
+/* The same (attend.py:102-139) with both products in the bf16 x 6 form: six bf16 MFMAs per product over exact three-piece
+ * splits, fp32 in / out / accumulate; the softmax is fh_attention_f32's, instruction for instruction (attn_form = 'bf16x6').
+ * qkv and out must be 16-byte aligned. */
+int fh_attention_bf16x6_f32(const float* qkv, float* out, int batch, int n, int heads, float scale, void* stream);
 
 /* Ragged batches: clips of DIFFERENT lengths packed back to back in the token-major tensors, no padding rows.
  * seg: device int32 [n_seg][2] = (first row, rows) of every clip; max_n = the longest clip.  These are the
@@ -439,6 +443,9 @@ int fh_attention_f32(const float* qkv, float* out, int batch, int n, int heads, 
  * cos_t / sin_t must cover max_n positions. */
 int fh_attention_seg_f32(const float* qkv, float* out, const int* seg, int n_seg, int max_n, int heads,
                          float scale, void* stream);
+/* fh_attention_seg_f32 in the bf16 x 6 form (the key mask of attend.py:127-128). */
+int fh_attention_bf16x6_seg_f32(const float* qkv, float* out, const int* seg, int n_seg, int max_n, int heads,
+                                float scale, void* stream);
 int fh_dwconv_gelu_res_seg_f32(const float* x, const float* w, const float* bias, float* y, const int* seg,
                                int n_seg, int max_n, int dim, int ksz, void* stream);
 int fh_qknorm_rope_seg_f32(float* qkv, const float* gq, const float* gk, const float* cos_t,

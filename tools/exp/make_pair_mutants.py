@@ -1,10 +1,13 @@
-"""Mutants of the four bf16 x 6 kernels (results wrong on purpose): does the suite notice a lost piece pair or a wrong device split?
+"""Mutants of the five bf16 x 6 kernels (results wrong on purpose): does the suite notice a lost piece pair or a wrong device split?
     python tools/exp/make_pair_mutants.py [name ...]     ->  tools/abl/pairs/<name>.so  (sources: tools/exp/abl_pairs/<name>/)
     python tools/exp/run_pair_mutants.py                 ->  profiles/r07_bf16x6_pair_mutants.txt
 Per kernel (gemm = gemm_bf.hip, narrow = narrow_bf.hip, w43 = conv_wino.hip's BF path, w54 = conv_wino54_kernel.h <BF>):
   <kernel>_pair_<ab>   the MFMA of pair (activation piece a, weight piece b) gets a zero activation operand (hh hm mh hl lh mm)
   <kernel>_split_l0    the device split writes l = 0
   <kernel>_split_trunc the device split truncates to bf16 instead of rounding to nearest even
+The attention kernel (attention_bf.hip) has two products, twelve pair MFMAs: attn_qk_pair_<ab> ((K piece, Q piece), the K operand
+zeroed), attn_pv_pair_<ab> ((V piece, P piece), the P operand zeroed, both output halves), and one split for all four operands:
+attn_qk_split_l0 / attn_qk_split_trunc.
 The split mutants edit a copy of the shared bf16x6.h next to the kernel's source: only that kernel is built against it.
 An operand is zeroed, no instruction deleted: addressing and register allocation stay the product's.  Built with build.py's flags
 for the file (-fno-slp-vectorize where the product has it) against the product's other objects (flowhigh_amd/build/, run
@@ -87,10 +90,33 @@ def w54(kind, arg):
     return {**files, "conv_wino54_kernel.h": t}
 
 
+def attn_qk(kind, arg):
+    t = (CSRC / "attention_bf.hip").read_text()
+    if kind == "split":
+        return {"attention_bf.hip": t, **split(arg)}
+    pp = ["lh", "hl", "mm", "mh", "hm", "hh"].index(arg)          # kBf16x6SmallFirst as (K piece, Q piece)
+    # (a zero the compiler cannot see, as in w43: with a constant zero the SPLIT = 1 kernel of some pairs spills 5 registers)
+    return {"attention_bf.hip": one(t, "        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[c.a],",
+                                    f"        unsigned z = 0u;\n        if (pp == {pp}) asm volatile(\"\" : \"+v\"(z));\n"
+                                    f"        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pp == {pp} ? as_bf((u32x4){{z, z, z, z}}) : kf[c.a],")}
+
+
+def attn_pv(kind, arg):
+    t = (CSRC / "attention_bf.hip").read_text()
+    pp = ["lh", "hl", "mm", "mh", "hm", "hh"].index(arg)          # kBf16x6SmallFirst as (V piece, P piece)
+    t = one(t, "        S.o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v0[c.a],",
+            f"        unsigned z = 0u;\n        if (pp == {pp}) asm volatile(\"\" : \"+v\"(z));\n"
+            "        S.o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v0[c.a],")
+    for v in ("v0", "v1"):
+        t = one(t, f"__builtin_amdgcn_mfma_f32_32x32x16_bf16({v}[c.a], as_bf(pq[c.b]),",
+                f"__builtin_amdgcn_mfma_f32_32x32x16_bf16({v}[c.a], pp == {pp} ? as_bf((u32x4){{z, z, z, z}}) : as_bf(pq[c.b]),")
+    return {"attention_bf.hip": t}
+
+
 KERNELS = {"gemm": (gemm, "gemm_bf.hip"), "narrow": (narrow, "narrow_bf.hip"), "w43": (w43, "conv_wino.hip"),
-           "w54": (w54, "conv_wino54_bf.hip")}
+           "w54": (w54, "conv_wino54_bf.hip"), "attn_qk": (attn_qk, "attention_bf.hip"), "attn_pv": (attn_pv, "attention_bf.hip")}
 MUTANTS = [(f"{k}_pair_{p}", k, "pair", p) for k in KERNELS for p in PAIRS] + \
-          [(f"{k}_split_{s}", k, "split", s) for k in KERNELS for s in ("l0", "trunc")]
+          [(f"{k}_split_{s}", k, "split", s) for k in KERNELS if k != "attn_pv" for s in ("l0", "trunc")]
 
 
 def build(name, kernel, kind, arg):

@@ -2,7 +2,10 @@
 own time limit, and write the table mutant x {tests/test_hip_bf16x6_pairs.py, the kernel's earlier bf16 x 6 tests}: killed or
 survived.  A mutant counts as killed only by assertion failures (a mismatch); anything else -- a crash, a time-out, a HIP or
 Python error, a fuzz subprocess that did not end normally -- stops the run there (the table then says so).
-    python tools/exp/run_pair_mutants.py [--out FILE] [kernel ...]      (kernel: gemm narrow w43 w54; default all)
+    python tools/exp/run_pair_mutants.py [--out FILE] [kernel ...]      (kernel: gemm narrow w43 w54 attn_qk attn_pv; default: the first four)
+The attention kernel's mutants (attn_qk, attn_pv) run against tests/test_hip_attention_bf.py: new = its pair pins (-k pairs),
+existing = its random-input accuracy tests (RMS error to float64 against the fp32 kernel's); their table is
+profiles/attention_bf16x6.md's, so give them an --out of their own.
 The table (default profiles/r07_bf16x6_pair_mutants.txt) is written anew on every run; the report of a test set that stopped the
 run goes beside it, <mutant>.stop.log."""
 import os
@@ -16,13 +19,18 @@ ROOT = Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT / "tools" / "exp"))
 from make_pair_mutants import LIB_DIR, MUTANTS      # noqa: E402
 
-NEW = {"gemm": "gemm_bf16x6", "narrow": "narrow_bf16x6", "w43": "wino43_bf16x6", "w54": "wino54_bf16x6"}
+PAIR_FILE = "tests/test_hip_bf16x6_pairs.py"
+ATTN_FILE = "tests/test_hip_attention_bf.py"
+NEW = {"gemm": [PAIR_FILE, "-k", "gemm_bf16x6"], "narrow": [PAIR_FILE, "-k", "narrow_bf16x6"], "w43": [PAIR_FILE, "-k", "wino43_bf16x6"],
+       "w54": [PAIR_FILE, "-k", "wino54_bf16x6"], "attn_qk": [ATTN_FILE, "-k", "pairs"], "attn_pv": [ATTN_FILE, "-k", "pairs"]}
+DEFAULT_KERNELS = ["gemm", "narrow", "w43", "w54"]
 OLD = {"gemm": ["tests/test_hip_ops.py::test_gemm_linear", "tests/test_hip_ops.py::test_gemm_geglu_packed", "-k", "bf16x6"],
        "narrow": ["tests/test_hip_amp.py::test_amp_conv_only", "tests/test_hip_amp.py::test_narrow_kernels_randomised_configurations",
                   "-k", "direct"],
        "w43": ["tests/test_hip_ops.py::test_conv_wino_bf16x6_fuzz"],
        "w54": ["tests/test_hip_ops.py::test_conv_wino54_bf16x6_fuzz",
-               "tests/test_hip_ops.py::test_conv_wino54_bf16x6_tile_heights_give_the_same_bits_and_the_fp32_forms_values"]}
+               "tests/test_hip_ops.py::test_conv_wino54_bf16x6_tile_heights_give_the_same_bits_and_the_fp32_forms_values"],
+       "attn_qk": [ATTN_FILE, "-k", "rms_error"], "attn_pv": [ATTN_FILE, "-k", "rms_error"]}
 LIMIT = {"new": 240, "old": 900}
 # a failure whose report says any of these is not a mismatch: the GPU or the process went wrong (the fuzz tests run a subprocess
 # and quote its stderr: a Python exception there shows its traceback, a signal a negative returncode; narrow_fuzz.py's own
@@ -76,7 +84,7 @@ def main():
         i = args.index("--out")
         out = Path(args[i + 1])
         del args[i:i + 2]
-    kernels = args or list(NEW)
+    kernels = args or DEFAULT_KERNELS
     rows, stop = [], False
     for name, kernel, _, _ in MUTANTS:
         if kernel not in kernels or stop:
@@ -86,7 +94,7 @@ def main():
             rows.append((name, ("not built", "make_pair_mutants.py did not build it", 0.0), ("not built", "", 0.0)))
             continue
         log = out.parent / f"{name}.stop.log"
-        r_new = pytest(lib, ["tests/test_hip_bf16x6_pairs.py", "-x", "-k", NEW[kernel]], LIMIT["new"], log)
+        r_new = pytest(lib, ["-x", *NEW[kernel]], LIMIT["new"], log)
         stop = r_new[0].startswith("STOP")
         r_old = ("not run", "", 0.0) if stop else pytest(lib, OLD[kernel], LIMIT["old"], log)
         stop = stop or r_old[0].startswith("STOP")
@@ -96,10 +104,9 @@ def main():
             print(f"  stopped: {(r_new if r_new[0].startswith('STOP') else r_old)[1]}", flush=True)
     with open(out, "w") as f:
         f.write("# bf16 x 6 pair / split mutants (tools/exp/make_pair_mutants.py), one pytest process per mutant and test set\n"
-                "# (tools/exp/run_pair_mutants.py).  new = tests/test_hip_bf16x6_pairs.py -k <kernel>; existing = the kernel's earlier\n"
-                "# bf16 x 6 tests:\n")
+                "# (tools/exp/run_pair_mutants.py).  new = the kernel's pair pins; existing = its other bf16 x 6 tests:\n")
         for k in kernels:
-            f.write(f"#   {k}: {' '.join(OLD[k])}\n")
+            f.write(f"#   {k}: new = {' '.join(NEW[k])}; existing = {' '.join(OLD[k])}\n")
         f.write("# killed = a test failed on an assertion (the new module: an exact torch.equal mismatch, its first failure below);\n"
                 "# survived = every test passed.\n")
         f.write(f"{'mutant':20s} {'new':10s} {'existing':10s} first failure of the new module\n")
