@@ -23,7 +23,7 @@ EXTRA_FLAGS = {"conv_wino54_bf.hip": ["-fno-slp-vectorize"], "conv_wino.hip": ["
 # fixed at the source, conv_wino.hip: prefetch_a; the limit here is about speed.)
 RESOURCE_FLAGS = ["-Rpass-analysis=kernel-resource-usage"]
 MAX_SCRATCH_BYTES = 16          # per lane: up to 4 spilled registers (prologue / epilogue values) are tolerated and reported
-HEADERS = ["fh_common.h", "bf16x6.h", "conv_wino54_kernel.h", "attention_softmax.h"]
+HEADERS = ["fh_common.h", "bf16x6.h", "conv_wino54_kernel.h", "attention_softmax.h", "gemm_common.h"]
 
 
 def _deps():

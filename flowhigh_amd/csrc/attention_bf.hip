@@ -5,9 +5,10 @@
 // fp32 in / out / accumulate; S^T = K Q^T and O^T = V^T P^T are six v_mfma_f32_32x32x16_bf16 per k-step over exact three-piece
 // splits (bf16x6.h), pair order kBf16x6SmallFirst with the pair read as (K piece, Q piece) and (V piece, P piece).
 //
-// Everything beside the two products is attention.hip's: 32-key tiles, two interleaved online-softmax streams per query row
-// merged by merge_streams (attention_softmax.h), base-2 exponent, the masking of the last tile, the SPLIT = 1 / 2 kernel shapes
-// and the rule that picks one.  Where both products are exact in both forms the two kernels give the same bits.
+// Everything beside the two products is the frame attention.hip has too, attention_softmax.h: block placement, 32-key tiles, two
+// interleaved online-softmax streams per query row and their merge, base-2 exponent, the masking of the last tile, the output,
+// the SPLIT = 1 / 2 kernel shapes and the rule that picks one.  Where both products are exact in both forms the two kernels give
+// the same bits.
 //
 // Every operand is split once:
 //   K   by the block that stages the tile, on the way into LDS: 16-byte units of 8 consecutive d, [piece][tile][d-octet][key];
@@ -38,7 +39,7 @@ __device__ __forceinline__ bf16x8 as_bf(const u32x4& v) { return __builtin_bit_c
 
 template <int WAVES, int SPLIT>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2))) void attention_bf_kernel(const float* __restrict__ qkv,
-                                                               float* __restrict__ out, int n, int heads,
+                                                               float* __restrict__ out, int n_max, int heads,
                                                                float scale, const int* __restrict__ seg) {
   constexpr int NT = 64 * WAVES;           // threads
   constexpr int NKI = 512 / NT;            // (key, d-octet) items of K staged per thread and iteration (64 keys)
@@ -47,31 +48,18 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2
   __shared__ __attribute__((aligned(16))) u32x4 smem[K_UNITS + V_UNITS];
   u32x4* const Ks = smem;
   u32x4* const Vs = smem + K_UNITS;
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int inner = heads * 64;
-  const size_t ld = (size_t)3 * inner;
-  // ragged batch (fh_attention_bf16x6_seg_f32): clip b is rows [seg[2b], seg[2b] + seg[2b+1]) of the token-major tensors;
-  // its keys are its own rows only (the reference's key mask, attend.py:127-128, for clips packed without padding)
-  size_t row0 = (size_t)b * n;
-  if (seg) {
-    row0 = (size_t)__builtin_amdgcn_readfirstlane(seg[2 * b]);
-    n = __builtin_amdgcn_readfirstlane(seg[2 * b + 1]);
-    if ((int)blockIdx.x * (32 * WAVES / SPLIT) >= n) return;        // (block-uniform: before any barrier)
-  }
-  const float* base = qkv + row0 * ld + h * 64;
-  const int qt = wave / SPLIT, sp = wave % SPLIT;      // query tile of the block, stream of this wave (SPLIT = 2)
-  const int q0 = blockIdx.x * (32 * WAVES / SPLIT) + qt * 32;
-  const int qi = q0 + l31;
+  const AttnBlock blk = attn_prologue<WAVES, SPLIT>(qkv, n_max, heads, seg);
+  if (!blk.live) return;
+  const int tid = blk.tid, l31 = blk.l31, lh = blk.lh, sp = blk.sp;
+  const int n = blk.n;                     // this clip's keys (n_max: the longest clip's)
 
   // Q pieces: element j of qp[piece][ks] = piece of Q[qi][16 ks + 8 lh + j]
   u32x4 qp[3][4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) {
     f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
-    if (qi < n) {
-      const float* p = base + (size_t)qi * ld + 16 * ks + 8 * lh;
+    if (blk.qi < n) {
+      const float* p = blk.base + (size_t)blk.qi * blk.ld + 16 * ks + 8 * lh;
       v0 = *reinterpret_cast<const f32x4*>(p);
       v1 = *reinterpret_cast<const f32x4*>(p + 4);
     }
@@ -81,13 +69,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2
 
   constexpr int NS = 3 - SPLIT;            // streams this wave runs: 2 (SPLIT = 1) or 1 (SPLIT = 2)
   Stream st[NS];
-#pragma unroll
-  for (int i = 0; i < NS; ++i) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { st[i].o0[r] = 0.f; st[i].o1[r] = 0.f; }
-    st[i].m = -INFINITY;
-    st[i].l = 0.f;
-  }
+  init_streams(st);
 
   // one 32-key tile (tile t of the staged 64 keys) into one stream
   auto tile = [&](Stream& S, int k0, int t) {
@@ -106,40 +88,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[c.a], as_bf(qp[c.b][ks]), s, 0, 0, 0);
       }
     }
-    // online softmax for this lane's query, in base 2, exactly as attention.hip's; key of reg r = k0 + (r&3) + 8 (r>>2) + 4 lh
-    float mx = -INFINITY;
-    if (k0 + 32 <= n) {                              // (whole tile: no key mask -- wave-uniform)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        s[r] = __fmul_rn(s[r], scale);
-        mx = fmaxf(mx, s[r]);
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const float v = key < n ? __fmul_rn(s[r], scale) : -INFINITY;
-        s[r] = v;
-        mx = fmaxf(mx, v);
-      }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(S.m, mx);            // finite: every tile has >= 1 valid key
-    const float corr = __builtin_amdgcn_exp2f(S.m - m_new);        // exp2(-inf) = 0 on the first tile
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float p = __builtin_amdgcn_exp2f(s[r] - m_new);
-      s[r] = p;
-      psum += p;
-    }
-    psum += __shfl_xor(psum, 32, 64);
-    S.l = __fmaf_rn(S.l, corr, psum);
-    S.m = m_new;
-    if (__builtin_amdgcn_ballot_w64(corr != 1.f) != 0ull) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { S.o0[r] *= corr; S.o1[r] *= corr; }
-    }
+    softmax_step(S, s, k0, n, lh, scale);
     // O^T += V^T P^T: registers 8 s2 .. 8 s2 + 7 are k-step s2 of the B operand
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
@@ -173,7 +122,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2
       const int item = tid + NT * i, key = item >> 3, oct = item & 7;
       f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = a;
       if (k0 + key < n) {
-        const float* rowp = base + (size_t)(k0 + key) * ld + inner + 8 * oct;
+        const float* rowp = blk.base + (size_t)(k0 + key) * blk.ld + blk.inner + 8 * oct;
         a = *reinterpret_cast<const f32x4*>(rowp);
         c = *reinterpret_cast<const f32x4*>(rowp + 4);
       }
@@ -185,7 +134,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2
       const int item = tid + NT * i, d = item & 63, key = 4 * (item >> 6);
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        vreg[i][e] = k0 + key + e < n ? base[(size_t)(k0 + key + e) * ld + 2 * inner + d] : 0.f;
+        vreg[i][e] = k0 + key + e < n ? blk.base[(size_t)(k0 + key + e) * blk.ld + 2 * blk.inner + d] : 0.f;
     }
   };
   auto store_kv = [&]() {
@@ -231,52 +180,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2
     }
   }
 
-  if constexpr (SPLIT == 2) {      // stream 1 -> the sp == 0 wave (through the K / V tiles' LDS)
-    __syncthreads();
-    float* X = reinterpret_cast<float*>(smem) + qt * (34 * 64);              // per query tile: 32 O values + m + l per lane
-    static_assert((WAVES / SPLIT) * 34 * 64 <= 4 * (K_UNITS + V_UNITS), "exchange area");
-    if (sp == 1) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { X[r * 64 + lane] = st[0].o0[r]; X[(16 + r) * 64 + lane] = st[0].o1[r]; }
-      X[32 * 64 + lane] = st[0].m;
-      X[33 * 64 + lane] = st[0].l;
-    }
-    __syncthreads();
-    if (sp != 0) return;
-    float b0[16], b1[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { b0[r] = X[r * 64 + lane]; b1[r] = X[(16 + r) * 64 + lane]; }
-    merge_streams(st[0], b0, b1, X[32 * 64 + lane], X[33 * 64 + lane]);
-  } else {
-    float b0[16], b1[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { b0[r] = st[NS - 1].o0[r]; b1[r] = st[NS - 1].o1[r]; }
-    merge_streams(st[0], b0, b1, st[NS - 1].m, st[NS - 1].l);
-  }
-  if (qi < n) {
-    const float inv = 1.f / st[0].l;
-    float* orow = out + (row0 + qi) * inner + h * 64;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      // regs 4g..4g+3 -> d = 8 g + 4 lh + (0..3)
-      f32x4 a = {st[0].o0[4 * g] * inv, st[0].o0[4 * g + 1] * inv, st[0].o0[4 * g + 2] * inv, st[0].o0[4 * g + 3] * inv};
-      f32x4 c = {st[0].o1[4 * g] * inv, st[0].o1[4 * g + 1] * inv, st[0].o1[4 * g + 2] * inv, st[0].o1[4 * g + 3] * inv};
-      *reinterpret_cast<f32x4*>(orow + 8 * g + 4 * lh) = a;
-      *reinterpret_cast<f32x4*>(orow + 32 + 8 * g + 4 * lh) = c;
-    }
-  }
-}
-
-int launch_attention_bf(const float* qkv, float* out, const int* seg, int batch, int n, int heads, float scale, void* stream) {
-  scale *= 1.44269504088896340736f;        // the kernel's softmax runs in base 2: exp(x) = exp2(x log2(e))
-  if ((long long)fh_cdiv(n, 128) * heads * batch >= 512) {         // (attention.hip's rule)
-    dim3 grid(fh_cdiv(n, 128), heads, batch);
-    hipLaunchKernelGGL((attention_bf_kernel<4, 1>), grid, dim3(256), 0, (hipStream_t)stream, qkv, out, n, heads, scale, seg);
-  } else {
-    dim3 grid(fh_cdiv(n, 64), heads, batch);
-    hipLaunchKernelGGL((attention_bf_kernel<4, 2>), grid, dim3(256), 0, (hipStream_t)stream, qkv, out, n, heads, scale, seg);
-  }
-  return 0;
+  static_assert(kAttnExchangeFloats<WAVES, SPLIT> <= 4 * (K_UNITS + V_UNITS), "exchange area: all of smem");
+  attn_finish<WAVES, SPLIT>(st, blk, reinterpret_cast<float*>(smem), out);
 }
 
 }  // namespace
@@ -284,7 +189,7 @@ int launch_attention_bf(const float* qkv, float* out, const int* seg, int batch,
 extern "C" int fh_attention_bf16x6_f32(const float* qkv, float* out, int batch, int n, int heads, float scale, void* stream) {
   FH_CHECK_ARG(qkv && out && batch > 0 && n > 0 && heads > 0, "fh_attention_bf16x6_f32: bad args");
   FH_CHECK_ARG((((uintptr_t)qkv | (uintptr_t)out) & 15) == 0, "fh_attention_bf16x6_f32: qkv / out must be 16-byte aligned");
-  launch_attention_bf(qkv, out, nullptr, batch, n, heads, scale, stream);
+  launch_attention(attention_bf_kernel<4, 1>, attention_bf_kernel<4, 2>, qkv, out, nullptr, batch, n, heads, scale, stream);
   FH_CHECK_LAUNCH("fh_attention_bf16x6_f32");
   return FH_OK;
 }
@@ -293,7 +198,7 @@ extern "C" int fh_attention_bf16x6_seg_f32(const float* qkv, float* out, const i
                                            float scale, void* stream) {
   FH_CHECK_ARG(qkv && out && seg && n_seg > 0 && max_n > 0 && heads > 0, "fh_attention_bf16x6_seg_f32: bad args");
   FH_CHECK_ARG((((uintptr_t)qkv | (uintptr_t)out) & 15) == 0, "fh_attention_bf16x6_seg_f32: qkv / out must be 16-byte aligned");
-  launch_attention_bf(qkv, out, seg, n_seg, max_n, heads, scale, stream);
+  launch_attention(attention_bf_kernel<4, 1>, attention_bf_kernel<4, 2>, qkv, out, seg, n_seg, max_n, heads, scale, stream);
   FH_CHECK_LAUNCH("fh_attention_bf16x6_seg_f32");
   return FH_OK;
 }

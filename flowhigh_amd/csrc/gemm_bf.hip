@@ -3,7 +3,8 @@
 // conv_form = 'bf16x6' model.
 //
 // Replaces the same nn.Linear call sites as gemm_mfma.hip (/root/reference/src/flowhigh/models/flow.py:239,261; attend.py:170-171,
-// 176,189; transformer.py:98-104) -- same epilogues (bias, alpha, residual; GEGLU pairs), same tile variants and block order.
+// 176,189; transformer.py:98-104) and shares its frame, gemm_common.h: the epilogues (bias, alpha, residual; GEGLU pairs), the
+// tile variants, the block order, the argument checks and the launch.
 //
 // The recipe of narrow_bf.hip: an operand is split ONCE, on its way into LDS (A: by the block that stages the tile, 11 vector
 // instructions per pair of values; W: on the host, packing.pack_gemm_bf_weight), and the K loop is ds_read_b128 + MFMA with no
@@ -13,17 +14,12 @@
 // W in memory: [64-row granule][k stage][piece][k-octet][64 rows][8 bf16] (12 KB per granule and stage: a stage's W tile is a
 // straight copy of 1-2 granules).
 #include "bf16x6.h"
-#include "fh_common.h"
+#include "gemm_common.h"
 
 namespace {
 
 constexpr int GB_BK = 32;
 constexpr int GB_GRAN = 3 * 4 * 64;        // 16-byte units of one (64-row granule, k stage) of packed W
-
-__device__ __forceinline__ float gb_epi_pair(float first, float second, int mode) {
-  if (mode == FH_EPI_GEGLU) return gelu_erf(second) * first;
-  return sqrtf(first * first + second * second + 1e-9f);
-}
 
 template <int MT, int NT>   // wave tile = (32 MT) x (32 NT), block tile = (64 MT) x (64 NT)
 __global__ __launch_bounds__(256) void gemm_bf_kernel(const float* __restrict__ A, int lda, const u32x4* __restrict__ Wp,
@@ -38,27 +34,14 @@ __global__ __launch_bounds__(256) void gemm_bf_kernel(const float* __restrict__ 
   __shared__ __attribute__((aligned(16))) u32x4 As[3 * 4 * AP];
   __shared__ __attribute__((aligned(16))) u32x4 Ws[3 * 4 * BN];
 
-  // XCD-aware order: the m-tiles of one n-tile (sharing the W panel) go to one XCD
-  const int bid = blockIdx.x;
-  const int per_xcd = gridDim.x >> 3;              // grid is a multiple of 8
-  const int work = (bid & 7) * per_xcd + (bid >> 3);
-  const int nt_idx = work / m_tiles;
-  const int mt_idx = work % m_tiles;
-  const int m0 = mt_idx * BM, n0 = nt_idx * BN;
+  const GemmBlock g = gemm_block<MT, NT>(m_tiles);
+  const int m0 = g.m0, n0 = g.n0;
   if (n0 >= N) return;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l31 = lane & 31, lh = lane >> 5;
+  const int tid = g.tid, wm = g.wm, wn = g.wn, l31 = g.l31, lh = g.lh;
   const int kstages = K / GB_BK;
 
   f32x16 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   f32x4 areg[AIT][2];
   u32x4 wreg[WIT];
@@ -128,81 +111,13 @@ __global__ __launch_bounds__(256) void gemm_bf_kernel(const float* __restrict__ 
     }
   }
 
-  // ---- epilogue (as gemm_mfma.hip).  D reg r of lane l: row = (r&3) + 8 (r>>2) + 4 lh, col = l31 --------------------------
-  if (mode == FH_EPI_LINEAR || mode == FH_EPI_LOGCLAMP) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        const int n = n0 + (wn * NT + nt) * 32 + l31;
-        if (n >= N) continue;
-        const float bv = bias ? bias[n] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int m = m0 + (wm * MT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (m >= M) continue;
-          float v = acc[mt][nt][r] + bv;
-          if (mode == FH_EPI_LOGCLAMP) {
-            v = logf(fmaxf(v, 1e-5f));
-          } else {
-            v *= alpha;
-            if (R) v += R[(size_t)m * ldr + n];
-          }
-          C[(size_t)m * ldc + n] = v;
-        }
-      }
-  } else {
-    // pair modes: the wave's two 32-column tiles are (first, second) of one packed 64 block
-    const int blk = (n0 >> 6) + wn;                 // packed block index
-    const int n_out = blk * 32 + l31;
-    const int n_first = n0 + wn * 64 + l31;         // packed column of `first`
-    if (NT == 2 && n_first < N) {
-      const float b1 = bias ? bias[n_first] : 0.f;
-      const float b2 = bias ? bias[n_first + 32] : 0.f;
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int m = m0 + (wm * MT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (m >= M) continue;
-          C[(size_t)m * ldc + n_out] = gb_epi_pair(acc[mt][0][r] + b1, acc[mt][NT - 1][r] + b2, mode);
-        }
-    }
-  }
+  gemm_epilogue(acc, g, bias, R, ldr, C, ldc, M, N, alpha, mode);
 }
 
 }  // namespace
 
 extern "C" int fh_gemm_bf16x6_f32(const float* A, int lda, const float* Wp, const float* bias, const float* R, int ldr, float* C,
                                   int ldc, int M, int N, int K, float alpha, int epilogue, void* stream) {
-  FH_CHECK_ARG(A && Wp && C && M > 0 && N > 0 && K > 0, "fh_gemm_bf16x6_f32: bad args");
-  FH_CHECK_ARG(K % GB_BK == 0, "fh_gemm_bf16x6_f32: K=%d must be a multiple of %d", K, GB_BK);
-  FH_CHECK_ARG(lda % 4 == 0 && (((uintptr_t)A) & 15) == 0 && (((uintptr_t)Wp) & 15) == 0,
-               "fh_gemm_bf16x6_f32: A/W must be 16-byte aligned with lda %% 4 == 0");
-  FH_CHECK_ARG(epilogue >= 0 && epilogue <= 3, "fh_gemm_bf16x6_f32: unknown epilogue %d", epilogue);
-  if (epilogue == FH_EPI_GEGLU || epilogue == FH_EPI_MAG)
-    FH_CHECK_ARG(N % 64 == 0, "fh_gemm_bf16x6_f32: pair epilogue needs N %% 64 == 0");
-  hipStream_t st = (hipStream_t)stream;
-  const u32x4* W4 = reinterpret_cast<const u32x4*>(Wp);
-  const bool plain = epilogue == FH_EPI_LINEAR || epilogue == FH_EPI_LOGCLAMP;
-  const long long t128 = (long long)fh_cdiv(M, 128) * fh_cdiv(N, 128);
-  const long long t64x128 = (long long)fh_cdiv(M, 64) * fh_cdiv(N, 128);
-  if (plain && t64x128 < 200) {
-    const int m_tiles = fh_cdiv(M, 64);
-    const int blocks = fh_cdiv((long long)m_tiles * fh_cdiv(N, 64), 8) * 8;
-    hipLaunchKernelGGL((gemm_bf_kernel<1, 1>), dim3(blocks), dim3(256), 0, st, A, lda, W4, bias, R, ldr, C, ldc, M, N, K, alpha,
-                       epilogue, m_tiles);
-  } else if (t128 < 512) {
-    const int m_tiles = fh_cdiv(M, 64);
-    const int blocks = fh_cdiv((long long)m_tiles * fh_cdiv(N, 128), 8) * 8;
-    hipLaunchKernelGGL((gemm_bf_kernel<1, 2>), dim3(blocks), dim3(256), 0, st, A, lda, W4, bias, R, ldr, C, ldc, M, N, K, alpha,
-                       epilogue, m_tiles);
-  } else {
-    const int m_tiles = fh_cdiv(M, 128);
-    const int blocks = fh_cdiv((long long)m_tiles * fh_cdiv(N, 128), 8) * 8;
-    hipLaunchKernelGGL((gemm_bf_kernel<2, 2>), dim3(blocks), dim3(256), 0, st, A, lda, W4, bias, R, ldr, C, ldc, M, N, K, alpha,
-                       epilogue, m_tiles);
-  }
-  FH_CHECK_LAUNCH("fh_gemm_bf16x6_f32");
-  return FH_OK;
+  return launch_gemm<u32x4>("fh_gemm_bf16x6_f32", GB_BK, gemm_bf_kernel<1, 1>, gemm_bf_kernel<1, 2>, gemm_bf_kernel<2, 2>, A, lda, Wp,
+                            bias, R, ldr, C, ldc, M, N, K, alpha, epilogue, stream);
 }

@@ -12,19 +12,14 @@
 // 8q + e and 8q + 4 + e).  Global loads of tile i+1 are issued into registers before the MFMAs of
 // tile i (register prefetch), LDS is single buffered, two barriers per tile.
 //
-// Tile variants: 128 x 128 (wave 64 x 64), 64 x 128 (wave 32 x 64) and 64 x 64 (wave 32 x 32) -- the
-// smaller ones keep more CUs busy at M = N_frames ~ 1000.  W is padded to a multiple of 128 rows.
-#include "fh_common.h"
+// The frame around the products -- tile variants, block order, epilogues, argument checks and the launch -- is gemm_common.h's,
+// shared with gemm_bf.hip.  W is padded to a multiple of 128 rows.
+#include "gemm_common.h"
 
 namespace {
 
 constexpr int BK = 32;
 constexpr int LP = BK + 4;   // LDS row pitch, floats
-
-__device__ __forceinline__ float epi_pair(float first, float second, int mode) {
-  if (mode == FH_EPI_GEGLU) return gelu_erf(second) * first;
-  return sqrtf(first * first + second * second + 1e-9f);
-}
 
 template <int MT, int NT>   // wave tile = (32 MT) x (32 NT), block tile = (64 MT) x (64 NT)
 __global__ __launch_bounds__(256) void gemm_kernel(const float* __restrict__ A, int lda,
@@ -39,26 +34,13 @@ __global__ __launch_bounds__(256) void gemm_kernel(const float* __restrict__ A, 
   __shared__ __attribute__((aligned(16))) float As[BM * LP];
   __shared__ __attribute__((aligned(16))) float Ws[BN * LP];
 
-  // XCD-aware order: the m-tiles of one n-tile (sharing the W panel) go to one XCD
-  const int bid = blockIdx.x;
-  const int per_xcd = gridDim.x >> 3;              // grid is a multiple of 8
-  const int work = (bid & 7) * per_xcd + (bid >> 3);
-  const int nt_idx = work / m_tiles;
-  const int mt_idx = work % m_tiles;
-  const int m0 = mt_idx * BM, n0 = nt_idx * BN;
+  const GemmBlock g = gemm_block<MT, NT>(m_tiles);
+  const int m0 = g.m0, n0 = g.n0;
   if (n0 >= N) return;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l31 = lane & 31, lh = lane >> 5;
+  const int tid = g.tid, wm = g.wm, wn = g.wn, l31 = g.l31, lh = g.lh;
 
   f32x16 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   f32x4 areg[AREG], wreg[WREGS];
   auto gload = [&](int k0) {
@@ -113,48 +95,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const float* __restrict__ A, 
     }
   }
 
-  // ---- epilogue.  D reg r of lane l: row = (r&3) + 8 (r>>2) + 4 lh, col = l31 --------------
-  // The MFMA computed D[i][j] = sum_k A[i][k] W[j][k] with i = A row (m), j = W row (n).
-  if (mode == FH_EPI_LINEAR || mode == FH_EPI_LOGCLAMP) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        const int n = n0 + (wn * NT + nt) * 32 + l31;
-        if (n >= N) continue;
-        const float bv = bias ? bias[n] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int m = m0 + (wm * MT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (m >= M) continue;
-          float v = acc[mt][nt][r] + bv;
-          if (mode == FH_EPI_LOGCLAMP) {
-            v = logf(fmaxf(v, 1e-5f));
-          } else {
-            v *= alpha;
-            if (R) v += R[(size_t)m * ldr + n];
-          }
-          C[(size_t)m * ldc + n] = v;
-        }
-      }
-  } else {
-    // pair modes: the wave's two 32-column tiles are (first, second) of one packed 64 block
-    const int blk = (n0 >> 6) + wn;                 // packed block index
-    const int n_out = blk * 32 + l31;
-    const int n_first = n0 + wn * 64 + l31;         // packed column of `first`
-    if (NT == 2 && n_first < N) {
-      const float b1 = bias ? bias[n_first] : 0.f;
-      const float b2 = bias ? bias[n_first + 32] : 0.f;
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int m = m0 + (wm * MT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (m >= M) continue;
-          C[(size_t)m * ldc + n_out] = epi_pair(acc[mt][0][r] + b1, acc[mt][NT - 1][r] + b2, mode);
-        }
-    }
-  }
+  gemm_epilogue(acc, g, bias, R, ldr, C, ldc, M, N, alpha, mode);
 }
 
 // ---- y = act(W x + b), one wave per output row ------------------------------------------
@@ -200,36 +141,8 @@ __global__ void time_fourier_kernel(const float* __restrict__ w, float t, float*
 extern "C" int fh_gemm_f32(const float* A, int lda, const float* W, const float* bias,
                            const float* R, int ldr, float* C, int ldc, int M, int N, int K,
                            float alpha, int epilogue, void* stream) {
-  FH_CHECK_ARG(A && W && C && M > 0 && N > 0 && K > 0, "fh_gemm_f32: bad args");
-  FH_CHECK_ARG(K % BK == 0, "fh_gemm_f32: K=%d must be a multiple of %d", K, BK);
-  FH_CHECK_ARG(lda % 4 == 0 && (((uintptr_t)A) & 15) == 0 && (((uintptr_t)W) & 15) == 0,
-               "fh_gemm_f32: A/W must be 16-byte aligned with lda %% 4 == 0");
-  FH_CHECK_ARG(epilogue >= 0 && epilogue <= 3, "fh_gemm_f32: unknown epilogue %d", epilogue);
-  if (epilogue == FH_EPI_GEGLU || epilogue == FH_EPI_MAG)
-    FH_CHECK_ARG(N % 64 == 0, "fh_gemm_f32: pair epilogue needs N %% 64 == 0");
-  hipStream_t st = (hipStream_t)stream;
-  const bool plain = epilogue == FH_EPI_LINEAR || epilogue == FH_EPI_LOGCLAMP;
-  const long long t128 = (long long)fh_cdiv(M, 128) * fh_cdiv(N, 128);
-  const long long t64x128 = (long long)fh_cdiv(M, 64) * fh_cdiv(N, 128);
-  if (plain && t64x128 < 200) {
-    // few tiles (M = frames ~ 1000, N = 1024): 64 x 64 tiles put a block on every CU
-    const int m_tiles = fh_cdiv(M, 64);
-    const int blocks = fh_cdiv((long long)m_tiles * fh_cdiv(N, 64), 8) * 8;
-    hipLaunchKernelGGL((gemm_kernel<1, 1>), dim3(blocks), dim3(256), 0, st, A, lda, W, bias, R, ldr, C, ldc,
-                       M, N, K, alpha, epilogue, m_tiles);
-  } else if (t128 < 512) {
-    const int m_tiles = fh_cdiv(M, 64);
-    const int blocks = fh_cdiv((long long)m_tiles * fh_cdiv(N, 128), 8) * 8;
-    hipLaunchKernelGGL((gemm_kernel<1, 2>), dim3(blocks), dim3(256), 0, st, A, lda, W, bias, R, ldr, C, ldc,
-                       M, N, K, alpha, epilogue, m_tiles);
-  } else {
-    const int m_tiles = fh_cdiv(M, 128);
-    const int blocks = fh_cdiv((long long)m_tiles * fh_cdiv(N, 128), 8) * 8;
-    hipLaunchKernelGGL((gemm_kernel<2, 2>), dim3(blocks), dim3(256), 0, st, A, lda, W, bias, R, ldr, C, ldc,
-                       M, N, K, alpha, epilogue, m_tiles);
-  }
-  FH_CHECK_LAUNCH("fh_gemm_f32");
-  return FH_OK;
+  return launch_gemm<float>("fh_gemm_f32", BK, gemm_kernel<1, 1>, gemm_kernel<1, 2>, gemm_kernel<2, 2>, A, lda, W, bias, R, ldr, C,
+                            ldc, M, N, K, alpha, epilogue, stream);
 }
 
 extern "C" int fh_gemv_f32(const float* W, const float* x, const float* bias, float* y, int N,
