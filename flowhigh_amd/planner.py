@@ -1,6 +1,6 @@
 """Launch planning of the BigVGAN generator: which kernel and tile shape a conv position runs on (per STAGE, never per
 length or batch), the launch-time model that ranks tile shapes, descriptor builders, and `_PlanBuilder`, which turns one
-[batch, num_mels, n_frames] shape into the ordered list of launches `runtime.launch_step` enqueues.
+[batch, num_mels, n_frames] shape into the ordered list of step records (a NamedTuple per kind) `runtime.launch_step` enqueues.
 (Split out of vocoder.py in round 5; `flowhigh_amd.vocoder` re-exports every name.)
 
 Mirrors /root/reference/src/flowhigh/models/bigvgan/models.py:124-194 (BigVGAN.forward), AMPBlock1 :21-78, AMPBlock2 :81-121.
@@ -8,6 +8,7 @@ Mirrors /root/reference/src/flowhigh/models/bigvgan/models.py:124-194 (BigVGAN.f
 import ctypes as C
 import functools
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -146,6 +147,15 @@ def make_act_group(x, y, p):
     return g
 
 
+def _segs(*groups):
+    """(group, K segment) of every segment of the descriptor groups, in order."""
+    return [(g, g.seg[i]) for g in groups for i in range(g.nseg)]
+
+
+def _ksteps(g):
+    """K steps (16 input channels x one tap group) of a Winograd group."""
+    return sum(s.cin // 16 * s.ngrp for _, s in _segs(g))
+
 
 # Winograd tiles (tile_cfg -> rows x outputs) and their measured block time on one CU: _WINO_COST[cfg] = (a, b),
 # a us per K step (16 input channels x one tap group), b us of prologue + epilogue (tools/wino_cfg_sweep.py)
@@ -191,6 +201,11 @@ def wino_n_tiles(cfg, length, dil, pm):
     return -(-(-(-length // dil)) // bt) * dil
 
 
+def wino_run_len(n_tiles):
+    """Consecutive tiles of a panel that one XCD runs (fh_wino_run_len / fh_wino54_run_len: W_RUN = V_RUN = 8)."""
+    return -(-n_tiles // -(-n_tiles // _WINO_RUN))
+
+
 def wino_launch_cost(ksteps, batch, wpad, length, dil, cfg, cus_per_xcd=32, bf=False):
     """Estimated duration (us) of one fh_conv_wino_f32 launch: the kernel's block -> (panel, tile) map replayed
     on 8 XCDs x 32 CUs with in-order dispatch per XCD (block i goes to XCD i % 8).  ksteps: K steps
@@ -205,7 +220,7 @@ def wino_launch_cost(ksteps, batch, wpad, length, dil, cfg, cus_per_xcd=32, bf=F
     n_tiles = wino_n_tiles(cfg, length, dil, dil > 1)       # (dilated Winograd launches of the model are phase-major)
     cot = wpad // bm
     panel_w = [a * k + b for k in ksteps for _ in range(batch * cot)]
-    run_len = -(-n_tiles // -(-n_tiles // _WINO_RUN))
+    run_len = wino_run_len(n_tiles)
     rpp = -(-n_tiles // run_len)
     real = len(panel_w) * n_tiles
     load = 1.12 if real > 200 else 1.0 + 0.12 * real / 200        # blocks run ~12 % slower on a full chip
@@ -402,7 +417,7 @@ def amp_tile_list(lens, batch, dilation, interleave=True, direct=False):
 def amp_max_center(groups, direct=False):
     """max_center of a narrow-stage launch; raises if some segment's taps do not fit the slab it implies (direct form: every
     segment has its own slab, nothing to check)."""
-    segs = [g.seg[i] for g in groups for i in range(g.nseg)]
+    segs = [s for _, s in _segs(*groups)]
     cmax = max(s.center for s in segs)
     if direct:
         return cmax
@@ -473,10 +488,10 @@ def wino_block_mapping(groups, batch, wpad, length, dil, wcfg):
     # the L2, and the time-range order measured 4-6 % SLOWER at B = 8 and 32; at B = 1 it is neutral in time)
     if batch > 1 or n_tiles < 16 or any(g.out_stride > 1 for g in groups):
         return 0
-    weights = sum(g.seg[i].cin * g.seg[i].ngrp * 6 * wpad * 4.0 for g in groups for i in range(g.nseg))
-    inputs = sum(g.seg[i].cin * length * 4.0 * batch for g in groups for i in range(g.nseg))
+    weights = sum(s.cin * s.ngrp * 6 * wpad * 4.0 for _, s in _segs(*groups))
+    inputs = sum(s.cin * length * 4.0 * batch for _, s in _segs(*groups))
     co_tiles = wpad // bm
-    run_len = -(-n_tiles // -(-n_tiles // _WINO_RUN))
+    run_len = wino_run_len(n_tiles)
     runs_per_panel = -(-n_tiles // run_len)             # (a panel's runs are dealt to different XCDs)
     by_panel = weights * min(runs_per_panel, 8) + inputs * min(co_tiles, 8)
     tpx = -(-n_tiles // 8)
@@ -514,10 +529,37 @@ def make_wino_group(segs, bias, res, out, cout, cpad, length, scale=1.0, stride=
     return g
 
 
+# ---- step records, one launch each: a NamedTuple per kind whose field 0 is the kind (the key of runtime's dispatch table), the others
+# the launch's arguments in the order below (desc: the uploaded descriptor array, its host structs are in meta; flops: algorithmic).
+# They stay tuples: hip.ShapeCache sizes a plan by walking tuples / lists / dicts (a slotted object's tensors would not be counted) ---
+STEP_TYPES = {kind: NamedTuple(kind.capitalize() + "Step", [(f, object) for f in ["kind"] + fields.split()]) for kind, fields in dict(
+    conv="desc ng cpad n_len tcfg ck flops",
+    convt="desc ng cpad n_len tcfg phases flops",
+    # (wcfg: plan tile id | WINO_XCD_RANGES | WINO_NOVL; pm: phase-major rows; batch: 1 where the groups are per batch item)
+    wino="desc ng wpad length dil flops wcfg pm batch",
+    amp="desc ng tiles n_tiles c dil cmax flags flops",
+    act="desc ng c length din dout",
+    mean="a b c out n scale",
+    sum="srcs out n scale",
+    post="x wav c length",
+    # ... of a merged (ragged) plan: off / off_map / off_tiles are byte offsets into the plan's descriptor blob rp["desc"]
+    rwino="off ng wpad maxlen dil wcfg pmflag off_map n_runs",
+    rconv="off ng cpad maxlen tcfg ck",
+    rconvt="off ng cpad maxlen tcfg phases",
+    ramp="off ng off_tiles n_tiles c dil cmax flags",
+    ract="off ng c din dout tiles mult4",
+    rsum="off n_jobs max_n").items()}
+
+
+def make_step(kind, *fields):
+    """The record of a launch of `kind`."""
+    return STEP_TYPES[kind](kind, *fields)
+
+
 class _PlanBuilder:
     """Builds the launch plan of one [batch, num_mels, n_frames] shape (Vocoder.plan): workspace pool, descriptor
     arrays and the ordered list of launch steps.
-    steps[i] = (kind, ...) is what Vocoder._launch runs; meta[i] = (position key, host descriptor structs): the position
+    steps[i] is the step record (STEP_TYPES) runtime.launch_step enqueues; meta[i] = (position key, host descriptor structs): the position
     key names the step's place in the model -- (stage, sub-block, slot, index) -- so that the plans of different clips
     can be merged launch by launch (Vocoder.plan_ragged) although their optional steps differ."""
 
@@ -550,6 +592,12 @@ class _PlanBuilder:
         self.meta.append((key if key is not None else self.key, structs))
         self.steps.append(step)
 
+    def upload(self, groups):
+        """The launch's descriptor array on the device; the plan keeps it alive."""
+        d = hip.to_device_struct_array(groups, self.v.device)
+        self.keep.append(d)
+        return d
+
     def parts_buffer(self):
         if self.parts is None:
             self.parts = torch.empty(2 * self.v.nk, self.B * self.max_elems, **self.f32)
@@ -562,71 +610,59 @@ class _PlanBuilder:
         sequence lengths) switch from the 128 x 128 to the 128 x 64 tile to fill the 256 CUs."""
         if tcfg == 0 and len(groups) * self.B * (cpad // 128) * -(-n_len // 128) < 512:
             tcfg = 5
-        d = hip.to_device_struct_array(groups, self.v.device)
-        self.keep.append(d)
-        flops = sum(2.0 * g.cout * g.seg[i].cin * g.seg[i].ntaps * n_len * self.B for g in groups for i in range(g.nseg))
-        self.executed += flops
-        self.direct += flops
-        self.conv_launches.append(("direct", flops, flops))
-        self.add(("conv", d, len(groups), cpad, n_len, tcfg, ck, flops), groups)
+        self._direct("conv", groups, cpad, n_len, tcfg, ck)
 
     def convt(self, groups, cpad, n_len, tcfg, phases):
         """Direct-kernel launch of phase-fused transposed-conv groups (fh_conv_transpose_fused_f32)."""
-        d = hip.to_device_struct_array(groups, self.v.device)
-        self.keep.append(d)
-        flops = sum(2.0 * g.cout * g.seg[i].cin * g.seg[i].ntaps * n_len * self.B for g in groups for i in range(g.nseg))
+        self._direct("convt", groups, cpad, n_len, tcfg, phases)
+
+    def _direct(self, kind, groups, cpad, n_len, tcfg, ck_or_phases):
+        flops = sum(2.0 * g.cout * s.cin * s.ntaps * n_len * self.B for g, s in _segs(*groups))
         self.executed += flops
         self.direct += flops
         self.conv_launches.append(("direct", flops, flops))
-        self.add(("convt", d, len(groups), cpad, n_len, tcfg, phases, flops), groups)
+        self.add(make_step(kind, self.upload(groups), len(groups), cpad, n_len, tcfg, ck_or_phases, flops), groups)
 
     def wino(self, groups, wpad, length, dil, wcfg, pm=False, flops=None, batch=None, novl=False):
         """Winograd launch; the tile shape is the launch model's (choose_wino_cfg).  batch: launches whose groups are
         per batch item (input-channel slices) pass 1.  novl: some row of the launch is not 16-byte aligned although
         `length` may be a multiple of 4 (segments with xlen)."""
         B = self.B if batch is None else batch
-        wcfg, _ = choose_wino_cfg([sum(g.seg[i].cin // 16 * g.seg[i].ngrp for i in range(g.nseg)) for g in groups],
-                                  B, wpad, length, dil, default=wcfg, bf=self.v.bf)
+        wcfg, _ = choose_wino_cfg([_ksteps(g) for g in groups], B, wpad, length, dil, default=wcfg, bf=self.v.bf)
         wcfg |= wino_block_mapping(groups, B, wpad, length, dil, wcfg)
-        if wcfg & WINO_F54 and any(g.out_stride > 1 or g.out_len or g.seg[i].ngrp > 3 or g.seg[i].xlen
-                                   for g in groups for i in range(g.nseg)):
+        if wcfg & WINO_F54 and any(g.out_stride > 1 or g.out_len or s.ngrp > 3 or s.xlen for g, s in _segs(*groups)):
             raise NotImplementedError("the F(5,4) kernel takes plain convs of at most 12 taps (no strided outputs, xlen, out_len)")
         if novl:
             if wcfg & WINO_F54:
                 raise NotImplementedError("the F(5,4) kernel takes no segments with xlen")
             wcfg |= WINO_NOVL
-        d = hip.to_device_struct_array(groups, self.v.device)
-        self.keep.append(d)
         if flops is None:
-            flops = sum(2.0 * g.cout * g.seg[i].cin * (2 * g.seg[i].center + 1) * length * B
-                        for g in groups for i in range(g.nseg))
+            flops = sum(2.0 * g.cout * s.cin * (2 * s.center + 1) * length * B for g, s in _segs(*groups))
         # multiply-adds the matrix cores actually execute: 6 per 4 outputs per group of 3 taps, or 8 per 5 per group of 4
         per_out = 1.6 if wcfg & WINO_F54 else 1.5
-        ex = sum(2.0 * g.cout * g.seg[i].cin * per_out * g.seg[i].ngrp * length * B for g in groups for i in range(g.nseg))
+        ex = sum(2.0 * g.cout * s.cin * per_out * s.ngrp * length * B for g, s in _segs(*groups))
         self.executed += ex
         self.conv_launches.append((("wino54" if wcfg & WINO_F54 else "wino43") + ("_bf16x6" if self.v.bf else ""), ex, flops))
-        self.add(("wino", d, len(groups), wpad, length, dil, flops, wcfg, int(pm), B), groups)
+        self.add(make_step("wino", self.upload(groups), len(groups), wpad, length, dil, flops, wcfg, int(pm), B), groups)
 
     def amp(self, groups, c, length, dil):
         """Narrow-stage launch: the groups' convs (fh_amp_actconv_f32; the model's narrow stages in the direct bf16 x 6 form:
         fh_narrow_conv_bf16x6_f32, plan flag AMP_DIRECT)."""
         B = self.B
         direct = self.v.amp_direct
+        d = self.upload(groups)
         tiles = amp_tile_list([g.len for g in groups], B, dil, direct=direct).to(self.v.device)
-        d = hip.to_device_struct_array(groups, self.v.device)
-        self.keep += [d, tiles]
-        flops = sum(2.0 * c * c * (2 * g.seg[i].center + 1) * length * B for g in groups for i in range(g.nseg))
+        self.keep.append(tiles)
+        flops = sum(2.0 * c * c * (2 * s.center + 1) * length * B for _, s in _segs(*groups))
         # executed: Winograd F(5,4) 1.6 ceil(k / 4) multiply-adds per output; direct: the taps themselves
-        ex = flops if direct else sum(2.0 * c * c * 1.6 * g.seg[i].ngrp * length * B for g in groups for i in range(g.nseg))
+        ex = flops if direct else sum(2.0 * c * c * 1.6 * s.ngrp * length * B for _, s in _segs(*groups))
         self.executed += ex
         self.conv_launches.append(("narrow_bf16x6" if direct else "amp", ex, flops))
         flags = int(all(g.len % 4 == 0 for g in groups)) | (AMP_DIRECT if direct else 2)
-        self.add(("amp", d, len(groups), tiles, tiles.shape[0], c, dil, amp_max_center(groups, direct), flags, flops), groups)
+        self.add(make_step("amp", d, len(groups), tiles, tiles.shape[0], c, dil, amp_max_center(groups, direct), flags, flops), groups)
 
     def act(self, groups, c, length, din=1, dout=1):
-        d = hip.to_device_struct_array(groups, self.v.device)
-        self.keep.append(d)
-        self.add(("act", d, len(groups), c, length, din, dout), groups)
+        self.add(make_step("act", self.upload(groups), len(groups), c, length, din, dout), groups)
 
     def res_conv(self, st, ents, xs_in, ks, dil, outs, res, pm=False, defer_sum=False):
         """One launch of the same conv position in the nk AMP blocks (one group per block) at the current stage
@@ -663,7 +699,7 @@ class _PlanBuilder:
             pieces = [[outs[i]] + [parts[2 * i + sl] for sl in range(nsplit - 1)] for i in range(len(ents))]
             if not defer_sum:
                 for i in range(len(ents)):
-                    self.add(("sum", pieces[i], outs[i], B * c * pitch, 1.0), key=self.key[:2] + (self.key[2] + 1, i))
+                    self.add(make_step("sum", pieces[i], outs[i], B * c * pitch, 1.0), key=self.key[:2] + (self.key[2] + 1, i))
             return pieces
         if all_wino:
             self.wino([make_wino_group([make_wino_seg(xs_in[i], ents[i]["u"], c, ks[i], taps=st["taps"])], biases[i], res[i],
@@ -703,9 +739,9 @@ class _PlanBuilder:
         """out = scale * (((ys[0] + ys[1]) + ys[2]) + ...): the `xs += resblock(x)` / `xs / num_kernels` of
         models.py:181-187 in the reference's block order, for stages whose closing conv is not fused."""
         if len(ys) in (2, 3):
-            self.add(("mean", ys[0], ys[1], ys[2] if len(ys) == 3 else None, out, n, scale), key=key)
+            self.add(make_step("mean", ys[0], ys[1], ys[2] if len(ys) == 3 else None, out, n, scale), key=key)
         elif len(ys) <= 12:
-            self.add(("sum", list(ys), out, n, scale), key=key)
+            self.add(make_step("sum", list(ys), out, n, scale), key=key)
         else:
             raise NotImplementedError("more than 12 resblock kernel sizes")
 
@@ -765,7 +801,7 @@ class _PlanBuilder:
                                   c, st["up_wpad"], npos, stride=u, phase=r, out_len=olen)
                   for r, ph in enumerate(st["up_wino"]) for sl in range(nsplit) for b in range(B)]
         self.wino(groups, st["up_wpad"], npos, 1, st["up_wcfg"], flops=up_flops, batch=1, novl=bool(extra))
-        self.add(("sum", dsts, X, B * c * L, 1.0), key=(i, -1, 1, 0))
+        self.add(make_step("sum", dsts, X, B * c * L, 1.0), key=(i, -1, 1, 0))
 
     def amp1_stack(self, i):
         """The nk AMPBlock1 of stage i (models.py:21-78), position by position: act -> conv1 (dilated) -> act -> conv2
@@ -863,7 +899,7 @@ class _PlanBuilder:
                                    [[xin[j]] for j in order], defer_sum=one_pass)
             if len(pieces[0]) > 1 and one_pass:                 # input-channel slices: all partial outputs in one pass
                 by_block = {j: pieces[n_] for n_, j in enumerate(order)}
-                self.add(("sum", [t for j in range(v.nk) for t in by_block[j]], S, B * c * L, scale), key=(i, m, 6, 0))
+                self.add(make_step("sum", [t for j in range(v.nk) for t in by_block[j]], S, B * c * L, scale), key=(i, m, 6, 0))
             else:
                 self.average([Y[j][m % 2] for j in range(v.nk)], S, B * c * L, scale, key=(i, m, 6, 0))
             return
@@ -890,12 +926,126 @@ class _PlanBuilder:
         post_t = self.pool[2, :B * c_last * L].view(B, c_last, L)
         self.at(99, 0, 0, 0)
         self.act([make_act_group(cur, post_t, v.post_act)], c_last, L)
-        self.add(("post", post_t, wav, c_last, L), key=(99, 0, 1, 0))
+        self.add(make_step("post", post_t, wav, c_last, L), key=(99, 0, 1, 0))
         # algorithmic HBM bytes of the Activation1d launches: every site reads and writes its [B, C, L] tensor once
-        act_bytes = sum(8.0 * s_[2] * B * s_[3] * s_[4] for s_ in self.steps if s_[0] == "act")
+        acts = [s for s in self.steps if s.kind == "act"]
+        act_bytes = sum(8.0 * s.ng * B * s.c * s.length for s in acts)
         return dict(steps=self.steps, meta=self.meta, keep=self.keep, mel_in=self.mel_in, wav=wav, B=B, N=self.N, L=L,
                     conv_executed_flops=self.executed, conv_direct_flops=self.direct, conv_launches=self.conv_launches, act_bytes=act_bytes,
-                    n_act=sum(s_[0] == "act" for s_ in self.steps))
+                    n_act=len(acts))
+
+
+def _append(blobs, data):
+    """Append a list of descriptor structs, a ctypes array or bytes to a ragged plan's descriptor blob, padded to 16 bytes -> offset."""
+    raw = bytes((type(data[0]) * len(data))(*data) if isinstance(data, list) else data)
+    off = sum(len(b) for b in blobs)
+    blobs.append(raw + bytes(-len(raw) % 16))
+    return off
+
+
+def _classes(items, key):
+    """The (clip, step, host structs) items of one position by kernel class: {key(step): [(step, structs), ...]}.items()."""
+    out = {}
+    for _, s, groups in items:
+        out.setdefault(key(s), []).append((s, groups))
+    return out.items()
+
+
+# ---- one merge per step kind: (voc, [(clip, step, host structs)] of one position, blobs) -> the merged steps ------------------
+def _merge_wino(voc, items, blobs):
+    assert all(s.batch == 1 and s.ng == len(groups) for _, s, groups in items)
+    for (wpad, dil, pm, fam), lst in _classes(items, lambda s: (s.wpad, s.dil, s.pm, s.wcfg & WINO_F54)):
+        allg = [(_ksteps(g), s.length, g) for s, groups in lst for g in groups]
+        allg.sort(key=lambda t: (-t[0], -t[1]))                 # heavy groups first (dispatch order)
+        maxlen = max(t[1] for t in allg)
+        default = max(lst, key=lambda t: t[0].length)[0].wcfg & (15 | WINO_F54)          # the longest clip's tile shape
+        wcfg = default
+        if default in (0, 1, 4, 5) or fam:
+            # the launch model takes one length: the mean one keeps the block count honest
+            mean_len = max(1, sum(t[1] for t in allg) // len(allg))
+            wcfg, _ = choose_wino_cfg([t[0] for t in allg], 1, wpad, mean_len, dil, default=default, bf=voc.bf)
+        novl = 0 if (pm or all(t[1] % 4 == 0 for t in allg)) else 2
+        if any(s.wcfg & WINO_NOVL for s, _ in lst):             # (segments with xlen: odd-(k - u) upsamplers)
+            novl = 2
+        # runs (consecutive tiles of one (group, co tile) panel, dealt to one XCD) that hold real tiles
+        bm, bt = _WINO_TILES[wcfg]
+        cot = wpad // bm
+        n_tiles = wino_n_tiles(wcfg, maxlen, dil, pm)
+        run_len = wino_run_len(n_tiles)
+        rpp = -(-n_tiles // run_len)
+        runs = []
+        for gi, (_, length, _) in enumerate(allg):
+            # tile index = (block of bt outputs within the phase) * dil + phase: real while its first
+            # output (phase + dil * bt * block) lies inside the row
+            # (blocks per phase differ by at most one, so the real tiles are 0 .. t_last without holes)
+            if fam and pm:                  # (the F(5,4) kernel's concatenated tiling: a group's real tiles are the first ones)
+                t_last = wino_n_tiles(wcfg, length, dil, pm) - 1
+            else:
+                nb = [max(0, -(-(length - ph) // (dil * bt))) for ph in range(dil)]
+                t_last = dil * (nb[0] - 1) + sum(1 for v in nb if v == nb[0]) - 1
+            own = range(t_last // run_len + 1)
+            for ct in range(cot):
+                runs += [(gi * cot + ct) * rpp + r for r in own]
+        off_map = _append(blobs, (C.c_int32 * len(runs))(*runs))
+        yield make_step("rwino", _append(blobs, [t[2] for t in allg]), len(allg), wpad, maxlen, dil, wcfg, int(pm) | novl,
+                        off_map, len(runs))
+
+
+def _merge_conv(voc, items, blobs):
+    for (cpad, ck), lst in _classes(items, lambda s: (s.cpad, s.ck)):
+        allg = [(sum(seg.cin * seg.ntaps for _, seg in _segs(g)), s.n_len, g) for s, groups in lst for g in groups]
+        allg.sort(key=lambda t: (-t[0], -t[1]))
+        tcfg = max(lst, key=lambda t: t[0].n_len)[0].tcfg
+        yield make_step("rconv", _append(blobs, [t[2] for t in allg]), len(allg), cpad, max(t[1] for t in allg), tcfg, ck)
+
+
+def _merge_convt(voc, items, blobs):
+    for (cpad, tcfg, phases), lst in _classes(items, lambda s: (s.cpad, s.tcfg, s.phases)):
+        allg = sorted(((s.n_len, g) for s, groups in lst for g in groups), key=lambda t: -t[0])
+        yield make_step("rconvt", _append(blobs, [t[1] for t in allg]), len(allg), cpad, allg[0][0], tcfg, phases)
+
+
+def _merge_amp(voc, items, blobs):
+    for (c, dil, form_bits), lst in _classes(items, lambda s: (s.c, s.dil, s.flags & (2 | AMP_DIRECT))):
+        allg = [g for _, groups in lst for g in groups]
+        direct = bool(form_bits & AMP_DIRECT)
+        # heavy groups first (the persistent blocks walk the tile list in order), then long ones
+        allg.sort(key=lambda g: (-sum(s.ngrp for _, s in _segs(g)), -g.len))
+        tl = amp_tile_list([g.len for g in allg], 1, dil, direct=direct)
+        off_tiles = _append(blobs, tl.numpy().tobytes())
+        yield make_step("ramp", _append(blobs, allg), len(allg), off_tiles, tl.shape[0], c, dil, amp_max_center(allg, direct),
+                       int(all(g.len % 4 == 0 for g in allg)) | form_bits)
+
+
+def _merge_act(voc, items, blobs):
+    tt = hip.lib().fh_act_tile_len()
+    for (c, din, dout), lst in _classes(items, lambda s: (s.c, s.din, s.dout)):
+        out, base = [], 0
+        for s, groups in sorted(lst, key=lambda t: -t[0].length):
+            for g in groups:
+                g2 = hip.ActGroup.from_buffer_copy(g)
+                g2.len, g2.tile_base = s.length, base
+                base += c * -(-s.length // tt)
+                out.append(g2)
+        yield make_step("ract", _append(blobs, out), len(out), c, din, dout, base, int(all(g.len % 4 == 0 for g in out)))
+
+
+def _merge_sum(voc, items, blobs):
+    jobs = []
+    for _, s, _ in items:
+        srcs = s.srcs if s.kind == "sum" else [s.a, s.b] + ([s.c] if s.c is not None else [])
+        j = hip.SumJob()
+        for i, t in enumerate(srcs):
+            j.src[i] = t.data_ptr()
+        j.out, j.n, j.n_src, j.scale = s.out.data_ptr(), s.n, len(srcs), s.scale
+        if s.n % 4 or len(srcs) > 12:
+            raise NotImplementedError("partial-sum job shape")
+        jobs.append(j)
+    return [make_step("rsum", _append(blobs, jobs), len(jobs), max(j.n for j in jobs))]
+
+
+_MERGE = dict(wino=_merge_wino, conv=_merge_conv, convt=_merge_convt, amp=_merge_amp, act=_merge_act, sum=_merge_sum,
+              post=lambda voc, items, blobs: [s for _, s, _ in items])          # (conv_post runs per clip)
 
 
 def merge_ragged(voc, frames):
@@ -922,137 +1072,15 @@ def merge_ragged(voc, frames):
         for step, (k, structs) in zip(sp["steps"], sp["meta"]):
             by_key.setdefault(k, []).append((ci, step, structs))
     blobs, merged = [], []          # host bytes of every descriptor array (one upload), merged steps
-
-    def blob(structs):
-        arr = (type(structs[0]) * len(structs))(*structs)
-        off = sum(len(b) for b in blobs)
-        raw = bytes(arr)
-        blobs.append(raw + bytes(-len(raw) % 16))
-        return off
-
-    tt = hip.lib().fh_act_tile_len()
-    for k in sorted(by_key):
-        items = by_key[k]
+    for k, items in sorted(by_key.items()):          # (keys are unique: the sort never compares the items)
         # (a mean is a 2-3 term sum job; the fused tail launch and conv_post share a position: both run per clip)
-        kinds = {{"mean": "sum"}.get(it[1][0], it[1][0]) for it in items}
+        kinds = {{"mean": "sum"}.get(s.kind, s.kind) for _, s, _ in items}
         if len(kinds) != 1:
             raise NotImplementedError(f"launch position {k}: kinds {kinds} cannot be merged")
         kind = kinds.pop()
-        if kind == "wino":
-            classes = {}
-            for ci, st_, groups in items:
-                _, _d, ng, wpad, length, dil, _fl, wcfg, pm, bb = st_
-                assert bb == 1 and ng == len(groups)
-                classes.setdefault((wpad, dil, pm, wcfg & WINO_F54), []).append((length, wcfg, groups))
-            for (wpad, dil, pm, fam), lst in classes.items():
-                allg = [(sum(g.seg[i].cin // 16 * g.seg[i].ngrp for i in range(g.nseg)), length, g)
-                        for length, _, groups in lst for g in groups]
-                allg.sort(key=lambda t: (-t[0], -t[1]))                 # heavy groups first (dispatch order)
-                maxlen = max(t[1] for t in allg)
-                default = max(lst, key=lambda t: t[0])[1] & (15 | WINO_F54)          # the longest clip's tile shape
-                wcfg = default
-                if default in (0, 1, 4, 5) or fam:
-                    # the launch model takes one length: the mean one keeps the block count honest
-                    mean_len = max(1, sum(t[1] for t in allg) // len(allg))
-                    wcfg, _ = choose_wino_cfg([t[0] for t in allg], 1, wpad, mean_len, dil, default=default, bf=voc.bf)
-                novl = 0 if (pm or all(t[1] % 4 == 0 for t in allg)) else 2
-                if any(w & WINO_NOVL for _, w, _ in lst):               # (segments with xlen: odd-(k - u) upsamplers)
-                    novl = 2
-                # runs (consecutive tiles of one (group, co tile) panel, dealt to one XCD) that hold real tiles
-                bm, bt = _WINO_TILES[wcfg]
-                cot = wpad // bm
-                n_tiles = wino_n_tiles(wcfg, maxlen, dil, pm)
-                run_len = (hip.lib().fh_wino54_run_len if fam else hip.lib().fh_wino_run_len)(n_tiles)
-                rpp = -(-n_tiles // run_len)
-                runs = []
-                for gi, (_, length, _) in enumerate(allg):
-                    # tile index = (block of bt outputs within the phase) * dil + phase: real while its first
-                    # output (phase + dil * bt * block) lies inside the row
-                    # (blocks per phase differ by at most one, so the real tiles are 0 .. t_last without holes)
-                    if fam and pm:                  # (the F(5,4) kernel's concatenated tiling: a group's real tiles are the first ones)
-                        t_last = wino_n_tiles(wcfg, length, dil, pm) - 1
-                    else:
-                        nb = [max(0, -(-(length - ph) // (dil * bt))) for ph in range(dil)]
-                        t_last = dil * (nb[0] - 1) + sum(1 for v in nb if v == nb[0]) - 1
-                    own = range(t_last // run_len + 1)
-                    for ct in range(cot):
-                        runs += [(gi * cot + ct) * rpp + r for r in own]
-                rmap = (C.c_int32 * len(runs))(*runs)
-                off_map = sum(len(b) for b in blobs)
-                raw = bytes(rmap)
-                blobs.append(raw + bytes(-len(raw) % 16))
-                merged.append(("rwino", blob([t[2] for t in allg]), len(allg), wpad, maxlen, dil, wcfg,
-                               int(pm) | novl, off_map, len(runs)))
-        elif kind == "conv":
-            classes = {}
-            for ci, st_, groups in items:
-                _, _d, ng, cpad, n_len, tcfg, ck, _fl = st_
-                classes.setdefault((cpad, ck), []).append((n_len, tcfg, groups))
-            for (cpad, ck), lst in classes.items():
-                allg = [(sum(g.seg[i].cin * g.seg[i].ntaps for i in range(g.nseg)), n_len, g)
-                        for n_len, _, groups in lst for g in groups]
-                allg.sort(key=lambda t: (-t[0], -t[1]))
-                tcfg = max(lst, key=lambda t: t[0])[1]
-                merged.append(("rconv", blob([t[2] for t in allg]), len(allg), cpad, max(t[1] for t in allg), tcfg, ck))
-        elif kind == "convt":
-            classes = {}
-            for ci, st_, groups in items:
-                _, _d, ng, cpad, n_len, tcfg, phases, _fl = st_
-                classes.setdefault((cpad, tcfg, phases), []).append((n_len, groups))
-            for (cpad, tcfg, phases), lst in classes.items():
-                allg = sorted(((n_len, g) for n_len, groups in lst for g in groups), key=lambda t: -t[0])
-                merged.append(("rconvt", blob([t[1] for t in allg]), len(allg), cpad, allg[0][0], tcfg, phases))
-        elif kind == "amp":
-            classes = {}
-            for ci, st_, groups in items:
-                _, _d, ng, _t, _nt, c, dil, _cm, flags, _fl = st_
-                classes.setdefault((c, dil, flags & (2 | AMP_DIRECT)), []).append(groups)
-            for (c, dil, form_bits), lst in classes.items():
-                allg = [g for groups in lst for g in groups]
-                direct = bool(form_bits & AMP_DIRECT)
-                # heavy groups first (the persistent blocks walk the tile list in order), then long ones
-                allg.sort(key=lambda g: (-sum(g.seg[i].ngrp for i in range(g.nseg)), -g.len))
-                tl = amp_tile_list([g.len for g in allg], 1, dil, direct=direct)
-                off_t = sum(len(b) for b in blobs)
-                raw = tl.numpy().tobytes()
-                blobs.append(raw + bytes(-len(raw) % 16))
-                merged.append(("ramp", blob(allg), len(allg), off_t, tl.shape[0], c, dil, amp_max_center(allg, direct),
-                               int(all(g.len % 4 == 0 for g in allg)) | form_bits))
-        elif kind == "act":
-            classes = {}
-            for ci, st_, groups in items:
-                _, _d, ng, c, length, din, dout = st_
-                classes.setdefault((c, din, dout), []).append((length, groups))
-            for (c, din, dout), lst in classes.items():
-                out, base = [], 0
-                for length, groups in sorted(lst, key=lambda t: -t[0]):
-                    for g in groups:
-                        g2 = hip.ActGroup.from_buffer_copy(g)
-                        g2.len, g2.tile_base = length, base
-                        base += c * -(-length // tt)
-                        out.append(g2)
-                merged.append(("ract", blob(out), len(out), c, din, dout, base, int(all(g.len % 4 == 0 for g in out))))
-        elif kind == "sum":
-            jobs = []
-            for ci, st_, _ in items:
-                if st_[0] == "sum":
-                    _, srcs, out, n, scale = st_
-                else:
-                    _, a, b_, c_, out, n, scale = st_
-                    srcs = [a, b_] + ([c_] if c_ is not None else [])
-                j = hip.SumJob()
-                for i, t in enumerate(srcs):
-                    j.src[i] = t.data_ptr()
-                j.out, j.n, j.n_src, j.scale = out.data_ptr(), n, len(srcs), scale
-                if n % 4 or len(srcs) > 12:
-                    raise NotImplementedError("partial-sum job shape")
-                jobs.append(j)
-            merged.append(("rsum", blob(jobs), len(jobs), max(j.n for j in jobs)))
-        elif kind == "post":
-            for ci, st_, _ in items:
-                merged.append(st_)
-        else:
+        if kind not in _MERGE:
             raise NotImplementedError(kind)
+        merged += _MERGE[kind](voc, items, blobs)
     host = torch.frombuffer(bytearray(b"".join(blobs)), dtype=torch.uint8)
     desc = host.to(voc.device)
     rp = dict(subs=subs, steps=merged, desc=desc, frames=frames)

@@ -1,5 +1,5 @@
 """Enqueueing: one-off launchers of the conv / activation entry points (tests, tools), the per-device occupancy setting of
-the activation launches, and the step / ragged-step dispatch a plan is run with.
+the activation launches, and the dispatch a plan is run with: step kind (planner.STEP_TYPES, plain and ragged) -> enqueueing function.
 (Split out of vocoder.py in round 5; `flowhigh_amd.vocoder` re-exports every name.)
 """
 import ctypes as C
@@ -9,7 +9,7 @@ import torch
 
 from . import hip
 from .packing import pack_wino54_weight_any, pack_wino_weight_any
-from .planner import (AMP_DIRECT, WINO_F54, amp_max_center, amp_tile_list, make_act_group, make_wino_group, make_wino_seg, pick_wino54_tile,
+from .planner import (AMP_DIRECT, WINO_BF16X6, WINO_F54, amp_max_center, amp_tile_list, make_act_group, make_wino_group, make_wino_seg, pick_wino54_tile,
                       pick_wino_tile, use_wino54)
 
 def amp_actconv(groups, batch, channels, dilation, device, direct=False):
@@ -17,42 +17,32 @@ def amp_actconv(groups, batch, channels, dilation, device, direct=False):
     make_amp_seg / make_amp_group(..., direct=True), weights from pack_narrow_bf_weight)."""
     tiles = amp_tile_list([g.len for g in groups], batch, dilation, direct=direct).to(device)
     d = hip.to_device_struct_array(groups, device)
-    vec = int(all(g.len % 4 == 0 for g in groups))
-    if direct:
-        hip.check(hip.lib().fh_narrow_conv_bf16x6_f32(d.data_ptr(), len(groups), tiles.data_ptr(), tiles.shape[0], channels, dilation,
-                                                      vec, hip.stream()), "fh_narrow_conv_bf16x6_f32")
-    else:
-        hip.check(hip.lib().fh_amp_actconv_f32(d.data_ptr(), len(groups), tiles.data_ptr(), tiles.shape[0], channels, dilation,
-                                               amp_max_center(groups), vec | 2, hip.stream()), "fh_amp_actconv_f32")
+    name, tail = narrow_entry(int(all(g.len % 4 == 0 for g in groups)) | (AMP_DIRECT if direct else 2), amp_max_center(groups, direct))
+    enqueue(getattr(hip.lib(), name), (d.data_ptr(), len(groups), tiles.data_ptr(), tiles.shape[0], channels, dilation, *tail, hip.stream()))
     return d, tiles
 
 
 def conv_wino(groups, batch, cout_pad, length, dilation, device, tile_cfg=0, phase_major=False):
     """Upload descriptors and enqueue one Winograd conv launch (test / one-off use)."""
     d = hip.to_device_struct_array(groups, device)
-    if tile_cfg & WINO_F54:            # (F(5,4) kernel: the groups' weights are pack_wino54_weight, ngrp = ceil(k / 4))
-        if any(g.out_stride > 1 or g.out_len or g.seg[i].ngrp > 3 or g.seg[i].xlen for g in groups for i in range(g.nseg)):
-            raise NotImplementedError("the F(5,4) kernel takes plain convs of at most 12 taps (no strided outputs, xlen, out_len)")
-        hip.check(hip.lib().fh_conv_wino54_f32(d.data_ptr(), len(groups), batch, cout_pad, length, dilation,
-                                               int(phase_major), tile_cfg & 31, hip.stream()), "fh_conv_wino54_f32")
-        return d
-    hip.check(hip.lib().fh_conv_wino_f32(d.data_ptr(), len(groups), batch, cout_pad, length, dilation,
-                                         int(phase_major), tile_cfg, hip.stream()), "fh_conv_wino_f32")
+    # (F(5,4) kernel: the groups' weights are pack_wino54_weight, ngrp = ceil(k / 4))
+    if tile_cfg & WINO_F54 and any(g.out_stride > 1 or g.out_len or g.seg[i].ngrp > 3 or g.seg[i].xlen for g in groups for i in range(g.nseg)):
+        raise NotImplementedError("the F(5,4) kernel takes plain convs of at most 12 taps (no strided outputs, xlen, out_len)")
+    name, cfg = wino_entry(tile_cfg, tile_cfg & WINO_BF16X6)           # (a caller's FH_WINO_BF16X6 flag stays)
+    enqueue(getattr(hip.lib(), name), (d.data_ptr(), len(groups), batch, cout_pad, length, dilation, int(phase_major), cfg, hip.stream()))
     return d
 
 
 def conv_grouped(groups, batch, cout_pad, n_len, tile_cfg, device, ck=8):
     """Upload descriptors and enqueue one grouped conv launch (test / one-off use)."""
     d = hip.to_device_struct_array(groups, device)
-    hip.check(hip.lib().fh_conv_grouped_f32(d.data_ptr(), len(groups), batch, cout_pad, n_len, tile_cfg, ck,
-                                            hip.stream()), "fh_conv_grouped_f32")
+    enqueue(hip.lib().fh_conv_grouped_f32, (d.data_ptr(), len(groups), batch, cout_pad, n_len, tile_cfg, ck, hip.stream()))
     return d
 
 
 def act1d_grouped(groups, batch, channels, length, device, din=1, dout=1):
     d = hip.to_device_struct_array(groups, device)
-    hip.check(hip.lib().fh_act1d_grouped_pm_f32(d.data_ptr(), len(groups), batch, channels, length, din, dout,
-                                                hip.stream()), "fh_act1d_grouped_pm_f32")
+    enqueue(hip.lib().fh_act1d_grouped_pm_f32, (d.data_ptr(), len(groups), batch, channels, length, din, dout, hip.stream()))
     return d
 
 
@@ -166,7 +156,7 @@ def measure_act_conv_pair(device, blocks, c=192, length=60000, warm=60, reps=100
         f54 = use_wino54(c, "bf16x6" if bf else "winograd")
         wcfg, wpad = pick_wino54_tile(c, bf) if f54 else pick_wino_tile(c)
         pack = (lambda w_, p_: pack_wino54_weight_any(w_, p_, bf)) if f54 else (lambda w_, p_: pack_wino_weight_any(w_, p_, bf))
-        flag = 16 if bf else 0                         # FH_WINO_BF16X6
+        name, cfg = wino_entry(wcfg, WINO_BF16X6 if bf else 0)
         us = [pack(torch.randn(c, c, k, generator=g) * 0.02, wpad).to(dev) for k in ks]
         gw = hip.to_device_struct_array([make_wino_group([make_wino_seg(ys[i], us[i], c, k, taps=4 if f54 else 3)], bias, [],
                                                          outs[i], c, wpad, length) for i, k in enumerate(ks)], dev)
@@ -178,11 +168,8 @@ def measure_act_conv_pair(device, blocks, c=192, length=60000, warm=60, reps=100
         hip.check(lib.fh_act_set_blocks_per_cu(blocks), "fh_act_set_blocks_per_cu")
         try:
             def pair():
-                hip.check(lib.fh_act1d_grouped_pm_f32(ga.data_ptr(), len(ks), 1, c, length, 1, 1, st), "fh_act1d_grouped_pm_f32")
-                if f54:
-                    hip.check(lib.fh_conv_wino54_f32(gw.data_ptr(), len(ks), 1, wpad, length, 1, 0, (wcfg & 15) | flag, st), "fh_conv_wino54_f32")
-                else:
-                    hip.check(lib.fh_conv_wino_f32(gw.data_ptr(), len(ks), 1, wpad, length, 1, 0, wcfg | flag, st), "fh_conv_wino_f32")
+                enqueue(lib.fh_act1d_grouped_pm_f32, (ga.data_ptr(), len(ks), 1, c, length, 1, 1, st))
+                enqueue(getattr(lib, name), (gw.data_ptr(), len(ks), 1, wpad, length, 1, 0, cfg, st))
             for _ in range(warm):
                 pair()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -243,111 +230,95 @@ def ensure_act_blocks(device, choice):
 calibrate_act_occupancy.last_measurement = None
 
 
-def launch_step(voc, s, B, st):
+def wino_entry(wcfg, flag, ragged=False):
+    """(library entry's name, its tile_cfg argument) of a Winograd launch with plan tile id `wcfg` (| mapping / alignment flags): the
+    F(5,4) kernel takes the tile in the low four bits, the F(4,3) kernel the whole id; flag: FH_WINO_BF16X6 or 0."""
+    f54 = wcfg & WINO_F54
+    return ("fh_conv_wino54" if f54 else "fh_conv_wino") + ("_ragged_f32" if ragged else "_f32"), ((wcfg & 15) if f54 else wcfg) | flag
+
+
+def narrow_entry(flags, cmax):
+    """(library entry's name, its arguments behind the dilation) of a narrow-stage launch with plan flags `flags`."""
+    return ("fh_narrow_conv_bf16x6_f32", (flags & 1,)) if flags & AMP_DIRECT else ("fh_amp_actconv_f32", (cmax, flags))
+
+
+def enqueue(fn, args, timing=None):
+    """One call of the library entry `fn` on the stream in `args`.  timing: None, or the list that receives the launch's (start, end) events."""
+    if timing is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    rc = fn(*args)
+    if rc:
+        hip.check(rc, fn.__name__)
+    if timing is not None:
+        e1.record()
+        timing.append((e0, e1))
+
+
+# ---- one function per step kind (planner's records): (library, voc, step, batch, stream, address of the ragged plan's descriptor blob).
+# voc.conv_timing / voc.act_timing, when lists, receive one event pair per conv / convt / wino / amp and per act launch, in launch
+# order (bench.py zips them with plan["conv_launches"]); the ragged kinds record nothing.  Enqueue only: graph-capturable. -----------
+def _conv(L, voc, s, B, st, base):
+    enqueue(L.fh_conv_grouped_f32, (s.desc.data_ptr(), s.ng, B, s.cpad, s.n_len, s.tcfg, s.ck, st), voc.conv_timing)
+
+def _convt(L, voc, s, B, st, base):
+    enqueue(L.fh_conv_transpose_fused_f32, (s.desc.data_ptr(), s.ng, B, s.cpad, s.n_len, s.tcfg, s.phases, st), voc.conv_timing)
+
+def _wino(L, voc, s, B, st, base):
+    name, cfg = wino_entry(s.wcfg, voc.wino_flag)
+    enqueue(getattr(L, name), (s.desc.data_ptr(), s.ng, s.batch, s.wpad, s.length, s.dil, s.pm, cfg, st), voc.conv_timing)
+
+def _amp(L, voc, s, B, st, base):
+    name, tail = narrow_entry(s.flags, s.cmax)
+    enqueue(getattr(L, name), (s.desc.data_ptr(), s.ng, s.tiles.data_ptr(), s.n_tiles, s.c, s.dil, *tail, st), voc.conv_timing)
+
+def _act(L, voc, s, B, st, base):
+    enqueue(L.fh_act1d_grouped_pm_f32, (s.desc.data_ptr(), s.ng, B, s.c, s.length, s.din, s.dout, st), voc.act_timing)
+
+def _mean(L, voc, s, B, st, base):
+    enqueue(L.fh_mean_f32, (s.a.data_ptr(), s.b.data_ptr(), s.c.data_ptr() if s.c is not None else None, s.out.data_ptr(), s.n, s.scale, st))
+
+def _sum(L, voc, s, B, st, base):
+    arr = (C.c_void_p * len(s.srcs))(*[t.data_ptr() for t in s.srcs])
+    enqueue(L.fh_sum_f32, (arr, len(s.srcs), s.out.data_ptr(), s.n, s.scale, st))
+
+def _post(L, voc, s, B, st, base):
+    enqueue(L.fh_conv_post_tanh_f32, (s.x.data_ptr(), voc.post_w.data_ptr(), voc.post_b.data_ptr(), s.wav.data_ptr(), B, s.c, s.length, voc.post_k, st))
+
+def _rwino(L, voc, s, B, st, base):
+    name, cfg = wino_entry(s.wcfg, voc.wino_flag, ragged=True)
+    enqueue(getattr(L, name), (base + s.off, s.ng, s.wpad, s.maxlen, s.dil, s.pmflag, cfg, base + s.off_map, s.n_runs, st))
+
+def _rconv(L, voc, s, B, st, base):
+    enqueue(L.fh_conv_grouped_f32, (base + s.off, s.ng, 1, s.cpad, s.maxlen, s.tcfg, s.ck, st))
+
+def _rconvt(L, voc, s, B, st, base):
+    enqueue(L.fh_conv_transpose_fused_f32, (base + s.off, s.ng, 1, s.cpad, s.maxlen, s.tcfg, s.phases, st))
+
+def _ramp(L, voc, s, B, st, base):
+    name, tail = narrow_entry(s.flags, s.cmax)
+    enqueue(getattr(L, name), (base + s.off, s.ng, base + s.off_tiles, s.n_tiles, s.c, s.dil, *tail, st))
+
+def _ract(L, voc, s, B, st, base):
+    enqueue(L.fh_act1d_ragged_f32, (base + s.off, s.ng, s.c, s.din, s.dout, s.tiles, s.mult4, st))
+
+def _rsum(L, voc, s, B, st, base):
+    enqueue(L.fh_sum_multi_f32, (base + s.off, s.n_jobs, s.max_n, st))
+
+
+LAUNCH = dict(conv=_conv, convt=_convt, wino=_wino, amp=_amp, act=_act, mean=_mean, sum=_sum, post=_post,
+              rwino=_rwino, rconv=_rconv, rconvt=_rconvt, ramp=_ramp, ract=_ract, rsum=_rsum)
+
+
+def launch_step(voc, s, B, st, base=0):          # (one step, for callers outside; run_steps does the same lookup in its loop)
+    LAUNCH[s.kind](hip.lib(), voc, s, B, st, base)
+
+
+def run_steps(voc, steps, B, st, base=0):
     L = hip.lib()
-    if s[0] == "conv":
-        _, d, ng, cpad, n_len, tcfg, ck, _flops = s
-        timing = voc.conv_timing          # optional list of (start, end) events around conv launches
-        if timing is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        hip.check(L.fh_conv_grouped_f32(d.data_ptr(), ng, B, cpad, n_len, tcfg, ck, st), "fh_conv_grouped_f32")
-        if timing is not None:
-            e1.record()
-            timing.append((e0, e1))
-    elif s[0] == "wino":
-        _, d, ng, wpad, length, dil, _flops, wcfg, pm, bb = s
-        timing = voc.conv_timing
-        if timing is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        if wcfg & WINO_F54:
-            hip.check(L.fh_conv_wino54_f32(d.data_ptr(), ng, bb, wpad, length, dil, pm, (wcfg & 15) | voc.wino_flag, st), "fh_conv_wino54_f32")
-        else:
-            hip.check(L.fh_conv_wino_f32(d.data_ptr(), ng, bb, wpad, length, dil, pm, wcfg | voc.wino_flag, st), "fh_conv_wino_f32")
-        if timing is not None:
-            e1.record()
-            timing.append((e0, e1))
-    elif s[0] == "convt":
-        _, d, ng, cpad, n_len, tcfg, phases, _flops = s
-        timing = voc.conv_timing
-        if timing is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        hip.check(L.fh_conv_transpose_fused_f32(d.data_ptr(), ng, B, cpad, n_len, tcfg, phases, st), "fh_conv_transpose_fused_f32")
-        if timing is not None:
-            e1.record()
-            timing.append((e0, e1))
-    elif s[0] == "amp":
-        _, d, ng, tiles, nt, c, dil, cmax, flags, _flops = s
-        timing = voc.conv_timing
-        if timing is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        if flags & AMP_DIRECT:
-            hip.check(L.fh_narrow_conv_bf16x6_f32(d.data_ptr(), ng, tiles.data_ptr(), nt, c, dil, flags & 1, st), "fh_narrow_conv_bf16x6_f32")
-        else:
-            hip.check(L.fh_amp_actconv_f32(d.data_ptr(), ng, tiles.data_ptr(), nt, c, dil, cmax, flags, st), "fh_amp_actconv_f32")
-        if timing is not None:
-            e1.record()
-            timing.append((e0, e1))
-    elif s[0] == "mean":
-        _, a, b_, c_, out, n, scale = s
-        hip.check(L.fh_mean_f32(a.data_ptr(), b_.data_ptr(), c_.data_ptr() if c_ is not None else None,
-                                out.data_ptr(), n, scale, st), "fh_mean_f32")
-    elif s[0] == "sum":
-        _, srcs, out, n, scale = s
-        arr = (C.c_void_p * len(srcs))(*[t.data_ptr() for t in srcs])
-        hip.check(L.fh_sum_f32(arr, len(srcs), out.data_ptr(), n, scale, st), "fh_sum_f32")
-    elif s[0] == "act":
-        _, d, ng, c, length, din, dout = s
-        timing = voc.act_timing           # optional list of (start, end) events around activation launches
-        if timing is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        hip.check(L.fh_act1d_grouped_pm_f32(d.data_ptr(), ng, B, c, length, din, dout, st), "fh_act1d_grouped_pm_f32")
-        if timing is not None:
-            e1.record()
-            timing.append((e0, e1))
-    else:
-        _, x, wav, c, length = s
-        hip.check(L.fh_conv_post_tanh_f32(x.data_ptr(), voc.post_w.data_ptr(), voc.post_b.data_ptr(),
-                                          wav.data_ptr(), B, c, length, voc.post_k, st), "fh_conv_post_tanh_f32")
-
-
-def run_steps(voc, steps, B, st):
     for s in steps:
-        launch_step(voc, s, B, st)
+        LAUNCH[s.kind](L, voc, s, B, st, base)
 
 
 def run_ragged_steps(voc, rp):
-    L, st, base = hip.lib(), hip.stream(), rp["desc"].data_ptr()
-    for s in rp["steps"]:
-        if s[0] == "rwino":
-            _, off, ng, wpad, maxlen, dil, wcfg, pmflag, off_map, n_runs = s
-            if wcfg & WINO_F54:
-                hip.check(L.fh_conv_wino54_ragged_f32(base + off, ng, wpad, maxlen, dil, pmflag, (wcfg & 15) | voc.wino_flag, base + off_map,
-                                                      n_runs, st), "fh_conv_wino54_ragged_f32")
-            else:
-                hip.check(L.fh_conv_wino_ragged_f32(base + off, ng, wpad, maxlen, dil, pmflag, wcfg | voc.wino_flag,
-                                                    base + off_map, n_runs, st), "fh_conv_wino_ragged_f32")
-        elif s[0] == "rconv":
-            _, off, ng, cpad, maxlen, tcfg, ck = s
-            hip.check(L.fh_conv_grouped_f32(base + off, ng, 1, cpad, maxlen, tcfg, ck, st), "fh_conv_grouped_f32")
-        elif s[0] == "ract":
-            _, off, ng, c, din, dout, tiles, mult4 = s
-            hip.check(L.fh_act1d_ragged_f32(base + off, ng, c, din, dout, tiles, mult4, st), "fh_act1d_ragged_f32")
-        elif s[0] == "rconvt":
-            _, off, ng, cpad, maxlen, tcfg, phases = s
-            hip.check(L.fh_conv_transpose_fused_f32(base + off, ng, 1, cpad, maxlen, tcfg, phases, st), "fh_conv_transpose_fused_f32")
-        elif s[0] == "ramp":
-            _, off, ng, off_t, nt, c, dil, cmax, flags = s
-            if flags & AMP_DIRECT:
-                hip.check(L.fh_narrow_conv_bf16x6_f32(base + off, ng, base + off_t, nt, c, dil, flags & 1, st), "fh_narrow_conv_bf16x6_f32")
-            else:
-                hip.check(L.fh_amp_actconv_f32(base + off, ng, base + off_t, nt, c, dil, cmax, flags, st), "fh_amp_actconv_f32")
-        elif s[0] == "rsum":
-            _, off, nj, max_n = s
-            hip.check(L.fh_sum_multi_f32(base + off, nj, max_n, st), "fh_sum_multi_f32")
-        else:
-            launch_step(voc, s, 1, st)
+    run_steps(voc, rp["steps"], 1, hip.stream(), rp["desc"].data_ptr())

@@ -460,3 +460,29 @@ def test_plan_switches_are_read_when_the_model_is_built(monkeypatch):
     voc2 = _cpu_vocoder("SYNTH_CFG")
     kinds2 = [s_[0] for s_ in voc2.plan(1, 50)["steps"]]
     assert "sum" not in kinds2 and "convt" not in kinds2 and kinds2.count("act") == 37
+
+
+@pytest.mark.parametrize("cfgname", ["SYNTH_CFG", "ODD_CFG", "NK5_AMP2_CFG", "PAD_CFG"])
+def test_plan_steps_are_named_records_of_their_kind(cfgname):
+    """Every step of a plan and of a ragged plan is the NamedTuple of its kind (planner.STEP_TYPES): field 0 is the kind that
+    runtime's dispatch table is keyed by, the fields keep their positions, and every kind has a function that enqueues it."""
+    from flowhigh_amd import planner, runtime
+    assert set(runtime.LAUNCH) == set(planner.STEP_TYPES)
+    assert all(issubclass(t, tuple) and t._fields[0] == "kind" for t in planner.STEP_TYPES.values())
+    voc = _cpu_vocoder(cfgname)
+    steps = [s for n in (7, 50, 333) for s in voc.plan(1, n)["steps"]] + voc.plan(2, 40)["steps"]
+    if cfgname == "SYNTH_CFG":              # ... and a direct-form model: between them every record class occurs
+        from flowhigh_amd.vocoder import Vocoder
+        direct = Vocoder(synth.SYNTH_CFG, synth.make_vocoder_state_dict(synth.SYNTH_CFG, 1), "cpu", conv_form="direct")
+        for v in (voc, direct):
+            steps += v.plan(1, 50)["steps"] + v.plan_ragged([50, 333, 50, 120])["steps"]
+        assert {s.kind for s in steps} == set(planner.STEP_TYPES)
+    for s in steps:
+        assert type(s) is planner.STEP_TYPES[s.kind] and s.kind == s[0] and tuple(s) == tuple(getattr(s, f) for f in s._fields)
+
+
+def test_wino_run_len_is_the_kernels():
+    """planner.wino_run_len (launch model, block mapping, ragged run maps) against both Winograd launchers' own run length."""
+    from flowhigh_amd import hip, planner
+    for n_tiles in range(1, 4097):
+        assert planner.wino_run_len(n_tiles) == hip.lib().fh_wino_run_len(n_tiles) == hip.lib().fh_wino54_run_len(n_tiles)

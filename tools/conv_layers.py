@@ -22,7 +22,7 @@ p["mel_in"].copy_(mel.transpose(1, 2).to('cuda:0'))
 for _ in range(3):
     voc.run(p)
 torch.cuda.synchronize()
-convs = [s for s in p['steps'] if s[0] in ('conv', 'wino', 'convt', 'amp')]
+convs = [s for s in p['steps'] if s.kind in ('conv', 'wino', 'convt', 'amp')]
 launches = p["conv_launches"]                     # (family, executed FLOPs, algorithmic FLOPs) per conv launch: planner
 assert len(convs) == len(launches)
 acc = [0.0] * len(convs)
@@ -37,19 +37,19 @@ voc.conv_timing = None
 tot_f = tot_e = tot_t = 0.0
 print(f"{'#':>3} {'family':>14} {'tile':>8} {'grp':>3} {'cpad':>5} {'n_len':>7} {'d':>2} {'blocks':>6} {'alg GFLOP':>9} {'exec GFLOP':>10} {'us':>8} {'exec TF/s':>9}")
 for i, (s, (fam, ex, fl)) in enumerate(zip(convs, launches)):
-    d_ = 1
-    if s[0] == 'wino':
-        _, d, ng, cpad, n_len, d_, _fl, wcfg, _pm = s[:9]
-        f54, wcfg = wcfg & V.WINO_F54, wcfg & 15
-        bm, bn = V._WINO_TILES[wcfg | f54]
-        blocks = ng * s[9] * (cpad // bm) * V.wino_n_tiles(wcfg | f54, n_len, d_, _pm)
-    elif s[0] == 'amp':
-        _, d, ng, tiles, nt, c, d_ = s[:7]
-        bn = V.hip.lib().fh_narrow_tile_len() if s[9] & V.AMP_DIRECT else V.amp_tile_len(d_)
-        bm, cpad, n_len, blocks = c, c, 0, nt
+    ng, d_ = s.ng, 1
+    if s.kind == 'wino':
+        cpad, n_len, d_ = s.wpad, s.length, s.dil
+        tile = s.wcfg & (15 | V.WINO_F54)
+        bm, bn = V._WINO_TILES[tile]
+        blocks = ng * s.batch * (cpad // bm) * V.wino_n_tiles(tile, n_len, d_, s.pm)
+    elif s.kind == 'amp':
+        d_ = s.dil
+        bn = V.hip.lib().fh_narrow_tile_len() if s.flags & V.AMP_DIRECT else V.amp_tile_len(d_)
+        bm, cpad, n_len, blocks = s.c, s.c, 0, s.n_tiles
     else:
-        _, d, ng, cpad, n_len, tcfg = s[:6]
-        bm, bn = TILES[tcfg]
+        cpad, n_len = s.cpad, s.n_len
+        bm, bn = TILES[s.tcfg]
         blocks = ng * B * (cpad // bm) * -(-n_len // bn)
     tot_f += fl; tot_e += ex; tot_t += acc[i]
     print(f"{i:3d} {fam:>14} {bm:>4}x{bn:<3} {ng:3d} {cpad:5d} {n_len:7d} {d_:2d} {blocks:6d} {fl/1e9:9.2f} {ex/1e9:10.2f} {acc[i]:8.1f} {ex/acc[i]/1e6:9.1f}")

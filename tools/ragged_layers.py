@@ -32,6 +32,7 @@ for _ in range(R):
         acc[i] += a.elapsed_time(b) * 1e3 / R
 tot = {}
 for s, t in zip(steps, acc):
-    tot[s[0]] = tot.get(s[0], 0.0) + t
-    print(f"{s[0]:6s} {str(s[2:]):60s} {t:9.1f} us")
+    tot[s.kind] = tot.get(s.kind, 0.0) + t
+    args = {f: v for f, v in s._asdict().items() if isinstance(v, (int, float))}          # (the launch's scalar arguments, by name)
+    print(f"{s.kind:6s} {str(args):60s} {t:9.1f} us")
 print({k: round(v / 1e3, 3) for k, v in tot.items()}, "ms; total", round(sum(acc) / 1e3, 3), "ms for", sum(frames) / 100, "s of audio")

@@ -22,7 +22,7 @@ fs, ws = series(fetch_dir, 'FETCH_SIZE'), series(write_dir, 'WRITE_SIZE')
 cfg = synth.SYNTH_CFG
 voc = Vocoder(cfg, synth.make_vocoder_state_dict(cfg, 0), 'cpu')
 p = voc.plan(1, 1000)
-convs = [(s, m) for s, m in zip(p['steps'], p['meta']) if s[0] in ('conv', 'wino')]
+convs = [(s, m) for s, m in zip(p['steps'], p['meta']) if s.kind in ('conv', 'wino')]
 n = len(convs)
 assert len(fs) % n == 0 and len(fs) == len(ws), (len(fs), len(ws), n)
 fs, ws = fs[-n:], ws[-n:]                   # the last (timed) step
@@ -30,17 +30,17 @@ print(f"{'#':>3} {'kind':>5} {'C':>5} {'L':>7} {'read MB':>8} {'alg':>7} {'x':>5
 tot = [0.0] * 4
 for i, ((s, (key, groups)), f, w) in enumerate(zip(convs, fs, ws)):
     rd, wr = 2.0 * f * 1024 / 1e6, w * 1024 / 1e6
-    kind = s[0]
-    if s[0] == 'wino':
-        _, _d, ng, wpad, length, dil, _fl, wcfg, pm, bb = s
-        kind = 'winoR' if wcfg & 32 else 'wino'
-        a_in = sum(g.seg[j].cin * length * 4 for g in groups for j in range(g.nseg)) * (1 if bb == 1 and ng > 3 else 1)
+    kind = s.kind
+    if kind == 'wino':
+        wpad, length = s.wpad, s.length
+        kind = 'winoR' if s.wcfg & 32 else 'wino'
+        a_in = sum(g.seg[j].cin * length * 4 for g in groups for j in range(g.nseg))
         a_res = sum(g.nres * g.cout * length * 4 for g in groups)
         a_out = sum(g.cout * length * 4 * max(1, g.out_stride) / max(1, g.out_stride) for g in groups)
         wts = sum(g.seg[j].cin * g.seg[j].ngrp * 6 * wpad * 4 for g in groups for j in range(g.nseg))
         c = groups[0].seg[0].cin
     else:
-        _, _d, ng, cpad, n_len, tcfg, ck, _fl = s
+        cpad, n_len = s.cpad, s.n_len
         length = n_len
         a_in = sum(g.seg[j].cin * g.lin * 4 for g in groups for j in range(g.nseg))
         a_res = sum(g.nres * g.cout * n_len * 4 for g in groups)
