@@ -25,11 +25,12 @@
 // Block -> work mapping is XCD aware: blocks with equal (id mod 8) share an L2; the n-tiles of one
 // (group, batch, co-tile) panel are dealt to one XCD in runs of 8, so the weight tiles they share
 // are fetched into that L2 once.
+// The tile table, the block mapping and the epilogue are shared with the bf16 x 6 form of this kernel (conv_mfma_bf.hip):
+// conv_mfma_common.h, conv_mfma_epilogue.h.
+#include "conv_mfma_common.h"
 #include "fh_common.h"
 
 namespace {
-
-constexpr int NT_RUN = 8;       // n-tiles of a panel that run together on one XCD
 
 template <int MT, int NT, int WM, int WN, int CK>
 struct ConvCfg {
@@ -77,22 +78,7 @@ __global__ __launch_bounds__(256, (MT * NT * PH <= 4 && !(MT == 1 && NT == 4 && 
   float* xs = lds + 2 * BM * WP;
   int* toff = reinterpret_cast<int*>(lds + Cfg::LDS_FLOATS);   // [seg][tap] column shift of each tap
 
-  // ---- block -> (panel, n tile); panels = (group, batch, co tile), heavy groups first ----
-  const int panels = n_groups * batch * co_tiles;
-  const int runs_per_panel = (n_tiles + NT_RUN - 1) / NT_RUN;
-  const int total_runs = panels * runs_per_panel;
-  const int bid = blockIdx.x;
-  const int slot = bid >> 3;
-  const int run = (slot / NT_RUN) * 8 + (bid & 7);
-  if (run >= total_runs) return;
-  // (runtime integer divisions are done on the VALU: pin the results back to SGPRs)
-  const int panel = uni(run / runs_per_panel);
-  const int ntile = uni((run % runs_per_panel) * NT_RUN + (slot % NT_RUN));
-  if (ntile >= n_tiles) return;
-  const int cot = uni(panel % co_tiles);
-  const int gb = uni(panel / co_tiles);
-  const int b = uni(gb % batch);
-  const fh_conv_group* __restrict__ G = groups + uni(gb / batch);
+  FH_CONV_BLOCK_MAP(groups, n_groups, batch, co_tiles, n_tiles);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -301,116 +287,16 @@ __global__ __launch_bounds__(256, (MT * NT * PH <= 4 && !(MT == 1 && NT == 4 && 
     }
   }
 
-  // ---- epilogue: bias + residuals, scale, strided store -------------------------------------
-  // One buffer descriptor per tensor spans this batch item's [cout, lout] slab, so rows past
-  // cout fall out of range by themselves; columns past n_len get an out-of-range offset.  Every
-  // load and store is then unconditional (no exec-mask branches) and can be issued in bulk.
-  const int nres = uni(G->nres);
-  const float scale = G->scale;
-  const int cout = uni(G->cout), lout = uni(G->lout), n_len = uni(G->n_len);
-  const int ostride = uni(G->out_stride), ophase = uni(G->out_phase);
-  const float* __restrict__ bias = uni(G->bias);
-  const size_t slab = (size_t)b * cout * lout;
-  const unsigned slab_bytes = (unsigned)cout * (unsigned)lout * 4u;
-  const __amdgpu_buffer_rsrc_t ro = make_rsrc(uni((const float*)G->out) + slab, slab_bytes);
-  const __amdgpu_buffer_rsrc_t rr0 = make_rsrc(nres > 0 ? uni(G->res[0]) + slab : nullptr, nres > 0 ? slab_bytes : 0u);
-  const __amdgpu_buffer_rsrc_t rr1 = make_rsrc(nres > 1 ? uni(G->res[1]) + slab : nullptr, nres > 1 ? slab_bytes : 0u);
-  const __amdgpu_buffer_rsrc_t rr2 = make_rsrc(nres > 2 ? uni(G->res[2]) + slab : nullptr, nres > 2 ? slab_bytes : 0u);
-  unsigned coloff[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int n = n0 + (wn * NT + nt) * 32 + l31;
-    coloff[nt] = n < n_len ? (unsigned)(n * ostride + ophase) * 4u : 0x80000000u;
-  }
-  if constexpr (PH > 1) {
-    // out[co, PH n + p] for p < PH: PH consecutive floats per lane, lanes on consecutive positions: whole lines per wave store
-    // (ostride == PH, ophase == 0, no residuals: checked by the launcher / the host)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = co0 + (wm * MT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const float bv = (bias && co < cout) ? bias[co] : 0.f;
-        const unsigned rowoff = (unsigned)co * (unsigned)lout * 4u;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-          const unsigned off = (co < cout) ? rowoff + coloff[nt] : 0x80000000u;
-          if constexpr (PH == 2) {
-            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-            const u32x2 v = {__float_as_uint((acc[0][mt][nt][r] + bv) * scale), __float_as_uint((acc[1][mt][nt][r] + bv) * scale)};
-            __builtin_amdgcn_raw_buffer_store_b64(v, ro, off, 0, 0);
-          } else {
-            typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-            const u32x3 v = {__float_as_uint((acc[0][mt][nt][r] + bv) * scale), __float_as_uint((acc[1][mt][nt][r] + bv) * scale),
-                             __float_as_uint((acc[PH - 1][mt][nt][r] + bv) * scale)};
-            __builtin_amdgcn_raw_buffer_store_b96(v, ro, off, 0, 0);
-          }
-        }
-      }
-    return;
-  }
-  auto& acc1 = acc[0];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      float v[4][NT];
-      unsigned off[4][NT];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int co = co0 + (wm * MT + mt) * 32 + q + 8 * g4 + 4 * lh;
-        const float bv = (bias && co < cout) ? bias[co] : 0.f;
-        const unsigned rowoff = (unsigned)co * (unsigned)lout * 4u;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-          off[q][nt] = (co < cout) ? rowoff + coloff[nt] : 0x80000000u;
-          v[q][nt] = acc1[mt][nt][4 * g4 + q] + bv;
-        }
-      }
-      if (nres > 0) {
-        float t0[4][NT];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt)
-            t0[q][nt] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr0, off[q][nt], 0, 0));
-        if (nres > 1) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-              t0[q][nt] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr1, off[q][nt], 0, 0));
-        }
-        if (nres > 2) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-              t0[q][nt] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr2, off[q][nt], 0, 0));
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt) v[q][nt] += t0[q][nt];
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[q][nt] * scale), ro, off[q][nt], 0, 0);
-    }
-  }
+  // (kernel body fragment: reads PH, MT, NT, acc, G, b, co0, n0, wm, wn, l31, lh of this scope -- see the header's static_asserts)
+#include "conv_mfma_epilogue.h"
 }
 
 template <int MT, int NT, int WM, int WN, int CK, int PH = 1>
 int launch_conv(const fh_conv_group* groups, int n_groups, int batch, int cout_pad, int n_len,
                 hipStream_t stream) {
   using Cfg = ConvCfg<MT, NT, WM, WN, CK>;
-  const int co_tiles = cout_pad / Cfg::BM;
-  const int n_tiles = fh_cdiv(n_len, Cfg::BN);
-  const long long panels = (long long)n_groups * batch * co_tiles;
-  const long long runs = panels * fh_cdiv(n_tiles, NT_RUN);
-  const long long blocks = (long long)fh_cdiv(runs, 8) * 8 * NT_RUN;
+  int co_tiles, n_tiles;
+  const long long blocks = conv_grid_blocks(n_groups, batch, cout_pad, n_len, Cfg::BM, Cfg::BN, &co_tiles, &n_tiles);
   FH_CHECK_ARG(blocks > 0 && blocks < (1ll << 31), "fh_conv_grouped_f32: grid too large");
   hipLaunchKernelGGL((conv_mfma_kernel<MT, NT, WM, WN, CK, PH>), dim3((unsigned)blocks), dim3(256), 0, stream,
                      groups, n_groups, batch, co_tiles, n_tiles);
@@ -476,10 +362,6 @@ __global__ __launch_bounds__(256) void conv_post_tanh_vec_kernel(const float* __
   const f32x4 o = {tanhf(acc[0]), tanhf(acc[1]), tanhf(acc[2]), tanhf(acc[3])};
   *reinterpret_cast<f32x4*>(out + (size_t)b * len + t) = o;
 }
-
-struct TileInfo { int bm, bn; };
-constexpr TileInfo kTiles[] = {{128, 128}, {192, 128}, {96, 256}, {64, 256}, {32, 512}, {128, 64}, {96, 128}};
-constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
 
 }  // namespace
 

@@ -63,7 +63,7 @@ class FlowNet:
         g = lambda name: sd[FH + name].detach().float().cpu()
         self.depth, self.heads = depth, heads
         # bf: the linears run in the bf16 x 6 form (gemm_bf.hip: six bf16 MFMAs per product over exact three-piece splits,
-        # fp32-grade; the model's conv_form = 'bf16x6'): their weights are stored split (6 bytes per weight)
+        # fp32-grade; the model's conv_form = 'bf16x6' or 'direct_bf16x6'): their weights are stored split (6 bytes per weight)
         self.bf = bool(bf)
         # attn_form: 'f32' (attention.hip) | 'bf16x6' (attention_bf.hip: the two products of attention in the same six-MFMA form,
         # the softmax unchanged).  The entry pair is picked here, once; a missing entry is an error at the first forward.
@@ -71,10 +71,11 @@ class FlowNet:
         self.attn_form = resolve_attn_form(attn_form)
         self._attn, self._attn_seg = (("fh_attention_bf16x6_f32", "fh_attention_bf16x6_seg_f32") if self.attn_form == "bf16x6"
                                       else ("fh_attention_f32", "fh_attention_seg_f32"))
-        if getattr(W, "form", None) is not None and (W.form == "bf16x6") != self.bf:
+        from .planner import use_gemm_bf16x6
+        if getattr(W, "form", None) is not None and use_gemm_bf16x6(W.form) != self.bf:
             # (a blob holds the linears in ONE form: asking it for the other would fail on the first missing key)
             raise ValueError(f"the weight blob was packed for conv_form={W.form!r}: its linears are "
-                             f"{'split into bf16 pieces' if W.form == 'bf16x6' else 'fp32'}, this model asks for the other form")
+                             f"{'split into bf16 pieces' if use_gemm_bf16x6(W.form) else 'fp32'}, this model asks for the other form")
         if self.bf:
             from .packing import pack_gemm_bf_weight
             dev_w = lambda key, make: W.dev(key + ".bf3", lambda: pack_gemm_bf_weight(make()))

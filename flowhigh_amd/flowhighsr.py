@@ -217,7 +217,7 @@ class FLowHigh:
             from .planner import resolve_conv_form, use_gemm_bf16x6
             self.net = FlowNet(state_dict, device, depth=depth, store=store, bf=use_gemm_bf16x6(resolve_conv_form(conv_form, conv_bf16x6)[0]),
                                attn_form=attn_form)
-            # conv_form: the arithmetic form of the vocoder's convs, 'auto' | 'winograd' | 'bf16x6' | 'direct'
+            # conv_form: the arithmetic form of the vocoder's convs, 'auto' | 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6'
             # (planner.resolve_conv_form; None: FH_CONV_FORM / the older switches, else 'auto'.  conv_bf16x6: the boolean keyword
             # of rounds 2-5.)  'auto' = the default form, checked once against the direct form through THESE weights when the
             # checkpoint is at hand (probe_conv_form below): a model whose weights amplify the Winograd transforms' rounding is
@@ -319,7 +319,7 @@ class FlowHighSR:
 
     @classmethod
     def from_local(cls, ckpt_dir, device='cuda', conv_form=None, attn_form=None, **kwargs) -> 'FlowHighSR':
-        """from_local of the reference (flowhighsr.py:110-137) + conv_form = 'auto' (default) | 'winograd' | 'bf16x6' | 'direct': the
+        """from_local of the reference (flowhighsr.py:110-137) + conv_form = 'auto' (default) | 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6': the
         arithmetic form of the vocoder's convs (planner.resolve_conv_form; the environment's
         FH_CONV_FORM overrides nothing a caller passes here); attn_form = None | 'f32' (default) | 'bf16x6': the form of the two
         products of attention (planner.resolve_attn_form; no part of a weight blob)."""

@@ -80,6 +80,7 @@ _SIGS = {
     "fh_conv_tile_n": [_I],
     "fh_conv_grouped_f32": [_P, _I, _I, _I, _I, _I, _I, _P],
     "fh_conv_transpose_fused_f32": [_P, _I, _I, _I, _I, _I, _I, _P],
+    "fh_conv_grouped_bf16x6_f32": [_P, _I, _I, _I, _I, _I, _P],
     "fh_sizeof_wino_group": [],
     "fh_wino_tile_m": [_I],
     "fh_phase_len": [_I, _I],
@@ -154,6 +155,11 @@ def lib():
         raise HipError(f"{LIB_PATH} is missing: build it with `python -m flowhigh_amd.build` "
                        "(there is no CPU fallback)")
     L = C.CDLL(str(LIB_PATH))
+    missing = [name for name in EXPORTS if not hasattr(L, name)]
+    if missing:
+        # (entries are added without an ABI bump: a library built before one of them has the right version and not the symbol)
+        raise HipError(f"{LIB_PATH} does not export {', '.join(missing)}: it was built from older sources; rebuild it with "
+                       "`python -m flowhigh_amd.build --force`")
     for name, args in _SIGS.items():
         fn = getattr(L, name)
         fn.argtypes = args

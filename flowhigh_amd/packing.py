@@ -197,6 +197,13 @@ def split_bf3(u):
     return torch.stack([h, m, l], dim=-2).contiguous().view(torch.int16)
 
 
+def pack_conv_bf_weight(w, cout_pad):
+    """Conv1d weight [co, ci, k] (ci % 16 == 0) -> the bf16 x 6 direct kernel's weights (conv_mfma_bf.hip, flowhigh_hip.h:
+    fh_conv_grouped_bf16x6_f32): int16 bf16 bit patterns [ci/16, k, cout_pad, piece h, m, l, 16] -- pack_conv_weight(w, cout_pad, 16)
+    with every row of 16 channels split into its three pieces (the row format of the Winograd bf16 x 6 weights)."""
+    return split_bf3(pack_conv_weight(w, cout_pad, 16))
+
+
 def pack_wino_weight_any(w, cout_pad, bf):
     """pack_wino_weight, in the three-piece bf16 form when bf."""
     u = pack_wino_weight(w, cout_pad)

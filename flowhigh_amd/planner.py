@@ -42,16 +42,21 @@ def wino_ups_min_cin(form):
 #               (gemm_bf.hip); the last two upsamplers stay on the fp32 matrix instructions
 #   'direct'    no Winograd anywhere: the direct implicit-GEMM kernel (fp32 MFMA), ~20 % closer to a float64 run where the
 #               weights' gain is high (profiles/r05_regime_sweep.txt) and ~2 x slower
+#   'direct_bf16x6'  the launch plan of 'direct' with its direct convs on the BF16 matrix cores in the exact three-piece arithmetic of
+#               'bf16x6' (conv_mfma_bf.hip: every conv / closing-conv / unfused-upsampler launch whose segments have cin % 16 == 0),
+#               the narrow stages on narrow_bf.hip and the transformer's linears on gemm_bf.hip as in 'bf16x6'; no Winograd
+#               rounding anywhere; the phase-fused stride-2 upsamplers (0.6 % of the FLOPs) and 8-channel chunks stay on fp32 MFMA
 #   'auto'      DEFAULT_CONV_FORM, unless a load-time probe through the loaded weights (Vocoder.probe_conv_form: the default
 #               form against the direct form on a 20-frame random mel) differs by more than PROBE_LIMIT: then 'direct'
 # Keyword > environment (FH_CONV_FORM; the older switches FH_WINO=0 -> direct, FH_CONV_BF16X6=1 / 0 -> bf16x6 / winograd) > 'auto'.
-CONV_FORMS = ("auto", "winograd", "bf16x6", "direct")
+CONV_FORMS = ("auto", "winograd", "bf16x6", "direct", "direct_bf16x6")
+DIRECT_FORMS = ("direct", "direct_bf16x6")          # the forms without Winograd kernels
 DEFAULT_CONV_FORM = "bf16x6"
 PROBE_LIMIT = 3e-5
 
 
 def resolve_conv_form(conv_form=None, bf16x6=None):
-    """-> (form, from_auto): one of 'winograd' / 'bf16x6' / 'direct', and whether it came from 'auto' (a probe may still change
+    """-> (form, from_auto): one of 'winograd' / 'bf16x6' / 'direct' / 'direct_bf16x6', and whether it came from 'auto' (a probe may still change
     it).  conv_form: the keyword (None: ask the environment); bf16x6: the older boolean keyword (True / False / None)."""
     form = conv_form
     if form is None and bf16x6 is not None:
@@ -87,8 +92,15 @@ def resolve_attn_form(attn_form=None):
 
 
 def _wino_on(form):
-    """Winograd kernels allowed?  form None: the environment (FH_WINO=0 / FH_CONV_FORM=direct switch them off)."""
-    return (resolve_conv_form()[0] if form is None else form) != "direct"
+    """Winograd kernels allowed?  form None: the environment (FH_WINO=0 / FH_CONV_FORM=direct / direct_bf16x6 switch them off)."""
+    return (resolve_conv_form()[0] if form is None else form) not in DIRECT_FORMS
+
+
+def use_direct_bf16x6(form=None):
+    """The direct convs of the model run in the bf16 x 6 form (conv_mfma_bf.hip, fh_conv_grouped_bf16x6_f32) wherever every
+    segment's input channels are a multiple of 16: conv_form='direct_bf16x6'.  Per conv POSITION (channel counts), never per length
+    or batch: a clip gets the same bits alone, batched, ragged, chunked."""
+    return (resolve_conv_form()[0] if form is None else form) == "direct_bf16x6"
 
 
 def use_wino(c, d, form=None):
@@ -308,8 +320,10 @@ def use_amp(c, ks, dils, form=None):
     """Residual-stack convs of a stage that run on the narrow-stage kernel (amp_fused.hip, conv-only form: the activation stays
     a launch of its own): at most 48 channels (a multiple of 8), odd kernels of at most 11 taps, dilations of at most 6.
     A property of the STAGE (channel count and checkpoint configuration), never of the length or the batch.  FH_AMP=0 switches
-    it off (those stages then run as in round 4: F(5,4) 48-row blocks / the direct kernel)."""
-    if os.environ.get("FH_AMP", "1") == "0" or not _wino_on(form):
+    it off (those stages then run as in round 4: F(5,4) 48-row blocks / the direct kernel).  conv_form='direct' has no narrow-stage
+    kernel (amp_fused.hip is a Winograd kernel); 'direct_bf16x6' runs these stages on narrow_bf.hip, a direct conv (use_amp_bf16x6)."""
+    form = resolve_conv_form()[0] if form is None else form
+    if os.environ.get("FH_AMP", "1") == "0" or form == "direct":
         return False
     cmax = max((k - 1) // 2 for k in ks)
     return (c % 8 == 0 and 8 <= c <= 48 and all(k % 2 == 1 and k <= 11 for k in ks)
@@ -341,8 +355,9 @@ def plan_switches():
 def use_gemm_bf16x6(form=None):
     """The transformer's linears of a bf16 x 6 model run in the bf16 x 6 form too (gemm_bf.hip; flow.FlowNet(bf=)).  (The A/B
     against the fp32 GEMM inside a bf16 x 6 model -- 12.89 against 13.02 ms per step, configs[4] 632 against 593 x real time --
-    was run with an environment switch that left with the measurement; conv_form='winograd' is the fp32 path.)"""
-    return (resolve_conv_form()[0] if form is None else form) == "bf16x6"
+    was run with an environment switch that left with the measurement; conv_form='winograd' is the fp32 path.)  So do those of a
+    'direct_bf16x6' model."""
+    return (resolve_conv_form()[0] if form is None else form) in ("bf16x6", "direct_bf16x6")
 
 
 def amp_tile_len(d):
@@ -358,8 +373,9 @@ NARROW_TILE = 256         # fh_narrow_tile_len(): outputs per block and row of t
 def use_amp_bf16x6(form=None):
     """Narrow stages of a bf16 x 6 model run the direct bf16 x 6 kernel (narrow_bf.hip) instead of the fp32-MFMA Winograd one
     (amp_fused.hip, the narrow-stage kernel of conv_form='winograd').  (A/B inside a bf16 x 6 model: same speed, five times
-    closer to float64 -- profiles/r06_narrow_bf16x6.txt; the switch it was run with left with the measurement.)"""
-    return (resolve_conv_form()[0] if form is None else form) == "bf16x6"
+    closer to float64 -- profiles/r06_narrow_bf16x6.txt; the switch it was run with left with the measurement.)  The narrow stages
+    of a 'direct_bf16x6' model run the same kernel."""
+    return (resolve_conv_form()[0] if form is None else form) in ("bf16x6", "direct_bf16x6")
 
 
 def make_amp_seg(x, u, k, center=None, direct=False):
@@ -533,7 +549,8 @@ def make_wino_group(segs, bias, res, out, cout, cpad, length, scale=1.0, stride=
 # the launch's arguments in the order below (desc: the uploaded descriptor array, its host structs are in meta; flops: algorithmic).
 # They stay tuples: hip.ShapeCache sizes a plan by walking tuples / lists / dicts (a slotted object's tensors would not be counted) ---
 STEP_TYPES = {kind: NamedTuple(kind.capitalize() + "Step", [(f, object) for f in ["kind"] + fields.split()]) for kind, fields in dict(
-    conv="desc ng cpad n_len tcfg ck flops",
+    # (bf: the bf16 x 6 entry, fh_conv_grouped_bf16x6_f32, on three-piece weights; ck is 16 then)
+    conv="desc ng cpad n_len tcfg ck flops bf",
     convt="desc ng cpad n_len tcfg phases flops",
     # (wcfg: plan tile id | WINO_XCD_RANGES | WINO_NOVL; pm: phase-major rows; batch: 1 where the groups are per batch item)
     wino="desc ng wpad length dil flops wcfg pm batch",
@@ -544,7 +561,7 @@ STEP_TYPES = {kind: NamedTuple(kind.capitalize() + "Step", [(f, object) for f in
     post="x wav c length",
     # ... of a merged (ragged) plan: off / off_map / off_tiles are byte offsets into the plan's descriptor blob rp["desc"]
     rwino="off ng wpad maxlen dil wcfg pmflag off_map n_runs",
-    rconv="off ng cpad maxlen tcfg ck",
+    rconv="off ng cpad maxlen tcfg ck bf",
     rconvt="off ng cpad maxlen tcfg phases",
     ramp="off ng off_tiles n_tiles c dil cmax flags",
     ract="off ng c din dout tiles mult4",
@@ -605,23 +622,29 @@ class _PlanBuilder:
         return self.parts
 
     # ---- one launch each ----------------------------------------------------------------------------------------
-    def conv(self, groups, cpad, n_len, tcfg, ck):
+    def conv(self, groups, cpad, n_len, tcfg, ck, bf=False):
         """Direct-kernel launch.  Few-block launches (first-stage upsampler, fused stage-closing conv at short
-        sequence lengths) switch from the 128 x 128 to the 128 x 64 tile to fill the 256 CUs."""
+        sequence lengths) switch from the 128 x 128 to the 128 x 64 tile to fill the 256 CUs.  bf: the groups' weights are
+        pack_conv_bf_weight's, the launch runs the bf16 x 6 entry (same tiles, same descriptors)."""
         if tcfg == 0 and len(groups) * self.B * (cpad // 128) * -(-n_len // 128) < 512:
             tcfg = 5
-        self._direct("conv", groups, cpad, n_len, tcfg, ck)
+        if bf and (ck != 16 or any(s.cin % 16 for _, s in _segs(*groups))):
+            raise NotImplementedError("the bf16 x 6 direct kernel takes 16-channel chunks")
+        if bf and any(g.lin * 64 >= 2 ** 31 for g in groups):        # (its slab descriptor spans the 16 rows of a channel chunk)
+            raise NotImplementedError("per-clip rows exceed the range of the bf16 x 6 direct kernel's slab descriptor")
+        self._direct("conv", groups, cpad, n_len, tcfg, ck, bf)
 
     def convt(self, groups, cpad, n_len, tcfg, phases):
         """Direct-kernel launch of phase-fused transposed-conv groups (fh_conv_transpose_fused_f32)."""
         self._direct("convt", groups, cpad, n_len, tcfg, phases)
 
-    def _direct(self, kind, groups, cpad, n_len, tcfg, ck_or_phases):
+    def _direct(self, kind, groups, cpad, n_len, tcfg, ck_or_phases, bf=False):
         flops = sum(2.0 * g.cout * s.cin * s.ntaps * n_len * self.B for g, s in _segs(*groups))
         self.executed += flops
         self.direct += flops
-        self.conv_launches.append(("direct", flops, flops))
-        self.add(make_step(kind, self.upload(groups), len(groups), cpad, n_len, tcfg, ck_or_phases, flops), groups)
+        self.conv_launches.append(("direct_bf16x6" if bf else "direct", flops, flops))
+        tail = (int(bf),) if kind == "conv" else ()
+        self.add(make_step(kind, self.upload(groups), len(groups), cpad, n_len, tcfg, ck_or_phases, flops, *tail), groups)
 
     def wino(self, groups, wpad, length, dil, wcfg, pm=False, flops=None, batch=None, novl=False):
         """Winograd launch; the tile shape is the launch model's (choose_wino_cfg).  batch: launches whose groups are
@@ -710,7 +733,7 @@ class _PlanBuilder:
                 offs = [(t - (ks[i] - 1) // 2) * dil for t in range(ks[i])]
                 groups.append(make_conv_group([make_conv_seg(xs_in[i], e["w"], c, offs)], biases[i], res[i], outs[i],
                                               c, cpad, L, L, L))
-            self.conv(groups, cpad, L, st["tile_cfg"], st["ck"])
+            self.conv(groups, cpad, L, st["tile_cfg"], st["ck"], st["conv_bf"])
         return [[o] for o in outs]
 
     def mixed_dilation_conv(self, st, order, ents, ks, ds, xs_in, outs, res):
@@ -718,7 +741,7 @@ class _PlanBuilder:
         c, cpad, L = st["c"], st["cpad"], self.L
         self.conv([make_conv_group([make_conv_seg(xs_in[n], e["w"], c, [(t - (k - 1) // 2) * d for t in range(k)])],
                                    e["b"], res[n], outs[n], c, cpad, L, L, L)
-                   for n, (e, k, d) in enumerate(zip(ents, ks, ds))], cpad, L, st["tile_cfg"], st["ck"])
+                   for n, (e, k, d) in enumerate(zip(ents, ks, ds))], cpad, L, st["tile_cfg"], st["ck"], st["conv_bf"])
 
     # ---- model sections -------------------------------------------------------------------------------------------
     def conv_pre(self):
@@ -732,7 +755,7 @@ class _PlanBuilder:
         else:
             k7 = [j - 3 for j in range(7)]
             self.conv([make_conv_group([make_conv_seg(self.mel_in, v.pre_w, v.num_mels, k7)], v.pre_b, [], pre, v.c0,
-                                       v.pre_cpad, N, N, N)], v.pre_cpad, N, v.pre_cfg, v.pre_ck)
+                                       v.pre_cpad, N, N, N)], v.pre_cpad, N, v.pre_cfg, v.pre_ck, v.pre_bf)
         return pre
 
     def average(self, ys, out, n, scale, key):
@@ -779,7 +802,7 @@ class _PlanBuilder:
         if st["up_wino"] is None:
             self.conv([make_conv_group([make_conv_seg(cur, ph["w"], st["cin"], ph["offs"])], st["up_b"], [], X, c,
                                        st["cpad"], lin, L, npos if r == 0 else lin, stride=u, phase=r)
-                       for r, ph in enumerate(st["up_phases"])], st["cpad"], npos, st["tile_cfg"], st["up_ck"])
+                       for r, ph in enumerate(st["up_phases"])], st["cpad"], npos, st["tile_cfg"], st["up_ck"], st["up_bf"])
             return
         # (Winograd phase groups: all have `npos` positions, writes at u * n + r >= L are masked: fh_wino_group.out_len)
         xlen, olen = (lin, L) if extra else (0, 0)
@@ -914,7 +937,7 @@ class _PlanBuilder:
         segs = [make_conv_seg(T1[j], e["w"], c, [(t - (k - 1) // 2) * d for t in range(k)])
                 for j, e, k, d in zip(order, ents, ks, ds)]
         self.conv([make_conv_group(segs, st["last_bias"], [xin[j] for j in order], S, c, cpad, L, L, L, scale=scale)],
-                  cpad, L, st["tile_cfg"], st["ck"])
+                  cpad, L, st["tile_cfg"], st["ck"], st["conv_bf"])
 
     def finish(self, cur):
         """activation_post + conv_post + tanh, and the plan record."""
@@ -992,11 +1015,11 @@ def _merge_wino(voc, items, blobs):
 
 
 def _merge_conv(voc, items, blobs):
-    for (cpad, ck), lst in _classes(items, lambda s: (s.cpad, s.ck)):
+    for (cpad, ck, bf), lst in _classes(items, lambda s: (s.cpad, s.ck, s.bf)):
         allg = [(sum(seg.cin * seg.ntaps for _, seg in _segs(g)), s.n_len, g) for s, groups in lst for g in groups]
         allg.sort(key=lambda t: (-t[0], -t[1]))
         tcfg = max(lst, key=lambda t: t[0].n_len)[0].tcfg
-        yield make_step("rconv", _append(blobs, [t[2] for t in allg]), len(allg), cpad, max(t[1] for t in allg), tcfg, ck)
+        yield make_step("rconv", _append(blobs, [t[2] for t in allg]), len(allg), cpad, max(t[1] for t in allg), tcfg, ck, bf)
 
 
 def _merge_convt(voc, items, blobs):

@@ -33,10 +33,12 @@ def conv_wino(groups, batch, cout_pad, length, dilation, device, tile_cfg=0, pha
     return d
 
 
-def conv_grouped(groups, batch, cout_pad, n_len, tile_cfg, device, ck=8):
-    """Upload descriptors and enqueue one grouped conv launch (test / one-off use)."""
+def conv_grouped(groups, batch, cout_pad, n_len, tile_cfg, device, ck=8, bf=False):
+    """Upload descriptors and enqueue one grouped conv launch (test / one-off use).  bf: the bf16 x 6 entry (the groups' weights
+    are pack_conv_bf_weight's; every cin a multiple of 16)."""
     d = hip.to_device_struct_array(groups, device)
-    enqueue(hip.lib().fh_conv_grouped_f32, (d.data_ptr(), len(groups), batch, cout_pad, n_len, tile_cfg, ck, hip.stream()))
+    name, tail = conv_entry(bf, ck)
+    enqueue(getattr(hip.lib(), name), (d.data_ptr(), len(groups), batch, cout_pad, n_len, tile_cfg, *tail, hip.stream()))
     return d
 
 
@@ -237,6 +239,11 @@ def wino_entry(wcfg, flag, ragged=False):
     return ("fh_conv_wino54" if f54 else "fh_conv_wino") + ("_ragged_f32" if ragged else "_f32"), ((wcfg & 15) if f54 else wcfg) | flag
 
 
+def conv_entry(bf, ck):
+    """(library entry's name, its arguments behind tile_cfg) of a direct-kernel launch: the bf16 x 6 entry takes no channel chunk."""
+    return ("fh_conv_grouped_bf16x6_f32", ()) if bf else ("fh_conv_grouped_f32", (ck,))
+
+
 def narrow_entry(flags, cmax):
     """(library entry's name, its arguments behind the dilation) of a narrow-stage launch with plan flags `flags`."""
     return ("fh_narrow_conv_bf16x6_f32", (flags & 1,)) if flags & AMP_DIRECT else ("fh_amp_actconv_f32", (cmax, flags))
@@ -259,7 +266,8 @@ def enqueue(fn, args, timing=None):
 # voc.conv_timing / voc.act_timing, when lists, receive one event pair per conv / convt / wino / amp and per act launch, in launch
 # order (bench.py zips them with plan["conv_launches"]); the ragged kinds record nothing.  Enqueue only: graph-capturable. -----------
 def _conv(L, voc, s, B, st, base):
-    enqueue(L.fh_conv_grouped_f32, (s.desc.data_ptr(), s.ng, B, s.cpad, s.n_len, s.tcfg, s.ck, st), voc.conv_timing)
+    name, tail = conv_entry(s.bf, s.ck)
+    enqueue(getattr(L, name), (s.desc.data_ptr(), s.ng, B, s.cpad, s.n_len, s.tcfg, *tail, st), voc.conv_timing)
 
 def _convt(L, voc, s, B, st, base):
     enqueue(L.fh_conv_transpose_fused_f32, (s.desc.data_ptr(), s.ng, B, s.cpad, s.n_len, s.tcfg, s.phases, st), voc.conv_timing)
@@ -290,7 +298,8 @@ def _rwino(L, voc, s, B, st, base):
     enqueue(getattr(L, name), (base + s.off, s.ng, s.wpad, s.maxlen, s.dil, s.pmflag, cfg, base + s.off_map, s.n_runs, st))
 
 def _rconv(L, voc, s, B, st, base):
-    enqueue(L.fh_conv_grouped_f32, (base + s.off, s.ng, 1, s.cpad, s.maxlen, s.tcfg, s.ck, st))
+    name, tail = conv_entry(s.bf, s.ck)
+    enqueue(getattr(L, name), (base + s.off, s.ng, 1, s.cpad, s.maxlen, s.tcfg, *tail, st))
 
 def _rconvt(L, voc, s, B, st, base):
     enqueue(L.fh_conv_transpose_fused_f32, (base + s.off, s.ng, 1, s.cpad, s.maxlen, s.tcfg, s.phases, st))

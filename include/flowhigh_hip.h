@@ -98,6 +98,20 @@ int fh_conv_grouped_f32(const fh_conv_group* groups, int n_groups, int batch, in
 int fh_conv_transpose_fused_f32(const fh_conv_group* groups, int n_groups, int batch, int cout_pad, int n_len,
                                 int tile_cfg, int phases, void* stream);
 
+/* fh_conv_grouped_f32 in the bf16 x 6 form (conv_mfma_bf.hip; conv_form = 'direct_bf16x6'): the same call sites
+ * (models/bigvgan/models.py:63-72 AMPBlock1 convs, :141-146 ConvTranspose1d as phase groups, :172-194 conv_pre / forward), the same
+ * descriptors (1 .. 3 K segments, tap lists, bias, residuals, scale, out_stride / out_phase, groups of different n_len), the same
+ * tile_cfg ids and cout_pad, the same block -> work mapping.  Every product w x is the six piece-pair v_mfma_f32_32x32x16_bf16
+ * of exact three-piece splits (h h, h m, m h, h l, l h, m m; small terms first) into one fp32 accumulator: fp32-grade sums at
+ * 6 / 16 of the fp32 instruction's matrix-pipe time.  Steps run in (segment, 16-channel chunk, tap) order, so the bits of an
+ * output depend on its (group, channel, position) only, not on tile_cfg, the batch size or the launch it is part of.
+ * Differences: every segment has cin % 16 == 0 (no ck argument), and seg.w points at three-piece weights, bf16 bit patterns
+ * [cin/16][ntaps][cout_pad][piece h, m, l][16] (packing.pack_conv_bf_weight: the fp32 layout with ck = 16, each row of 16
+ * channels split; 6 bytes per weight); x is split on the device.  A descriptor array in pinned host memory is checked by the
+ * launcher (segments, taps, cin % 16); one in device memory is the caller's to get right, as for fh_conv_grouped_f32. */
+int fh_conv_grouped_bf16x6_f32(const fh_conv_group* groups, int n_groups, int batch, int cout_pad, int n_len, int tile_cfg,
+                               void* stream);
+
 /* ------------------------------------------------------------------------------------
  * The same Conv1d call sites (models/bigvgan/models.py:63-72, "same"-padded, stride 1, square
  * cin x cout residual-stack convs) evaluated with the Winograd minimal-filtering identity
