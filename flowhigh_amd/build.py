@@ -8,7 +8,7 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "lib" / "libflowhigh_hip.so"
-SOURCES = ["api_common.hip", "conv_mfma.hip", "conv_mfma_bf.hip", "conv_wino.hip", "conv_wino54.hip", "conv_wino54_bf.hip", "amp_fused.hip", "narrow_bf.hip", "act1d.hip", "gemm_mfma.hip", "gemm_bf.hip", "flow_ops.hip",
+SOURCES = ["api_common.hip", "conv_mfma.hip", "conv_mfma_bf.hip", "conv_wino.hip", "conv_wino54.hip", "conv_wino54_bf.hip", "amp_fused.hip", "narrow_bf.hip", "act1d.hip", "gemm_mfma.hip", "gemm_bf.hip", "flow_ops.hip", "sum_ops.hip",
            "attention.hip", "attention_bf.hip", "frontend.hip", "fft.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-source extra flags.  The bf16 x 6 kernels keep everything beside their MFMAs one result per lane: the SLP vectoriser
@@ -20,10 +20,10 @@ EXTRA_FLAGS = {"conv_wino54_bf.hip": ["-fno-slp-vectorize"], "conv_wino.hip": ["
 # The conv kernels fill every register they are given; a variant that spills a hundred (it happened three times in round 6: the
 # scheduler hoisting the next tile column's work until the file is full) runs its K loop through scratch.  (Round 6 also found
 # such variants computing garbage: an inline-asm prefetch wrote a register the compiler had meanwhile given to something else --
-# fixed at the source, conv_wino.hip: prefetch_a; the limit here is about speed.)
+# fixed at the source, conv_wino_common.h: wino_prefetch_a; the limit here is about speed.)
 RESOURCE_FLAGS = ["-Rpass-analysis=kernel-resource-usage"]
 MAX_SCRATCH_BYTES = 16          # per lane: up to 4 spilled registers (prologue / epilogue values) are tolerated and reported
-HEADERS = ["fh_common.h", "bf16x6.h", "conv_mfma_common.h", "conv_mfma_epilogue.h", "conv_wino54_kernel.h", "attention_softmax.h", "gemm_common.h"]
+HEADERS = ["fh_common.h", "bf16x6.h", "conv_mfma_common.h", "conv_mfma_epilogue.h", "conv_wino_common.h", "conv_wino54_kernel.h", "attention_softmax.h", "gemm_common.h"]
 
 
 def _deps():

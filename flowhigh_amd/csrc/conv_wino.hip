@@ -35,7 +35,7 @@
 // MFMA work per output: 1.5 ceil(k/3) instead of k multiply-adds per channel pair (k = 3 / 7 / 11:
 // 2.0x / 1.56x / 1.83x fewer matrix-core cycles).
 #include "bf16x6.h"
-#include "fh_common.h"
+#include "conv_wino_common.h"
 
 #include <stdlib.h>
 
@@ -58,10 +58,6 @@ constexpr int W_CK = 16;             // input channels per chunk
 constexpr int W_THREADS = 768;       // 12 waves = 6 transform points x 2 tile halves
 constexpr int W_EP = 36;             // pitch (floats) of a COLUMN of the epilogue exchange tiles: 16-byte aligned, and
                                      // 36 col mod 64 takes 16 distinct multiples of 4 over 16 lanes: conflict-free b128
-#ifndef W_RUN_N
-#define W_RUN_N 8
-#endif
-constexpr int W_RUN = W_RUN_N;             // n-blocks of a panel that run together on one XCD
 
 // Wave tile = (32 MT) co x (32 NT) tiles; block tile = (32 MT) co x (64 NT) tiles (256 NT outputs).
 //   <2, 2>: 64 x 512 outputs  (C % 64 == 0)        <3, 1>: 96 x 256 outputs  (C = 96)
@@ -102,31 +98,15 @@ __device__ const int kBtOff[6][4] = {{2, 4, 0, 0}, {2, 4, 1, 3}, {2, 4, 1, 3}, {
 __device__ const float kBtCoef[6][3] = {{-5.f, 0.f, 4.f}, {-4.f, -4.f, 1.f}, {-4.f, -4.f, -1.f},
                                         {-1.f, -1.f, 2.f}, {-1.f, -1.f, -2.f}, {-5.f, 0.f, 4.f}};
 
-struct WSeg {
-  const float* x;
-  const float* u;
-  int cin, ngrp, center, xlen;
-};
-__device__ __forceinline__ WSeg load_wseg(const fh_wino_seg* S) {
-  WSeg w;
-  w.x = uni(S->x);
-  w.u = uni(S->u);
-  w.cin = uni(S->cin);
-  w.ngrp = uni(S->ngrp);
-  w.center = uni(S->center);
-  w.xlen = uni(S->xlen);
-  return w;
-}
-
 // VL: the slab is fetched with 16-byte loads (4 consecutive samples of 2 channels per thread) and written with
 // 8-byte LDS stores; needs contiguous, 16-byte aligned rows: phase-major tensors, or dilation 1 and len % 4 == 0.
 // BF: the transformed weights are stored as three bf16 pieces, [C_in/16][tap group][6][C_out_pad][3][16] (96 bytes per
 // row and chunk: lane (row, half) reads its 8 channels of each piece as one 16-byte load), the B fragments are
 // split in registers, and a 16-channel k-block is six v_mfma_f32_32x32x16_bf16 (bf16x6.h).  The lane <->
 // channel assignment is the one of the fp32 form: lane half h owns channels 8 h .. 8 h + 7 of the chunk.
-// launch constants the block -> work mapping divides by (fh_common.h: fh_fastdiv); rect_*: the xcd_ranges mapping
-struct WDivs {
-  fh_fastdiv run_len, runs_per_panel, co_tiles, batch, dil, rect_r, rect_cr, rect_gb;
+// launch constants the block -> work mapping divides by: the shared ones + rect_*: the xcd_ranges mapping
+struct WDivs : WinoDivs {
+  fh_fastdiv rect_r, rect_cr, rect_gb;
 };
 
 template <int MT, int NT, int SUBS, bool VL, bool BF>
@@ -139,12 +119,7 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
   constexpr int W_SUB = (W_CK / 2) * W_RP2;          // floats of one 16-channel chunk inside a slab buffer
   extern __shared__ __attribute__((aligned(16))) float lds[];      // Cfg::LDS_FLOATS
 
-  // ---- block -> (panel, n block); panels = (group, batch, co tile), heavy groups first ----------
-  const int panels = n_groups * batch * co_tiles;
-  // (a panel's n blocks are cut into equal runs of <= W_RUN: with fixed runs of 8 and 10 blocks per
-  // panel, every other XCD would get the 2-block remainders only)
-  const int runs_per_panel = (int)dv.runs_per_panel.d;
-  const int total_runs = panels * runs_per_panel;
+  // ---- block -> (panel, n block) (conv_wino_common.h), or the xcd_ranges mapping ----------
   const int bid = blockIdx.x;
   const int slot = bid >> 3;
   int panel, ntile;
@@ -167,26 +142,11 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
     panel = gbi * co_tiles + wq;
     ntile = (bid & 7) * tpx + t;
     if (ntile >= n_tiles) return;
-  } else {
-    const int slot_run = fh_div(slot, dv.run_len);
-    int run = slot_run * 8 + (bid & 7);
-    // Ragged launches (groups of different lengths, grid sized for the longest): only the runs that hold real tiles
-    // are launched, listed heavy-first in run_map -- otherwise the empty runs of the short clips, which fall on
-    // the same XCDs for every panel (run r of a panel -> XCD (panel * runs_per_panel + r) % 8), leave the real work
-    // on 2-4 of the 8 XCDs.
-    if (run_map) {
-      if (run >= n_runs) return;
-      run = uni(run_map[run]);
-    }
-    if (run >= total_runs) return;
-    panel = fh_div(run, dv.runs_per_panel);
-    ntile = fh_mod(run, panel, dv.runs_per_panel) * run_len + fh_mod(slot, slot_run, dv.run_len);
-    if (ntile >= n_tiles) return;
+  } else if (!wino_block_work(bid, run_map, n_runs, n_groups * batch * co_tiles, run_len, n_tiles, dv, panel, ntile)) {
+    return;
   }
-  const int gb = fh_div(panel, dv.co_tiles);
-  const int cot = fh_mod(panel, gb, dv.co_tiles);
-  const int gi = fh_div(gb, dv.batch);
-  const int b = fh_mod(gb, gi, dv.batch);
+  int gi, b, cot;
+  wino_split_panel(panel, dv, gi, b, cot);
   const fh_wino_group* __restrict__ G = groups + gi;
   const int tb = fh_div(ntile, dv.dil);              // 256-output block within the phase
   const int ph = fh_mod(ntile, tb, dv.dil);          // phase of the decimated sequence
@@ -220,17 +180,15 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   // ---- loaders ------------------------------------------------------------------------------
-  // Every load below is issued unconditionally from straight-line code ("nothing to load" is a
-  // zero-sized descriptor: the hardware returns 0 without touching memory), so the number of loads
-  // in flight at each use is a compile-time constant and the s_waitcnt the compiler places are
-  // exact; with loads under branches it has to assume the worst path and drains the queue.
+  // Every load below is issued unconditionally from straight-line code (conv_wino_common.h); with loads under branches the
+  // compiler has to assume the worst path and drains the queue.
   // slab: thread (row = tid / 48, tt = tid % 48) stages decimated samples u = tt + 48 i of its row
   const int lrow = tid / 48, ltt = tid % 48;
   const int lds_st = (lrow >> 1) * W_RP2 + ((ltt & 3) * W_P + (ltt >> 2)) * 2 + (lrow & 1);   // + 24 i
   unsigned xreg[W_XPT];
   // (S.xlen > 0: the segment's rows are xlen samples long, not len -- a transposed-conv phase whose output has one
   // sample more than u * its input, plain layout only)
-  auto load_x = [&](const WSeg& S, int chunk, bool valid) {
+  auto load_x = [&](const WinoSeg& S, int chunk, bool valid) {
     const int xl = S.xlen > 0 ? S.xlen : len, xp = S.xlen > 0 ? S.xlen : pitch;
     const __amdgpu_buffer_rsrc_t r =
         make_rsrc(uni(S.x + (size_t)b * S.cin * xp), valid ? (unsigned)(S.cin * xp) * 4u : 0u);
@@ -265,7 +223,7 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
   constexpr int W_NITEM = (W_XQ + 95) / 96;
   const int vp = tid / 96, vt = tid % 96;
   u32x4 xq[2][2];                                      // [item slot][channel of the pair]
-  auto vl_load = [&](const WSeg& S, int chunk, bool valid, int item, int slot) {
+  auto vl_load = [&](const WinoSeg& S, int chunk, bool valid, int item, int slot) {
     const int xl = S.xlen > 0 ? S.xlen : len, xp = S.xlen > 0 ? S.xlen : pitch;      // (xlen % 4 == 0 here: host)
     const __amdgpu_buffer_rsrc_t r =
         make_rsrc(uni(S.x + (size_t)b * S.cin * xp), valid ? (unsigned)(S.cin * xp) * 4u : 0u);
@@ -278,7 +236,7 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
     xq[slot][0] = __builtin_amdgcn_raw_buffer_load_b128(r, ok ? (unsigned)e0 * 4u : 0x80000000u, 0, 0);
     xq[slot][1] = __builtin_amdgcn_raw_buffer_load_b128(r, ok ? (unsigned)(e0 + xp) * 4u : 0x80000000u, 0, 0);
   };
-  auto vl_store = [&](const WSeg& S, int buf, int sub, int item, int slot) {
+  auto vl_store = [&](const WinoSeg& S, int buf, int sub, int item, int slot) {
     const int ub = tb * (4 * W_BT) - S.center;
     const int ua = ub - (ub & 3);                                        // decimated index of slab sample 0
     const int q = vt + 96 * item;
@@ -298,20 +256,16 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
   // A fragments of one step, [mt][half]: half h holds k-steps 4h .. 4h+3
   u32x4 areg[MT][2];
   const int a_lane = (l31 * W_CK + lh * 8) * 4;
-  auto load_a_half = [&](int h, const WSeg& S, int chunk, int g, bool valid) {
-    const float* up = uni(S.u + ((size_t)((chunk * S.ngrp + g) * 6 + xi) * cout_pad + co0) * W_CK);
-    const __amdgpu_buffer_rsrc_t r = make_rsrc(up, valid ? W_BM * W_CK * 4 : 0);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-      areg[mt][h] = __builtin_amdgcn_raw_buffer_load_b128(r, a_lane + mt * 32 * W_CK * 4 + 16 * h, 0, 0);
+  const WinoWts wts = {xi, co0, cout_pad};
+  auto load_a_half = [&](int h, const WinoSeg& S, int chunk, int g, bool valid) {
+    wino_load_a_half<6, W_BM, MT>(areg, h, S, chunk, g, valid, wts, a_lane);
   };
 
   // BF: the three pieces of one step, [mt][piece]
   u32x4 a3[BF ? MT : 1][3];
   const int a3_lane = (l31 * W_A3 + lh * 4) * 4;
-  auto load_a3 = [&](const WSeg& S, int chunk, int g, bool valid) {
-    const float* up = uni(S.u + ((size_t)((chunk * S.ngrp + g) * 6 + xi) * cout_pad + co0) * W_A3);
-    const __amdgpu_buffer_rsrc_t r = make_rsrc(up, valid ? W_BM * W_A3 * 4 : 0);
+  auto load_a3 = [&](const WinoSeg& S, int chunk, int g, bool valid) {
+    const __amdgpu_buffer_rsrc_t r = make_rsrc(wino_a_tile<6, W_A3>(S, chunk, g, wts), valid ? W_BM * W_A3 * 4 : 0);
 #pragma unroll
     for (int mt = 0; mt < (BF ? MT : 1); ++mt)
 #pragma unroll
@@ -319,33 +273,14 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
         a3[mt][pc] = __builtin_amdgcn_raw_buffer_load_b128(r, a3_lane + mt * 32 * W_A3 * 4 + 32 * pc, 0, 0);
   };
 
-  // L2 warm-up of the A tiles of the NEXT chunk (all its tap groups, this wave's xi): the register
-  // prefetch above is only half a step deep, enough for an L2 hit but not for HBM, and the blocks
-  // that share a weight panel run in lockstep, so without this every tile is a first touch for all
-  // of them.  One lane per 128-byte line, lanes 0-31 tap group 2j, lanes 32-63 group 2j + 1; the
-  // result is never used.  The loads are ordinary builtin loads into two registers that the NEXT prefetch "reads" (an empty asm)
-  // before it overwrites them: the compiler then knows when they land.  (Until round 6 this was an inline-asm load into one
-  // register the compiler knew nothing about -- correct only while the allocator happened to keep that register for the
-  // kernel's whole life: every instantiation that spilled moved it, the late write then hit whatever lived there, and the
-  // result was garbage that changed from run to run: tools/exp/ragged_bf_debug.py)
+  // L2 warm-up of the A tiles of the NEXT chunk (conv_wino_common.h)
   unsigned pf[2] = {0u, 0u};
-  auto prefetch_a = [&](const WSeg& S, int chunk, bool valid) {
-    constexpr int ROWF = BF ? W_A3 : W_CK;                                 // floats per weight row and chunk
-    const float* up = uni(S.u + ((size_t)(chunk * S.ngrp * 6 + xi) * cout_pad + co0) * ROWF);
-    const unsigned gstride = 6u * (unsigned)cout_pad * ROWF * 4u;          // bytes between tap groups
-    const __amdgpu_buffer_rsrc_t r = make_rsrc(up, valid ? (unsigned)(S.ngrp - 1) * gstride + W_BM * ROWF * 4 : 0u);
-    asm volatile("" :: "v"(pf[0]), "v"(pf[1]));          // the previous prefetch has landed before its registers are reused
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      // (lanes past the tile's lines: out of range; the 96-byte rows of the BF form are 0.75 W_BM lines, the first
-      // 32 lanes' worth of which is touched: enough to start the L2 fill of the tile)
-      const unsigned off = l31 < W_BM * ROWF / 32 ? (unsigned)(2 * j + lh) * gstride + (unsigned)l31 * 128u : 0x80000000u;
-      pf[j] = __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0);
-    }
+  auto prefetch_a = [&](const WinoSeg& S, int chunk, bool valid) {
+    wino_prefetch_a<6, W_BM, BF ? W_A3 : W_CK>(pf, S, chunk, valid, wts, l31, lh);
   };
 
   // ---- prologue -------------------------------------------------------------------------------
-  WSeg S0 = load_wseg(&G->seg[0]);
+  WinoSeg S0 = load_wino_seg(&G->seg[0]);
   if constexpr (BF) {
     load_a3(S0, 0, 0, true);
   } else {
@@ -375,19 +310,19 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
   // channel pair W_RP2 floats on); the packed math runs over the k-step pair; the samples of pair
   // p + 1 are requested before the MFMAs of pair p, across tap groups, so LDS latency is exposed once
   // per chunk only.
-  auto run_segment = [&](auto gc, const WSeg& S, const WSeg& Sn, bool more_seg) {
+  auto run_segment = [&](auto gc, const WinoSeg& S, const WinoSeg& Sn, bool more_seg) {
     constexpr int GC = decltype(gc)::value;
     const int nch = S.cin / W_CK;
     for (int c = 0; c < nch; ++c) {
       const bool last_chunk = c == nch - 1;
       const bool has_next = !last_chunk || more_seg;
-      const WSeg& Sx = last_chunk ? Sn : S;              // owner of the next chunk
+      const WinoSeg& Sx = last_chunk ? Sn : S;              // owner of the next chunk
       const int cx = last_chunk ? 0 : c + 1;
       // the slab rows this chunk occupies are refilled (in the other buffer) by the chunk SUBS ahead
       const int sub = c % SUBS;
       const bool wrap = SUBS == 1 ? last_chunk : c + SUBS >= nch;
       const bool has_slab = SUBS == 1 ? has_next : (!wrap || more_seg);
-      const WSeg& Ss = SUBS == 1 ? Sx : (wrap ? Sn : S);
+      const WinoSeg& Ss = SUBS == 1 ? Sx : (wrap ? Sn : S);
       const int cs = SUBS == 1 ? cx : (wrap ? c + SUBS - nch : c + SUBS);
       const float* xsb = lds + xbuf * W_SLAB + sub * W_SUB + lh * 4 * W_RP2 + (th * 32 + l31) * 2;
       f32x2 xr[2][4][NT];                                // [slot][sample][column] = (k-step 2 kp, 2 kp + 1)
@@ -474,7 +409,7 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
             }
           }
           const bool same_chunk = g + 1 < GC;      // the A registers are free: request the next tap group's pieces
-          const WSeg& Sa = same_chunk ? S : Sx;
+          const WinoSeg& Sa = same_chunk ? S : Sx;
           load_a3(Sa, same_chunk ? c : cx, same_chunk ? g + 1 : 0, same_chunk || has_next);
         }
       } else {
@@ -512,7 +447,7 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
         }
         if (kp & 1) {                              // this half of the A registers is free: refill it for the next step
           const bool same_chunk = g + 1 < GC;
-          const WSeg& Sa = same_chunk ? S : Sx;
+          const WinoSeg& Sa = same_chunk ? S : Sx;
           load_a_half(h, Sa, same_chunk ? c : cx, same_chunk ? g + 1 : 0, same_chunk || has_next);
         }
       }
@@ -538,7 +473,7 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
   auto run_all = [&](auto gc) {
     while (sg < nseg && S0.ngrp == decltype(gc)::value) {
       const bool more_seg = sg + 1 < nseg;
-      const WSeg Sn = load_wseg(&G->seg[more_seg ? sg + 1 : sg]);
+      const WinoSeg Sn = load_wino_seg(&G->seg[more_seg ? sg + 1 : sg]);
       run_segment(gc, S0, Sn, more_seg);
       S0 = Sn;
       ++sg;
@@ -558,13 +493,8 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
   const int ophase = uni(G->out_phase);
   // out_len > 0: row pitch of out (and res); a transposed conv with an odd (k - u) returns u * len_in + 1 samples per row
   const int opitch = uni(G->out_len) > 0 ? uni(G->out_len) : pitch * ostride;
-  const size_t slab = (size_t)b * cout * opitch;
-  const unsigned slab_bytes = (unsigned)cout * (unsigned)opitch * 4u;
-  const __amdgpu_buffer_rsrc_t ro = make_rsrc(uni((const float*)G->out) + slab, slab_bytes);
-  const __amdgpu_buffer_rsrc_t rr0 = make_rsrc(nres > 0 ? uni(G->res[0]) + slab : nullptr, nres > 0 ? slab_bytes : 0u);
-  const __amdgpu_buffer_rsrc_t rr1 = make_rsrc(nres > 1 ? uni(G->res[1]) + slab : nullptr, nres > 1 ? slab_bytes : 0u);
-  const __amdgpu_buffer_rsrc_t rr2 = make_rsrc(nres > 2 ? uni(G->res[2]) + slab : nullptr, nres > 2 ? slab_bytes : 0u);
-  const __amdgpu_buffer_rsrc_t rbias = make_rsrc(bias, bias ? (unsigned)cout * 4u : 0u);
+  const float* const resp[3] = {uni(G->res[0]), uni(G->res[1]), uni(G->res[2])};
+  const WinoOut O = wino_make_out(uni((const float*)G->out), resp, bias, nres, scale, (size_t)b * cout * opitch, cout, opitch);
   const bool vec = (pm || (dil == 1 && (len & 3) == 0)) && ostride == 1;   // 4 outputs of a tile = one aligned 16-byte vector
   // Exchange tiles are COLUMN-major, E[th][xi][col (tile) 32][row (co) W_EP]: a lane's 16 accumulators of a
   // 32 x 32 tile are 4 runs of 4 consecutive rows (8 q + 4 lh + 0..3) of its column l31, i.e. four ds_write_b128,
@@ -585,7 +515,7 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int co = co0 + mt * 32 + 4 * erq + i;
-      bpre[mt][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rbias, (eact && co < cout) ? (unsigned)co * 4u : 0x80000000u, 0, 0));
+      bpre[mt][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(O.rbias, (eact && co < cout) ? (unsigned)co * 4u : 0x80000000u, 0, 0));
     }
   auto request = [&](int mt, int nt, u32x4 (&rp)[4]) {
     const int corow = co0 + mt * 32 + 4 * erq;
@@ -597,7 +527,7 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
       for (int i = 0; i < 4; ++i) {
         const bool ok = colok && corow + i < cout;
         rp[i] = __builtin_amdgcn_raw_buffer_load_b128(
-            rr0, ok ? ((unsigned)(corow + i) * (unsigned)opitch + coloff) * 4u : 0x80000000u, 0, 0);
+            O.rr0, ok ? ((unsigned)(corow + i) * (unsigned)opitch + coloff) * 4u : 0x80000000u, 0, 0);
       }
     }
   };
@@ -616,13 +546,7 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
       const int v0 = tb * (4 * W_BT) + (nt * 64 + eth * 32 + ecol) * 4;   // decimated index of y[0]
       const bool colok = eact && (v0 + 3) * dil + ph < len;
       if (kRB > 1 && sub + kRB - 1 < MT * NT) request((sub + kRB - 1) / NT, (sub + kRB - 1) % NT, rpre[(sub + kRB - 1) % kRB]);
-      {
-        float* ew = E + ((th * 6 + xi) * 32 + l31) * W_EP + 4 * lh;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          *reinterpret_cast<f32x4*>(ew + 8 * q) =
-              (f32x4){acc[mt][nt][4 * q], acc[mt][nt][4 * q + 1], acc[mt][nt][4 * q + 2], acc[mt][nt][4 * q + 3]};
-      }
+      wino_exchange_write(E + ((th * 6 + xi) * 32 + l31) * W_EP + 4 * lh, acc[mt][nt]);
       __syncthreads();
       if (eact) {
         const float* er = E + (eth * 6 * 32 + ecol) * W_EP + 4 * erq;
@@ -635,10 +559,7 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
         const f32x4 y1 = __builtin_elementwise_fma((f32x4)(2.f), d34, d12);
         const f32x4 y2 = __builtin_elementwise_fma((f32x4)(4.f), s34, s12);
         const f32x4 y3 = __builtin_elementwise_fma((f32x4)(8.f), d34, d12) + m5;
-        // One store path per WAVE, every access an unconditional buffer operation (nothing to do = out-of-range offset):
-        // with a per-lane "whole vector?" branch around them the compiler's s_waitcnt in front of each residual use let
-        // only 2-3 operations stay in flight, and vmcnt counts loads and stores in order -- every sub-tile then waited
-        // for the write acknowledge of the one before it (conv_wino54.hip, tools/exp/w54_fixed_cost.py).
+        // One store path per WAVE (conv_wino_common.h: WinoOut)
         const float y[4][4] = {{y0[0], y1[0], y2[0], y3[0]}, {y0[1], y1[1], y2[1], y3[1]}, {y0[2], y1[2], y2[2], y3[2]},
                                {y0[3], y1[3], y2[3], y3[3]}};                       // [row i][output q]
         const unsigned phoff = pm ? (unsigned)(ph * lp) : 0u;
@@ -648,139 +569,33 @@ void conv_wino_kernel(const fh_wino_group* __restrict__ groups, int n_groups, in
             const unsigned off = corow + i < cout ? ((unsigned)(corow + i) * (unsigned)opitch + phoff + (unsigned)v0) * 4u : 0x80000000u;
             const float bv = bpre[mt][i];
             f32x4 o = {y[i][0] + bv, y[i][1] + bv, y[i][2] + bv, y[i][3] + bv};
-            if (nres > 0) {
-              u32x4 t = rpre[sub % kRB][i];
-              f32x4 rs = {__uint_as_float(t[0]), __uint_as_float(t[1]), __uint_as_float(t[2]), __uint_as_float(t[3])};
-              if (nres > 1) {
-                t = __builtin_amdgcn_raw_buffer_load_b128(rr1, off, 0, 0);
-                rs += (f32x4){__uint_as_float(t[0]), __uint_as_float(t[1]), __uint_as_float(t[2]), __uint_as_float(t[3])};
-              }
-              if (nres > 2) {
-                t = __builtin_amdgcn_raw_buffer_load_b128(rr2, off, 0, 0);
-                rs += (f32x4){__uint_as_float(t[0]), __uint_as_float(t[1]), __uint_as_float(t[2]), __uint_as_float(t[3])};
-              }
-              o += rs;
-            }
+            if (nres > 0) o += wino_add_res16(O, rpre[sub % kRB][i], off);
             o *= scale;
             const u32x4 ou = {__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3])};
-            __builtin_amdgcn_raw_buffer_store_b128(ou, ro, off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(ou, O.ro, off, 0, 0);
           }
         } else {                                        // a row ends inside this wave's tiles, strided or unaligned rows
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int co = corow + i;
             const unsigned rowoff = (unsigned)co * (unsigned)opitch + phoff;
-            const float bv = bpre[mt][i];
             unsigned off[4];
-            float rs[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
               const int n = ph + dil * (v0 + q);
               off[q] = (co < cout && n < len && (ostride == 1 || n * ostride + ophase < opitch))
                            ? (rowoff + (unsigned)(pm ? v0 + q : n * ostride + ophase)) * 4u : 0x80000000u;
-              rs[q] = 0.f;
             }
-            if (nres > 0) {
-#pragma unroll
-              for (int q = 0; q < 4; ++q) rs[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr0, off[q], 0, 0));
-              if (nres > 1) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) rs[q] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr1, off[q], 0, 0));
-              }
-              if (nres > 2) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) rs[q] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr2, off[q], 0, 0));
-              }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              float o = y[i][q] + bv;
-              if (nres > 0) o += rs[q];
-              __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o * scale), ro, off[q], 0, 0);
-            }
+            wino_store_tail(O, off, y[i], bpre[mt][i]);
           }
         }
       }
     }
   }
-  asm volatile("" :: "v"(pf[0]), "v"(pf[1]));            // (the last prefetch: waited for, never used)
-}
-
-// out = ((a + b) + c) * scale, 4 elements per thread (the reference's xs += ...; xs / n order)
-__global__ __launch_bounds__(256) void mean_kernel(const f32x4* __restrict__ a, const f32x4* __restrict__ b,
-                                                   const f32x4* __restrict__ c, f32x4* __restrict__ out,
-                                                   long long n4, float scale) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  f32x4 v = a[i] + b[i];
-  if (c) v += c[i];
-  out[i] = v * scale;
+  wino_prefetch_done(pf);
 }
 
 }  // namespace
-
-extern "C" int fh_mean_f32(const float* a, const float* b, const float* c, float* out, long long n, float scale,
-                           void* stream) {
-  FH_CHECK_ARG(a && b && out && n > 0 && n % 4 == 0, "fh_mean_f32: bad args (n must be a multiple of 4)");
-  FH_CHECK_ARG(((((size_t)a) | ((size_t)b) | ((size_t)c) | ((size_t)out)) & 15) == 0, "fh_mean_f32: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(mean_kernel, dim3(fh_cdiv(n / 4, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const f32x4*)a, (const f32x4*)b, (const f32x4*)c, (f32x4*)out, n / 4, scale);
-  FH_CHECK_LAUNCH("fh_mean_f32");
-  return FH_OK;
-}
-
-// out = (((p0 + p1) + p2) + ...) * scale over up to 12 tensors (split-K partial outputs: fixed order of addition)
-namespace {
-struct SumArgs {
-  const f32x4* p[12];
-  int n;
-};
-__global__ __launch_bounds__(256) void sum_kernel(SumArgs a, f32x4* __restrict__ out, long long n4, float scale) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  f32x4 v = a.p[0][i];
-#pragma unroll
-  for (int k = 1; k < 12; ++k)
-    if (k < a.n) v += a.p[k][i];
-  out[i] = v * scale;
-}
-}  // namespace
-
-extern "C" int fh_sum_f32(const float* const* srcs, int n_srcs, float* out, long long n, float scale, void* stream) {
-  FH_CHECK_ARG(srcs && n_srcs >= 1 && n_srcs <= 12 && out && n > 0 && n % 4 == 0,
-               "fh_sum_f32: bad args (1..12 sources, n a multiple of 4)");
-  SumArgs a;
-  a.n = n_srcs;
-  for (int k = 0; k < 12; ++k) {
-    a.p[k] = (const f32x4*)(k < n_srcs ? srcs[k] : srcs[0]);
-    FH_CHECK_ARG(a.p[k] && (((size_t)a.p[k]) & 15) == 0, "fh_sum_f32: source %d is null or not 16-byte aligned", k);
-  }
-  FH_CHECK_ARG((((size_t)out) & 15) == 0, "fh_sum_f32: out must be 16-byte aligned");
-  hipLaunchKernelGGL(sum_kernel, dim3(fh_cdiv(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, a, (f32x4*)out, n / 4,
-                     scale);
-  FH_CHECK_LAUNCH("fh_sum_f32");
-  return FH_OK;
-}
-
-namespace {
-__global__ __launch_bounds__(256) void sum_multi_kernel(const fh_sum_job* __restrict__ jobs) {
-  const fh_sum_job& J = jobs[blockIdx.y];
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= J.n / 4) return;
-  f32x4 v = reinterpret_cast<const f32x4*>(J.src[0])[i];
-  for (int k = 1; k < J.n_src; ++k) v += reinterpret_cast<const f32x4*>(J.src[k])[i];
-  reinterpret_cast<f32x4*>(J.out)[i] = v * J.scale;
-}
-}  // namespace
-
-extern "C" int fh_sizeof_sum_job(void) { return (int)sizeof(fh_sum_job); }
-
-extern "C" int fh_sum_multi_f32(const fh_sum_job* jobs, int n_jobs, long long max_n, void* stream) {
-  FH_CHECK_ARG(jobs && n_jobs > 0 && n_jobs < 65536 && max_n > 0 && max_n % 4 == 0, "fh_sum_multi_f32: bad args");
-  hipLaunchKernelGGL(sum_multi_kernel, dim3(fh_cdiv(max_n / 4, 256), n_jobs), dim3(256), 0, (hipStream_t)stream, jobs);
-  FH_CHECK_LAUNCH("fh_sum_multi_f32");
-  return FH_OK;
-}
 
 extern "C" int fh_sizeof_wino_group(void) { return (int)sizeof(fh_wino_group); }
 
@@ -794,35 +609,15 @@ int launch_wino_vl(const fh_wino_group* groups, int n_groups, int batch, int cou
   const int co_tiles = cout_pad / Cfg::BM;
   const int n_tiles = fh_cdiv(fh_cdiv(len, dilation), 4 * Cfg::BT) * dilation;
   const long long panels = (long long)n_groups * batch * co_tiles;
-  const int run_len = fh_cdiv(n_tiles, fh_cdiv(n_tiles, W_RUN));
-  const long long runs = run_map ? (long long)n_runs : panels * fh_cdiv(n_tiles, run_len);
+  const WinoGeom geo = wino_geometry(n_tiles, panels, run_map, n_runs, co_tiles, batch, dilation);
   const int rect_r = co_tiles < 32 ? 32 / co_tiles : 1, tpx = fh_cdiv(n_tiles, 8);        // (see the kernel's xcd_ranges branch)
-  const long long blocks = xcd_ranges ? 8ll * n_groups * batch * co_tiles * fh_cdiv(tpx, rect_r) * rect_r
-                                      : (long long)fh_cdiv(runs, 8) * 8 * run_len;
+  const long long blocks = xcd_ranges ? 8ll * n_groups * batch * co_tiles * fh_cdiv(tpx, rect_r) * rect_r : geo.blocks;
   FH_CHECK_ARG(blocks > 0 && blocks < (1ll << 31), "fh_conv_wino_f32: grid too large");
-  const WDivs dv = {fh_make_fastdiv((unsigned)run_len), fh_make_fastdiv((unsigned)fh_cdiv(n_tiles, run_len)),
-                    fh_make_fastdiv((unsigned)co_tiles), fh_make_fastdiv((unsigned)batch), fh_make_fastdiv((unsigned)dilation),
-                    fh_make_fastdiv((unsigned)rect_r), fh_make_fastdiv((unsigned)(co_tiles * rect_r)),
+  const WDivs dv = {geo.dv, fh_make_fastdiv((unsigned)rect_r), fh_make_fastdiv((unsigned)(co_tiles * rect_r)),
                     fh_make_fastdiv((unsigned)(co_tiles * fh_cdiv(tpx, rect_r) * rect_r))};
-  // > 64 KB of dynamic LDS needs the attribute once per DEVICE (a kernel has one function object per device, and
-  // a process may hold models on several): one flag per device ordinal and template instance.
-  static std::atomic<bool> lds_opt_in[FH_MAX_DEVICES];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= FH_MAX_DEVICES) {
-    fh_set_error("fh_conv_wino_f32: no current HIP device (or ordinal >= %d)", FH_MAX_DEVICES);
-    return FH_E_LAUNCH;
-  }
-  if (!lds_opt_in[dev].load(std::memory_order_acquire)) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_wino_kernel<MT, NT, SUBS, VL, BF>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       Cfg::LDS_FLOATS * 4);
-    if (e != hipSuccess) {
-      fh_set_error("fh_conv_wino_f32: cannot reserve %d bytes of LDS on device %d: %s", Cfg::LDS_FLOATS * 4, dev, hipGetErrorString(e));
-      return FH_E_LAUNCH;
-    }
-    lds_opt_in[dev].store(true, std::memory_order_release);
-  }
+  if (int rc = wino_lds_opt_in<&conv_wino_kernel<MT, NT, SUBS, VL, BF>>(Cfg::LDS_FLOATS * 4, "fh_conv_wino_f32")) return rc;
   hipLaunchKernelGGL((conv_wino_kernel<MT, NT, SUBS, VL, BF>), dim3((unsigned)blocks), dim3(W_THREADS), Cfg::LDS_FLOATS * 4,
-                     stream, groups, n_groups, batch, co_tiles, n_tiles, run_len, dilation, phase_major, run_map, n_runs,
+                     stream, groups, n_groups, batch, co_tiles, n_tiles, geo.run_len, dilation, phase_major, run_map, n_runs,
                      xcd_ranges ? 1 : 0, dv);
   FH_CHECK_LAUNCH("fh_conv_wino_f32");
   return FH_OK;
@@ -889,7 +684,7 @@ extern "C" int fh_conv_wino_f32(const fh_wino_group* groups, int n_groups, int b
 }
 
 extern "C" int fh_wino_tile_n(int tile_cfg) { tile_cfg &= ~(FH_WINO_BF16X6 | FH_WINO_XCD_RANGES | FH_WINO_NOVL); return tile_cfg == 0 ? 512 : (fh_wino_tile_m(tile_cfg) > 0 ? 256 : -1); }
-extern "C" int fh_wino_run_len(int n_tiles) { return n_tiles > 0 ? fh_cdiv(n_tiles, fh_cdiv(n_tiles, W_RUN)) : -1; }
+extern "C" int fh_wino_run_len(int n_tiles) { return n_tiles > 0 ? wino_run_len(n_tiles) : -1; }
 
 extern "C" int fh_conv_wino_ragged_f32(const fh_wino_group* groups, int n_groups, int cout_pad, int max_len, int dilation,
                                        int layout_flags, int tile_cfg, const int* run_map, int n_runs, void* stream) {

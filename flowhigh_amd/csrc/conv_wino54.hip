@@ -60,7 +60,7 @@ extern "C" int fh_wino54_n_tiles(int len, int dilation, int phase_major) {
   return (len > 0 && dilation >= 1) ? wino54_n_tiles(len, dilation, phase_major != 0) : -1;
 }
 
-extern "C" int fh_wino54_run_len(int n_tiles) { return n_tiles > 0 ? fh_cdiv(n_tiles, fh_cdiv(n_tiles, V_RUN)) : -1; }
+extern "C" int fh_wino54_run_len(int n_tiles) { return n_tiles > 0 ? wino_run_len(n_tiles) : -1; }
 
 extern "C" int fh_conv_wino54_ragged_f32(const fh_wino_group* groups, int n_groups, int cout_pad, int max_len, int dilation,
                                          int layout_flags, int tile_cfg, const int* run_map, int n_runs, void* stream) {

@@ -19,8 +19,8 @@
 // (0.83 + 0.5 in the 96-row shape), for a fifth fewer MFMAs.
 // On this chip every instruction a SIMD issues beside v_mfma_f32_32x32x2_f32 costs matrix-pipe time wherever it is
 // placed (profiles/r04_wino_kloop_handsched.txt), so the instruction count per MFMA is what sets the K loop's rate.
-//   * A (transformed weights [cin/16][tap group][8][cout_pad][16]) goes global -> registers in fragment layout as in
-//     conv_wino.hip;
+//   * A (transformed weights [cin/16][tap group][8][cout_pad][16]) goes global -> registers in fragment layout
+//     (conv_wino_common.h);
 //   * B: the raw 16-channel slab is staged in LDS once per chunk (double buffered, one barrier per chunk), wave w
 //     stages channel pair w.  Samples are de-interleaved into 5 planes (local sample v -> plane v % 5, index v / 5),
 //     channel pairs interleaved, so that lane `tile` reading sample 5 tile + c is a stride-1, conflict-free
@@ -33,7 +33,7 @@
 //     and scale applied.
 #pragma once
 #include "bf16x6.h"
-#include "fh_common.h"
+#include "conv_wino_common.h"
 
 #include <type_traits>
 
@@ -63,7 +63,7 @@ constexpr int V_PP = 8 * V_PAIR;     // plane pitch, floats
 constexpr int V_SLAB = 5 * V_PP;     // floats of a slab (one 16-channel chunk)
 constexpr int V_BUF = V_SLAB + 128;  // ... of a slab buffer: + one trash slot per lane for samples that are not needed
 constexpr int V_XQ = (5 * (V_BT - 1) + 4 * 3 + 7 + 3) / 4 + 1;      // aligned quads a slab can touch (85)
-constexpr int V_EP = 36;             // column pitch (floats) of the exchange tiles: conflict-free b128 (conv_wino.hip)
+constexpr int V_EP = 36;             // column pitch (floats) of the exchange tiles: conflict-free b128 (conv_wino_common.h)
 constexpr int V_YP = 168;            // row pitch (floats) of the output staging: 16-byte aligned, 4 * 168 % 64 == 32
 constexpr int V_EPI = 2 * 8 * 32 * V_EP;        // exchange tiles of two 32 x 32 sub-tiles (both columns of one mt)
 constexpr int V_Y = 2 * 32 * V_YP;
@@ -72,7 +72,6 @@ constexpr int V_Y = 2 * 32 * V_YP;
 // for the previous round's stores: 2 MT block barriers in the epilogue instead of 3 MT)
 static_assert(V_Y <= 2 * V_BUF, "output staging does not fit the slab space");
 constexpr int V_LDS_FLOATS = 2 * V_BUF + V_EPI;
-constexpr int V_RUN = 8;             // n-blocks of a panel that run together on one XCD (conv_wino.hip: W_RUN)
 
 // Phase-major rows (dilated convs) are tiled as ONE sequence: the d phases one after the other in a "position" space in which
 // every phase owns TS tile slots = its ceil(n / 5) tiles + >= 3 empty ones (multiple of 4, so that a phase starts on a 16-byte
@@ -109,28 +108,9 @@ constexpr VToff make_vtoff() {
 }
 __device__ const VToff kB8Toff = make_vtoff();
 
-struct VSeg {
-  const float* x;
-  const float* u;
-  int cin, ngrp, center;
-};
-__device__ __forceinline__ VSeg load_vseg(const fh_wino_seg* S) {
-  VSeg w;
-  w.x = uni(S->x);
-  w.u = uni(S->u);
-  w.cin = uni(S->cin);
-  w.ngrp = uni(S->ngrp);
-  w.center = uni(S->center);
-  return w;
-}
-
 // VL: rows are contiguous and 16-byte aligned (phase-major tensors, or dilation 1 and len % 4 == 0): the slab is fetched
 // with 16-byte loads and the outputs leave as 16-byte vectors; else 4-byte accesses (any length, any dilation in the
 // plain layout).  Same arithmetic either way.
-// launch constants the block -> work mapping divides by (fh_common.h: fh_fastdiv)
-struct VDivs {
-  fh_fastdiv run_len, runs_per_panel, co_tiles, batch, dil;
-};
 
 // H16 (MT = 2 only): the block is 48 output channels, three 16-row tiles of v_mfma_f32_16x16x4_f32 instead of two 32-row tiles of
 // the 32x32x2 form -- the C = 48 stage in 64-row blocks spent a quarter of its matrix instructions on padding rows.  The B
@@ -143,33 +123,17 @@ struct VDivs {
 template <int MT, bool VL, bool H16 = false, bool BF = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(V_THREADS, V_THREADS), amdgpu_waves_per_eu(2, 2)))
 void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, int batch, int co_tiles, int n_tiles,
-                        int run_len, int dil, int pm, const int* __restrict__ run_map, int n_runs, VDivs dv) {
+                        int run_len, int dil, int pm, const int* __restrict__ run_map, int n_runs, WinoDivs dv) {
   static_assert(!H16 || MT == 2, "the 16-row form is the 48-row block");
   static_assert(!(H16 && BF), "the bf16 x 6 form has 32-row tiles only");
   constexpr int BM = H16 ? 48 : 32 * MT;
   constexpr int MA = H16 ? 3 : MT;                    // A fragments (row tiles) per wave
   extern __shared__ __attribute__((aligned(16))) float lds[];      // V_LDS_FLOATS
 
-  // ---- block -> (panel, n block): panels = (group, batch, co tile), heavy groups first (conv_wino.hip) ----------
-  const int panels = n_groups * batch * co_tiles;
-  const int runs_per_panel = (int)dv.runs_per_panel.d;
-  const int total_runs = panels * runs_per_panel;
-  const int bid = blockIdx.x;
-  const int slot = bid >> 3;
-  const int slot_run = fh_div(slot, dv.run_len);
-  int run = slot_run * 8 + (bid & 7);
-  if (run_map) {
-    if (run >= n_runs) return;
-    run = uni(run_map[run]);
-  }
-  if (run >= total_runs) return;
-  const int panel = fh_div(run, dv.runs_per_panel);
-  const int ntile = fh_mod(run, panel, dv.runs_per_panel) * run_len + fh_mod(slot, slot_run, dv.run_len);
-  if (ntile >= n_tiles) return;
-  const int gb = fh_div(panel, dv.co_tiles);
-  const int cot = fh_mod(panel, gb, dv.co_tiles);
-  const int gi = fh_div(gb, dv.batch);
-  const int b = fh_mod(gb, gi, dv.batch);
+  // ---- block -> (panel, n block), panel -> (group, batch item, co tile) (conv_wino_common.h) ----------
+  int panel, ntile, gi, b, cot;
+  if (!wino_block_work(blockIdx.x, run_map, n_runs, n_groups * batch * co_tiles, run_len, n_tiles, dv, panel, ntile)) return;
+  wino_split_panel(panel, dv, gi, b, cot);
   const fh_wino_group* __restrict__ G = groups + gi;
   const bool cat = pm != 0;                   // phase-major rows: tiled in the concatenated position space (above)
   const int ntile_d = cat ? 0 : fh_div(ntile, dv.dil);
@@ -260,7 +224,7 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
   int ua = 0;                                          // position of local sample 0 (VL: a multiple of 4)
   int nvq[NLD];                                        // (VL) real samples from each quad's first sample on
   bool tail = false;                                   // (VL) the slab holds positions that are not real samples
-  auto setup_seg = [&](const VSeg& S) {
+  auto setup_seg = [&](const WinoSeg& S) {
     const int ub = tb * V_OUT - S.center;
     const int sh = VL ? (ub & 3) : 0;
     ua = ub - sh;
@@ -290,7 +254,7 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
     }
   };
   unsigned xq[2][NXS];                                 // [channel of the pair][sample]
-  auto load_x = [&](const VSeg& S, int chunk, bool valid) {
+  auto load_x = [&](const WinoSeg& S, int chunk, bool valid) {
     const __amdgpu_buffer_rsrc_t r =
         make_rsrc(uni(S.x + (size_t)b * S.cin * pitch), valid ? (unsigned)(S.cin * pitch) * 4u : 0u);
     const int so0 = (chunk * V_CK + 2 * xi) * pitch * 4, so1 = so0 + pitch * 4;        // scalar offsets of the pair's rows
@@ -325,16 +289,13 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
     }
   };
 
-  // A fragments of one step, [mt][half]: half h holds k-steps 4h .. 4h+3 (conv_wino.hip)
+  // A fragments of one step, [mt][half]: half h holds k-steps 4h .. 4h+3
   // (H16: row l & 15 of a 16-row tile, channels 8 (g >> 1) + (g & 1) + 4 h .. + 3 with g = l >> 4: a 4-byte aligned 16-byte load)
   u32x4 areg[BF ? 1 : MA][2];
   const int a_lane = H16 ? ((lane & 15) * V_CK + 8 * (lane >> 5) + ((lane >> 4) & 1)) * 4 : (l31 * V_CK + lh * 8) * 4;
-  auto load_a_half = [&](int h, const VSeg& S, int chunk, int g, bool valid) {
-    const float* up = uni(S.u + ((size_t)((chunk * S.ngrp + g) * 8 + xi) * cout_pad + co0) * V_CK);
-    const __amdgpu_buffer_rsrc_t r = make_rsrc(up, valid ? BM * V_CK * 4 : 0);
-#pragma unroll
-    for (int mt = 0; mt < (BF ? 1 : MA); ++mt)
-      areg[mt][h] = __builtin_amdgcn_raw_buffer_load_b128(r, a_lane + mt * (H16 ? 16 : 32) * V_CK * 4 + 16 * h, 0, 0);
+  const WinoWts wts = {xi, co0, cout_pad};
+  auto load_a_half = [&](int h, const WinoSeg& S, int chunk, int g, bool valid) {
+    wino_load_a_half<8, BM, BF ? 1 : MA, H16 ? 16 : 32>(areg, h, S, chunk, g, valid, wts, a_lane);
   };
   // BF: the three pieces of one tap group, [mt][piece]: lane (row l31, half lh) reads its 8 channels of each piece (16 bytes).
   // One register set, refilled behind the group's last MFMA: a second set (request a group ahead) measured no faster on the
@@ -342,9 +303,8 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
   u32x4 a3[BF ? MT : 1][3];
   const int a3_lane = (l31 * V_A3 + lh * 4) * 4;
   // pieces = bit mask of the pieces to request (1 h, 2 m, 4 l)
-  auto load_a3 = [&](const VSeg& S, int chunk, int g, bool valid, int pieces = 7) {
-    const float* up = uni(S.u + ((size_t)((chunk * S.ngrp + g) * 8 + xi) * cout_pad + co0) * V_A3);
-    const __amdgpu_buffer_rsrc_t r = make_rsrc(up, valid ? BM * V_A3 * 4 : 0);
+  auto load_a3 = [&](const WinoSeg& S, int chunk, int g, bool valid, int pieces = 7) {
+    const __amdgpu_buffer_rsrc_t r = make_rsrc(wino_a_tile<8, V_A3>(S, chunk, g, wts), valid ? BM * V_A3 * 4 : 0);
     // (the lane offset passes through an empty asm: the 3 MT offsets are then immediates of the loads (row tile 2 on: one add),
     // not 3 MT loop-invariant registers carried through the K loop)
     int o = a3_lane;
@@ -358,23 +318,10 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
           a3[mt][pc] = __builtin_amdgcn_raw_buffer_load_b128(r, om + (mt & 1) * 32 * V_A3 * 4 + 32 * pc, 0, 0);
     }
   };
-  // L2 warm-up of the A tiles of the NEXT chunk (all its tap groups, this wave's xi), as in conv_wino.hip
-  // (ordinary loads into two registers that the next prefetch "reads" before it overwrites them -- not the untracked inline-asm
-  // load of rounds 2-5, whose late write hit a reused register in every instantiation that spilled: conv_wino.hip)
+  // L2 warm-up of the A tiles of the NEXT chunk (conv_wino_common.h)
   unsigned pf[2] = {0u, 0u};
-  auto prefetch_a = [&](const VSeg& S, int chunk, bool valid) {
-    constexpr int ROWF = BF ? V_A3 : V_CK;                                 // floats per weight row and chunk
-    const float* up = uni(S.u + ((size_t)(chunk * S.ngrp * 8 + xi) * cout_pad + co0) * ROWF);
-    const unsigned gstride = 8u * (unsigned)cout_pad * ROWF * 4u;          // bytes between tap groups
-    const __amdgpu_buffer_rsrc_t r = make_rsrc(up, valid ? (unsigned)(S.ngrp - 1) * gstride + BM * ROWF * 4 : 0u);
-    asm volatile("" :: "v"(pf[0]), "v"(pf[1]));          // the previous prefetch has landed before its registers are reused
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      // (lanes past the tile's lines: out of range; the 96-byte rows of the BF form are 0.75 BM lines, the first 32 lanes' worth
-      // of which is touched: enough to start the L2 fill of the tile)
-      const unsigned off = l31 < BM * ROWF / 32 ? (unsigned)(2 * j + lh) * gstride + (unsigned)l31 * 128u : 0x80000000u;
-      pf[j] = __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0);
-    }
+  auto prefetch_a = [&](const WinoSeg& S, int chunk, bool valid) {
+    wino_prefetch_a<8, BM, BF ? V_A3 : V_CK>(pf, S, chunk, valid, wts, l31, lh);
   };
 
   // ---- K loop -----------------------------------------------------------------------------------------------------
@@ -383,7 +330,7 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
   // requested behind the transform of pair p, in the same registers.
   int xbuf = 0;
   const int lane_base = lh * 4 * V_PAIR + l31 * 2;
-  auto run_segment = [&](auto gc, const VSeg& S) {
+  auto run_segment = [&](auto gc, const WinoSeg& S) {
     constexpr int GC = decltype(gc)::value;
     const int nch = S.cin / V_CK;
     setup_seg(S);
@@ -475,7 +422,7 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
         f32x2 bf[2];                                   // [column] = B values of k-steps 2 kp, 2 kp + 1
         // (inline asm: packed FMAs, and kept out of the MFMA groups below.  The two columns' chains are interleaved so that
         // no packed FMA reads the result of the one issued just before it; VALU result -> MFMA operand needs 2 wait states:
-        // the s_nop behind the last one covers both columns, conv_wino.hip)
+        // the s_nop behind the last one covers both columns)
         asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(bf[0]) : "s"(bco[0]), "v"(xr[0][0]), "v"(xr[5][0]));
         asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(bf[1]) : "s"(bco[0]), "v"(xr[0][1]), "v"(xr[5][1]));
 #pragma unroll
@@ -535,12 +482,12 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
 
   // Segments are sorted by tap-group count, descending (host: make_wino_group)
   int sg = 0;
-  VSeg S0 = load_vseg(&G->seg[0]);
+  WinoSeg S0 = load_wino_seg(&G->seg[0]);
   auto run_all = [&](auto gc) {
     while (sg < nseg && S0.ngrp == decltype(gc)::value) {
       run_segment(gc, S0);
       ++sg;
-      if (sg < nseg) S0 = load_vseg(&G->seg[sg]);
+      if (sg < nseg) S0 = load_wino_seg(&G->seg[sg]);
     }
   };
   // (1 .. 3 groups of 4 taps: k <= 12, the host's WINO_MAX_K.  Tried: the three row classes of B^T -- point 0, the six
@@ -554,13 +501,7 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
   if (sg < nseg) __builtin_trap();
 
   // ---- epilogue ---------------------------------------------------------------------------------------------------
-  const size_t oslab = (size_t)b * cout * pitch;
-  const unsigned slab_bytes = (unsigned)cout * (unsigned)pitch * 4u;
-  const __amdgpu_buffer_rsrc_t ro = make_rsrc(outp + oslab, slab_bytes);
-  const __amdgpu_buffer_rsrc_t rr0 = make_rsrc(nres > 0 ? resp[0] + oslab : nullptr, nres > 0 ? slab_bytes : 0u);
-  const __amdgpu_buffer_rsrc_t rr1 = make_rsrc(nres > 1 ? resp[1] + oslab : nullptr, nres > 1 ? slab_bytes : 0u);
-  const __amdgpu_buffer_rsrc_t rr2 = make_rsrc(nres > 2 ? resp[2] + oslab : nullptr, nres > 2 ? slab_bytes : 0u);
-  const __amdgpu_buffer_rsrc_t rbias = make_rsrc(bias, bias ? (unsigned)cout * 4u : 0u);
+  const WinoOut O = wino_make_out(outp, resp, bias, nres, scale, (size_t)b * cout * pitch, cout, pitch);
   float* const E = lds + 2 * V_BUF;                   // [column nt][xi][tile col 32][row, pitch V_EP]: behind the slab buffers
   float* const Y = lds;                               // [column nt][row 32][160 outputs, pitch V_YP]: in the slab space
   // (BF: the thread id the epilogue's geometry is made from passes through an empty asm, so that none of it -- ~40 registers of row /
@@ -601,7 +542,7 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
       int nreal;
       unsigned soff;
       item_geom(mt, i, nreal, soff);
-      rp[i] = __builtin_amdgcn_raw_buffer_load_b128(rr0, nreal >= 4 ? soff : 0x80000000u, 0, 0);
+      rp[i] = __builtin_amdgcn_raw_buffer_load_b128(O.rr0, nreal >= 4 ? soff : 0x80000000u, 0, 0);
     }
   };
 #pragma unroll
@@ -611,7 +552,7 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
       int nreal;
       unsigned soff;
       const int co = item_geom(mt, i, nreal, soff);
-      bvall[mt][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rbias, nreal > 0 ? (unsigned)co * 4u : 0x80000000u, 0, 0));
+      bvall[mt][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(O.rbias, nreal > 0 ? (unsigned)co * 4u : 0x80000000u, 0, 0));
     }
   if (AHEAD && VL && nres > 0) request_res(0, rpre[0]);
 #pragma unroll
@@ -631,13 +572,7 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
                   acc16[2 * mt + t][nt][hf];
     } else {
 #pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        float* ew = E + ((nt * 8 + xi) * 32 + l31) * V_EP + 4 * lh;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          *reinterpret_cast<f32x4*>(ew + 8 * q) =
-              (f32x4){acc[mt][nt][4 * q], acc[mt][nt][4 * q + 1], acc[mt][nt][4 * q + 2], acc[mt][nt][4 * q + 3]};
-      }
+      for (int nt = 0; nt < 2; ++nt) wino_exchange_write(E + ((nt * 8 + xi) * 32 + l31) * V_EP + 4 * lh, acc[mt][nt]);
     }
     __syncthreads();
     {
@@ -659,18 +594,16 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
 #pragma unroll
         for (int q = 0; q < 5; ++q) yw[i * V_YP + q] = y[q][i];
     }
-    // Store phase.  Every global access below is an unconditional buffer operation (nothing to do = out-of-range offset)
-    // in straight-line code.  (With the bias load and a per-lane "whole vector?" branch inside the item loop the compiler put
-    // s_waitcnt vmcnt(0) behind every item's loads: each of the 15 items of a block waited for its load AND for the write
-    // acknowledge of the item before it: tools/exp/w54_fixed_cost.py.)
+    // Store phase: one path per WAVE, unconditional buffer operations in straight-line code (conv_wino_common.h: WinoOut)
     const float (&bv)[5] = bvall[mt];
-    unsigned soff[5];
+    unsigned soff[5], voff[5];                          // byte offset of the item's vector; ... or out of range unless whole
     int nreal[5];
     bool vec = VL;                                      // every item of this lane is a whole vector, or nothing
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
       item_geom(mt, i, nreal[i], soff[i]);
       vec = vec && (nreal[i] >= 4 || nreal[i] <= 0);
+      voff[i] = nreal[i] >= 4 ? soff[i] : 0x80000000u;
     }
     if (VL && nres > 0 && (AHEAD ? mt + 1 < MT : true)) request_res(AHEAD ? mt + 1 : mt, rpre[AHEAD ? (mt + 1) & 1 : 0]);
     const u32x4 (&rp)[5] = rpre[AHEAD ? mt & 1 : 0];
@@ -682,68 +615,27 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
     for (int i = 0; i < 5; ++i) yv[i] = *reinterpret_cast<const f32x4*>(Y + (ent * 32 + srow[i]) * V_YP + scol[i]);
     if (wave_vec) {
       f32x4 rs[5];
-      if (nres > 0) {
-#pragma unroll
-        for (int i = 0; i < 5; ++i)
-          rs[i] = (f32x4){__uint_as_float(rp[i][0]), __uint_as_float(rp[i][1]), __uint_as_float(rp[i][2]), __uint_as_float(rp[i][3])};
-        if (nres > 1) {
-          u32x4 t[5];
-#pragma unroll
-          for (int i = 0; i < 5; ++i) t[i] = __builtin_amdgcn_raw_buffer_load_b128(rr1, nreal[i] >= 4 ? soff[i] : 0x80000000u, 0, 0);
-#pragma unroll
-          for (int i = 0; i < 5; ++i)
-            rs[i] += (f32x4){__uint_as_float(t[i][0]), __uint_as_float(t[i][1]), __uint_as_float(t[i][2]), __uint_as_float(t[i][3])};
-        }
-        if (nres > 2) {
-          u32x4 t[5];
-#pragma unroll
-          for (int i = 0; i < 5; ++i) t[i] = __builtin_amdgcn_raw_buffer_load_b128(rr2, nreal[i] >= 4 ? soff[i] : 0x80000000u, 0, 0);
-#pragma unroll
-          for (int i = 0; i < 5; ++i)
-            rs[i] += (f32x4){__uint_as_float(t[i][0]), __uint_as_float(t[i][1]), __uint_as_float(t[i][2]), __uint_as_float(t[i][3])};
-        }
-      }
+      if (nres > 0) wino_add_res16(O, rp, voff, rs);
 #pragma unroll
       for (int i = 0; i < 5; ++i) {
         f32x4 o = {yv[i][0] + bv[i], yv[i][1] + bv[i], yv[i][2] + bv[i], yv[i][3] + bv[i]};
         if (nres > 0) o += rs[i];
         o *= scale;
         const u32x4 ou = {__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3])};
-        __builtin_amdgcn_raw_buffer_store_b128(ou, ro, nreal[i] >= 4 ? soff[i] : 0x80000000u, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(ou, O.ro, voff[i], 0, 0);
       }
     } else {                                            // a row ends inside this wave's vectors, or rows are not 16-byte aligned
 #pragma unroll
       for (int i = 0; i < 5; ++i) {
         unsigned off[4];
-        float rs[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          // (plain layout with a dilation: output v sits at ph + dil v of the row)
+        for (int q = 0; q < 4; ++q)      // (plain layout with a dilation: output v sits at ph + dil v of the row)
           off[q] = q < nreal[i] ? (pm || dil == 1 ? soff[i] + 4u * q : soff[i] + 4u * (unsigned)(ph + (dil - 1) * (v_first + ent * 160 + scol[i]) + dil * q)) : 0x80000000u;
-          rs[q] = 0.f;
-        }
-        if (nres > 0) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) rs[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr0, off[q], 0, 0));
-          if (nres > 1) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) rs[q] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr1, off[q], 0, 0));
-          }
-          if (nres > 2) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) rs[q] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr2, off[q], 0, 0));
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float o = yv[i][q] + bv[i];
-          if (nres > 0) o += rs[q];
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o * scale), ro, off[q], 0, 0);
-        }
+        wino_store_tail(O, off, yv[i], bv[i]);
       }
     }
   }
-  asm volatile("" :: "v"(pf[0]), "v"(pf[1]));            // (the last prefetch: waited for, never used)
+  wino_prefetch_done(pf);
 }
 
 // 320-output blocks of a row: per phase in the plain layout, over the concatenated tile slots of all phases in the phase-major one
@@ -759,29 +651,11 @@ int launch_wino54(const fh_wino_group* groups, int n_groups, int batch, int cout
   const int co_tiles = cout_pad / BM;
   const int n_tiles = wino54_n_tiles(len, dilation, pm);
   const long long panels = (long long)n_groups * batch * co_tiles;
-  const int run_len = fh_cdiv(n_tiles, fh_cdiv(n_tiles, V_RUN));
-  const long long runs = run_map ? (long long)n_runs : panels * fh_cdiv(n_tiles, run_len);
-  const long long blocks = (long long)fh_cdiv(runs, 8) * 8 * run_len;
-  FH_CHECK_ARG(blocks > 0 && blocks < (1ll << 31), "fh_conv_wino54_f32: grid too large");
-  const VDivs dv = {fh_make_fastdiv((unsigned)run_len), fh_make_fastdiv((unsigned)fh_cdiv(n_tiles, run_len)),
-                    fh_make_fastdiv((unsigned)co_tiles), fh_make_fastdiv((unsigned)batch), fh_make_fastdiv((unsigned)dilation)};
-  static std::atomic<bool> lds_opt_in[FH_MAX_DEVICES];      // (> 64 KB of dynamic LDS: once per device, conv_wino.hip)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= FH_MAX_DEVICES) {
-    fh_set_error("fh_conv_wino54_f32: no current HIP device (or ordinal >= %d)", FH_MAX_DEVICES);
-    return FH_E_LAUNCH;
-  }
-  if (!lds_opt_in[dev].load(std::memory_order_acquire)) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_wino54_kernel<MT, VL, H16, BF>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       V_LDS_FLOATS * 4);
-    if (e != hipSuccess) {
-      fh_set_error("fh_conv_wino54_f32: cannot reserve %d bytes of LDS on device %d: %s", V_LDS_FLOATS * 4, dev, hipGetErrorString(e));
-      return FH_E_LAUNCH;
-    }
-    lds_opt_in[dev].store(true, std::memory_order_release);
-  }
-  hipLaunchKernelGGL((conv_wino54_kernel<MT, VL, H16, BF>), dim3((unsigned)blocks), dim3(V_THREADS), V_LDS_FLOATS * 4, stream, groups,
-                     n_groups, batch, co_tiles, n_tiles, run_len, dilation, pm, run_map, n_runs, dv);
+  const WinoGeom geo = wino_geometry(n_tiles, panels, run_map, n_runs, co_tiles, batch, dilation);
+  FH_CHECK_ARG(geo.blocks > 0 && geo.blocks < (1ll << 31), "fh_conv_wino54_f32: grid too large");
+  if (int rc = wino_lds_opt_in<&conv_wino54_kernel<MT, VL, H16, BF>>(V_LDS_FLOATS * 4, "fh_conv_wino54_f32")) return rc;
+  hipLaunchKernelGGL((conv_wino54_kernel<MT, VL, H16, BF>), dim3((unsigned)geo.blocks), dim3(V_THREADS), V_LDS_FLOATS * 4, stream, groups,
+                     n_groups, batch, co_tiles, n_tiles, geo.run_len, dilation, pm, run_map, n_runs, geo.dv);
   FH_CHECK_LAUNCH("fh_conv_wino54_f32");
   return FH_OK;
 }

@@ -188,7 +188,7 @@ _WINO_COST = {0: (2.98, 20.0), 1: (2.21, 16.0), 4: (1.564, 14.7), 5: (0.917, 17.
 # such blocks thrashes the 4 MB L2s (C = 768: 857 us against 732 us with 64 x 512 tiles)
 _WINO_WIDE_PANEL_MAX = 6 * 2 ** 20
 _WINO_TILES_OFF = set()            # (A/B experiments: tools add tile ids here before the first plan)
-_WINO_RUN = 8                      # W_RUN of conv_wino.hip
+_WINO_RUN = 8                      # WINO_RUN of conv_wino_common.h
 
 
 # K-loop time per step of the bf16 x 6 form relative to the fp32 form, per tile shape (tools/wino_cost_fit.py:
@@ -214,7 +214,7 @@ def wino_n_tiles(cfg, length, dil, pm):
 
 
 def wino_run_len(n_tiles):
-    """Consecutive tiles of a panel that one XCD runs (fh_wino_run_len / fh_wino54_run_len: W_RUN = V_RUN = 8)."""
+    """Consecutive tiles of a panel that one XCD runs (fh_wino_run_len / fh_wino54_run_len: WINO_RUN = 8)."""
     return -(-n_tiles // -(-n_tiles // _WINO_RUN))
 
 

@@ -21,12 +21,12 @@ def emit(name, text):
     (d / "conv_wino54_bf.hip").write_text(tu)
 
 
-emit("noa", hdr.replace("          load_a3(S, same_chunk ? c : c + 1, same_chunk ? g + 1 : 0, same_chunk || has_next);\n", ""))
+emit("noa", hdr.replace("              if (nt == 1 && pp == bf16x6_last_use(kBf16x6AMajor, s.a)) load_a3(S, nc, ng, nv, 1 << s.a);\n", ""))
 emit("nobar", hdr.replace("      if (has_next) {\n        store_x(xbuf ^ 1);\n        __syncthreads();\n        xbuf ^= 1;",
                           "      if (has_next) {\n        store_x(xbuf ^ 1);\n        if (!BF) __syncthreads();\n        xbuf ^= 1;"))
-emit("nosplit", hdr.replace("            v_split8(v, bh, bm, bl);\n",
-                            "            bh = __builtin_bit_cast(v_bf16x8, (f32x4){v[0], v[1], v[2], v[3]}); bm = __builtin_bit_cast(v_bf16x8, (f32x4){v[4], v[5], v[6], v[7]});\n"
-                            "            bl = __builtin_bit_cast(v_bf16x8, (f32x4){v[0] + v[4], v[1], v[2], v[7]});\n"))
+emit("nosplit", hdr.replace("            bf16x6_split(v, bp[0], bp[1], bp[2]);\n",
+                            "            bp[0] = __builtin_bit_cast(u32x4, (f32x4){v[0], v[1], v[2], v[3]}); bp[1] = __builtin_bit_cast(u32x4, (f32x4){v[4], v[5], v[6], v[7]});\n"
+                            "            bp[2] = __builtin_bit_cast(u32x4, (f32x4){v[0] + v[4], v[1], v[2], v[7]});\n"))
 emit("noxf", hdr.replace("                float t = __builtin_fmaf(bco[0][0], x[0][e], x[5][e]);\n#pragma unroll\n"
                          "                for (int j = 1; j < 5; ++j) t = __builtin_fmaf(bco[j][0], x[j][e], t);\n",
                          "                float t = x[0][e] + x[5][e];\n"))

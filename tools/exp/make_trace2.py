@@ -20,9 +20,9 @@ def sub(old, new, count=1):
 
 
 # the product kernel carries no debug state: the trace pointer, its setter and every stamp are added here
-sub('''struct WSeg {''', '''__device__ unsigned long long* g_wino_trace = nullptr;
+sub('''struct WDivs : WinoDivs {''', '''__device__ unsigned long long* g_wino_trace = nullptr;
 
-struct WSeg {''')
+struct WDivs : WinoDivs {''')
 sub('''  extern __shared__ __attribute__((aligned(16))) float lds[];      // Cfg::LDS_FLOATS
 ''', '''  extern __shared__ __attribute__((aligned(16))) float lds[];      // Cfg::LDS_FLOATS
   unsigned long long* const trace = g_wino_trace;
@@ -32,8 +32,8 @@ sub('''  extern __shared__ __attribute__((aligned(16))) float lds[];      // Cfg
   if (trace) rec2 = trace + 1 + 24 * ((unsigned long long)blockIdx.x * 12ull + (unsigned long long)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
 #define STAMP(k) do { if (rec2 && (threadIdx.x & 63) == 0) rec2[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
 ''')
-sub('''  WSeg S0 = load_wseg(&G->seg[0]);''', '''  STAMP(3);
-  WSeg S0 = load_wseg(&G->seg[0]);
+sub('''  WinoSeg S0 = load_wino_seg(&G->seg[0]);''', '''  STAMP(3);
+  WinoSeg S0 = load_wino_seg(&G->seg[0]);
   STAMP(4);''')
 sub('''  int xbuf = 0;
 #pragma unroll
@@ -58,9 +58,9 @@ sub('''      const int sub = mt * NT + nt;
       const int sb_ = sub < 3 ? 7 + 3 * sub : 19;
       STAMP(sb_);       // (first sub-tile: after the barrier that ends the K loop; later ones: after the previous stores)
 ''')
-sub('''      }
+sub('''W_EP + 4 * lh, acc[mt][nt]);
       __syncthreads();
-      if (eact) {''', '''      }
+      if (eact) {''', '''W_EP + 4 * lh, acc[mt][nt]);
       __syncthreads();
       STAMP(sb_ + 1);
       if (eact) {''')
@@ -69,16 +69,16 @@ sub('''          }
       }
     }
   }
-  // (keeps pf alive''', '''          }
+  wino_prefetch_done(pf);''', '''          }
         }
       }
       STAMP(sb_ + 2);
     }
   }
-  // (keeps pf alive''')
-sub('''  if (pf == 0x7fc12345u) __builtin_amdgcn_s_sleep(1);
+  wino_prefetch_done(pf);''')
+sub('''  wino_prefetch_done(pf);
 }
-''', '''  if (pf == 0x7fc12345u) __builtin_amdgcn_s_sleep(1);
+''', '''  wino_prefetch_done(pf);
   if (rec2 && (tid & 63) == 0) {
     unsigned hw, xcc;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
