@@ -12,6 +12,7 @@ a non-CUDA device, or without the built library, raises.
 
 Extensions over the reference (all keyword-only, defaults keep reference behaviour):
   generate(..., noise=, generator=)   explicit prior draw / CPU generator (parity hook)
+  prior='device', generate(..., seed=) the prior drawn on the device from (seed, stream) keys (csrc/prior.hip, prior.py)
   sample(..., cond_scale=, mel_pp=)    as in the reference, evaluated on the device (no python bin loops)
   generate_batch(clips, sr, ...)      B equal-length clips, every per-clip normalisation kept per clip
   upsampling_method='hip'             resample_poly on the device instead of scipy on the host
@@ -27,6 +28,7 @@ import torch
 from . import hip
 from .flow import FlowNet
 from .frontend import LogMel, PostProcessor, Resampler
+from .prior import expand_seed, normalize_key
 from .tables import HOP
 from .vocoder import VOC, Vocoder, fold_weight_norm
 
@@ -54,6 +56,10 @@ def read_checkpoints(ckpt_dir):
     sd.update(model)                                                       # wrapper checkpoint wins
     return sd, cfg
 _CFM_METHODS = ("basic_cfm", "independent_cfm_adaptive", "independent_cfm_constant", "independent_cfm_mix")
+# where the flow-matching prior eps ~ N(0, 1) of a call without noise= comes from.  'reference': torch's CPU stream, drawn on the
+# host (reference_prior_draw below; the default).  'device': this project's own counter-based stream, drawn by fh_prior_normal_f32
+# from one (seed, stream) key per clip (prior.py restates it on the host)
+_PRIORS = ("reference", "device")
 
 
 def reference_prior_draw(n_frames, n_mels=256, generator=None):
@@ -148,18 +154,24 @@ class GraphedGenerate:
     def _capture(self, model, batch, n_in, sr, timestep, dev):
         self.x = torch.zeros(batch, n_in, dtype=torch.float32, device=dev)
         t48 = -(-n_in * 48000 // sr)
-        self.noise = torch.zeros(batch * (t48 // 480), model.flowhigh.n_mels, dtype=torch.float32, device=dev)
+        # the prior: a static noise buffer, or on a prior='device' model the keys the recorded prior launch reads at every replay
+        if model.prior == 'device':
+            self.keys = torch.zeros(batch, 2, dtype=torch.int64, device=dev)
+            prior = dict(keys=self.keys)
+        else:
+            self.noise = torch.zeros(batch * (t48 // 480), model.flowhigh.n_mels, dtype=torch.float32, device=dev)
+            prior = dict(noise=self.noise)
         self.x[:, 0] = 1.0                                  # any non-silent clip: the peak normalisation divides by max |x|
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):                       # warm-up outside the capture: plans, workspaces, LDS opt-in
             for _ in range(2):
-                model.generate_from_device(self.x, sr, timestep, noise=self.noise)
+                model._generate_from_device(self.x, sr, timestep, **prior)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.out = model.generate_from_device(self.x, sr, timestep, noise=self.noise)
+            self.out = model._generate_from_device(self.x, sr, timestep, **prior)
         # The graph holds raw pointers into the per-shape plans / workspaces of the model (vocoder pool and
         # descriptor arrays, transformer / front-end / post-processing buffers).  Those live in byte-bounded LRU
         # caches (hip.ShapeCache): keep a strong reference to every entry of this shape, so that an eviction only
@@ -282,7 +294,11 @@ class FlowHighSR:
         cond_drop_prob=0.,
         #
         upsampling_method='scipy',
+        prior='reference',                   # [reference, device]: _PRIORS above
     ):
+        if prior not in _PRIORS:
+            raise ValueError(f"prior must be one of {_PRIORS}, got {prior!r}")
+        self.prior = prior
         if use_torchode:
             raise NotImplementedError("the torchode adaptive solver path is out of scope (SURVEY.md 8a row 2)")
         self.flowhigh = flowhigh
@@ -406,6 +422,64 @@ class FlowHighSR:
         n_mels = self.flowhigh.n_mels
         return torch.cat([reference_prior_draw(n_frames, n_mels, generator) for _ in range(batch)], 0)
 
+    def _prior_keys(self, seed, n_clips, generator=None, noise=None):
+        """The (seed, stream) key of every clip of a call, or None where the call does not draw on the device (a
+        prior='reference' model, or an explicit noise=, which always wins).  seed=: prior.expand_seed.  No seed=: one
+        torch.randint per clip from `generator` (torch's global one when None), in clip order, stream 0 -- so
+        torch.manual_seed / generator= make runs reproducible and a list consumes the generator as a loop over its clips does."""
+        if self.prior != 'device':
+            if seed is not None:
+                raise ValueError("seed= names a key of the device prior: construct the model with prior='device' "
+                                 "(a prior='reference' model draws from generator=)")
+            return None
+        keys = expand_seed(seed, n_clips) if seed is not None else None
+        if noise is not None:
+            return None
+        if keys is None:
+            keys = [normalize_key(int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator)), 0) for _ in range(n_clips)]
+        return keys
+
+    def _device_prior(self, keys, n_seg, n, seg=None, rows=None):
+        """fh_prior_normal_f32: [n_seg * n, n_mels] noise rows of the keys (a list of (seed, stream), or a device int64
+        [n_seg, 2]); seg: the ragged segment table, rows = its total."""
+        if not isinstance(keys, torch.Tensor):
+            host = np.array([[k[0], k[1]] for k in keys], dtype=np.uint64).view(np.int64)
+            keys = self._upload(torch.from_numpy(host))
+        if keys.shape != (n_seg, 2) or keys.dtype != torch.int64 or not keys.is_contiguous():
+            raise ValueError(f"keys must be a contiguous int64 [{n_seg}, 2], got {keys.dtype} {tuple(keys.shape)}")
+        d = self.flowhigh.n_mels
+        out = torch.empty(n_seg * n if rows is None else rows, d, dtype=torch.float32, device=self.device)
+        hip.check(hip.lib().fh_prior_normal_f32(out.data_ptr(), keys.data_ptr(), hip.ptr(seg), n_seg, n, d, hip.stream()),
+                  "fh_prior_normal_f32")
+        return out
+
+    @torch.no_grad()
+    @hip.on_device
+    def draw_prior(self, frames, seed, *, stream=0):
+        """The noise a prior='device' call with that key uses, as a device tensor (read it back to rebuild a call with noise=,
+        or to hand it to the oracle; prior.prior_normal_host gives the same values without a GPU).
+        frames = N, seed = s            -> [1, N, n_mels]: key (s, stream)
+        frames = N, seed = [s_0, ...]   -> [len(seed), N, n_mels]: clip i's key (an int s_i = (s_i, stream), or a pair)
+        frames = [N_0, N_1, ...]        -> a list of [1, N_i, n_mels] (the ragged form, one launch); seed an int s = keys
+                                           (s, stream + i) as seed=s gives a call over the list, or one item per clip."""
+        ragged = not isinstance(frames, (int, np.integer))
+        count = len(frames) if ragged else (1 if isinstance(seed, (int, np.integer)) else len(seed))
+        if isinstance(seed, (int, np.integer)):
+            keys = [normalize_key(seed, stream + i) for i in range(count)]
+        else:
+            keys = [normalize_key(s_, stream) if isinstance(s_, (int, np.integer)) else k
+                    for k, s_ in zip(expand_seed(seed, count), seed)]
+        if not ragged:
+            return self._device_prior(keys, count, int(frames)).view(count, int(frames), -1)
+        frames = [int(n) for n in frames]
+        seg = self.flowhigh.net.ragged_workspace(frames)["seg"]
+        z = self._device_prior(keys, count, max(frames), seg=seg, rows=sum(frames))
+        out, r = [], 0
+        for n in frames:
+            out.append(z[r:r + n][None])
+            r += n
+        return out
+
     def _integrate(self, y0, cond_mel, batch, n, time_steps, cond_scale=1., ragged=None):
         """Fixed-grid euler / midpoint (torchdiffeq semantics); y0, cond_mel [B*n, n_mels] on device.
         Every update `out = base + h * v(x, t)` is the epilogue of the last GEMM of the vector field;
@@ -458,17 +532,18 @@ class FlowHighSR:
     @torch.no_grad()
     @hip.on_device
     def sample(self, *, cond=None, cond_mask=None, time_steps=4, cond_scale=1., decode_to_audio=True,
-               std_1=None, std_2=None, mel_pp=False, cfm_method=None, noise=None, generator=None):
+               std_1=None, std_2=None, mel_pp=False, cfm_method=None, noise=None, generator=None, seed=None):
         """The reference's `sample` (cfm:162-284).  The returned tensor is the caller's own (the vocoder's output
         buffer belongs to a per-shape launch plan and is overwritten by the next call of the same shape, so the
-        public entry hands out a copy; `generate*` read the plan's buffer in place)."""
+        public entry hands out a copy; `generate*` read the plan's buffer in place).  seed=: _prior_keys."""
+        keys = self._prior_keys(seed, cond.shape[0], generator, noise)
         out = self._sample(cond=cond, cond_mask=cond_mask, time_steps=time_steps, cond_scale=cond_scale,
                            decode_to_audio=decode_to_audio, std_1=std_1, std_2=std_2, mel_pp=mel_pp,
-                           cfm_method=cfm_method, noise=noise, generator=generator)
+                           cfm_method=cfm_method, noise=noise, generator=generator, keys=keys)
         return out.clone() if decode_to_audio else out
 
     def _sample(self, *, cond=None, cond_mask=None, time_steps=4, cond_scale=1., decode_to_audio=True,
-                std_1=None, std_2=None, mel_pp=False, cfm_method=None, noise=None, generator=None):
+                std_1=None, std_2=None, mel_pp=False, cfm_method=None, noise=None, generator=None, keys=None):
         if cfm_method not in _CFM_METHODS:
             cfm_method = self.cfm_method
         if cfm_method in _CFM_METHODS[1:]:
@@ -487,9 +562,12 @@ class FlowHighSR:
         else:
             batch, n, _ = cond.shape
             cond_mel = cond.reshape(batch * n, -1).contiguous()
-        if noise is None:
-            noise = self._draw_noise(batch, n, generator)
-        noise = self._upload(noise.to(torch.float32)).reshape(batch * n, -1).contiguous()
+        if noise is None and keys is not None:                              # prior='device': drawn where it is used
+            noise = self._device_prior(keys, batch, n)
+        else:
+            if noise is None:
+                noise = self._draw_noise(batch, n, generator)
+            noise = self._upload(noise.to(torch.float32)).reshape(batch * n, -1).contiguous()
         cut = None
         if cfm_method == 'basic_cfm':
             y0 = noise
@@ -528,10 +606,11 @@ class FlowHighSR:
         return out
 
     def _sample_ragged(self, conds, noises, time_steps, cfm_method, std_1=None, std_2=None, mels=None, cond_scale=1.,
-                       mel_pp=False, decode_to_audio=True):
+                       mel_pp=False, decode_to_audio=True, keys=None):
         """`sample()` (cfm:162-284, incl. cond_scale != 1 and mel_pp, cfm:162-175,278-279) for clips of DIFFERENT
         lengths as one launch sequence.
-        conds: list of [T48_i] device tensors (peak-normalised), noises: list of [1, N_i, n_mels] host tensors.
+        conds: list of [T48_i] device tensors (peak-normalised), noises: list of [1, N_i, n_mels] host tensors, or None and
+        keys = the clips' (seed, stream) keys: the prior is then drawn on the device, one launch over the segment table.
         Returns the vocoder's waveforms, a list of [1, 480 N_i] (plan-owned buffers; decode_to_audio=False: the mels,
         a list of [N_i, n_mels]), each what _sample gives for that clip alone: the log-mels are made per clip, every
         row-wise operator runs on the packed rows, the operators that look across rows take the clip boundaries (the
@@ -544,11 +623,14 @@ class FlowHighSR:
             mels = [fh.logmel(c[None]) for c in conds]       # [N_i, n_mels] each
         frames = [m.shape[0] for m in mels]
         cond_mel = torch.cat(mels, 0)
-        noise = self._upload(torch.cat([z.reshape(-1, z.shape[-1]).to(torch.float32) for z in noises], 0)).contiguous()
-        if noise.shape != cond_mel.shape:
-            raise ValueError(f"noise rows {tuple(noise.shape)} do not match the clips' frames {tuple(cond_mel.shape)}")
         rws = fh.net.ragged_workspace(frames)
         seg, n_seg, max_n = rws["seg"], len(frames), max(frames)
+        if noises is None:
+            noise = self._device_prior(keys, n_seg, max_n, seg=seg, rows=sum(frames))
+        else:
+            noise = self._upload(torch.cat([z.reshape(-1, z.shape[-1]).to(torch.float32) for z in noises], 0)).contiguous()
+        if noise.shape != cond_mel.shape:
+            raise ValueError(f"noise rows {tuple(noise.shape)} do not match the clips' frames {tuple(cond_mel.shape)}")
         cut = None
         if cfm_method == 'basic_cfm':
             y0 = noise
@@ -572,7 +654,7 @@ class FlowHighSR:
     @torch.no_grad()
     @hip.on_device
     def sample_many(self, conds, *, time_steps=4, cond_scale=1., decode_to_audio=True, std_1=None, std_2=None, mel_pp=False,
-                    cfm_method=None, noise=None, generator=None):
+                    cfm_method=None, noise=None, generator=None, seed=None):
         """`sample()` for a LIST of conditioning clips of different lengths (each [T48_i], 48 kHz, peak-normalised) as
         one masked / ragged launch sequence, with the reference's sampler options (cond_scale: classifier-free
         guidance against null_cond, mel_pp: low-band replacement with per-clip cutoff bins, std_1 / std_2: prior scales of the
@@ -581,22 +663,26 @@ class FlowHighSR:
         [1, 1, 480 N_i] waveforms (or [1, N_i, n_mels] mels)."""
         if cfm_method not in _CFM_METHODS:
             cfm_method = self.cfm_method
+        conds = list(conds)
+        keys = self._prior_keys(seed, len(conds), generator, noise)
         conds = [c.to(self.device, torch.float32).reshape(-1) for c in conds]
         frames = [c.shape[0] // 480 for c in conds]
-        if noise is None:
+        if noise is None and keys is None:
             noise = [self._draw_noise(1, n, generator) for n in frames]
         outs = self._sample_ragged(conds, noise, time_steps, cfm_method, std_1=std_1, std_2=std_2, cond_scale=cond_scale,
-                                   mel_pp=mel_pp, decode_to_audio=decode_to_audio)
+                                   mel_pp=mel_pp, decode_to_audio=decode_to_audio, keys=keys)
         return [o.clone().unsqueeze(1) if decode_to_audio else o.clone()[None] for o in outs]
 
     @torch.no_grad()
     @hip.on_device
     def generate_batch(self, clips, sr, target_sampling_rate=48000, timestep=1, *, noise=None,
-                       generator=None, return_stages=False):
-        cond = self._prepare_cond(list(clips), sr, target_sampling_rate)
+                       generator=None, return_stages=False, seed=None, _keys=None):
+        clips = list(clips)
+        keys = _keys if _keys is not None else self._prior_keys(seed, len(clips), generator, noise)
+        cond = self._prepare_cond(clips, sr, target_sampling_rate)
         kw = dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
         HR_audio = self._sample(cond=cond, time_steps=timestep, cfm_method=self.cfm_method, noise=noise,
-                                generator=generator, **kw)
+                                generator=generator, keys=keys, **kw)
         HR_audio = HR_audio.squeeze(1)
         out = self.postproc(HR_audio, cond, cond.size(-1), return_cr=return_stages)
         if return_stages:
@@ -606,11 +692,13 @@ class FlowHighSR:
     @torch.no_grad()
     @hip.on_device
     def generate_many(self, clips, sr, target_sampling_rate=48000, timestep=1, *, noise=None, generator=None,
-                      max_batch=64, streams=None, ragged=None, max_frames=None):
+                      max_batch=64, streams=None, ragged=None, max_frames=None, seed=None):
         """Serving-side entry (the gradio caller of app.py:8-26, many requests at once): clips of ANY lengths,
         int16 or float.  Clips of equal length run as one batch (at most max_batch rows), so every result is
         what generate() returns for that clip alone; the prior noise is drawn in the order of `clips`, as a loop
         over generate() would.  noise: optional list of [1, N_i, n_mels] tensors.  Returns a list of [1, T48_i].
+        On a prior='device' model nothing is drawn on the host: every clip has a (seed, stream) key (seed=, or one
+        torch.randint per clip from the generator, in the order of `clips`: _prior_keys) and the launch sequences draw from them.
         ragged (default on, FH_RAGGED=0 switches it off): clips of different lengths run as ONE launch sequence
         (masked / ragged batch, the reference's mask paths transformer.py:35-44, attend.py:127-128): ~120 launches for
         the whole list instead of ~120 per distinct length; at most max_frames (FH_RAGGED_MAX_FRAMES, default 12 000 =
@@ -624,21 +712,27 @@ class FlowHighSR:
         mix of 0.5-4 s clips: between -15 % and +40 % of the single-stream time from run to run (the host enqueues
         ~120 launches per clip and is the bottleneck either way), hence off by default."""
         clips = list(clips)
+        keys = self._prior_keys(seed, len(clips), generator, noise)
         if noise is None:
-            noise = []
+            frames = []
             for a in clips:
                 n_in = int(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).shape[-1])
                 t48 = n_in * target_sampling_rate // sr if (n_in * target_sampling_rate) % sr == 0 \
                     else -(-n_in * target_sampling_rate // sr)
-                noise.append(self._draw_noise(1, t48 // 480, generator))
-        if len(noise) != len(clips):
+                frames.append(t48 // 480)
+            if keys is None:
+                noise = [self._draw_noise(1, n, generator) for n in frames]
+        if noise is not None and len(noise) != len(clips):
             raise ValueError("one noise tensor per clip")
+        # the shape of every clip's noise: given or drawn on the host, or what the device draws from the clip's key
+        shapes = [tuple(z.shape) for z in noise] if noise is not None else [(1, n, self.flowhigh.n_mels) for n in frames]
         if ragged is None:
             ragged = os.environ.get("FH_RAGGED", "1") != "0"
         lengths = [int(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).shape[-1]) for a in clips]
         if ragged and len(set(lengths)) > 1 and target_sampling_rate == 48000:
             try:
-                return self._generate_many_ragged(clips, lengths, sr, timestep, noise, max_frames)
+                return self._generate_many_ragged(clips, lengths, sr, timestep, noise, max_frames, keys=keys,
+                                                  frames=[sh[1] for sh in shapes])
             except NotImplementedError as e:
                 # a vocoder configuration whose launch positions cannot be merged: one batch per length (said once)
                 if not getattr(self, "_ragged_fallback_logged", False):
@@ -648,7 +742,7 @@ class FlowHighSR:
                                                               "running one batch per clip length", e)
         buckets = {}
         for i, a in enumerate(clips):
-            key = (int(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).shape[-1]), tuple(noise[i].shape))
+            key = (int(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).shape[-1]), shapes[i])
             buckets.setdefault(key, []).append(i)
         out = [None] * len(clips)
         if streams is None:
@@ -666,9 +760,11 @@ class FlowHighSR:
             with torch.cuda.stream(st):
                 for k in range(0, len(idx), max_batch):
                     part = idx[k:k + max_batch]
-                    y = self.generate_batch([clips[i] for i in part], sr, target_sampling_rate, timestep,
-                                            noise=noise[part[0]] if len(part) == 1 else
-                                            torch.cat([noise[i] for i in part], 0))
+                    if keys is not None:
+                        prior = dict(_keys=[keys[i] for i in part])
+                    else:
+                        prior = dict(noise=noise[part[0]] if len(part) == 1 else torch.cat([noise[i] for i in part], 0))
+                    y = self.generate_batch([clips[i] for i in part], sr, target_sampling_rate, timestep, **prior)
                     for r, i in enumerate(part):
                         out[i] = y[r:r + 1].clone()
                         if st is not main:
@@ -678,18 +774,22 @@ class FlowHighSR:
                 main.wait_stream(s_)
         return out
 
-    def _generate_many_ragged(self, clips, lengths, sr, timestep, noise, max_frames):
+    def _generate_many_ragged(self, clips, lengths, sr, timestep, noise, max_frames, keys=None, frames=None):
         if max_frames is None:
             max_frames = int(os.environ.get("FH_RAGGED_MAX_FRAMES", "12000"))
         chunk_limit = int(os.environ.get("FH_VOCODER_CHUNK_FRAMES", "6000"))
-        frames = [n.shape[1] for n in noise]
+        if frames is None:
+            frames = [n.shape[1] for n in noise]
+
+        def prior_of(i):              # one clip on its own: its noise, or its key
+            return dict(_keys=[keys[i]]) if keys is not None else dict(noise=noise[i])
         out = [None] * len(clips)
         kw = dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
         # greedy packing in list order; a clip that does not fit a sequence of its own runs through generate()
         groups, cur, tot = [], [], 0
         for i, n in enumerate(frames):
             if n > max_frames or (chunk_limit > 0 and n > chunk_limit):
-                out[i] = self.generate_batch([clips[i]], sr, 48000, timestep, noise=noise[i]).clone()
+                out[i] = self.generate_batch([clips[i]], sr, 48000, timestep, **prior_of(i)).clone()
                 continue
             if cur and tot + n > max_frames:
                 groups.append(cur)
@@ -700,12 +800,15 @@ class FlowHighSR:
             groups.append(cur)
         for idx in groups:
             if len(idx) == 1:
-                out[idx[0]] = self.generate_batch([clips[idx[0]]], sr, 48000, timestep, noise=noise[idx[0]]).clone()
+                out[idx[0]] = self.generate_batch([clips[idx[0]]], sr, 48000, timestep, **prior_of(idx[0])).clone()
                 continue
             # (the per-clip front and back ends -- ~8 + ~12 small launches per clip -- on up to 4 side streams measured
             # 121.5 ms against 121.3 ms on one stream for the 24-clip mix: not worth the cross-stream bookkeeping)
             conds = [self._prepare_cond([clips[i]], sr, 48000)[0] for i in idx]
-            wavs = self._sample_ragged(conds, [noise[i] for i in idx], timestep, self.cfm_method, **kw)
+            if keys is not None:
+                wavs = self._sample_ragged(conds, None, timestep, self.cfm_method, keys=[keys[i] for i in idx], **kw)
+            else:
+                wavs = self._sample_ragged(conds, [noise[i] for i in idx], timestep, self.cfm_method, **kw)
             for i, cond, wav in zip(idx, conds, wavs):
                 out[i] = self.postproc(wav, cond[None], cond.shape[0]).clone()
         return out
@@ -718,13 +821,22 @@ class FlowHighSR:
 
     @torch.no_grad()
     @hip.on_device
-    def generate_from_device(self, x, sr, timestep=1, *, noise):
+    def generate_from_device(self, x, sr, timestep=1, *, noise=None, seed=None, generator=None):
         """Device-resident variant (no host work, no sync; graph-capturable): x [B, T_in] float32
         low-rate clips already in HBM (|x| <= 1), noise [B, N, n_mels] -> [B, T48].  Same
-        arithmetic as generate_batch with upsampling_method='hip'."""
+        arithmetic as generate_batch with upsampling_method='hip'.  On a prior='device' model `noise` may be left out:
+        the prior is drawn on the device from seed= (or from keys taken from the generator: _prior_keys); a
+        prior='reference' model has no device-side draw and needs `noise`."""
+        keys = self._prior_keys(seed, x.shape[0], generator, noise)
+        if noise is None and keys is None:
+            raise ValueError("generate_from_device: a prior='reference' model needs noise= (its prior is drawn on the host); "
+                             "construct the model with prior='device' to draw it on the device")
+        return self._generate_from_device(x, sr, timestep, noise=noise, keys=keys)
+
+    def _generate_from_device(self, x, sr, timestep=1, *, noise=None, keys=None):
         cond = self.resampler(x, sr, 48000)
         kw = dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
-        wav = self._sample(cond=cond, time_steps=timestep, cfm_method=self.cfm_method, noise=noise, **kw).squeeze(1)
+        wav = self._sample(cond=cond, time_steps=timestep, cfm_method=self.cfm_method, noise=noise, keys=keys, **kw).squeeze(1)
         return self.postproc(wav, cond, cond.size(-1))
 
     @torch.no_grad()
@@ -732,11 +844,14 @@ class FlowHighSR:
     def capture(self, batch, n_in, sr, timestep=1):
         """HIP-graph form of generate_from_device for one input shape: the ~150 launches of a call are recorded once
         and replayed with a single enqueue (short clips are launch-bound from Python).  Returns a `GraphedGenerate`
-        with static buffers `.x` [batch, n_in] and `.noise` [batch * N, n_mels]; fill them and call `.replay()`."""
+        with static buffers `.x` [batch, n_in] and `.noise` [batch * N, n_mels]; fill them and call `.replay()`.
+        On a prior='device' model the graph records the prior launch and has `.keys` (device int64 [batch, 2] = the clips'
+        (seed, stream)) in place of `.noise`: a replay draws from the keys that are there."""
         return GraphedGenerate(self, batch, n_in, sr, timestep)
 
     @torch.no_grad()
     @hip.on_device
-    def generate(self, audio, sr: int, target_sampling_rate=48000, timestep=1, *, noise=None, generator=None):
-        """One clip, reference contract: returns float32 [1, T48] on the model device."""
-        return self.generate_batch([audio], sr, target_sampling_rate, timestep, noise=noise, generator=generator)
+    def generate(self, audio, sr: int, target_sampling_rate=48000, timestep=1, *, noise=None, generator=None, seed=None):
+        """One clip, reference contract: returns float32 [1, T48] on the model device.  seed= (prior='device' models): the
+        clip's noise is that of the key (seed, 0), or of a (seed, stream) pair given as [(seed, stream)]."""
+        return self.generate_batch([audio], sr, target_sampling_rate, timestep, noise=noise, generator=generator, seed=seed)

@@ -4,7 +4,8 @@
 Requests from any number of caller threads are collected for a few milliseconds, grouped by (input rate,
 steps) and pushed through `FlowHighSR.generate_many`: clips of ANY lengths then run as one ragged launch
 sequence on the GPU (equal lengths as one batch) while every caller still gets exactly what `generate()` would
-have returned for its clip alone (same per-clip noise draw when a seed is given).  Host logic only: no gradio,
+have returned for its clip alone (same per-clip noise draw when a seed is given; on a prior='device' model the seed is the
+clip's key (seed, 0) and the noise is drawn on the device).  Host logic only: no gradio,
 no sockets (the reference's UI / network layers are out of scope); `generate()` below has the signature of
 the function `app.py` hands to `gr.Interface`.
 """
@@ -84,15 +85,19 @@ class BatchingServer:
                 groups.setdefault((item[1], item[2]), []).append(item)      # same input rate and step count
             for (sr_in, steps), items in groups.items():
                 try:
-                    noise = None
-                    if any(it[3] is not None for it in items):
+                    noise, prior = None, {}
+                    if getattr(self.model, "prior", "reference") == "device":
+                        # the device prior: a request's seed is its key (seed, 0); nothing is drawn on the host
+                        if any(it[3] is not None for it in items):
+                            prior = dict(seed=[0 if it[3] is None else int(it[3]) for it in items])
+                    elif any(it[3] is not None for it in items):
                         noise = []
                         for a, _, _, seed, _ in items:
                             g = torch.Generator().manual_seed(0 if seed is None else int(seed))
                             t48 = -(-a.shape[-1] * 48000 // sr_in)
                             noise.append(self.model._draw_noise(1, t48 // 480, g))
                     outs = self.model.generate_many([it[0] for it in items], sr_in, 48000, steps, noise=noise,
-                                                    max_batch=self.max_batch)
+                                                    max_batch=self.max_batch, **prior)
                     for it, y in zip(items, outs):
                         it[4].set_result(y.detach().cpu().squeeze(0).numpy())
                 except Exception as e:            # noqa: BLE001  (every waiting caller must be released)

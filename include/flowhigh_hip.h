@@ -509,7 +509,17 @@ int fh_mel_splice_seg_f32(const float* low, const float* high, const int32_t* cu
 int fh_axpby_f32(const float* x, float a, const float* y, float b, float* out, long long n,
                  void* stream);
 
-/* out[b,t,:] = bins < cr[b] ? src : pred   (P-layout, postprocessing.py:36-37). */
+/* eps ~ N(0,1) for the sampler's prior (cfm_superresolution.py:219-236), drawn on the device: counter-based Philox4x32-10 +
+ * Box-Muller.  out [rows, d] token-major.  keys: DEVICE uint64 [n_seg][2] = (seed, stream) of every clip.
+ * seg NULL: n_seg clips of n rows each; seg = device int32 [n_seg][2] = (first row, rows) as in the *_seg entries, n = longest clip.
+ * d % 4 == 0, out 16-byte aligned.  An element's value depends on (seed, stream, row within its clip, column, d) only.
+ * Element (f, m) of a clip: e = f d + m, quad q = e >> 2, lane e & 3; (r0 .. r3) = Philox4x32-10 of the counter
+ * (q & 0xffffffff, q >> 32, stream & 0xffffffff, stream >> 32) under the key (seed & 0xffffffff, seed >> 32); with
+ * u1 = ((r >> 8) + 1) 2^-24 and u2 = (r' >> 8) 2^-24, lanes 0, 1 = sqrt(-2 ln u1) (cos, sin)(2 pi u2) of (r0, r1), lanes 2, 3 the same
+ * of (r2, r3); within 1e-5 of the float64 evaluation (flowhigh_amd/prior.py: prior_normal_host).  n_seg <= 65535, n d < 2^33. */
+int fh_prior_normal_f32(float* out, const uint64_t* keys, const int32_t* seg, int n_seg, int n, int d, void* stream);
+
+/* out[b,t,:] = bins < cr[b] ? src : pred  (P-layout, postprocessing.py:36-37). */
 int fh_spec_splice_f32(const float* pred, const float* src, const int32_t* cr, float* out,
                        int batch, int n_frames, void* stream);
 
