@@ -10,12 +10,13 @@
 //   fh_istft_ola_f32      the overlap-add half of torch.istft               postprocessing.py:8,39
 //   fh_peak_*             audio / max|audio| * 0.99 ; cond /= max|cond|      postprocessing.py:40, flowhighsr.py:69
 //   fh_resample_poly_f32  scipy.signal.resample_poly (host numpy in the ref) flowhighsr.py:68
-#include "fh_common.h"
+// The per-element arithmetic lives in frontend_elem.h, shared with the segment forms of these entries (frontend_seg.hip).
+#include "frontend_elem.h"
 
 namespace {
 
-constexpr int P_BLOCKS = 33;               // 33 * 32 = 1056 >= 1025 bins
-constexpr int P_WIDTH = P_BLOCKS * 64;     // 2112 floats per frame
+constexpr int P_BLOCKS = FE_P_BLOCKS;
+constexpr int P_WIDTH = FE_P_WIDTH;        // 2112 floats per frame
 
 __global__ __launch_bounds__(256) void frame_kernel(const float* __restrict__ audio,
                                                     const float* __restrict__ window,
@@ -25,49 +26,17 @@ __global__ __launch_bounds__(256) void frame_kernel(const float* __restrict__ au
   const int t = blockIdx.x, b = blockIdx.y;
   const float* a = audio + (size_t)b * len;
   float* f = frames + ((size_t)b * n_frames + t) * nfft;
-  for (int k = threadIdx.x; k < nfft; k += 256) {
-    int i = hop * t + k - pad;
-    float v;
-    if (pad_mode == 0) {            // reflect (no edge repeat); pad < len
-      if (i < 0) i = -i;
-      if (i >= len) i = 2 * (len - 1) - i;
-      v = a[i];
-    } else {
-      v = (i >= 0 && i < len) ? a[i] : 0.f;
-    }
-    f[k] = v * window[k];
-  }
+  for (int k = threadIdx.x; k < nfft; k += 256) f[k] = fe_frame_value(a, window, len, t, k, hop, pad, pad_mode);
 }
 
 // grid (33, batch); thread -> (bin i = tid & 31, frame lane = tid >> 5); 32 frame lanes x 2 independent
 // partial sums keep enough loads in flight (8 lanes with one dependent chain each took 46 us at B = 1)
-constexpr int SE_LANES = 32;
+constexpr int SE_LANES = FE_SE_LANES;
 __global__ __launch_bounds__(32 * SE_LANES) void spec_energy_kernel(const float* __restrict__ spec,
                                                                     float* __restrict__ energy,
                                                                     int n_frames) {
-  __shared__ double part[SE_LANES][32];
-  const int blk = blockIdx.x, b = blockIdx.y;
-  const int i = threadIdx.x & 31, fl = threadIdx.x >> 5;
-  const float* s = spec + (size_t)b * n_frames * P_WIDTH + blk * 64;
-  double acc = 0.0, acc2 = 0.0;
-  for (int t = fl; t < n_frames; t += 2 * SE_LANES) {
-    float re = s[(size_t)t * P_WIDTH + i], im = s[(size_t)t * P_WIDTH + 32 + i];
-    acc += (double)sqrtf(re * re + im * im);
-    const int t2 = t + SE_LANES;
-    if (t2 < n_frames) {
-      re = s[(size_t)t2 * P_WIDTH + i], im = s[(size_t)t2 * P_WIDTH + 32 + i];
-      acc2 += (double)sqrtf(re * re + im * im);
-    }
-  }
-  part[fl][i] = acc + acc2;
-  __syncthreads();
-  if (fl == 0) {
-    double tot = 0.0;
-#pragma unroll
-    for (int q = 0; q < SE_LANES; ++q) tot += part[q][i];
-    int bin = blk * 32 + i;
-    if (bin < 1025) energy[b * 1025 + bin] = (float)tot;
-  }
+  const int b = blockIdx.y;
+  fe_spec_energy_block(spec + (size_t)b * n_frames * P_WIDTH, energy + b * 1025, n_frames, blockIdx.x);
 }
 
 // torch.cumsum on CPU accumulates float32 input in double and rounds every prefix to float;
@@ -155,7 +124,7 @@ __global__ __launch_bounds__(256) void splice_kernel(const float* __restrict__ p
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= per_clip) return;
   const int col = (int)(idx % P_WIDTH);
-  const int bin = (col >> 6) * 32 + (col & 31);
+  const int bin = fe_p_bin(col);
   const size_t g = (size_t)b * per_clip + idx;
   out[g] = bin < cr[b] ? src[g] : pred[g];
 }
@@ -165,53 +134,23 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
                                                         float* __restrict__ y,
                                                         uint32_t* __restrict__ peak_bits,
                                                         int n_frames, int len, int nfft, int hop) {
-  __shared__ float red[4];
   const int b = blockIdx.y;
   const int j = blockIdx.x * 256 + threadIdx.x;
   float v = 0.f;
   if (j < len) {
-    const int avail = hop * (n_frames - 1) + nfft / 2;   // torch.istft zero-fills past the OLA signal's end
-    if (j < avail) {
-      const int p = j + nfft / 2;
-      int t_hi = p / hop;
-      if (t_hi > n_frames - 1) t_hi = n_frames - 1;
-      int t_lo = (p - nfft + hop) / hop;          // ceil((p - nfft + 1) / hop) for p - nfft + 1 > 0
-      if (p - nfft + 1 <= 0) t_lo = 0;
-      float num = 0.f, den = 0.f;
-      const float* fb = frames + (size_t)b * n_frames * nfft;
-      for (int t = t_lo; t <= t_hi; ++t) {
-        const int k = p - hop * t;
-        const float w = window[k];
-        num = fmaf(w, fb[(size_t)t * nfft + k], num);
-        den = fmaf(w, w, den);
-      }
-      v = num / den;
-    }
+    v = fe_istft_ola_value(frames + (size_t)b * n_frames * nfft, window, j, n_frames, nfft, hop);
     y[(size_t)b * len + j] = v;
   }
-  float m = wave_max(fabsf(v));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    atomicMax(peak_bits + b, __float_as_uint(m));
-  }
+  fe_block_peak(fabsf(v), peak_bits + b);
 }
 
 __global__ __launch_bounds__(256) void peak_abs_kernel(const float* __restrict__ x,
                                                        uint32_t* __restrict__ peak_bits, int len) {
-  __shared__ float red[4];
   const int b = blockIdx.y;
   const float* xb = x + (size_t)b * len;
   float m = 0.f;
   for (int j = blockIdx.x * 256 + threadIdx.x; j < len; j += gridDim.x * 256) m = fmaxf(m, fabsf(xb[j]));
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    atomicMax(peak_bits + b, __float_as_uint(m));
-  }
+  fe_block_peak(m, peak_bits + b);
 }
 
 __global__ __launch_bounds__(256) void peak_scale_kernel(float* __restrict__ y,
@@ -221,8 +160,7 @@ __global__ __launch_bounds__(256) void peak_scale_kernel(float* __restrict__ y,
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= len) return;
   const float peak = __uint_as_float(peak_bits[b]);
-  float v = y[(size_t)b * len + j] / peak;       // same order as the reference: (y / peak) * 0.99
-  y[(size_t)b * len + j] = v * target;
+  y[(size_t)b * len + j] = fe_peak_scale_value(y[(size_t)b * len + j], peak, target);
 }
 
 // out[i] = sum_j x[j] * h[(i + pre) * down - j * up],  h zero outside [0, n_taps)
@@ -234,19 +172,7 @@ __global__ __launch_bounds__(256) void resample_poly_kernel(const float* __restr
   const int b = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= len_out) return;
-  const float* xb = x + (size_t)b * len_in;
-  const long long pos = (long long)(i + pre) * down;
-  long long j_hi = pos / up;
-  if (j_hi > len_in - 1) j_hi = len_in - 1;
-  float acc = 0.f;
-  // ascending j == descending tap index; scipy's upfirdn walks the taps in ascending order,
-  // so accumulate from the smallest tap index (largest j) down to match its summation order.
-  for (long long j = j_hi; j >= 0; --j) {
-    long long k = pos - j * up;
-    if (k >= n_taps) break;
-    acc = fmaf(xb[j], h[k], acc);
-  }
-  y[(size_t)b * len_out + i] = acc;
+  y[(size_t)b * len_out + i] = fe_resample_value(x + (size_t)b * len_in, h, i, len_in, up, down, n_taps, pre);
 }
 
 }  // namespace

@@ -60,6 +60,20 @@ _CFM_METHODS = ("basic_cfm", "independent_cfm_adaptive", "independent_cfm_consta
 # host (reference_prior_draw below; the default).  'device': this project's own counter-based stream, drawn by fh_prior_normal_f32
 # from one (seed, stream) key per clip (prior.py restates it on the host)
 _PRIORS = ("reference", "device")
+# how a ragged generate_many call runs what surrounds its one transformer + vocoder launch sequence (resampling, peak
+# normalisation, log-mel, the vocoder's input copies, post-processing).  'per_clip': once per clip, the batched entries on
+# batches of one (the default).  'ragged': the segment forms of the same entries (csrc/frontend_seg.hip), one launch per step
+# for the whole list; same bits per clip
+_ENDS = ("per_clip", "ragged")
+
+
+def resolve_ends(ends=None):
+    """ends= of generate_many / BatchingServer: the keyword, else FH_RAGGED_ENDS, else 'per_clip'."""
+    if ends is None:
+        ends = os.environ.get("FH_RAGGED_ENDS") or "per_clip"
+    if ends not in _ENDS:
+        raise ValueError(f"ends must be one of {_ENDS}, got {ends!r}")
+    return ends
 
 
 def reference_prior_draw(n_frames, n_mels=256, generator=None):
@@ -390,10 +404,8 @@ class FlowHighSR:
             return t.to(self.device)
         return t.pin_memory().to(self.device, non_blocking=True)
 
-    def _prepare_cond(self, clips, sr, target_sampling_rate):
-        """list of 1-D arrays (equal length) -> cond [B, T48] float32 on device, peak-normalised per clip."""
-        if target_sampling_rate != 48000:
-            raise NotImplementedError("the mel codec is fixed at 48 kHz")
+    @staticmethod
+    def _host_clips(clips):
         prepared = []
         for audio in clips:
             if isinstance(audio, torch.Tensor):
@@ -404,6 +416,29 @@ class FlowHighSR:
             if audio.max() > 1:
                 audio = audio / 32768.0
             prepared.append(audio)
+        return prepared
+
+    def _prepare_cond_ragged(self, clips, sr):
+        """_prepare_cond for clips of different lengths: (cond packed [sum T48_i], list of [T48_i] views) on the device,
+        peak-normalised per clip with the bits of _prepare_cond on each clip alone.  One upload for the list; 'hip': the
+        segment forms of the resampler's launches, 'scipy': the host resampling and normalisation per clip, as they are."""
+        prepared = self._host_clips(clips)
+        if self.upsampling_method == 'scipy':
+            import scipy.signal
+            conds = []
+            for audio in prepared:
+                cond = scipy.signal.resample_poly(audio, 48000, sr)
+                conds.append(cond / np.max(np.abs(cond)))
+            return self.resampler.upload_packed(conds)
+        if self.upsampling_method == 'hip':
+            return self.resampler.ragged(prepared, sr, 48000)
+        raise UnboundLocalError(f"cond: unsupported upsampling_method '{self.upsampling_method}'")
+
+    def _prepare_cond(self, clips, sr, target_sampling_rate):
+        """list of 1-D arrays (equal length) -> cond [B, T48] float32 on device, peak-normalised per clip."""
+        if target_sampling_rate != 48000:
+            raise NotImplementedError("the mel codec is fixed at 48 kHz")
+        prepared = self._host_clips(clips)
         if self.upsampling_method == 'scipy':
             import scipy.signal
             conds = []
@@ -606,7 +641,7 @@ class FlowHighSR:
         return out
 
     def _sample_ragged(self, conds, noises, time_steps, cfm_method, std_1=None, std_2=None, mels=None, cond_scale=1.,
-                       mel_pp=False, decode_to_audio=True, keys=None):
+                       mel_pp=False, decode_to_audio=True, keys=None, cond_mel=None):
         """`sample()` (cfm:162-284, incl. cond_scale != 1 and mel_pp, cfm:162-175,278-279) for clips of DIFFERENT
         lengths as one launch sequence.
         conds: list of [T48_i] device tensors (peak-normalised), noises: list of [1, N_i, n_mels] host tensors, or None and
@@ -614,7 +649,9 @@ class FlowHighSR:
         Returns the vocoder's waveforms, a list of [1, 480 N_i] (plan-owned buffers; decode_to_audio=False: the mels,
         a list of [N_i, n_mels]), each what _sample gives for that clip alone: the log-mels are made per clip, every
         row-wise operator runs on the packed rows, the operators that look across rows take the clip boundaries (the
-        mel cutoff bins are per clip: fh_mel_*_seg_f32), the vocoder runs its merged plan."""
+        mel cutoff bins are per clip: fh_mel_*_seg_f32), the vocoder runs its merged plan.
+        cond_mel (with mels = its per-clip views; ends='ragged'): the clips' log-mels packed already (LogMel.ragged); nothing
+        is concatenated and the vocoder takes the packed result (forward_ragged_packed)."""
         fh = self.flowhigh
         if cfm_method in _CFM_METHODS[1:]:
             if std_1 is None or std_2 is None:               # cfm:180-183 (resets BOTH; generate() never passes std_1)
@@ -622,7 +659,9 @@ class FlowHighSR:
         if mels is None:
             mels = [fh.logmel(c[None]) for c in conds]       # [N_i, n_mels] each
         frames = [m.shape[0] for m in mels]
-        cond_mel = torch.cat(mels, 0)
+        packed = cond_mel is not None
+        if not packed:
+            cond_mel = torch.cat(mels, 0)
         rws = fh.net.ragged_workspace(frames)
         seg, n_seg, max_n = rws["seg"], len(frames), max(frames)
         if noises is None:
@@ -645,6 +684,8 @@ class FlowHighSR:
         if mel_pp:                                           # cfm:278-279, per clip
             cut = cut if cut is not None else self._cutoff_bins_seg(cond_mel, seg, n_seg)
             mel = self._mel_replace_seg(mel, cond_mel, cut, seg, n_seg, max_n)
+        if packed and decode_to_audio:
+            return fh.vocoder.forward_ragged_packed(mel, frames)
         rows, out = 0, []
         for n in frames:
             out.append(mel[rows:rows + n])
@@ -692,7 +733,7 @@ class FlowHighSR:
     @torch.no_grad()
     @hip.on_device
     def generate_many(self, clips, sr, target_sampling_rate=48000, timestep=1, *, noise=None, generator=None,
-                      max_batch=64, streams=None, ragged=None, max_frames=None, seed=None):
+                      max_batch=64, streams=None, ragged=None, max_frames=None, seed=None, ends=None):
         """Serving-side entry (the gradio caller of app.py:8-26, many requests at once): clips of ANY lengths,
         int16 or float.  Clips of equal length run as one batch (at most max_batch rows), so every result is
         what generate() returns for that clip alone; the prior noise is drawn in the order of `clips`, as a loop
@@ -704,6 +745,10 @@ class FlowHighSR:
         the whole list instead of ~120 per distinct length; at most max_frames (FH_RAGGED_MAX_FRAMES, default 12 000 =
         120 s of audio) frames per sequence; clips too long for that (or for the unchunked vocoder) run alone.
         Results are bit-identical to generate() per clip either way.
+        ends ('per_clip' | 'ragged'; None: FH_RAGGED_ENDS, else 'per_clip'): what surrounds the launch sequence of a ragged
+        group of two or more clips -- resampling and peak normalisation, log-mel, the vocoder's input copies, post-processing.
+        'per_clip' runs them once per clip (~18 launches each); 'ragged' runs their segment forms (csrc/frontend_seg.hip), one
+        launch per step for the whole group, out of workspaces kept per mix of lengths; same bits per clip.
         streams (ragged off): batches of different FRAME COUNTS can be enqueued round-robin on several HIP streams (FH_SERVE_STREAMS,
         default 1), so that the launches of a short clip - a few dozen blocks each, a fraction of the 256 CUs - overlap
         with those of the next one.  The per-shape workspaces are keyed by (batch, frames): two input lengths with the
@@ -712,6 +757,7 @@ class FlowHighSR:
         mix of 0.5-4 s clips: between -15 % and +40 % of the single-stream time from run to run (the host enqueues
         ~120 launches per clip and is the bottleneck either way), hence off by default."""
         clips = list(clips)
+        ends = resolve_ends(ends)
         keys = self._prior_keys(seed, len(clips), generator, noise)
         if noise is None:
             frames = []
@@ -732,7 +778,7 @@ class FlowHighSR:
         if ragged and len(set(lengths)) > 1 and target_sampling_rate == 48000:
             try:
                 return self._generate_many_ragged(clips, lengths, sr, timestep, noise, max_frames, keys=keys,
-                                                  frames=[sh[1] for sh in shapes])
+                                                  frames=[sh[1] for sh in shapes], ends=ends)
             except NotImplementedError as e:
                 # a vocoder configuration whose launch positions cannot be merged: one batch per length (said once)
                 if not getattr(self, "_ragged_fallback_logged", False):
@@ -774,7 +820,7 @@ class FlowHighSR:
                 main.wait_stream(s_)
         return out
 
-    def _generate_many_ragged(self, clips, lengths, sr, timestep, noise, max_frames, keys=None, frames=None):
+    def _generate_many_ragged(self, clips, lengths, sr, timestep, noise, max_frames, keys=None, frames=None, ends="per_clip"):
         if max_frames is None:
             max_frames = int(os.environ.get("FH_RAGGED_MAX_FRAMES", "12000"))
         chunk_limit = int(os.environ.get("FH_VOCODER_CHUNK_FRAMES", "6000"))
@@ -801,6 +847,20 @@ class FlowHighSR:
         for idx in groups:
             if len(idx) == 1:
                 out[idx[0]] = self.generate_batch([clips[idx[0]]], sr, 48000, timestep, **prior_of(idx[0])).clone()
+                continue
+            prior = dict(keys=[keys[i] for i in idx]) if keys is not None else {}
+            if ends == "ragged":
+                # front and back end as segment-form launches over the group: nothing below depends on the number of clips
+                _, conds = self._prepare_cond_ragged([clips[i] for i in idx], sr)
+                cond_mel, mels = self.flowhigh.logmel.ragged(conds)
+                wavs = self._sample_ragged(conds, None if keys is not None else [noise[i] for i in idx], timestep, self.cfm_method,
+                                           mels=mels, cond_mel=cond_mel, **prior, **kw)
+                packed, views = self.postproc.ragged(wavs, conds, [c.shape[0] for c in conds])
+                packed = packed.clone()                      # (the caller's own: one copy for the group, handed out as views)
+                start = 0
+                for i, v in zip(idx, views):
+                    out[i] = packed[start:start + v.shape[0]][None]
+                    start += v.shape[0]
                 continue
             # (the per-clip front and back ends -- ~8 + ~12 small launches per clip -- on up to 4 side streams measured
             # 121.5 ms against 121.3 ms on one stream for the 24-clip mix: not worth the cross-stream bookkeeping)

@@ -11,6 +11,7 @@ device scan.
 """
 import os
 
+import numpy as np
 import torch
 
 from . import hip, tables
@@ -36,6 +37,74 @@ class _Const:
                 c["w_inv"] = tables.dft_inverse_weight().to(device)
             cls._cache[key] = c
         return cls._cache[key]
+
+
+# ---- ragged calls: clips of different lengths through the segment-form entries (csrc/frontend_seg.hip) -------------------
+def ragged_clip_tables(lengths_in, sr_in, sr_out=48000, pred_lens=None, check_mel=True):
+    """Host side of the clip tables of a ragged call, for clips of `lengths_in` samples at sr_in (lists, one item per clip):
+      len_in / in_off     samples and first sample of every clip in the packed low-rate input
+      len_out / out_off   T_i = tables.resample_out_len and first sample in the packed 48 kHz buffers (cond, output)
+      mel_rows / mel_row0 N_i = T_i // 480 frames of the mel front end and the clip's first row among the packed frames
+      pred_len            Tp_i, the vocoder's samples for N_i frames (480 N_i unless given: Vocoder.out_len)
+      pp_rows / pp_row0   F_i = min(1 + Tp_i // 480, 1 + T_i // 480) frames of the post-processing STFT, and their first row
+    Everything is back to back.  A clip too short for the reflect pad of the front end is refused as LogMel refuses it
+    (check_mel=False: the resampler alone takes any length)."""
+    len_in = [int(n) for n in lengths_in]
+    if not len_in:
+        raise ValueError("empty clip list")
+    len_out = [tables.resample_out_len(n, sr_out, sr_in) for n in len_in]
+    mel_rows = [t // HOP for t in len_out]
+    for t, n in zip(len_out, mel_rows):
+        if check_mel and (n < 1 or t <= (N_FFT - HOP) // 2):
+            raise ValueError(f"clip of {t} samples is too short for the mel front end")
+    pred_len = [HOP * n for n in mel_rows] if pred_lens is None else [int(n) for n in pred_lens]
+    if len(pred_len) != len(len_in):
+        raise ValueError("one pred length per clip")
+    pp_rows = [min(1 + tp // HOP, 1 + t // HOP) for tp, t in zip(pred_len, len_out)]
+
+    def starts(v):
+        return [int(x) for x in np.cumsum([0] + list(v[:-1]))]
+    return dict(len_in=len_in, in_off=starts(len_in), len_out=len_out, out_off=starts(len_out), mel_rows=mel_rows,
+                mel_row0=starts(mel_rows), pred_len=pred_len, pp_rows=pp_rows, pp_row0=starts(pp_rows))
+
+
+def _ptr(t):
+    return t.data_ptr()
+
+
+def upload_tables(parts, device):
+    """Descriptor arrays and segment tables of a call (ctypes arrays / int32 numpy arrays) as ONE pinned buffer and one copy;
+    returns (device uint8 tensor that owns them, device address of every part), parts 16-byte aligned."""
+    blobs, offs, pos = [], [], 0
+    for part in parts:
+        b = part.tobytes() if isinstance(part, np.ndarray) else bytes(part)
+        offs.append(pos)
+        b += bytes(-len(b) % 16)
+        blobs.append(b)
+        pos += len(b)
+    host = torch.frombuffer(bytearray(b"".join(blobs)), dtype=torch.uint8)
+    dev = host.pin_memory().to(device, non_blocking=True) if torch.device(device).type == "cuda" else host
+    return dev, [dev.data_ptr() + o for o in offs]
+
+
+def clip_array(src=None, dst=None, len_in=None, len_out=None, row0=None, rows=None, n=None):
+    """hip.Clip array from per-clip lists (a field left out is zero: the entry that takes the array does not read it)."""
+    n = n if n is not None else len(next(v for v in (src, dst, len_in, len_out, row0, rows) if v is not None))
+    z = [0] * n
+    cols = [v if v is not None else z for v in (src, dst, len_in, len_out, row0, rows)]
+    return (hip.Clip * n)(*[hip.Clip(*[int(c[i]) for c in cols]) for i in range(n)])
+
+
+def seg_table(row0, rows):
+    return np.array([[a, b] for a, b in zip(row0, rows)], dtype=np.int32)
+
+
+def _views(packed, offs, lens):
+    return [packed[o:o + n] for o, n in zip(offs, lens)]
+
+
+def _flat(ts):
+    return [t.reshape(-1) for t in ts]
 
 
 class LogMel:
@@ -68,6 +137,37 @@ class LogMel:
         mel = torch.empty(B * N, N_MELS, dtype=torch.float32, device=self.device)
         hip.gemm(mag, self.c["w_mel"], mel, B * N, N_MELS, MAG_WIDTH, epilogue=hip.EPI_LOGCLAMP)
         return mel
+
+    @hip.on_device
+    def ragged(self, conds):
+        """conds: list of [T_i] device clips (48 kHz) -> (log-mel [sum N_i, 256] of all clips packed back to back, list of the
+        clips' [N_i, 256] views), every clip's rows the bits of __call__ on that clip alone.  Three launches for the list.
+        The result belongs to the workspace of this mix of lengths (overwritten by the next call of the same mix)."""
+        conds = _flat(conds)
+        tab = ragged_clip_tables([c.shape[0] for c in conds], 48000)
+        key = tuple(tab["len_out"])
+        ptrs = tuple(_ptr(c) for c in conds)
+        M = sum(tab["mel_rows"])
+        if key not in self._ws:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            mel = torch.empty(M, N_MELS, **f32)
+            self._ws[key] = dict(frames=torch.empty(M, N_FFT, **f32), mag=torch.empty(M, MAG_WIDTH, **f32), mel=mel,
+                                 views=_views(mel, tab["mel_row0"], tab["mel_rows"]), ptrs=None)
+        w = self._ws[key]
+        if w["ptrs"] != ptrs:             # (clips at other addresses than last time: the descriptors go up again, one copy)
+            w["desc"], (w["clips"],) = upload_tables([clip_array(src=ptrs, len_in=tab["len_out"], row0=tab["mel_row0"],
+                                                                 rows=tab["mel_rows"])], self.device)
+            w["ptrs"] = ptrs
+        L, st = hip.lib(), hip.stream()
+        frames, mag, mel = w["frames"], w["mag"], w["mel"]
+        hip.check(L.fh_frame_seg_f32(w["clips"], len(conds), max(tab["mel_rows"]), min(tab["len_out"]), self.c["hann"].data_ptr(),
+                                     frames.data_ptr(), N_FFT, HOP, (N_FFT - HOP) // 2, 0, st), "fh_frame_seg_f32")
+        if _USE_FFT:
+            hip.check(L.fh_rfft2048_f32(frames.data_ptr(), self.c["tw"].data_ptr(), mag.data_ptr(), M, 1, st), "fh_rfft2048_f32")
+        else:
+            hip.gemm(frames, self.c["w_fwd"], mag, M, P_WIDTH, N_FFT, epilogue=hip.EPI_MAG)
+        hip.gemm(mag, self.c["w_mel"], mel, M, N_MELS, MAG_WIDTH, epilogue=hip.EPI_LOGCLAMP)
+        return mel, w["views"]
 
 
 class PostProcessor:
@@ -117,6 +217,64 @@ class PostProcessor:
         hip.check(L.fh_peak_scale_f32(out.data_ptr(), w["peak"].data_ptr(), B, length, 0.99, st), "fh_peak_scale_f32")
         return (out, w["cr"]) if return_cr else out
 
+    @hip.on_device
+    def ragged(self, preds, srcs, lengths, return_cr=False):
+        """preds: list of [Tp_i] (or [1, Tp_i]) vocoder waveforms, srcs: list of [T_i] conditioning clips, lengths: samples to
+        return per clip -> (output packed [sum length_i], list of the clips' [length_i] views[, cr int32 [n]]), every clip the
+        bits of __call__(pred_i[None], src_i[None], length_i): per-clip cutoff, splice, iSTFT, 0.99 peak.  11 launches for the
+        list.  The results belong to the workspace of this mix of lengths: a caller that keeps them clones them."""
+        preds, srcs = _flat(preds), _flat(srcs)
+        lengths = [int(n) for n in lengths]
+        n = len(preds)
+        if len(srcs) != n or len(lengths) != n or n < 1:
+            raise ValueError("one pred, one src and one length per clip")
+        Tp, T = [p.shape[0] for p in preds], [s_.shape[0] for s_ in srcs]
+        F = [min(1 + a // HOP, 1 + b // HOP) for a, b in zip(Tp, T)]
+        key = (tuple(Tp), tuple(T), tuple(lengths))
+        ptrs = tuple(_ptr(t) for t in preds + srcs)
+        R = sum(F)
+        if key not in self._ws:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            out = torch.empty(sum(lengths), **f32)
+            off = [int(x) for x in np.cumsum([0] + lengths[:-1])]
+            self._ws[key] = dict(frames=torch.empty(R, N_FFT, **f32), sp=torch.empty(R, P_WIDTH, **f32),
+                                 ss=torch.empty(R, P_WIDTH, **f32), energy=torch.empty(n, 1025, **f32),
+                                 cr=torch.empty(n, dtype=torch.int32, device=self.device),
+                                 peak=torch.empty(n, dtype=torch.int32, device=self.device), out=out, off=off,
+                                 views=_views(out, off, lengths), ptrs=None)
+        w = self._ws[key]
+        if w["ptrs"] != ptrs:
+            row0 = [int(x) for x in np.cumsum([0] + F[:-1])]
+            outs = [w["out"].data_ptr() + 4 * o for o in w["off"]]
+            w["desc"], (w["c_pred"], w["c_src"], w["seg"]) = upload_tables(
+                [clip_array(src=ptrs[:n], len_in=Tp, row0=row0, rows=F),
+                 clip_array(src=ptrs[n:], len_in=T, row0=row0, rows=F, dst=outs, len_out=lengths), seg_table(row0, F)], self.device)
+            w["ptrs"] = ptrs
+        L, st = hip.lib(), hip.stream()
+        hann = self.c["hann"].data_ptr()
+        for clips, lens, spec in ((w["c_pred"], Tp, w["sp"]), (w["c_src"], T, w["ss"])):
+            hip.check(L.fh_frame_seg_f32(clips, n, max(F), min(lens), hann, w["frames"].data_ptr(), N_FFT, HOP, N_FFT // 2, 1, st),
+                      "fh_frame_seg_f32")
+            if _USE_FFT:
+                hip.check(L.fh_rfft2048_f32(w["frames"].data_ptr(), self.c["tw"].data_ptr(), spec.data_ptr(), R, 0, st),
+                          "fh_rfft2048_f32")
+            else:
+                hip.gemm(w["frames"], self.c["w_fwd"], spec, R, P_WIDTH, N_FFT)
+        hip.check(L.fh_spec_energy_seg_f32(w["ss"].data_ptr(), w["energy"].data_ptr(), w["seg"], n, st), "fh_spec_energy_seg_f32")
+        hip.check(L.fh_cutoff_index_f32(w["energy"].data_ptr(), w["cr"].data_ptr(), n, 1025, 0.99, st), "fh_cutoff_index_f32")
+        hip.check(L.fh_spec_splice_seg_f32(w["sp"].data_ptr(), w["ss"].data_ptr(), w["cr"].data_ptr(), w["sp"].data_ptr(),
+                                           w["seg"], n, max(F), st), "fh_spec_splice_seg_f32")
+        if _USE_FFT:
+            hip.check(L.fh_irfft2048_f32(w["sp"].data_ptr(), self.c["tw"].data_ptr(), w["frames"].data_ptr(), R, st),
+                      "fh_irfft2048_f32")
+        else:
+            hip.gemm(w["sp"], self.c["w_inv"], w["frames"], R, N_FFT, P_WIDTH)
+        w["peak"].zero_()
+        hip.check(L.fh_istft_ola_seg_f32(w["frames"].data_ptr(), hann, w["c_src"], n, max(lengths), w["peak"].data_ptr(),
+                                         N_FFT, HOP, st), "fh_istft_ola_seg_f32")
+        hip.check(L.fh_peak_scale_seg_f32(w["c_src"], n, max(lengths), w["peak"].data_ptr(), 0.99, st), "fh_peak_scale_seg_f32")
+        return (w["out"], w["views"], w["cr"]) if return_cr else (w["out"], w["views"])
+
 
 class Resampler:
     """Device polyphase resampler + peak normalise (the reference does this on the host in numpy)."""
@@ -124,6 +282,7 @@ class Resampler:
     def __init__(self, device):
         self.device = hip.norm_device(device)
         self._taps = {}
+        self._ws = hip.ShapeCache()
 
     @hip.on_device
     def __call__(self, x, sr_in, sr_out=48000):
@@ -147,3 +306,62 @@ class Resampler:
         hip.check(L.fh_peak_abs_f32(y.data_ptr(), peak.data_ptr(), B, y.shape[1], st), "fh_peak_abs_f32")
         hip.check(L.fh_peak_scale_f32(y.data_ptr(), peak.data_ptr(), B, y.shape[1], 1.0, st), "fh_peak_scale_f32")
         return y
+
+    def _fill(self, buf, xs):
+        """list of 1-D float32 clips -> the packed device buffer `buf`.  Host arrays go up as one pinned buffer and one copy."""
+        if all(isinstance(x, torch.Tensor) and x.device.type == "cuda" for x in xs):
+            torch.cat([x.reshape(-1).to(torch.float32) for x in xs], out=buf)
+            return
+        xs = [x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x for x in xs]
+        host = torch.from_numpy(np.concatenate([np.asarray(x, dtype=np.float32).reshape(-1) for x in xs]))
+        buf.copy_(host.pin_memory() if buf.is_cuda else host, non_blocking=True)
+
+    @hip.on_device
+    def ragged(self, xs, sr_in, sr_out=48000):
+        """xs: list of 1-D float32 clips at sr_in (host arrays: packed and uploaded with one copy; or device tensors) ->
+        (the 48 kHz clips packed back to back [sum T_i], list of their [T_i] views), each resampled and divided by its
+        max |.| with the bits of __call__ on that clip alone.  Four launches for the list.  The result belongs to the
+        workspace of this mix of lengths: its address is the same at every call of the mix."""
+        tab = ragged_clip_tables([int(np.prod(x.shape)) for x in xs], sr_in, sr_out, check_mel=False)
+        n = len(xs)
+        plan = tables.resample_poly_plan(sr_out, sr_in)
+        key = (sr_in, sr_out, tuple(tab["len_in"]))
+        if key not in self._ws:           # (input, output and descriptors belong to the mix: a mix seen before uploads only its samples)
+            f32 = dict(dtype=torch.float32, device=self.device)
+            x, y = torch.empty(sum(tab["len_in"]), **f32), torch.empty(sum(tab["len_out"]), **f32)
+            desc, (clips,) = upload_tables(
+                [clip_array(src=[x.data_ptr() + 4 * o for o in tab["in_off"]], len_in=tab["len_in"],
+                            dst=[y.data_ptr() + 4 * o for o in tab["out_off"]], len_out=tab["len_out"])], self.device)
+            self._ws[key] = dict(x=x, y=y, views=_views(y, tab["out_off"], tab["len_out"]), desc=desc, clips=clips,
+                                 peak=torch.empty(n, dtype=torch.int32, device=self.device))
+        w = self._ws[key]
+        self._fill(w["x"], xs)
+        L, st = hip.lib(), hip.stream()
+        if plan is None:
+            taps, n_taps, pre, up, down = 0, 0, 0, 1, 1
+        else:
+            taps_t, pre, up, down = plan
+            tk = (sr_out, sr_in)
+            if tk not in self._taps:
+                self._taps[tk] = taps_t.to(self.device)
+            taps, n_taps = self._taps[tk].data_ptr(), self._taps[tk].numel()
+        max_len = max(tab["len_out"])
+        hip.check(L.fh_resample_poly_seg_f32(w["clips"], n, max_len, taps, up, down, n_taps, pre, st), "fh_resample_poly_seg_f32")
+        w["peak"].zero_()
+        hip.check(L.fh_peak_abs_seg_f32(w["clips"], n, max_len, w["peak"].data_ptr(), st), "fh_peak_abs_seg_f32")
+        hip.check(L.fh_peak_scale_seg_f32(w["clips"], n, max_len, w["peak"].data_ptr(), 1.0, st), "fh_peak_scale_seg_f32")
+        return w["y"], w["views"]
+
+    @hip.on_device
+    def upload_packed(self, conds):
+        """conds: list of 1-D float32 host clips that are 48 kHz already (resampled and normalised on the host,
+        upsampling_method='scipy') -> (packed device tensor [sum T_i], views): one pinned buffer, one copy, into the
+        workspace of this mix of lengths."""
+        lens = [int(np.prod(c.shape)) for c in conds]
+        key = ("host",) + tuple(lens)
+        if key not in self._ws:
+            y = torch.empty(sum(lens), dtype=torch.float32, device=self.device)
+            self._ws[key] = dict(y=y, views=_views(y, [int(v) for v in np.cumsum([0] + lens[:-1])], lens))
+        w = self._ws[key]
+        self._fill(w["y"], conds)
+        return w["y"], w["views"]

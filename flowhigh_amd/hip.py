@@ -67,6 +67,12 @@ class SumJob(C.Structure):
     _fields_ = [("src", C.c_void_p * 12), ("out", C.c_void_p), ("n", C.c_int64), ("n_src", C.c_int32), ("scale", C.c_float)]
 
 
+class Clip(C.Structure):
+    """fh_clip: one clip of a segment-form front / back end launch (csrc/frontend_seg.hip)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("len_in", C.c_int32), ("len_out", C.c_int32),
+                ("row0", C.c_int32), ("rows", C.c_int32)]
+
+
 class HipError(RuntimeError):
     pass
 
@@ -141,6 +147,15 @@ _SIGS = {
     "fh_peak_scale_f32": [_P, _P, _I, _I, _F, _P],
     "fh_peak_abs_f32": [_P, _P, _I, _I, _P],
     "fh_resample_poly_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "fh_sizeof_clip": [],
+    "fh_resample_poly_seg_f32": [_P, _I, _I, _P, _I, _I, _I, _I, _P],
+    "fh_peak_abs_seg_f32": [_P, _I, _I, _P, _P],
+    "fh_peak_scale_seg_f32": [_P, _I, _I, _P, _F, _P],
+    "fh_frame_seg_f32": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P],
+    "fh_spec_energy_seg_f32": [_P, _P, _P, _I, _P],
+    "fh_spec_splice_seg_f32": [_P, _P, _P, _P, _P, _I, _I, _P],
+    "fh_istft_ola_seg_f32": [_P, _P, _P, _I, _I, _P, _I, _I, _P],
+    "fh_rows_to_channels_seg_f32": [_P, _P, _I, _I, _I, _P],
 }
 EXPORTS = sorted(_SIGS) + ["fh_last_error"]
 
@@ -171,7 +186,7 @@ def lib():
         raise HipError("libflowhigh_hip.so ABI version mismatch")
     if L.fh_sizeof_conv_group() != C.sizeof(ConvGroup) or L.fh_sizeof_act_group() != C.sizeof(ActGroup) \
             or L.fh_sizeof_wino_group() != C.sizeof(WinoGroup) or L.fh_sizeof_sum_job() != C.sizeof(SumJob) \
-            or L.fh_sizeof_amp_group() != C.sizeof(AmpGroup):
+            or L.fh_sizeof_amp_group() != C.sizeof(AmpGroup) or L.fh_sizeof_clip() != C.sizeof(Clip):
         raise HipError("descriptor struct layout mismatch between hip.py and flowhigh_hip.h")
     _lib = L
     return L

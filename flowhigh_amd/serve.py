@@ -9,6 +9,7 @@ clip's key (seed, 0) and the noise is drawn on the device).  Host logic only: no
 no sockets (the reference's UI / network layers are out of scope); `generate()` below has the signature of
 the function `app.py` hands to `gr.Interface`.
 """
+import os
 import queue
 import threading
 from concurrent.futures import Future
@@ -18,7 +19,13 @@ import torch
 
 
 class BatchingServer:
-    def __init__(self, model, max_batch=32, max_wait_ms=5.0):
+    def __init__(self, model, max_batch=32, max_wait_ms=5.0, ends=None):
+        """ends: 'per_clip' | 'ragged' | None (FH_RAGGED_ENDS, else 'per_clip'), handed to generate_many: how the front and back
+        end of a ragged group run (flowhighsr.resolve_ends); a wrong value is a ValueError here, not in the worker."""
+        from .flowhighsr import resolve_ends
+        self.ends = resolve_ends(ends)
+        # (handed on only when something asked for a form: a model whose generate_many predates ends= keeps working)
+        self._ends_kw = dict(ends=self.ends) if (ends is not None or os.environ.get("FH_RAGGED_ENDS")) else {}
         self.model = model
         self.max_batch = int(max_batch)
         self.max_wait = float(max_wait_ms) / 1e3
@@ -97,7 +104,7 @@ class BatchingServer:
                             t48 = -(-a.shape[-1] * 48000 // sr_in)
                             noise.append(self.model._draw_noise(1, t48 // 480, g))
                     outs = self.model.generate_many([it[0] for it in items], sr_in, 48000, steps, noise=noise,
-                                                    max_batch=self.max_batch, **prior)
+                                                    max_batch=self.max_batch, **self._ends_kw, **prior)
                     for it, y in zip(items, outs):
                         it[4].set_result(y.detach().cpu().squeeze(0).numpy())
                 except Exception as e:            # noqa: BLE001  (every waiting caller must be released)

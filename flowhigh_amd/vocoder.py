@@ -351,6 +351,26 @@ class Vocoder:
         self.run_ragged(rp)
         return [sp["wav"] for sp in rp["subs"]]
 
+    @hip.on_device
+    def forward_ragged_packed(self, mel, frames):
+        """forward_ragged for the clips' rows packed back to back: mel [sum N_i, num_mels] (as the ragged sampler leaves them),
+        frames = [N_i].  The 'b n d -> b d n' copies into the clips' mel_in buffers are one launch (fh_rows_to_channels_seg_f32;
+        a plain copy, same bits); the descriptors name plan-owned buffers and stay with the merged plan."""
+        frames = [int(n) for n in frames]
+        rp = self.plan_ragged(frames)
+        if mel.shape[0] != sum(frames) or mel.shape[1] != self.true_mels or not mel.is_contiguous():
+            raise ValueError(f"mel {tuple(mel.shape)} is not the packed [{sum(frames)}, {self.true_mels}] rows of the clips")
+        if "r2c" not in rp:
+            from .frontend import clip_array, upload_tables
+            row0 = [sum(frames[:i]) for i in range(len(frames))]
+            desc, (clips,) = upload_tables([clip_array(dst=[sp["mel_in"].data_ptr() for sp in rp["subs"]], row0=row0,
+                                                       rows=frames, len_out=[self.true_mels * n for n in frames])], self.device)
+            rp["r2c"] = (desc, clips)
+        hip.check(hip.lib().fh_rows_to_channels_seg_f32(mel.data_ptr(), rp["r2c"][1], len(frames), max(frames), self.true_mels,
+                                                        hip.stream()), "fh_rows_to_channels_seg_f32")
+        self.run_ragged(rp)
+        return [sp["wav"] for sp in rp["subs"]]
+
     # ---- time-chunked execution (SURVEY.md 8f-4: streaming / chunked vocoder) ----------------------------------
     def chunk_geometry(self):
         """(halo, align) in mel frames for time-chunked execution.

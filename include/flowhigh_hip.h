@@ -546,6 +546,51 @@ int fh_resample_poly_f32(const float* x, const float* taps, float* y, int batch,
                          int len_out, int up, int down, int n_taps, int n_pre_remove,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Segment forms of the entries above (flowhigh_amd/csrc/frontend_seg.hip): clips of DIFFERENT lengths in one
+ * launch, the front and back end of a ragged call (generate_many(ends='ragged')).  Every clip gets the bits of the
+ * batched entry called on that clip alone (one copy of the arithmetic: csrc/frontend_elem.h).
+ *
+ * A clip is described by the device int32 [n][2] table (first row, rows) of fh_mel_energy_seg_f32 where only packed
+ * rows are involved, or by one fh_clip where it has a pointer or a sample range of its own.  An entry reads only
+ * the fields its comment names; the others may hold anything.  n_clips <= 65535; the max_* / min_* arguments are the
+ * largest / smallest value of that field over the table (the table lives on the device: the host that builds it
+ * knows them and checks every clip; the entries check what they are given).
+ * --------------------------------------------------------------------------------- */
+typedef struct {
+  const float* src;    /* the clip's input samples */
+  float* dst;          /* the clip's output */
+  int32_t len_in;      /* samples at src */
+  int32_t len_out;     /* samples (elements) at dst */
+  int32_t row0;        /* first of the clip's rows in the packed row buffer of the call */
+  int32_t rows;
+} fh_clip;
+int fh_sizeof_clip(void);
+
+/* dst[0 .. len_out) = resample_poly(src[0 .. len_in)); every clip of a call shares up, down, the taps and n_pre_remove.
+ * taps == NULL (up == down == 1, equal rates): dst = src, len_in == len_out. */
+int fh_resample_poly_seg_f32(const fh_clip* clips, int n_clips, int max_len_out, const float* taps, int up, int down,
+                             int n_taps, int n_pre_remove, void* stream);
+/* peak_bits[c] = bits(max |dst[0 .. len_out)|) (caller zeroes peak_bits first); dst[j] = (dst[j] / peak[c]) * target. */
+int fh_peak_abs_seg_f32(const fh_clip* clips, int n_clips, int max_len, uint32_t* peak_bits, void* stream);
+int fh_peak_scale_seg_f32(const fh_clip* clips, int n_clips, int max_len, const uint32_t* peak_bits, float target,
+                          void* stream);
+/* frames[row0 + t, k] = pad(src[0 .. len_in))[hop t + k] * window[k] for t < rows; pad modes as fh_frame_f32.
+ * min_len: the shortest len_in (reflect: pad < min_len); hop (rows - 1) + nfft <= len_in + 2 pad for every clip. */
+int fh_frame_seg_f32(const fh_clip* clips, int n_clips, int max_rows, int min_len, const float* window, float* frames,
+                     int nfft, int hop, int pad, int pad_mode, void* stream);
+/* energy [n_seg, 1025] over each clip's own rows of the packed P-layout spectrum; fh_cutoff_index_f32 takes it as it is. */
+int fh_spec_energy_seg_f32(const float* spec, float* energy, const int32_t* seg, int n_seg, void* stream);
+/* fh_spec_splice_f32 with clip c's cr[c] on its rows. */
+int fh_spec_splice_seg_f32(const float* pred, const float* src, const int32_t* cr, float* out, const int32_t* seg,
+                           int n_seg, int max_rows, void* stream);
+/* fh_istft_ola_f32 per clip: dst[0 .. len_out) from the clip's rows [row0, row0 + rows) of frames, peak_bits[c]. */
+int fh_istft_ola_seg_f32(const float* frames, const float* window, const fh_clip* clips, int n_clips, int max_len,
+                         uint32_t* peak_bits, int nfft, int hop, void* stream);
+/* dst[ch * rows + n] = mel[(row0 + n) * d + ch]: the packed token-major rows of a ragged batch into every clip's own
+ * channel-major [d, rows] buffer (the vocoder's input), a plain copy. */
+int fh_rows_to_channels_seg_f32(const float* mel, const fh_clip* clips, int n_clips, int max_rows, int d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
