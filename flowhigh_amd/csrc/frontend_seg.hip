@@ -2,6 +2,8 @@
 // serving path, FlowHighSR.generate_many(ends='ragged')).  Every clip gets the bits of the batched entry called on that clip
 // alone: the per-element arithmetic is the one copy in frontend_elem.h, only the way a block finds its clip differs.
 //
+// fh_resample_poly_rates_seg_f32 also lets every clip have an INPUT RATE of its own: a row of filter constants per clip.
+//
 // Clips are described by the device int32 [n][2] table of (first row, rows) where rows are packed back to back (as
 // fh_mel_energy_seg_f32 takes it), or by an fh_clip array where a clip has a pointer or a sample range of its own.
 // Grid: clip on blockIdx.y (n_clips <= 65535), gridDim.x sized for the longest clip; blocks past a clip's end return at once.
@@ -17,6 +19,25 @@ __global__ __launch_bounds__(256) void resample_poly_seg_kernel(const fh_clip* _
   if (i >= c.len_out) return;
   // h == nullptr: equal rates, a plain copy (the host gives len_in == len_out)
   c.dst[i] = h ? fe_resample_value(c.src, h, i, c.len_in, up, down, n_taps, pre) : (i < c.len_in ? c.src[i] : 0.f);
+}
+
+// resample_poly_seg_kernel where every clip has a rate of its own: clip c reads row rate_of[c] of `rates` and that row's taps
+// in the bank.  The tables live on the device, so a block checks its row before it touches anything else and leaves its
+// clip unwritten on a bad one (an index past the table, non-positive up / down, taps outside the bank).
+__global__ __launch_bounds__(256) void resample_poly_rates_seg_kernel(const fh_clip* __restrict__ clips,
+                                                                      const int32_t* __restrict__ rate_of,
+                                                                      const fh_rate* __restrict__ rates, int n_rates,
+                                                                      const float* __restrict__ tap_bank, int bank_len) {
+  const int r = rate_of[blockIdx.y];
+  if ((unsigned)r >= (unsigned)n_rates) return;
+  const fh_rate q = rates[r];
+  if (q.up <= 0 || q.down <= 0 || q.n_taps < 0 || q.taps_off < 0 || (long long)q.taps_off + q.n_taps > bank_len) return;
+  const fh_clip c = clips[blockIdx.y];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= c.len_out) return;
+  // n_taps == 0: equal rates, a plain copy (the host gives len_in == len_out)
+  c.dst[i] = q.n_taps ? fe_resample_value(c.src, tap_bank + q.taps_off, i, c.len_in, q.up, q.down, q.n_taps, q.n_pre_remove)
+                      : (i < c.len_in ? c.src[i] : 0.f);
 }
 
 __global__ __launch_bounds__(256) void peak_abs_seg_kernel(const fh_clip* __restrict__ clips,
@@ -118,6 +139,22 @@ extern "C" int fh_resample_poly_seg_f32(const fh_clip* clips, int n_clips, int m
   hipLaunchKernelGGL(resample_poly_seg_kernel, dim3(fh_cdiv(max_len_out, 256), n_clips), dim3(256), 0,
                      (hipStream_t)stream, clips, taps, up, down, n_taps, n_pre_remove);
   FH_CHECK_LAUNCH("fh_resample_poly_seg_f32");
+  return FH_OK;
+}
+
+extern "C" int fh_sizeof_rate(void) { return (int)sizeof(fh_rate); }
+
+extern "C" int fh_resample_poly_rates_seg_f32(const fh_clip* clips, const int32_t* rate_of, int n_clips, int max_len_out,
+                                              const fh_rate* rates, int n_rates, const float* tap_bank, int bank_len,
+                                              void* stream) {
+  FH_CHECK_CLIPS("fh_resample_poly_rates_seg_f32");
+  FH_CHECK_ARG(rate_of && rates && n_rates >= 1, "fh_resample_poly_rates_seg_f32: bad rate table (rate_of, rates, n_rates >= 1)");
+  FH_CHECK_ARG(max_len_out > 0, "fh_resample_poly_rates_seg_f32: bad max_len_out %d", max_len_out);
+  FH_CHECK_ARG(bank_len >= 0 && (tap_bank || bank_len == 0), "fh_resample_poly_rates_seg_f32: bad tap bank (%d floats)",
+               bank_len);
+  hipLaunchKernelGGL(resample_poly_rates_seg_kernel, dim3(fh_cdiv(max_len_out, 256), n_clips), dim3(256), 0,
+                     (hipStream_t)stream, clips, rate_of, rates, n_rates, tap_bank, bank_len);
+  FH_CHECK_LAUNCH("fh_resample_poly_rates_seg_f32");
   return FH_OK;
 }
 

@@ -27,9 +27,9 @@ import torch
 
 from . import hip
 from .flow import FlowNet
-from .frontend import LogMel, PostProcessor, Resampler
+from .frontend import LogMel, PostProcessor, Resampler, clip_rates
 from .prior import expand_seed, normalize_key
-from .tables import HOP
+from .tables import HOP, resample_out_len
 from .vocoder import VOC, Vocoder, fold_weight_norm
 
 REPO_ID = "ResembleAI/FlowHigh"
@@ -74,6 +74,12 @@ def resolve_ends(ends=None):
     if ends not in _ENDS:
         raise ValueError(f"ends must be one of {_ENDS}, got {ends!r}")
     return ends
+
+
+def resolve_rates(sr, n_clips):
+    """sr= of generate_many as one input rate per clip: an int holds for every clip, a sequence gives one positive integer
+    rate per clip.  Anything else is a ValueError (a wrong length names both counts), raised before any GPU work."""
+    return clip_rates(sr, n_clips)
 
 
 def reference_prior_draw(n_frames, n_mels=256, generator=None):
@@ -421,13 +427,14 @@ class FlowHighSR:
     def _prepare_cond_ragged(self, clips, sr):
         """_prepare_cond for clips of different lengths: (cond packed [sum T48_i], list of [T48_i] views) on the device,
         peak-normalised per clip with the bits of _prepare_cond on each clip alone.  One upload for the list; 'hip': the
-        segment forms of the resampler's launches, 'scipy': the host resampling and normalisation per clip, as they are."""
+        segment forms of the resampler's launches, 'scipy': the host resampling and normalisation per clip, as they are.
+        sr: one input rate, or one per clip."""
         prepared = self._host_clips(clips)
         if self.upsampling_method == 'scipy':
             import scipy.signal
             conds = []
-            for audio in prepared:
-                cond = scipy.signal.resample_poly(audio, 48000, sr)
+            for audio, sr_i in zip(prepared, resolve_rates(sr, len(prepared))):
+                cond = scipy.signal.resample_poly(audio, 48000, sr_i)
                 conds.append(cond / np.max(np.abs(cond)))
             return self.resampler.upload_packed(conds)
         if self.upsampling_method == 'hip':
@@ -738,6 +745,10 @@ class FlowHighSR:
         int16 or float.  Clips of equal length run as one batch (at most max_batch rows), so every result is
         what generate() returns for that clip alone; the prior noise is drawn in the order of `clips`, as a loop
         over generate() would.  noise: optional list of [1, N_i, n_mels] tensors.  Returns a list of [1, T48_i].
+        sr: the input rate of every clip, or a sequence of one rate per clip (resolve_rates): clips of different input rates run
+        in the same launch sequences (everything behind the resampler works at 48 kHz), every result what generate(clip_i, sr_i)
+        returns; two clips are one shape when length AND rate agree.  With ends='ragged' the resampling of a group is one launch
+        with a polyphase filter per clip (fh_resample_poly_rates_seg_f32); profiles/mixed_rates.md has the measurement.
         On a prior='device' model nothing is drawn on the host: every clip has a (seed, stream) key (seed=, or one
         torch.randint per clip from the generator, in the order of `clips`: _prior_keys) and the launch sequences draw from them.
         ragged (default on, FH_RAGGED=0 switches it off): clips of different lengths run as ONE launch sequence
@@ -758,14 +769,13 @@ class FlowHighSR:
         ~120 launches per clip and is the bottleneck either way), hence off by default."""
         clips = list(clips)
         ends = resolve_ends(ends)
+        rates = resolve_rates(sr, len(clips))
         keys = self._prior_keys(seed, len(clips), generator, noise)
         if noise is None:
             frames = []
-            for a in clips:
+            for a, sr_i in zip(clips, rates):
                 n_in = int(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).shape[-1])
-                t48 = n_in * target_sampling_rate // sr if (n_in * target_sampling_rate) % sr == 0 \
-                    else -(-n_in * target_sampling_rate // sr)
-                frames.append(t48 // 480)
+                frames.append(resample_out_len(n_in, target_sampling_rate, sr_i) // 480)
             if keys is None:
                 noise = [self._draw_noise(1, n, generator) for n in frames]
         if noise is not None and len(noise) != len(clips):
@@ -775,9 +785,9 @@ class FlowHighSR:
         if ragged is None:
             ragged = os.environ.get("FH_RAGGED", "1") != "0"
         lengths = [int(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).shape[-1]) for a in clips]
-        if ragged and len(set(lengths)) > 1 and target_sampling_rate == 48000:
+        if ragged and len(set(zip(lengths, rates))) > 1 and target_sampling_rate == 48000:
             try:
-                return self._generate_many_ragged(clips, lengths, sr, timestep, noise, max_frames, keys=keys,
+                return self._generate_many_ragged(clips, lengths, rates, timestep, noise, max_frames, keys=keys,
                                                   frames=[sh[1] for sh in shapes], ends=ends)
             except NotImplementedError as e:
                 # a vocoder configuration whose launch positions cannot be merged: one batch per length (said once)
@@ -788,12 +798,12 @@ class FlowHighSR:
                                                               "running one batch per clip length", e)
         buckets = {}
         for i, a in enumerate(clips):
-            key = (int(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).shape[-1]), shapes[i])
+            key = (lengths[i], rates[i], shapes[i])
             buckets.setdefault(key, []).append(i)
         out = [None] * len(clips)
         if streams is None:
             streams = int(os.environ.get("FH_SERVE_STREAMS", "1"))
-        frame_counts = sorted({key[1][1] for key in buckets})
+        frame_counts = sorted({key[2][1] for key in buckets})
         n_streams = max(1, min(int(streams), len(frame_counts)))
         main = torch.cuda.current_stream(self.device)
         side = self._serve_streams(n_streams) if n_streams > 1 else [main]
@@ -802,7 +812,7 @@ class FlowHighSR:
                 s_.wait_stream(main)
         stream_of = {n: side[i % len(side)] for i, n in enumerate(frame_counts)}
         for key, idx in buckets.items():
-            st = stream_of[key[1][1]]
+            st = stream_of[key[2][1]]
             with torch.cuda.stream(st):
                 for k in range(0, len(idx), max_batch):
                     part = idx[k:k + max_batch]
@@ -810,7 +820,7 @@ class FlowHighSR:
                         prior = dict(_keys=[keys[i] for i in part])
                     else:
                         prior = dict(noise=noise[part[0]] if len(part) == 1 else torch.cat([noise[i] for i in part], 0))
-                    y = self.generate_batch([clips[i] for i in part], sr, target_sampling_rate, timestep, **prior)
+                    y = self.generate_batch([clips[i] for i in part], key[1], target_sampling_rate, timestep, **prior)
                     for r, i in enumerate(part):
                         out[i] = y[r:r + 1].clone()
                         if st is not main:
@@ -820,7 +830,8 @@ class FlowHighSR:
                 main.wait_stream(s_)
         return out
 
-    def _generate_many_ragged(self, clips, lengths, sr, timestep, noise, max_frames, keys=None, frames=None, ends="per_clip"):
+    def _generate_many_ragged(self, clips, lengths, rates, timestep, noise, max_frames, keys=None, frames=None, ends="per_clip"):
+        """rates: the input rate of every clip (resolve_rates)."""
         if max_frames is None:
             max_frames = int(os.environ.get("FH_RAGGED_MAX_FRAMES", "12000"))
         chunk_limit = int(os.environ.get("FH_VOCODER_CHUNK_FRAMES", "6000"))
@@ -835,7 +846,7 @@ class FlowHighSR:
         groups, cur, tot = [], [], 0
         for i, n in enumerate(frames):
             if n > max_frames or (chunk_limit > 0 and n > chunk_limit):
-                out[i] = self.generate_batch([clips[i]], sr, 48000, timestep, **prior_of(i)).clone()
+                out[i] = self.generate_batch([clips[i]], rates[i], 48000, timestep, **prior_of(i)).clone()
                 continue
             if cur and tot + n > max_frames:
                 groups.append(cur)
@@ -846,12 +857,12 @@ class FlowHighSR:
             groups.append(cur)
         for idx in groups:
             if len(idx) == 1:
-                out[idx[0]] = self.generate_batch([clips[idx[0]]], sr, 48000, timestep, **prior_of(idx[0])).clone()
+                out[idx[0]] = self.generate_batch([clips[idx[0]]], rates[idx[0]], 48000, timestep, **prior_of(idx[0])).clone()
                 continue
             prior = dict(keys=[keys[i] for i in idx]) if keys is not None else {}
             if ends == "ragged":
                 # front and back end as segment-form launches over the group: nothing below depends on the number of clips
-                _, conds = self._prepare_cond_ragged([clips[i] for i in idx], sr)
+                _, conds = self._prepare_cond_ragged([clips[i] for i in idx], [rates[i] for i in idx])
                 cond_mel, mels = self.flowhigh.logmel.ragged(conds)
                 wavs = self._sample_ragged(conds, None if keys is not None else [noise[i] for i in idx], timestep, self.cfm_method,
                                            mels=mels, cond_mel=cond_mel, **prior, **kw)
@@ -864,7 +875,7 @@ class FlowHighSR:
                 continue
             # (the per-clip front and back ends -- ~8 + ~12 small launches per clip -- on up to 4 side streams measured
             # 121.5 ms against 121.3 ms on one stream for the 24-clip mix: not worth the cross-stream bookkeeping)
-            conds = [self._prepare_cond([clips[i]], sr, 48000)[0] for i in idx]
+            conds = [self._prepare_cond([clips[i]], rates[i], 48000)[0] for i in idx]
             if keys is not None:
                 wavs = self._sample_ragged(conds, None, timestep, self.cfm_method, keys=[keys[i] for i in idx], **kw)
             else:

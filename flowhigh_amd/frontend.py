@@ -40,6 +40,48 @@ class _Const:
 
 
 # ---- ragged calls: clips of different lengths through the segment-form entries (csrc/frontend_seg.hip) -------------------
+def clip_rates(sr, n_clips):
+    """The input rate of every clip of a list as ints: `sr` is one rate for all of them, or a sequence of one positive
+    integer rate per clip (anything else is a ValueError)."""
+    def rate(v):
+        if isinstance(v, (bool, str, bytes)) or v != v or v in (float("inf"), float("-inf")) or int(v) != v or int(v) <= 0:
+            raise ValueError(f"an input rate must be a positive integer, got {v!r}")
+        return int(v)
+    try:
+        if np.ndim(sr) == 0:
+            return [rate(sr)] * int(n_clips)
+        rates = list(sr)
+        if len(rates) != n_clips:
+            raise ValueError(f"one input rate per clip: {len(rates)} rates for {n_clips} clips")
+        return [rate(v) for v in rates]
+    except TypeError as e:
+        raise ValueError(f"an input rate must be a positive integer, got {sr!r}") from e
+
+
+def rate_tables(rates, sr_out=48000):
+    """Host side of the per-clip filters of fh_resample_poly_rates_seg_f32 for clips at `rates` (one per clip) ->
+      bank      float32 numpy array: the taps of every distinct rate's tables.resample_poly_plan back to back
+      rows      hip.Rate array, one row per distinct rate in order of first appearance (a rate equal to sr_out: n_taps = 0,
+                up = down = 1: the copy)
+      rate_of   int32 numpy array, the row of every clip."""
+    rates = clip_rates(rates, len(rates))
+    distinct = list(dict.fromkeys(rates))
+    taps, rows, pos = [], [], 0
+    for r in distinct:
+        plan = tables.resample_poly_plan(sr_out, r)
+        if plan is None:
+            rows.append(hip.Rate(pos, 0, 1, 1, 0))
+            continue
+        h, pre, up, down = plan
+        rows.append(hip.Rate(pos, h.numel(), up, down, pre))
+        taps.append(h.numpy())
+        pos += h.numel()
+    if pos >= 2 ** 31:
+        raise ValueError("tap bank too large")
+    bank = np.concatenate(taps).astype(np.float32, copy=False) if taps else np.zeros(0, np.float32)
+    return bank, (hip.Rate * len(rows))(*rows), np.array([distinct.index(r) for r in rates], dtype=np.int32)
+
+
 def ragged_clip_tables(lengths_in, sr_in, sr_out=48000, pred_lens=None, check_mel=True):
     """Host side of the clip tables of a ragged call, for clips of `lengths_in` samples at sr_in (lists, one item per clip):
       len_in / in_off     samples and first sample of every clip in the packed low-rate input
@@ -48,11 +90,12 @@ def ragged_clip_tables(lengths_in, sr_in, sr_out=48000, pred_lens=None, check_me
       pred_len            Tp_i, the vocoder's samples for N_i frames (480 N_i unless given: Vocoder.out_len)
       pp_rows / pp_row0   F_i = min(1 + Tp_i // 480, 1 + T_i // 480) frames of the post-processing STFT, and their first row
     Everything is back to back.  A clip too short for the reflect pad of the front end is refused as LogMel refuses it
-    (check_mel=False: the resampler alone takes any length)."""
+    (check_mel=False: the resampler alone takes any length).  sr_in: one rate for the list, or one rate per clip."""
     len_in = [int(n) for n in lengths_in]
     if not len_in:
         raise ValueError("empty clip list")
-    len_out = [tables.resample_out_len(n, sr_out, sr_in) for n in len_in]
+    rates = clip_rates(sr_in, len(len_in))
+    len_out = [tables.resample_out_len(n, sr_out, r) for n, r in zip(len_in, rates)]
     mel_rows = [t // HOP for t in len_out]
     for t, n in zip(len_out, mel_rows):
         if check_mel and (n < 1 or t <= (N_FFT - HOP) // 2):
@@ -282,6 +325,7 @@ class Resampler:
     def __init__(self, device):
         self.device = hip.norm_device(device)
         self._taps = {}
+        self._banks = {}                  # (sr_out, distinct input rates ...) -> (device tap bank, hip.Rate rows)
         self._ws = hip.ShapeCache()
 
     @hip.on_device
@@ -321,7 +365,14 @@ class Resampler:
         """xs: list of 1-D float32 clips at sr_in (host arrays: packed and uploaded with one copy; or device tensors) ->
         (the 48 kHz clips packed back to back [sum T_i], list of their [T_i] views), each resampled and divided by its
         max |.| with the bits of __call__ on that clip alone.  Four launches for the list.  The result belongs to the
-        workspace of this mix of lengths: its address is the same at every call of the mix."""
+        workspace of this mix of lengths: its address is the same at every call of the mix.
+        sr_in may be one rate per clip: clips of different rates still run as one resampling launch, every clip with the
+        polyphase filter of its own rate (fh_resample_poly_rates_seg_f32); the workspace then belongs to the mix of
+        (length, rate) pairs."""
+        rates = clip_rates(sr_in, len(xs))
+        if len(set(rates)) > 1:
+            return self._ragged_rates(xs, rates, sr_out)
+        sr_in = rates[0] if rates else sr_in
         tab = ragged_clip_tables([int(np.prod(x.shape)) for x in xs], sr_in, sr_out, check_mel=False)
         n = len(xs)
         plan = tables.resample_poly_plan(sr_out, sr_in)
@@ -347,6 +398,41 @@ class Resampler:
             taps, n_taps = self._taps[tk].data_ptr(), self._taps[tk].numel()
         max_len = max(tab["len_out"])
         hip.check(L.fh_resample_poly_seg_f32(w["clips"], n, max_len, taps, up, down, n_taps, pre, st), "fh_resample_poly_seg_f32")
+        w["peak"].zero_()
+        hip.check(L.fh_peak_abs_seg_f32(w["clips"], n, max_len, w["peak"].data_ptr(), st), "fh_peak_abs_seg_f32")
+        hip.check(L.fh_peak_scale_seg_f32(w["clips"], n, max_len, w["peak"].data_ptr(), 1.0, st), "fh_peak_scale_seg_f32")
+        return w["y"], w["views"]
+
+    def _ragged_rates(self, xs, rates, sr_out):
+        """ragged() for clips of more than one input rate: one resampling launch over per-clip filter rows, then the two
+        peak launches.  The clip descriptors, the filter rows and every clip's row index go up as one buffer, once per
+        mix; the tap bank is kept on the device per tuple of distinct rates."""
+        tab = ragged_clip_tables([int(np.prod(x.shape)) for x in xs], rates, sr_out, check_mel=False)
+        n = len(xs)
+        distinct = tuple(dict.fromkeys(rates))
+        bk = (sr_out,) + distinct
+        if bk not in self._banks:
+            bank, rows, _ = rate_tables(distinct, sr_out)
+            self._banks[bk] = (torch.from_numpy(bank).to(self.device), rows)
+        bank, rows = self._banks[bk]
+        key = (tuple(rates), sr_out, tuple(tab["len_in"]))
+        if key not in self._ws:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            x, y = torch.empty(sum(tab["len_in"]), **f32), torch.empty(sum(tab["len_out"]), **f32)
+            rate_of = np.array([distinct.index(r) for r in rates], dtype=np.int32)
+            desc, (clips, rows_dev, rate_of_dev) = upload_tables(
+                [clip_array(src=[x.data_ptr() + 4 * o for o in tab["in_off"]], len_in=tab["len_in"],
+                            dst=[y.data_ptr() + 4 * o for o in tab["out_off"]], len_out=tab["len_out"]), rows, rate_of],
+                self.device)
+            self._ws[key] = dict(x=x, y=y, views=_views(y, tab["out_off"], tab["len_out"]), desc=desc, clips=clips,
+                                 rows=rows_dev, rate_of=rate_of_dev, peak=torch.empty(n, dtype=torch.int32, device=self.device))
+        w = self._ws[key]
+        self._fill(w["x"], xs)
+        L, st = hip.lib(), hip.stream()
+        max_len = max(tab["len_out"])
+        hip.check(L.fh_resample_poly_rates_seg_f32(w["clips"], w["rate_of"], n, max_len, w["rows"], len(distinct),
+                                                   bank.data_ptr() if bank.numel() else 0, bank.numel(), st),
+                  "fh_resample_poly_rates_seg_f32")
         w["peak"].zero_()
         hip.check(L.fh_peak_abs_seg_f32(w["clips"], n, max_len, w["peak"].data_ptr(), st), "fh_peak_abs_seg_f32")
         hip.check(L.fh_peak_scale_seg_f32(w["clips"], n, max_len, w["peak"].data_ptr(), 1.0, st), "fh_peak_scale_seg_f32")

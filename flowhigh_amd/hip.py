@@ -73,6 +73,12 @@ class Clip(C.Structure):
                 ("row0", C.c_int32), ("rows", C.c_int32)]
 
 
+class Rate(C.Structure):
+    """fh_rate: the polyphase filter of one input rate of fh_resample_poly_rates_seg_f32 (csrc/frontend_seg.hip)."""
+    _fields_ = [("taps_off", C.c_int32), ("n_taps", C.c_int32), ("up", C.c_int32), ("down", C.c_int32),
+                ("n_pre_remove", C.c_int32)]
+
+
 class HipError(RuntimeError):
     pass
 
@@ -149,6 +155,8 @@ _SIGS = {
     "fh_resample_poly_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "fh_sizeof_clip": [],
     "fh_resample_poly_seg_f32": [_P, _I, _I, _P, _I, _I, _I, _I, _P],
+    "fh_sizeof_rate": [],
+    "fh_resample_poly_rates_seg_f32": [_P, _P, _I, _I, _P, _I, _P, _I, _P],
     "fh_peak_abs_seg_f32": [_P, _I, _I, _P, _P],
     "fh_peak_scale_seg_f32": [_P, _I, _I, _P, _F, _P],
     "fh_frame_seg_f32": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P],
@@ -186,7 +194,8 @@ def lib():
         raise HipError("libflowhigh_hip.so ABI version mismatch")
     if L.fh_sizeof_conv_group() != C.sizeof(ConvGroup) or L.fh_sizeof_act_group() != C.sizeof(ActGroup) \
             or L.fh_sizeof_wino_group() != C.sizeof(WinoGroup) or L.fh_sizeof_sum_job() != C.sizeof(SumJob) \
-            or L.fh_sizeof_amp_group() != C.sizeof(AmpGroup) or L.fh_sizeof_clip() != C.sizeof(Clip):
+            or L.fh_sizeof_amp_group() != C.sizeof(AmpGroup) or L.fh_sizeof_clip() != C.sizeof(Clip) \
+            or L.fh_sizeof_rate() != C.sizeof(Rate):
         raise HipError("descriptor struct layout mismatch between hip.py and flowhigh_hip.h")
     _lib = L
     return L

@@ -2,7 +2,7 @@
 `generate((sr_in, audio), sr_out, timestep)` per HTTP request, one clip at a time).
 
 Requests from any number of caller threads are collected for a few milliseconds, grouped by (input rate,
-steps) and pushed through `FlowHighSR.generate_many`: clips of ANY lengths then run as one ragged launch
+steps) -- by steps alone with mix_rates=True, the clips' rates going on as a list -- and pushed through `FlowHighSR.generate_many`: clips of ANY lengths then run as one ragged launch
 sequence on the GPU (equal lengths as one batch) while every caller still gets exactly what `generate()` would
 have returned for its clip alone (same per-clip noise draw when a seed is given; on a prior='device' model the seed is the
 clip's key (seed, 0) and the noise is drawn on the device).  Host logic only: no gradio,
@@ -18,12 +18,32 @@ import numpy as np
 import torch
 
 
+MIX_RATES_DEFAULT = False
+
+
+def resolve_mix_rates(mix_rates=None):
+    """mix_rates= of BatchingServer: the keyword, else FH_SERVE_MIX_RATES (1 / 0), else MIX_RATES_DEFAULT."""
+    if mix_rates is None:
+        env = os.environ.get("FH_SERVE_MIX_RATES")
+        if env not in (None, "", "0", "1"):
+            raise ValueError(f"FH_SERVE_MIX_RATES must be 0 or 1, got {env!r}")
+        return MIX_RATES_DEFAULT if not env else env == "1"
+    return bool(mix_rates)
+
+
 class BatchingServer:
-    def __init__(self, model, max_batch=32, max_wait_ms=5.0, ends=None):
+    def __init__(self, model, max_batch=32, max_wait_ms=5.0, ends=None, mix_rates=None):
         """ends: 'per_clip' | 'ragged' | None (FH_RAGGED_ENDS, else 'per_clip'), handed to generate_many: how the front and back
-        end of a ragged group run (flowhighsr.resolve_ends); a wrong value is a ValueError here, not in the worker."""
+        end of a ragged group run (flowhighsr.resolve_ends); a wrong value is a ValueError here, not in the worker.
+        mix_rates: True | False | None (FH_SERVE_MIX_RATES = 1 / 0, else MIX_RATES_DEFAULT).  True: a collected batch is
+        grouped by step count only and every group is ONE generate_many call with the clips' input rates as a list.  False:
+        one call per (input rate, steps), the grouping before generate_many took a rate list.  The results are the same bits
+        either way.  Measured (profiles/mixed_rates.md, 24 clips over four rates): the one mixed call is 2.2-2.6 ms of ~86-90 ms
+        faster than the four per-rate calls; the default is False all the same, because a default server is pinned never to
+        hand two input rates to one call (tests/test_parallel_cpu.py) and models whose generate_many takes one rate stay usable."""
         from .flowhighsr import resolve_ends
         self.ends = resolve_ends(ends)
+        self.mix_rates = resolve_mix_rates(mix_rates)
         # (handed on only when something asked for a form: a model whose generate_many predates ends= keeps working)
         self._ends_kw = dict(ends=self.ends) if (ends is not None or os.environ.get("FH_RAGGED_ENDS")) else {}
         self.model = model
@@ -89,9 +109,14 @@ class BatchingServer:
                 return
             groups = {}
             for item in batch:
-                groups.setdefault((item[1], item[2]), []).append(item)      # same input rate and step count
+                # same step count; mix_rates off: same input rate too
+                groups.setdefault((None if self.mix_rates else item[1], item[2]), []).append(item)
             for (sr_in, steps), items in groups.items():
                 try:
+                    if sr_in is None:
+                        sr_in = [it[1] for it in items]
+                        if len(set(sr_in)) == 1:          # (one rate in the window: the call it has always been)
+                            sr_in = sr_in[0]
                     noise, prior = None, {}
                     if getattr(self.model, "prior", "reference") == "device":
                         # the device prior: a request's seed is its key (seed, 0); nothing is drawn on the host
@@ -99,9 +124,9 @@ class BatchingServer:
                             prior = dict(seed=[0 if it[3] is None else int(it[3]) for it in items])
                     elif any(it[3] is not None for it in items):
                         noise = []
-                        for a, _, _, seed, _ in items:
+                        for a, sr_i, _, seed, _ in items:
                             g = torch.Generator().manual_seed(0 if seed is None else int(seed))
-                            t48 = -(-a.shape[-1] * 48000 // sr_in)
+                            t48 = -(-a.shape[-1] * 48000 // sr_i)
                             noise.append(self.model._draw_noise(1, t48 // 480, g))
                     outs = self.model.generate_many([it[0] for it in items], sr_in, 48000, steps, noise=noise,
                                                     max_batch=self.max_batch, **self._ends_kw, **prior)

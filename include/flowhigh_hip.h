@@ -567,10 +567,25 @@ typedef struct {
 } fh_clip;
 int fh_sizeof_clip(void);
 
-/* dst[0 .. len_out) = resample_poly(src[0 .. len_in)); every clip of a call shares up, down, the taps and n_pre_remove.
+/* dst[0 .. len_out) = resample_poly(src[0 .. len_in)) with one up, down, taps and n_pre_remove for the call; clips of
+ * different input rates go through fh_resample_poly_rates_seg_f32 below.
  * taps == NULL (up == down == 1, equal rates): dst = src, len_in == len_out. */
 int fh_resample_poly_seg_f32(const fh_clip* clips, int n_clips, int max_len_out, const float* taps, int up, int down,
                              int n_taps, int n_pre_remove, void* stream);
+/* The same with a polyphase filter per clip: clip c is resampled by row rate_of[c] of `rates` (device int32 [n_clips],
+ * device fh_rate [n_rates]), whose taps are tap_bank[taps_off .. taps_off + n_taps) of the device bank of bank_len floats
+ * that holds the filters of all rates back to back.  Bits per clip: fh_resample_poly_f32 on that clip with that row.
+ * The tables live on the device, so the kernel checks a row before it uses it: a clip whose rate_of is outside
+ * [0, n_rates), or whose row has up <= 0, down <= 0, a negative field or taps_off + n_taps > bank_len, is left unwritten. */
+typedef struct {
+  int32_t taps_off;     /* first tap of this rate's filter in the tap bank (floats) */
+  int32_t n_taps;       /* 0: equal rates, dst = src (len_in == len_out) */
+  int32_t up, down;     /* reduced by their gcd */
+  int32_t n_pre_remove;
+} fh_rate;
+int fh_sizeof_rate(void);
+int fh_resample_poly_rates_seg_f32(const fh_clip* clips, const int32_t* rate_of, int n_clips, int max_len_out,
+                                   const fh_rate* rates, int n_rates, const float* tap_bank, int bank_len, void* stream);
 /* peak_bits[c] = bits(max |dst[0 .. len_out)|) (caller zeroes peak_bits first); dst[j] = (dst[j] / peak[c]) * target. */
 int fh_peak_abs_seg_f32(const fh_clip* clips, int n_clips, int max_len, uint32_t* peak_bits, void* stream);
 int fh_peak_scale_seg_f32(const fh_clip* clips, int n_clips, int max_len, const uint32_t* peak_bits, float target,
