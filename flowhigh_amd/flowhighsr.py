@@ -1,8 +1,8 @@
 """`FlowHighSR` -- drop-in host class for the reference's public API on MI355X.
 
-Mirrors /root/reference/src/flowhigh/flowhighsr.py:21-149 (`FlowHighSR`: ctor kwargs,
+Mirrors flowhighsr.py:21-149 of the reference's src/flowhigh/ (`FlowHighSR`: ctor kwargs,
 `generate`, `set_cfm_method`, `from_local`, `from_pretrained`) and the inference half of
-/root/reference/src/flowhigh/cfm_superresolution.py:94-284 (`ConditionalFlowMatcherWrapper`:
+cfm_superresolution.py:94-284 (`ConditionalFlowMatcherWrapper`:
 `sample`, `load`, `device`, `odeint_kwargs`, `sigma`, `cfm_method`).  torchdiffeq's fixed-grid
 euler / midpoint steppers (call site cfm:243) are restated in `_integrate`.
 
@@ -62,7 +62,7 @@ _CFM_METHODS = ("basic_cfm", "independent_cfm_adaptive", "independent_cfm_consta
 _PRIORS = ("reference", "device")
 # how a ragged generate_many call runs what surrounds its one transformer + vocoder launch sequence (resampling, peak
 # normalisation, log-mel, the vocoder's input copies, post-processing).  'per_clip': once per clip, the batched entries on
-# batches of one (the default).  'ragged': the segment forms of the same entries (csrc/frontend_seg.hip), one launch per step
+# batches of one (the default).  'ragged': the segment forms of the same entries (fh_*_seg_f32, csrc/frontend.hip), one launch per step
 # for the whole list; same bits per clip
 _ENDS = ("per_clip", "ragged")
 
@@ -424,37 +424,26 @@ class FlowHighSR:
             prepared.append(audio)
         return prepared
 
-    def _prepare_cond_ragged(self, clips, sr):
-        """_prepare_cond for clips of different lengths: (cond packed [sum T48_i], list of [T48_i] views) on the device,
-        peak-normalised per clip with the bits of _prepare_cond on each clip alone.  One upload for the list; 'hip': the
-        segment forms of the resampler's launches, 'scipy': the host resampling and normalisation per clip, as they are.
-        sr: one input rate, or one per clip."""
-        prepared = self._host_clips(clips)
-        if self.upsampling_method == 'scipy':
-            import scipy.signal
-            conds = []
-            for audio, sr_i in zip(prepared, resolve_rates(sr, len(prepared))):
-                cond = scipy.signal.resample_poly(audio, 48000, sr_i)
-                conds.append(cond / np.max(np.abs(cond)))
-            return self.resampler.upload_packed(conds)
-        if self.upsampling_method == 'hip':
-            return self.resampler.ragged(prepared, sr, 48000)
-        raise UnboundLocalError(f"cond: unsupported upsampling_method '{self.upsampling_method}'")
-
-    def _prepare_cond(self, clips, sr, target_sampling_rate):
-        """list of 1-D arrays (equal length) -> cond [B, T48] float32 on device, peak-normalised per clip."""
+    def _prepare_cond(self, clips, sr, target_sampling_rate=48000, ragged=False):
+        """list of 1-D arrays (equal length, one rate) -> cond [B, T48] float32 on device, peak-normalised per clip.
+        ragged: clips of different lengths, sr one input rate or one per clip -> (cond packed [sum T48_i], list of [T48_i]
+        views) on the device, every clip the bits of the batched form on that clip alone.  One upload for the list; 'hip': the
+        segment forms of the resampler's launches, 'scipy': the host resampling and normalisation per clip, as they are."""
         if target_sampling_rate != 48000:
             raise NotImplementedError("the mel codec is fixed at 48 kHz")
         prepared = self._host_clips(clips)
         if self.upsampling_method == 'scipy':
             import scipy.signal
             conds = []
-            for audio in prepared:
-                cond = scipy.signal.resample_poly(audio, target_sampling_rate, sr)
-                cond = cond / np.max(np.abs(cond))
-                conds.append(torch.tensor(cond).float())
-            return self._upload(torch.stack(conds))
+            for audio, sr_i in zip(prepared, resolve_rates(sr, len(prepared)) if ragged else [sr] * len(prepared)):
+                cond = scipy.signal.resample_poly(audio, target_sampling_rate, sr_i)
+                conds.append(cond / np.max(np.abs(cond)))
+            if ragged:
+                return self.resampler.upload_packed(conds)
+            return self._upload(torch.stack([torch.tensor(cond).float() for cond in conds]))
         if self.upsampling_method == 'hip':
+            if ragged:
+                return self.resampler.ragged(prepared, sr, target_sampling_rate)
             x = self._upload(torch.from_numpy(np.stack([a.astype(np.float32) for a in prepared])))
             return self.resampler(x, sr, target_sampling_rate)
         raise UnboundLocalError(f"cond: unsupported upsampling_method '{self.upsampling_method}'")
@@ -554,22 +543,62 @@ class FlowHighSR:
             y = out
         return y
 
+    def _cutoff_bins(self, cond_mel, n_seg, n, seg=None):
+        """int32 [n_seg] cutoff bin of every clip, two launches: n_seg clips of n rows, or (seg: the device segment table)
+        clips of different lengths packed back to back."""
+        L, st = hip.lib(), hip.stream()
+        d = cond_mel.shape[-1]
+        energy = torch.empty(n_seg, d, dtype=torch.float32, device=self.device)
+        cut = torch.empty(n_seg, dtype=torch.int32, device=self.device)
+        if seg is None:
+            hip.check(L.fh_mel_energy_f32(cond_mel.data_ptr(), energy.data_ptr(), n_seg, n, d, st), "fh_mel_energy_f32")
+        else:
+            hip.check(L.fh_mel_energy_seg_f32(cond_mel.data_ptr(), energy.data_ptr(), seg.data_ptr(), n_seg, d, st),
+                      "fh_mel_energy_seg_f32")
+        hip.check(L.fh_cutoff_index_f32(energy.data_ptr(), cut.data_ptr(), n_seg, d, 0.9995, st), "fh_cutoff_index_f32")
+        return cut
+
     @hip.on_device
     def mel_cutoff_bins(self, cond_mel, batch, n):
         """Device version of mel_cutoff_bins (cfm:134-159): int32 [B], no host loop, no sync."""
-        L, st = hip.lib(), hip.stream()
-        d = cond_mel.shape[-1]
-        energy = torch.empty(batch, d, dtype=torch.float32, device=self.device)
-        cut = torch.empty(batch, dtype=torch.int32, device=self.device)
-        hip.check(L.fh_mel_energy_f32(cond_mel.data_ptr(), energy.data_ptr(), batch, n, d, st), "fh_mel_energy_f32")
-        hip.check(L.fh_cutoff_index_f32(energy.data_ptr(), cut.data_ptr(), batch, d, 0.9995, st), "fh_cutoff_index_f32")
-        return cut
+        return self._cutoff_bins(cond_mel, batch, n)
 
-    def _mel_replace(self, high, low, cut, batch, n):
+    def _mel_replace(self, high, low, cut, n_seg, n, seg=None):
+        """out = bins below cut[clip] from low, the others from high; seg as in _cutoff_bins (n: then the longest clip's rows)."""
+        L, st = hip.lib(), hip.stream()
         out = torch.empty_like(high)
-        hip.check(hip.lib().fh_mel_splice_f32(low.data_ptr(), high.data_ptr(), cut.data_ptr(), out.data_ptr(), batch, n,
-                                              high.shape[-1], hip.stream()), "fh_mel_splice_f32")
+        args = (low.data_ptr(), high.data_ptr(), cut.data_ptr(), out.data_ptr())
+        if seg is None:
+            hip.check(L.fh_mel_splice_f32(*args, n_seg, n, high.shape[-1], st), "fh_mel_splice_f32")
+        else:
+            hip.check(L.fh_mel_splice_seg_f32(*args, seg.data_ptr(), n_seg, n, high.shape[-1], st), "fh_mel_splice_seg_f32")
         return out
+
+    def _sample_rows(self, cond_mel, noise, keys, n_seg, n, time_steps, cfm_method, std_1, std_2, cond_scale, mel_pp, ragged=None):
+        """The sampler behind the log-mel (cfm:176-279) on token-major rows: n_seg clips of n rows, or (ragged: the net's
+        ragged workspace) clips of different lengths packed back to back, n = the longest.  cond_mel, noise [rows, n_mels] on
+        the device; noise None: drawn on the device from the clips' keys.  Returns the mel rows."""
+        if cfm_method in _CFM_METHODS[1:]:
+            if std_1 is None or std_2 is None:          # cfm:180-183 (resets BOTH; generate() never passes std_1)
+                std_1, std_2 = 1.0, self.sigma
+        seg = ragged["seg"] if ragged is not None else None
+        if noise is None:                               # prior='device': drawn where it is used
+            noise = self._device_prior(keys, n_seg, n, seg=seg, rows=cond_mel.shape[0])
+        cut = None
+        if cfm_method == 'basic_cfm':
+            y0 = noise
+        else:
+            y0 = torch.empty_like(noise)                # cond * std_1 + eps * std_2
+            hip.check(hip.lib().fh_axpby_f32(cond_mel.data_ptr(), float(std_1), noise.data_ptr(), float(std_2),
+                                             y0.data_ptr(), y0.numel(), hip.stream()), "fh_axpby_f32")
+            if cfm_method == 'independent_cfm_mix':     # cfm:231-237, cutoff bins per clip
+                cut = self._cutoff_bins(cond_mel, n_seg, n, seg)
+                y0 = self._mel_replace(noise, y0, cut, n_seg, n, seg)
+        mel = self._integrate(y0, cond_mel, n_seg, n, time_steps, float(cond_scale), ragged=ragged)
+        if mel_pp:                                      # cfm:278-279, per clip
+            cut = cut if cut is not None else self._cutoff_bins(cond_mel, n_seg, n, seg)
+            mel = self._mel_replace(mel, cond_mel, cut, n_seg, n, seg)
+        return mel
 
     @torch.no_grad()
     @hip.on_device
@@ -588,9 +617,6 @@ class FlowHighSR:
                 std_1=None, std_2=None, mel_pp=False, cfm_method=None, noise=None, generator=None, keys=None):
         if cfm_method not in _CFM_METHODS:
             cfm_method = self.cfm_method
-        if cfm_method in _CFM_METHODS[1:]:
-            if std_1 is None or std_2 is None:          # cfm:180-183 (resets BOTH)
-                std_1, std_2 = 1.0, self.sigma
         if cond_mask is not None:
             raise NotImplementedError("cond_mask is a training-time option (SURVEY.md 8a row 2)")
         fh = self.flowhigh
@@ -604,50 +630,17 @@ class FlowHighSR:
         else:
             batch, n, _ = cond.shape
             cond_mel = cond.reshape(batch * n, -1).contiguous()
-        if noise is None and keys is not None:                              # prior='device': drawn where it is used
-            noise = self._device_prior(keys, batch, n)
-        else:
+        if noise is not None or keys is None:
             if noise is None:
                 noise = self._draw_noise(batch, n, generator)
             noise = self._upload(noise.to(torch.float32)).reshape(batch * n, -1).contiguous()
-        cut = None
-        if cfm_method == 'basic_cfm':
-            y0 = noise
-        else:
-            y0 = torch.empty_like(noise)                                    # cond * std_1 + eps * std_2
-            hip.check(hip.lib().fh_axpby_f32(cond_mel.data_ptr(), float(std_1), noise.data_ptr(), float(std_2),
-                                             y0.data_ptr(), y0.numel(), hip.stream()), "fh_axpby_f32")
-            if cfm_method == 'independent_cfm_mix':                         # cfm:231-237
-                cut = self.mel_cutoff_bins(cond_mel, batch, n)
-                y0 = self._mel_replace(noise, y0, cut, batch, n)
-        mel = self._integrate(y0, cond_mel, batch, n, time_steps, float(cond_scale))
-        if mel_pp:                                                          # cfm:278-279
-            cut = cut if cut is not None else self.mel_cutoff_bins(cond_mel, batch, n)
-            mel = self._mel_replace(mel, cond_mel, cut, batch, n)
+        mel = self._sample_rows(cond_mel, noise, keys, batch, n, time_steps, cfm_method, std_1, std_2, cond_scale, mel_pp)
         mel = mel.view(batch, n, -1)
         if not decode_to_audio:
             return mel
         return fh.vocoder.forward(mel).unsqueeze(1)           # [B, 1, hop * n]
 
-    def _cutoff_bins_seg(self, cond_mel, seg, n_seg):
-        """mel_cutoff_bins per clip of a packed batch: int32 [n_seg], two launches for the whole list."""
-        L, st = hip.lib(), hip.stream()
-        d = cond_mel.shape[-1]
-        energy = torch.empty(n_seg, d, dtype=torch.float32, device=self.device)
-        cut = torch.empty(n_seg, dtype=torch.int32, device=self.device)
-        hip.check(L.fh_mel_energy_seg_f32(cond_mel.data_ptr(), energy.data_ptr(), seg.data_ptr(), n_seg, d, st),
-                  "fh_mel_energy_seg_f32")
-        hip.check(L.fh_cutoff_index_f32(energy.data_ptr(), cut.data_ptr(), n_seg, d, 0.9995, st), "fh_cutoff_index_f32")
-        return cut
-
-    def _mel_replace_seg(self, high, low, cut, seg, n_seg, max_n):
-        out = torch.empty_like(high)
-        hip.check(hip.lib().fh_mel_splice_seg_f32(low.data_ptr(), high.data_ptr(), cut.data_ptr(), out.data_ptr(),
-                                                  seg.data_ptr(), n_seg, max_n, high.shape[-1], hip.stream()),
-                  "fh_mel_splice_seg_f32")
-        return out
-
-    def _sample_ragged(self, conds, noises, time_steps, cfm_method, std_1=None, std_2=None, mels=None, cond_scale=1.,
+    def _sample_ragged(self, conds, time_steps, cfm_method, noises=None, std_1=None, std_2=None, mels=None, cond_scale=1.,
                        mel_pp=False, decode_to_audio=True, keys=None, cond_mel=None):
         """`sample()` (cfm:162-284, incl. cond_scale != 1 and mel_pp, cfm:162-175,278-279) for clips of DIFFERENT
         lengths as one launch sequence.
@@ -660,37 +653,19 @@ class FlowHighSR:
         cond_mel (with mels = its per-clip views; ends='ragged'): the clips' log-mels packed already (LogMel.ragged); nothing
         is concatenated and the vocoder takes the packed result (forward_ragged_packed)."""
         fh = self.flowhigh
-        if cfm_method in _CFM_METHODS[1:]:
-            if std_1 is None or std_2 is None:               # cfm:180-183 (resets BOTH; generate() never passes std_1)
-                std_1, std_2 = 1.0, self.sigma
         if mels is None:
             mels = [fh.logmel(c[None]) for c in conds]       # [N_i, n_mels] each
         frames = [m.shape[0] for m in mels]
         packed = cond_mel is not None
         if not packed:
             cond_mel = torch.cat(mels, 0)
-        rws = fh.net.ragged_workspace(frames)
-        seg, n_seg, max_n = rws["seg"], len(frames), max(frames)
-        if noises is None:
-            noise = self._device_prior(keys, n_seg, max_n, seg=seg, rows=sum(frames))
-        else:
+        noise = None
+        if noises is not None:
             noise = self._upload(torch.cat([z.reshape(-1, z.shape[-1]).to(torch.float32) for z in noises], 0)).contiguous()
-        if noise.shape != cond_mel.shape:
-            raise ValueError(f"noise rows {tuple(noise.shape)} do not match the clips' frames {tuple(cond_mel.shape)}")
-        cut = None
-        if cfm_method == 'basic_cfm':
-            y0 = noise
-        else:
-            y0 = torch.empty_like(noise)
-            hip.check(hip.lib().fh_axpby_f32(cond_mel.data_ptr(), float(std_1), noise.data_ptr(), float(std_2),
-                                             y0.data_ptr(), y0.numel(), hip.stream()), "fh_axpby_f32")
-            if cfm_method == 'independent_cfm_mix':          # per-clip cutoff bins (cfm:231-237)
-                cut = self._cutoff_bins_seg(cond_mel, seg, n_seg)
-                y0 = self._mel_replace_seg(noise, y0, cut, seg, n_seg, max_n)
-        mel = self._integrate(y0, cond_mel, n_seg, max_n, time_steps, float(cond_scale), ragged=rws)
-        if mel_pp:                                           # cfm:278-279, per clip
-            cut = cut if cut is not None else self._cutoff_bins_seg(cond_mel, seg, n_seg)
-            mel = self._mel_replace_seg(mel, cond_mel, cut, seg, n_seg, max_n)
+            if noise.shape != cond_mel.shape:
+                raise ValueError(f"noise rows {tuple(noise.shape)} do not match the clips' frames {tuple(cond_mel.shape)}")
+        mel = self._sample_rows(cond_mel, noise, keys, len(frames), max(frames), time_steps, cfm_method, std_1, std_2, cond_scale,
+                                mel_pp, ragged=fh.net.ragged_workspace(frames))
         if packed and decode_to_audio:
             return fh.vocoder.forward_ragged_packed(mel, frames)
         rows, out = 0, []
@@ -717,7 +692,7 @@ class FlowHighSR:
         frames = [c.shape[0] // 480 for c in conds]
         if noise is None and keys is None:
             noise = [self._draw_noise(1, n, generator) for n in frames]
-        outs = self._sample_ragged(conds, noise, time_steps, cfm_method, std_1=std_1, std_2=std_2, cond_scale=cond_scale,
+        outs = self._sample_ragged(conds, time_steps, cfm_method, noises=noise, std_1=std_1, std_2=std_2, cond_scale=cond_scale,
                                    mel_pp=mel_pp, decode_to_audio=decode_to_audio, keys=keys)
         return [o.clone().unsqueeze(1) if decode_to_audio else o.clone()[None] for o in outs]
 
@@ -758,7 +733,7 @@ class FlowHighSR:
         Results are bit-identical to generate() per clip either way.
         ends ('per_clip' | 'ragged'; None: FH_RAGGED_ENDS, else 'per_clip'): what surrounds the launch sequence of a ragged
         group of two or more clips -- resampling and peak normalisation, log-mel, the vocoder's input copies, post-processing.
-        'per_clip' runs them once per clip (~18 launches each); 'ragged' runs their segment forms (csrc/frontend_seg.hip), one
+        'per_clip' runs them once per clip (~18 launches each); 'ragged' runs their segment forms (fh_*_seg_f32, csrc/frontend.hip), one
         launch per step for the whole group, out of workspaces kept per mix of lengths; same bits per clip.
         streams (ragged off): batches of different FRAME COUNTS can be enqueued round-robin on several HIP streams (FH_SERVE_STREAMS,
         default 1), so that the launches of a short clip - a few dozen blocks each, a fraction of the 256 CUs - overlap
@@ -771,11 +746,9 @@ class FlowHighSR:
         ends = resolve_ends(ends)
         rates = resolve_rates(sr, len(clips))
         keys = self._prior_keys(seed, len(clips), generator, noise)
+        lengths = [int(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).shape[-1]) for a in clips]
         if noise is None:
-            frames = []
-            for a, sr_i in zip(clips, rates):
-                n_in = int(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).shape[-1])
-                frames.append(resample_out_len(n_in, target_sampling_rate, sr_i) // 480)
+            frames = [resample_out_len(n_in, target_sampling_rate, sr_i) // 480 for n_in, sr_i in zip(lengths, rates)]
             if keys is None:
                 noise = [self._draw_noise(1, n, generator) for n in frames]
         if noise is not None and len(noise) != len(clips):
@@ -784,7 +757,6 @@ class FlowHighSR:
         shapes = [tuple(z.shape) for z in noise] if noise is not None else [(1, n, self.flowhigh.n_mels) for n in frames]
         if ragged is None:
             ragged = os.environ.get("FH_RAGGED", "1") != "0"
-        lengths = [int(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).shape[-1]) for a in clips]
         if ragged and len(set(zip(lengths, rates))) > 1 and target_sampling_rate == 48000:
             try:
                 return self._generate_many_ragged(clips, lengths, rates, timestep, noise, max_frames, keys=keys,
@@ -859,13 +831,12 @@ class FlowHighSR:
             if len(idx) == 1:
                 out[idx[0]] = self.generate_batch([clips[idx[0]]], rates[idx[0]], 48000, timestep, **prior_of(idx[0])).clone()
                 continue
-            prior = dict(keys=[keys[i] for i in idx]) if keys is not None else {}
+            prior = dict(keys=[keys[i] for i in idx]) if keys is not None else dict(noises=[noise[i] for i in idx])
             if ends == "ragged":
                 # front and back end as segment-form launches over the group: nothing below depends on the number of clips
-                _, conds = self._prepare_cond_ragged([clips[i] for i in idx], [rates[i] for i in idx])
+                _, conds = self._prepare_cond([clips[i] for i in idx], [rates[i] for i in idx], ragged=True)
                 cond_mel, mels = self.flowhigh.logmel.ragged(conds)
-                wavs = self._sample_ragged(conds, None if keys is not None else [noise[i] for i in idx], timestep, self.cfm_method,
-                                           mels=mels, cond_mel=cond_mel, **prior, **kw)
+                wavs = self._sample_ragged(conds, timestep, self.cfm_method, mels=mels, cond_mel=cond_mel, **prior, **kw)
                 packed, views = self.postproc.ragged(wavs, conds, [c.shape[0] for c in conds])
                 packed = packed.clone()                      # (the caller's own: one copy for the group, handed out as views)
                 start = 0
@@ -876,10 +847,7 @@ class FlowHighSR:
             # (the per-clip front and back ends -- ~8 + ~12 small launches per clip -- on up to 4 side streams measured
             # 121.5 ms against 121.3 ms on one stream for the 24-clip mix: not worth the cross-stream bookkeeping)
             conds = [self._prepare_cond([clips[i]], rates[i], 48000)[0] for i in idx]
-            if keys is not None:
-                wavs = self._sample_ragged(conds, None, timestep, self.cfm_method, keys=[keys[i] for i in idx], **kw)
-            else:
-                wavs = self._sample_ragged(conds, [noise[i] for i in idx], timestep, self.cfm_method, **kw)
+            wavs = self._sample_ragged(conds, timestep, self.cfm_method, **prior, **kw)
             for i, cond, wav in zip(idx, conds, wavs):
                 out[i] = self.postproc(wav, cond[None], cond.shape[0]).clone()
         return out

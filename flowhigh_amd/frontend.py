@@ -1,7 +1,7 @@
 """Log-mel front end, STFT-domain post-processing and the resampling pre-step on the HIP kernels.
 
-  LogMel          MelVoco.encode                   /root/reference/src/flowhigh/models/melvoco.py:56-86
-  PostProcessor   PostProcessing.post_processing   /root/reference/src/flowhigh/postprocessing.py:5-41
+  LogMel          MelVoco.encode                   models/melvoco.py:56-86 (paths under the reference's src/flowhigh/)
+  PostProcessor   PostProcessing.post_processing   postprocessing.py:5-41
   Resampler       scipy.signal.resample_poly + peak normalise   flowhighsr.py:68-69
 
 STFT / iSTFT are 2048-point FFTs in LDS (csrc/fft.hip; FH_FFT=0 selects the older DFT-by-GEMM on the
@@ -39,7 +39,7 @@ class _Const:
         return cls._cache[key]
 
 
-# ---- ragged calls: clips of different lengths through the segment-form entries (csrc/frontend_seg.hip) -------------------
+# ---- ragged calls: clips of different lengths through the segment-form entries (fh_*_seg_f32, csrc/frontend.hip) ----------
 def clip_rates(sr, n_clips):
     """The input rate of every clip of a list as ints: `sr` is one rate for all of them, or a sequence of one positive
     integer rate per clip (anything else is a ValueError)."""
@@ -58,14 +58,19 @@ def clip_rates(sr, n_clips):
         raise ValueError(f"an input rate must be a positive integer, got {sr!r}") from e
 
 
+def rate_index(rates):
+    """(the distinct rates of a clip list in order of first appearance, int32 numpy array: every clip's index among them)."""
+    distinct = list(dict.fromkeys(rates))
+    return distinct, np.array([distinct.index(r) for r in rates], dtype=np.int32)
+
+
 def rate_tables(rates, sr_out=48000):
     """Host side of the per-clip filters of fh_resample_poly_rates_seg_f32 for clips at `rates` (one per clip) ->
       bank      float32 numpy array: the taps of every distinct rate's tables.resample_poly_plan back to back
       rows      hip.Rate array, one row per distinct rate in order of first appearance (a rate equal to sr_out: n_taps = 0,
                 up = down = 1: the copy)
       rate_of   int32 numpy array, the row of every clip."""
-    rates = clip_rates(rates, len(rates))
-    distinct = list(dict.fromkeys(rates))
+    distinct, rate_of = rate_index(clip_rates(rates, len(rates)))
     taps, rows, pos = [], [], 0
     for r in distinct:
         plan = tables.resample_poly_plan(sr_out, r)
@@ -79,7 +84,7 @@ def rate_tables(rates, sr_out=48000):
     if pos >= 2 ** 31:
         raise ValueError("tap bank too large")
     bank = np.concatenate(taps).astype(np.float32, copy=False) if taps else np.zeros(0, np.float32)
-    return bank, (hip.Rate * len(rows))(*rows), np.array([distinct.index(r) for r in rates], dtype=np.int32)
+    return bank, (hip.Rate * len(rows))(*rows), rate_of
 
 
 def ragged_clip_tables(lengths_in, sr_in, sr_out=48000, pred_lens=None, check_mel=True):
@@ -115,6 +120,15 @@ def _ptr(t):
     return t.data_ptr()
 
 
+def _launch(name, *args):
+    """One library entry on the current stream."""
+    hip.check(getattr(hip.lib(), name)(*args, hip.stream()), name)
+
+
+def _starts(lens):
+    return [int(x) for x in np.cumsum([0] + list(lens[:-1]))]
+
+
 def upload_tables(parts, device):
     """Descriptor arrays and segment tables of a call (ctypes arrays / int32 numpy arrays) as ONE pinned buffer and one copy;
     returns (device uint8 tensor that owns them, device address of every part), parts 16-byte aligned."""
@@ -138,6 +152,13 @@ def clip_array(src=None, dst=None, len_in=None, len_out=None, row0=None, rows=No
     return (hip.Clip * n)(*[hip.Clip(*[int(c[i]) for c in cols]) for i in range(n)])
 
 
+def resample_clip_array(tab, x_ptr, y_ptr):
+    """The resampler's descriptors for the clips of `tab` (ragged_clip_tables), packed back to back at x_ptr (input) and
+    y_ptr (output): the same for one input rate and for a rate per clip."""
+    return clip_array(src=[x_ptr + 4 * o for o in tab["in_off"]], len_in=tab["len_in"],
+                      dst=[y_ptr + 4 * o for o in tab["out_off"]], len_out=tab["len_out"])
+
+
 def seg_table(row0, rows):
     return np.array([[a, b] for a, b in zip(row0, rows)], dtype=np.int32)
 
@@ -150,11 +171,37 @@ def _flat(ts):
     return [t.reshape(-1) for t in ts]
 
 
+def _rfft(c, frames, out, rows, mag):
+    """frames [rows, 2048] -> out [rows, .]: the P-layout spectrum, or (mag) its magnitude.  c: the device's _Const."""
+    if _USE_FFT:
+        _launch("fh_rfft2048_f32", _ptr(frames), _ptr(c["tw"]), _ptr(out), rows, int(mag))
+    else:
+        hip.gemm(frames, c["w_fwd"], out, rows, P_WIDTH, N_FFT, epilogue=hip.EPI_MAG if mag else hip.EPI_LINEAR)
+
+
+def _irfft(c, spec, frames, rows):
+    """P-layout spectrum [rows, .] -> frames [rows, 2048]."""
+    if _USE_FFT:
+        _launch("fh_irfft2048_f32", _ptr(spec), _ptr(c["tw"]), _ptr(frames), rows)
+    else:
+        hip.gemm(spec, c["w_inv"], frames, rows, N_FFT, P_WIDTH)
+
+
 class LogMel:
     def __init__(self, device):
         self.device = hip.norm_device(device)
         self.c = _Const.get(self.device)
         self._ws = hip.ShapeCache()
+
+    def _buffers(self, rows):
+        f32 = dict(dtype=torch.float32, device=self.device)
+        return torch.empty(rows, N_FFT, **f32), torch.empty(rows, MAG_WIDTH, **f32)
+
+    def _project(self, frames, mag, mel, rows):
+        """The framed clips -> log-mel rows: |STFT|, then the mel projection with its log."""
+        _rfft(self.c, frames, mag, rows, mag=True)
+        hip.gemm(mag, self.c["w_mel"], mel, rows, N_MELS, MAG_WIDTH, epilogue=hip.EPI_LOGCLAMP)
+        return mel
 
     @hip.on_device
     def __call__(self, audio):
@@ -165,21 +212,11 @@ class LogMel:
             raise ValueError(f"clip of {T} samples is too short for the mel front end")
         key = (B, T)
         if key not in self._ws:
-            f32 = dict(dtype=torch.float32, device=self.device)
-            self._ws[key] = (torch.empty(B * N, N_FFT, **f32), torch.empty(B * N, MAG_WIDTH, **f32))
+            self._ws[key] = self._buffers(B * N)
         frames, mag = self._ws[key]
-        L, st = hip.lib(), hip.stream()
         audio = audio.contiguous()
-        hip.check(L.fh_frame_f32(audio.data_ptr(), self.c["hann"].data_ptr(), frames.data_ptr(), B, T, N,
-                                 N_FFT, HOP, (N_FFT - HOP) // 2, 0, st), "fh_frame_f32")
-        if _USE_FFT:
-            hip.check(L.fh_rfft2048_f32(frames.data_ptr(), self.c["tw"].data_ptr(), mag.data_ptr(), B * N, 1, st),
-                      "fh_rfft2048_f32")
-        else:
-            hip.gemm(frames, self.c["w_fwd"], mag, B * N, P_WIDTH, N_FFT, epilogue=hip.EPI_MAG)
-        mel = torch.empty(B * N, N_MELS, dtype=torch.float32, device=self.device)
-        hip.gemm(mag, self.c["w_mel"], mel, B * N, N_MELS, MAG_WIDTH, epilogue=hip.EPI_LOGCLAMP)
-        return mel
+        _launch("fh_frame_f32", _ptr(audio), _ptr(self.c["hann"]), _ptr(frames), B, T, N, N_FFT, HOP, (N_FFT - HOP) // 2, 0)
+        return self._project(frames, mag, torch.empty(B * N, N_MELS, dtype=torch.float32, device=self.device), B * N)
 
     @hip.on_device
     def ragged(self, conds):
@@ -192,25 +229,65 @@ class LogMel:
         ptrs = tuple(_ptr(c) for c in conds)
         M = sum(tab["mel_rows"])
         if key not in self._ws:
-            f32 = dict(dtype=torch.float32, device=self.device)
-            mel = torch.empty(M, N_MELS, **f32)
-            self._ws[key] = dict(frames=torch.empty(M, N_FFT, **f32), mag=torch.empty(M, MAG_WIDTH, **f32), mel=mel,
-                                 views=_views(mel, tab["mel_row0"], tab["mel_rows"]), ptrs=None)
+            frames, mag = self._buffers(M)
+            mel = torch.empty(M, N_MELS, dtype=torch.float32, device=self.device)
+            self._ws[key] = dict(frames=frames, mag=mag, mel=mel, views=_views(mel, tab["mel_row0"], tab["mel_rows"]), ptrs=None)
         w = self._ws[key]
         if w["ptrs"] != ptrs:             # (clips at other addresses than last time: the descriptors go up again, one copy)
             w["desc"], (w["clips"],) = upload_tables([clip_array(src=ptrs, len_in=tab["len_out"], row0=tab["mel_row0"],
                                                                  rows=tab["mel_rows"])], self.device)
             w["ptrs"] = ptrs
-        L, st = hip.lib(), hip.stream()
-        frames, mag, mel = w["frames"], w["mag"], w["mel"]
-        hip.check(L.fh_frame_seg_f32(w["clips"], len(conds), max(tab["mel_rows"]), min(tab["len_out"]), self.c["hann"].data_ptr(),
-                                     frames.data_ptr(), N_FFT, HOP, (N_FFT - HOP) // 2, 0, st), "fh_frame_seg_f32")
-        if _USE_FFT:
-            hip.check(L.fh_rfft2048_f32(frames.data_ptr(), self.c["tw"].data_ptr(), mag.data_ptr(), M, 1, st), "fh_rfft2048_f32")
-        else:
-            hip.gemm(frames, self.c["w_fwd"], mag, M, P_WIDTH, N_FFT, epilogue=hip.EPI_MAG)
-        hip.gemm(mag, self.c["w_mel"], mel, M, N_MELS, MAG_WIDTH, epilogue=hip.EPI_LOGCLAMP)
-        return mel, w["views"]
+        _launch("fh_frame_seg_f32", w["clips"], len(conds), max(tab["mel_rows"]), min(tab["len_out"]), _ptr(self.c["hann"]),
+                _ptr(w["frames"]), N_FFT, HOP, (N_FFT - HOP) // 2, 0)
+        return self._project(w["frames"], w["mag"], w["mel"], M), w["views"]
+
+
+class _BatchedPost:
+    """PostProcessor's own launches for B equal-length clips: pred [B, Tp], src [B, T] -> out [B, length], F frames each."""
+
+    def __init__(self, pred, src, out, F):
+        self.sig, self.out, self.B, self.F = dict(pred=pred, src=src), out, out.shape[0], F
+
+    def frame(self, which, hann, frames):
+        x = self.sig[which]
+        _launch("fh_frame_f32", _ptr(x), hann, _ptr(frames), self.B, x.shape[1], self.F, N_FFT, HOP, N_FFT // 2, 1)
+
+    def spec_energy(self, ss, energy):
+        _launch("fh_spec_energy_f32", _ptr(ss), _ptr(energy), self.B, self.F)
+
+    def spec_splice(self, sp, ss, cr):
+        _launch("fh_spec_splice_f32", _ptr(sp), _ptr(ss), _ptr(cr), _ptr(sp), self.B, self.F)
+
+    def istft_ola(self, frames, hann, peak):
+        _launch("fh_istft_ola_f32", _ptr(frames), hann, _ptr(self.out), _ptr(peak), self.B, self.F, self.out.shape[1], N_FFT, HOP)
+
+    def peak_scale(self, peak):
+        _launch("fh_peak_scale_f32", _ptr(self.out), _ptr(peak), self.B, self.out.shape[1], 0.99)
+
+
+class _SegmentPost:
+    """The same launches for n clips of different lengths: w holds the device tables (c_pred, c_src: fh_clip arrays, seg: the
+    row table); Tp, T, F, lengths are per clip."""
+
+    def __init__(self, w, Tp, T, F, lengths):
+        self.clips, self.min_len = dict(pred=w["c_pred"], src=w["c_src"]), dict(pred=min(Tp), src=min(T))
+        self.seg, self.n, self.max_rows, self.max_len = w["seg"], len(F), max(F), max(lengths)
+
+    def frame(self, which, hann, frames):
+        _launch("fh_frame_seg_f32", self.clips[which], self.n, self.max_rows, self.min_len[which], hann, _ptr(frames), N_FFT, HOP,
+                N_FFT // 2, 1)
+
+    def spec_energy(self, ss, energy):
+        _launch("fh_spec_energy_seg_f32", _ptr(ss), _ptr(energy), self.seg, self.n)
+
+    def spec_splice(self, sp, ss, cr):
+        _launch("fh_spec_splice_seg_f32", _ptr(sp), _ptr(ss), _ptr(cr), _ptr(sp), self.seg, self.n, self.max_rows)
+
+    def istft_ola(self, frames, hann, peak):
+        _launch("fh_istft_ola_seg_f32", _ptr(frames), hann, self.clips["src"], self.n, self.max_len, _ptr(peak), N_FFT, HOP)
+
+    def peak_scale(self, peak):
+        _launch("fh_peak_scale_seg_f32", self.clips["src"], self.n, self.max_len, _ptr(peak), 0.99)
 
 
 class PostProcessor:
@@ -219,45 +296,39 @@ class PostProcessor:
         self.c = _Const.get(self.device)
         self._ws = hip.ShapeCache()
 
+    def _workspace(self, key, rows, n, **more):
+        """The buffers of a shape (rows STFT frames of n clips), made once per key; more: what else the entry starts with."""
+        if key not in self._ws:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            self._ws[key] = dict(frames=torch.empty(rows, N_FFT, **f32), sp=torch.empty(rows, P_WIDTH, **f32),
+                                 ss=torch.empty(rows, P_WIDTH, **f32), energy=torch.empty(n, 1025, **f32),
+                                 cr=torch.empty(n, dtype=torch.int32, device=self.device),
+                                 peak=torch.empty(n, dtype=torch.int32, device=self.device), **more)
+        return self._ws[key]
+
+    def _run(self, w, form, rows, n):
+        """The launch sequence of both forms: per-clip cutoff, splice, iSTFT, 0.99 peak.  form: _BatchedPost or _SegmentPost."""
+        hann = _ptr(self.c["hann"])
+        for which, spec in (("pred", w["sp"]), ("src", w["ss"])):
+            form.frame(which, hann, w["frames"])
+            _rfft(self.c, w["frames"], spec, rows, mag=False)
+        form.spec_energy(w["ss"], w["energy"])
+        _launch("fh_cutoff_index_f32", _ptr(w["energy"]), _ptr(w["cr"]), n, 1025, 0.99)
+        form.spec_splice(w["sp"], w["ss"], w["cr"])
+        _irfft(self.c, w["sp"], w["frames"], rows)
+        w["peak"].zero_()
+        form.istft_ola(w["frames"], hann, w["peak"])
+        form.peak_scale(w["peak"])
+
     @hip.on_device
     def __call__(self, pred, src, length, return_cr=False):
         """pred [B, Tp], src [B, T] -> [B, length]; per-clip cutoff, splice, iSTFT, 0.99 peak."""
         B, Tp = pred.shape
         T = src.shape[1]
         F = min(1 + Tp // HOP, 1 + T // HOP)
-        key = (B, Tp, T, length)
-        if key not in self._ws:
-            f32 = dict(dtype=torch.float32, device=self.device)
-            self._ws[key] = dict(frames=torch.empty(B * F, N_FFT, **f32), sp=torch.empty(B * F, P_WIDTH, **f32),
-                                 ss=torch.empty(B * F, P_WIDTH, **f32), energy=torch.empty(B, 1025, **f32),
-                                 cr=torch.empty(B, dtype=torch.int32, device=self.device),
-                                 peak=torch.empty(B, dtype=torch.int32, device=self.device))
-        w = self._ws[key]
-        L, st = hip.lib(), hip.stream()
-        hann = self.c["hann"].data_ptr()
-        pred, src = pred.contiguous(), src.contiguous()
-        for sig, n, spec in ((pred, Tp, w["sp"]), (src, T, w["ss"])):
-            hip.check(L.fh_frame_f32(sig.data_ptr(), hann, w["frames"].data_ptr(), B, n, F, N_FFT, HOP,
-                                     N_FFT // 2, 1, st), "fh_frame_f32")
-            if _USE_FFT:
-                hip.check(L.fh_rfft2048_f32(w["frames"].data_ptr(), self.c["tw"].data_ptr(), spec.data_ptr(), B * F,
-                                            0, st), "fh_rfft2048_f32")
-            else:
-                hip.gemm(w["frames"], self.c["w_fwd"], spec, B * F, P_WIDTH, N_FFT)
-        hip.check(L.fh_spec_energy_f32(w["ss"].data_ptr(), w["energy"].data_ptr(), B, F, st), "fh_spec_energy_f32")
-        hip.check(L.fh_cutoff_index_f32(w["energy"].data_ptr(), w["cr"].data_ptr(), B, 1025, 0.99, st), "fh_cutoff_index_f32")
-        hip.check(L.fh_spec_splice_f32(w["sp"].data_ptr(), w["ss"].data_ptr(), w["cr"].data_ptr(),
-                                       w["sp"].data_ptr(), B, F, st), "fh_spec_splice_f32")
-        if _USE_FFT:
-            hip.check(L.fh_irfft2048_f32(w["sp"].data_ptr(), self.c["tw"].data_ptr(), w["frames"].data_ptr(), B * F, st),
-                      "fh_irfft2048_f32")
-        else:
-            hip.gemm(w["sp"], self.c["w_inv"], w["frames"], B * F, N_FFT, P_WIDTH)
+        w = self._workspace((B, Tp, T, length), B * F, B)
         out = torch.empty(B, length, dtype=torch.float32, device=self.device)
-        w["peak"].zero_()
-        hip.check(L.fh_istft_ola_f32(w["frames"].data_ptr(), hann, out.data_ptr(), w["peak"].data_ptr(), B, F,
-                                     length, N_FFT, HOP, st), "fh_istft_ola_f32")
-        hip.check(L.fh_peak_scale_f32(out.data_ptr(), w["peak"].data_ptr(), B, length, 0.99, st), "fh_peak_scale_f32")
+        self._run(w, _BatchedPost(pred.contiguous(), src.contiguous(), out, F), B * F, B)
         return (out, w["cr"]) if return_cr else out
 
     @hip.on_device
@@ -275,47 +346,19 @@ class PostProcessor:
         F = [min(1 + a // HOP, 1 + b // HOP) for a, b in zip(Tp, T)]
         key = (tuple(Tp), tuple(T), tuple(lengths))
         ptrs = tuple(_ptr(t) for t in preds + srcs)
-        R = sum(F)
         if key not in self._ws:
-            f32 = dict(dtype=torch.float32, device=self.device)
-            out = torch.empty(sum(lengths), **f32)
-            off = [int(x) for x in np.cumsum([0] + lengths[:-1])]
-            self._ws[key] = dict(frames=torch.empty(R, N_FFT, **f32), sp=torch.empty(R, P_WIDTH, **f32),
-                                 ss=torch.empty(R, P_WIDTH, **f32), energy=torch.empty(n, 1025, **f32),
-                                 cr=torch.empty(n, dtype=torch.int32, device=self.device),
-                                 peak=torch.empty(n, dtype=torch.int32, device=self.device), out=out, off=off,
-                                 views=_views(out, off, lengths), ptrs=None)
+            out = torch.empty(sum(lengths), dtype=torch.float32, device=self.device)
+            off = _starts(lengths)
+            self._workspace(key, sum(F), n, out=out, off=off, views=_views(out, off, lengths), ptrs=None)
         w = self._ws[key]
         if w["ptrs"] != ptrs:
-            row0 = [int(x) for x in np.cumsum([0] + F[:-1])]
+            row0 = _starts(F)
             outs = [w["out"].data_ptr() + 4 * o for o in w["off"]]
             w["desc"], (w["c_pred"], w["c_src"], w["seg"]) = upload_tables(
                 [clip_array(src=ptrs[:n], len_in=Tp, row0=row0, rows=F),
                  clip_array(src=ptrs[n:], len_in=T, row0=row0, rows=F, dst=outs, len_out=lengths), seg_table(row0, F)], self.device)
             w["ptrs"] = ptrs
-        L, st = hip.lib(), hip.stream()
-        hann = self.c["hann"].data_ptr()
-        for clips, lens, spec in ((w["c_pred"], Tp, w["sp"]), (w["c_src"], T, w["ss"])):
-            hip.check(L.fh_frame_seg_f32(clips, n, max(F), min(lens), hann, w["frames"].data_ptr(), N_FFT, HOP, N_FFT // 2, 1, st),
-                      "fh_frame_seg_f32")
-            if _USE_FFT:
-                hip.check(L.fh_rfft2048_f32(w["frames"].data_ptr(), self.c["tw"].data_ptr(), spec.data_ptr(), R, 0, st),
-                          "fh_rfft2048_f32")
-            else:
-                hip.gemm(w["frames"], self.c["w_fwd"], spec, R, P_WIDTH, N_FFT)
-        hip.check(L.fh_spec_energy_seg_f32(w["ss"].data_ptr(), w["energy"].data_ptr(), w["seg"], n, st), "fh_spec_energy_seg_f32")
-        hip.check(L.fh_cutoff_index_f32(w["energy"].data_ptr(), w["cr"].data_ptr(), n, 1025, 0.99, st), "fh_cutoff_index_f32")
-        hip.check(L.fh_spec_splice_seg_f32(w["sp"].data_ptr(), w["ss"].data_ptr(), w["cr"].data_ptr(), w["sp"].data_ptr(),
-                                           w["seg"], n, max(F), st), "fh_spec_splice_seg_f32")
-        if _USE_FFT:
-            hip.check(L.fh_irfft2048_f32(w["sp"].data_ptr(), self.c["tw"].data_ptr(), w["frames"].data_ptr(), R, st),
-                      "fh_irfft2048_f32")
-        else:
-            hip.gemm(w["sp"], self.c["w_inv"], w["frames"], R, N_FFT, P_WIDTH)
-        w["peak"].zero_()
-        hip.check(L.fh_istft_ola_seg_f32(w["frames"].data_ptr(), hann, w["c_src"], n, max(lengths), w["peak"].data_ptr(),
-                                         N_FFT, HOP, st), "fh_istft_ola_seg_f32")
-        hip.check(L.fh_peak_scale_seg_f32(w["c_src"], n, max(lengths), w["peak"].data_ptr(), 0.99, st), "fh_peak_scale_seg_f32")
+        self._run(w, _SegmentPost(w, Tp, T, F, lengths), sum(F), n)
         return (w["out"], w["views"], w["cr"]) if return_cr else (w["out"], w["views"])
 
 
@@ -328,27 +371,41 @@ class Resampler:
         self._banks = {}                  # (sr_out, distinct input rates ...) -> (device tap bank, hip.Rate rows)
         self._ws = hip.ShapeCache()
 
+    def _filter(self, sr_out, sr_in):
+        """(device address of the taps, n_taps, n_pre_remove, up, down) of one input rate; None: equal rates."""
+        plan = tables.resample_poly_plan(sr_out, sr_in)
+        if plan is None:
+            return None
+        taps, pre, up, down = plan
+        key = (sr_out, sr_in)
+        if key not in self._taps:
+            self._taps[key] = taps.to(self.device)
+        return self._taps[key].data_ptr(), self._taps[key].numel(), pre, up, down
+
+    def _bank(self, distinct, sr_out):
+        """(device tap bank, hip.Rate rows) of a tuple of distinct input rates, kept on the device per tuple."""
+        key = (sr_out,) + tuple(distinct)
+        if key not in self._banks:
+            bank, rows, _ = rate_tables(distinct, sr_out)
+            self._banks[key] = (torch.from_numpy(bank).to(self.device), rows)
+        return self._banks[key]
+
     @hip.on_device
     def __call__(self, x, sr_in, sr_out=48000):
         """x [B, T_in] float32 on device -> [B, T_out], each clip divided by its max |.|."""
         B, n_in = x.shape
-        plan = tables.resample_poly_plan(sr_out, sr_in)
-        L, st = hip.lib(), hip.stream()
-        if plan is None:
+        flt = self._filter(sr_out, sr_in)
+        if flt is None:
             y = x.clone()
         else:
-            taps, pre, up, down = plan
-            key = (sr_out, sr_in)
-            if key not in self._taps:
-                self._taps[key] = taps.to(self.device)
+            taps, n_taps, pre, up, down = flt
             n_out = tables.resample_out_len(n_in, sr_out, sr_in)
             y = torch.empty(B, n_out, dtype=torch.float32, device=self.device)
             x = x.contiguous()
-            hip.check(L.fh_resample_poly_f32(x.data_ptr(), self._taps[key].data_ptr(), y.data_ptr(), B, n_in,
-                                             n_out, up, down, self._taps[key].numel(), pre, st), "fh_resample_poly_f32")
+            _launch("fh_resample_poly_f32", _ptr(x), taps, _ptr(y), B, n_in, n_out, up, down, n_taps, pre)
         peak = torch.zeros(B, dtype=torch.int32, device=self.device)
-        hip.check(L.fh_peak_abs_f32(y.data_ptr(), peak.data_ptr(), B, y.shape[1], st), "fh_peak_abs_f32")
-        hip.check(L.fh_peak_scale_f32(y.data_ptr(), peak.data_ptr(), B, y.shape[1], 1.0, st), "fh_peak_scale_f32")
+        _launch("fh_peak_abs_f32", _ptr(y), _ptr(peak), B, y.shape[1])
+        _launch("fh_peak_scale_f32", _ptr(y), _ptr(peak), B, y.shape[1], 1.0)
         return y
 
     def _fill(self, buf, xs):
@@ -367,75 +424,34 @@ class Resampler:
         max |.| with the bits of __call__ on that clip alone.  Four launches for the list.  The result belongs to the
         workspace of this mix of lengths: its address is the same at every call of the mix.
         sr_in may be one rate per clip: clips of different rates still run as one resampling launch, every clip with the
-        polyphase filter of its own rate (fh_resample_poly_rates_seg_f32); the workspace then belongs to the mix of
-        (length, rate) pairs."""
+        polyphase filter of its own rate (fh_resample_poly_rates_seg_f32: the filter rows and every clip's row index go up
+        with the clip descriptors, the tap bank is kept per tuple of distinct rates); the workspace then belongs to the mix
+        of (length, rate) pairs."""
         rates = clip_rates(sr_in, len(xs))
-        if len(set(rates)) > 1:
-            return self._ragged_rates(xs, rates, sr_out)
-        sr_in = rates[0] if rates else sr_in
-        tab = ragged_clip_tables([int(np.prod(x.shape)) for x in xs], sr_in, sr_out, check_mel=False)
-        n = len(xs)
-        plan = tables.resample_poly_plan(sr_out, sr_in)
-        key = (sr_in, sr_out, tuple(tab["len_in"]))
+        tab = ragged_clip_tables([int(np.prod(x.shape)) for x in xs], rates, sr_out, check_mel=False)
+        n, max_len = len(xs), max(tab["len_out"])
+        distinct, rate_of = rate_index(rates)
+        mixed = len(distinct) > 1
+        key = (tuple(rates) if mixed else rates[0], sr_out, tuple(tab["len_in"]))
         if key not in self._ws:           # (input, output and descriptors belong to the mix: a mix seen before uploads only its samples)
             f32 = dict(dtype=torch.float32, device=self.device)
             x, y = torch.empty(sum(tab["len_in"]), **f32), torch.empty(sum(tab["len_out"]), **f32)
-            desc, (clips,) = upload_tables(
-                [clip_array(src=[x.data_ptr() + 4 * o for o in tab["in_off"]], len_in=tab["len_in"],
-                            dst=[y.data_ptr() + 4 * o for o in tab["out_off"]], len_out=tab["len_out"])], self.device)
+            parts = [resample_clip_array(tab, x.data_ptr(), y.data_ptr())] + ([self._bank(distinct, sr_out)[1], rate_of] if mixed else [])
+            desc, (clips, *rate_tabs) = upload_tables(parts, self.device)
             self._ws[key] = dict(x=x, y=y, views=_views(y, tab["out_off"], tab["len_out"]), desc=desc, clips=clips,
-                                 peak=torch.empty(n, dtype=torch.int32, device=self.device))
+                                 rate_tabs=rate_tabs, peak=torch.empty(n, dtype=torch.int32, device=self.device))
         w = self._ws[key]
         self._fill(w["x"], xs)
-        L, st = hip.lib(), hip.stream()
-        if plan is None:
-            taps, n_taps, pre, up, down = 0, 0, 0, 1, 1
+        if mixed:
+            bank, (rows, rate_of_dev) = self._bank(distinct, sr_out)[0], w["rate_tabs"]
+            _launch("fh_resample_poly_rates_seg_f32", w["clips"], rate_of_dev, n, max_len, rows, len(distinct),
+                    bank.data_ptr() if bank.numel() else 0, bank.numel())
         else:
-            taps_t, pre, up, down = plan
-            tk = (sr_out, sr_in)
-            if tk not in self._taps:
-                self._taps[tk] = taps_t.to(self.device)
-            taps, n_taps = self._taps[tk].data_ptr(), self._taps[tk].numel()
-        max_len = max(tab["len_out"])
-        hip.check(L.fh_resample_poly_seg_f32(w["clips"], n, max_len, taps, up, down, n_taps, pre, st), "fh_resample_poly_seg_f32")
+            taps, n_taps, pre, up, down = self._filter(sr_out, rates[0]) or (0, 0, 0, 1, 1)
+            _launch("fh_resample_poly_seg_f32", w["clips"], n, max_len, taps, up, down, n_taps, pre)
         w["peak"].zero_()
-        hip.check(L.fh_peak_abs_seg_f32(w["clips"], n, max_len, w["peak"].data_ptr(), st), "fh_peak_abs_seg_f32")
-        hip.check(L.fh_peak_scale_seg_f32(w["clips"], n, max_len, w["peak"].data_ptr(), 1.0, st), "fh_peak_scale_seg_f32")
-        return w["y"], w["views"]
-
-    def _ragged_rates(self, xs, rates, sr_out):
-        """ragged() for clips of more than one input rate: one resampling launch over per-clip filter rows, then the two
-        peak launches.  The clip descriptors, the filter rows and every clip's row index go up as one buffer, once per
-        mix; the tap bank is kept on the device per tuple of distinct rates."""
-        tab = ragged_clip_tables([int(np.prod(x.shape)) for x in xs], rates, sr_out, check_mel=False)
-        n = len(xs)
-        distinct = tuple(dict.fromkeys(rates))
-        bk = (sr_out,) + distinct
-        if bk not in self._banks:
-            bank, rows, _ = rate_tables(distinct, sr_out)
-            self._banks[bk] = (torch.from_numpy(bank).to(self.device), rows)
-        bank, rows = self._banks[bk]
-        key = (tuple(rates), sr_out, tuple(tab["len_in"]))
-        if key not in self._ws:
-            f32 = dict(dtype=torch.float32, device=self.device)
-            x, y = torch.empty(sum(tab["len_in"]), **f32), torch.empty(sum(tab["len_out"]), **f32)
-            rate_of = np.array([distinct.index(r) for r in rates], dtype=np.int32)
-            desc, (clips, rows_dev, rate_of_dev) = upload_tables(
-                [clip_array(src=[x.data_ptr() + 4 * o for o in tab["in_off"]], len_in=tab["len_in"],
-                            dst=[y.data_ptr() + 4 * o for o in tab["out_off"]], len_out=tab["len_out"]), rows, rate_of],
-                self.device)
-            self._ws[key] = dict(x=x, y=y, views=_views(y, tab["out_off"], tab["len_out"]), desc=desc, clips=clips,
-                                 rows=rows_dev, rate_of=rate_of_dev, peak=torch.empty(n, dtype=torch.int32, device=self.device))
-        w = self._ws[key]
-        self._fill(w["x"], xs)
-        L, st = hip.lib(), hip.stream()
-        max_len = max(tab["len_out"])
-        hip.check(L.fh_resample_poly_rates_seg_f32(w["clips"], w["rate_of"], n, max_len, w["rows"], len(distinct),
-                                                   bank.data_ptr() if bank.numel() else 0, bank.numel(), st),
-                  "fh_resample_poly_rates_seg_f32")
-        w["peak"].zero_()
-        hip.check(L.fh_peak_abs_seg_f32(w["clips"], n, max_len, w["peak"].data_ptr(), st), "fh_peak_abs_seg_f32")
-        hip.check(L.fh_peak_scale_seg_f32(w["clips"], n, max_len, w["peak"].data_ptr(), 1.0, st), "fh_peak_scale_seg_f32")
+        _launch("fh_peak_abs_seg_f32", w["clips"], n, max_len, _ptr(w["peak"]))
+        _launch("fh_peak_scale_seg_f32", w["clips"], n, max_len, _ptr(w["peak"]), 1.0)
         return w["y"], w["views"]
 
     @hip.on_device
@@ -447,7 +463,7 @@ class Resampler:
         key = ("host",) + tuple(lens)
         if key not in self._ws:
             y = torch.empty(sum(lens), dtype=torch.float32, device=self.device)
-            self._ws[key] = dict(y=y, views=_views(y, [int(v) for v in np.cumsum([0] + lens[:-1])], lens))
+            self._ws[key] = dict(y=y, views=_views(y, _starts(lens), lens))
         w = self._ws[key]
         self._fill(w["y"], conds)
         return w["y"], w["views"]

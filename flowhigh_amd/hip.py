@@ -68,13 +68,13 @@ class SumJob(C.Structure):
 
 
 class Clip(C.Structure):
-    """fh_clip: one clip of a segment-form front / back end launch (csrc/frontend_seg.hip)."""
+    """fh_clip: one clip of a segment-form front / back end launch (csrc/frontend.hip)."""
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("len_in", C.c_int32), ("len_out", C.c_int32),
                 ("row0", C.c_int32), ("rows", C.c_int32)]
 
 
 class Rate(C.Structure):
-    """fh_rate: the polyphase filter of one input rate of fh_resample_poly_rates_seg_f32 (csrc/frontend_seg.hip)."""
+    """fh_rate: the polyphase filter of one input rate of fh_resample_poly_rates_seg_f32 (csrc/frontend.hip)."""
     _fields_ = [("taps_off", C.c_int32), ("n_taps", C.c_int32), ("up", C.c_int32), ("down", C.c_int32),
                 ("n_pre_remove", C.c_int32)]
 

@@ -547,9 +547,9 @@ int fh_resample_poly_f32(const float* x, const float* taps, float* y, int batch,
                          void* stream);
 
 /* ------------------------------------------------------------------------------------
- * Segment forms of the entries above (flowhigh_amd/csrc/frontend_seg.hip): clips of DIFFERENT lengths in one
+ * Segment forms of the entries above (flowhigh_amd/csrc/frontend.hip as well): clips of DIFFERENT lengths in one
  * launch, the front and back end of a ragged call (generate_many(ends='ragged')).  Every clip gets the bits of the
- * batched entry called on that clip alone (one copy of the arithmetic: csrc/frontend_elem.h).
+ * batched entry called on that clip alone (both are instantiations of one kernel body, which differ in the clip locator).
  *
  * A clip is described by the device int32 [n][2] table (first row, rows) of fh_mel_energy_seg_f32 where only packed
  * rows are involved, or by one fh_clip where it has a pointer or a sample range of its own.  An entry reads only

@@ -1,4 +1,4 @@
-"""GPU: clips of different INPUT RATES in one ragged sequence -- fh_resample_poly_rates_seg_f32 (csrc/frontend_seg.hip),
+"""GPU: clips of different INPUT RATES in one ragged sequence -- fh_resample_poly_rates_seg_f32 (csrc/frontend.hip),
 Resampler.ragged with a rate per clip, generate_many(clips, [sr_0, sr_1, ...]) and the BatchingServer on top of it.
 
 The contract is bitwise: every clip gets what the one-rate entry / generate() gives for that clip alone at its own rate, so

@@ -1,4 +1,4 @@
-"""GPU: the segment forms of the front / back end entries (csrc/frontend_seg.hip) and generate_many(ends='ragged').
+"""GPU: the segment forms of the front / back end entries (fh_*_seg_f32, csrc/frontend.hip) and generate_many(ends='ragged').
 
 The contract is bitwise: every clip of a ragged launch gets what the batched entry gives for that clip alone, so every
 comparison is torch.equal.  Entry tests run five clips of 600 / 1500 / 2401 / 2401 / 3000 samples at 12 kHz (48 kHz lengths

@@ -1,17 +1,13 @@
 #!/bin/bash
 # Build the library of another commit next to the real one, for same-box A/B runs:
 #   tools/build_prev.sh [rev = HEAD]  ->  tools/abl/prev.so ; run anything against it with FH_LIB_PATH=...
-# (sources of that revision are checked out to a scratch directory under /tmp; the working tree is not touched)
+# (sources of that revision are checked out to a temporary directory and built by that revision's own build.py, so
+# every file gets the flags it had there -- the per-source ones included; the working tree is not touched)
 set -e
 cd "$(dirname "$0")/.."
 rev=${1:-HEAD}
-d=/tmp/fh_prev_src; rm -rf $d; mkdir -p $d/flowhigh_amd $d/include tools/abl
-git archive $rev flowhigh_amd/csrc include | tar -x -C $d
-objs=""
-for f in $d/flowhigh_amd/csrc/*.hip; do
-  /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 -c $f -o $f.o &
-  objs="$objs $f.o"
-done
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tools/abl/prev.so $objs
+d=$(mktemp -d); trap 'rm -rf $d' EXIT; mkdir -p tools/abl
+git archive $rev flowhigh_amd/build.py flowhigh_amd/csrc include | tar -x -C $d
+python3 $d/flowhigh_amd/build.py --force > $d/build.log 2>&1 || { tail -20 $d/build.log; exit 1; }
+cp $d/flowhigh_amd/lib/libflowhigh_hip.so tools/abl/prev.so
 echo tools/abl/prev.so "($rev)"
