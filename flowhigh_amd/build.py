@@ -9,13 +9,14 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "lib" / "libflowhigh_hip.so"
 SOURCES = ["api_common.hip", "conv_mfma.hip", "conv_mfma_bf.hip", "conv_wino.hip", "conv_wino54.hip", "conv_wino54_bf.hip", "amp_fused.hip", "narrow_bf.hip", "act1d.hip", "gemm_mfma.hip", "gemm_bf.hip", "flow_ops.hip", "sum_ops.hip",
-           "attention.hip", "attention_bf.hip", "frontend.hip", "fft.hip", "prior.hip"]
+           "attention.hip", "attention_bf.hip", "attention_band.hip", "attention_bf_band.hip", "frontend.hip", "fft.hip", "prior.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-source extra flags.  The bf16 x 6 kernels keep everything beside their MFMAs one result per lane: the SLP vectoriser
 # would re-pack it into v_pk_*_f32, which stall a bf16 MFMA (conv_wino54_kernel.h)
 # (conv_wino.hip as a whole: its bf16 x 6 instantiations need it for the same reason, and without it the 128 x 256 one spills)
-# (attention_bf.hip: the softmax beside its bf16 MFMAs; 2-3 % at the large shapes, same bits)
-EXTRA_FLAGS = {"conv_wino54_bf.hip": ["-fno-slp-vectorize"], "conv_wino.hip": ["-fno-slp-vectorize"], "attention_bf.hip": ["-fno-slp-vectorize"]}
+# (attention_bf.hip: the softmax beside its bf16 MFMAs; 2-3 % at the large shapes, same bits; attention_bf_band.hip is the same kernel)
+EXTRA_FLAGS = {"conv_wino54_bf.hip": ["-fno-slp-vectorize"], "conv_wino.hip": ["-fno-slp-vectorize"], "attention_bf.hip": ["-fno-slp-vectorize"],
+               "attention_bf_band.hip": ["-fno-slp-vectorize"]}
 # every kernel's resources are read from the compiler's remarks: a kernel that spills more than a few registers fails the build.
 # The conv kernels fill every register they are given; a variant that spills a hundred (it happened three times in round 6: the
 # scheduler hoisting the next tile column's work until the file is full) runs its K loop through scratch.  (Round 6 also found
@@ -23,7 +24,7 @@ EXTRA_FLAGS = {"conv_wino54_bf.hip": ["-fno-slp-vectorize"], "conv_wino.hip": ["
 # fixed at the source, conv_wino_common.h: wino_prefetch_a; the limit here is about speed.)
 RESOURCE_FLAGS = ["-Rpass-analysis=kernel-resource-usage"]
 MAX_SCRATCH_BYTES = 16          # per lane: up to 4 spilled registers (prologue / epilogue values) are tolerated and reported
-HEADERS = ["fh_common.h", "bf16x6.h", "conv_mfma_common.h", "conv_mfma_epilogue.h", "conv_wino_common.h", "conv_wino54_kernel.h", "attention_softmax.h", "gemm_common.h"]
+HEADERS = ["fh_common.h", "bf16x6.h", "conv_mfma_common.h", "conv_mfma_epilogue.h", "conv_wino_common.h", "conv_wino54_kernel.h", "attention_softmax.h", "attention_kernel.h", "attention_bf_kernel.h", "gemm_common.h"]
 
 
 def _deps():

@@ -4,6 +4,7 @@
 // bit wherever their products are exact.  A kernel reads: attn_prologue, its Q fragments, init_streams, its staging loop with
 // per tile (S^T product, softmax_step, O^T product), attn_finish.
 #pragma once
+#include <float.h>
 #include <math.h>
 
 #include "fh_common.h"
@@ -63,6 +64,45 @@ __device__ __forceinline__ AttnBlock attn_prologue(const float* __restrict__ qkv
   return c;
 }
 
+// The band of the banded kernels (BAND): query i reads the keys j with |i - j| <= radius.  Two things follow from it.
+//   The keys [lo, hi) a block's staging loop walks, in 64-key iterations from lo: all of the clip's, or (BAND) the iterations that
+//   hold a key within `radius` of one of the block's `qb` queries.  lo is a multiple of 64, so a tile keeps its absolute index and
+//   with it its stream, (k0 / 32) & 1, whatever the band and the kernel shape; the range is block-uniform (the barriers of the loop
+//   stay outside any divergence, every wave runs the same trip count).
+//   The key mask of softmax_step.  A tile of the range that is out of a query's band is an exact no-op for that query, so a row's
+//   bits depend on its valid keys alone: not on the batch, the kernel shape or the form (batched / segment) of the launch.
+// The full kernels hold the empty AttnBand<false>: their code is what it was before there was a band.
+template <bool BAND>
+struct AttnBand;
+
+template <>
+struct AttnBand<false> {
+  __device__ __forceinline__ AttnBand(const AttnBlock&, int) {}
+  __device__ __forceinline__ int lo() const { return 0; }
+  __device__ __forceinline__ int hi(int n) const { return n; }
+};
+
+template <>
+struct AttnBand<true> {
+  int radius;              // <= the longest clip's rows (clamped by the entry): query + radius cannot overflow
+  int k_lo, k_hi;
+  int q_lo, q_hi;          // the lane's valid keys are [q_lo, q_hi] (and < n)
+  int w_lo, w_hi;          // a tile [k0, k0 + 32) with w_lo <= k0 <= w_hi is inside the band of all 32 queries of the wave's tile
+  __device__ __forceinline__ AttnBand(const AttnBlock& c, int qb, int r) : radius(r) {
+    const int q0 = blockIdx.x * qb;
+    const int first = q0 - r, end = q0 + qb + r;
+    k_lo = (first > 0 ? first : 0) / 64 * 64;
+    k_hi = end < c.n ? end : c.n;
+    q_lo = c.qi - r;
+    q_hi = c.qi + r;
+    const int qw0 = __builtin_amdgcn_readfirstlane(c.qi - c.l31);        // first query of the wave's tile (wave-uniform)
+    w_lo = qw0 + 31 - r;
+    w_hi = qw0 + r - 31;
+  }
+  __device__ __forceinline__ int lo() const { return k_lo; }
+  __device__ __forceinline__ int hi(int) const { return k_hi; }
+};
+
 template <int NS>
 __device__ __forceinline__ void init_streams(Stream (&st)[NS]) {
 #pragma unroll
@@ -79,9 +119,17 @@ __device__ __forceinline__ void init_streams(Stream (&st)[NS]) {
 // Online softmax in base 2 (scores arrive multiplied by scale * log2(e): one v_exp_f32 per probability instead of the libm
 // expf's ~10 instructions -- matrix and vector instructions share the fp32 ALUs, so every one of the ~420 vector instructions
 // per tile cost matrix time: round 6).
-__device__ __forceinline__ void softmax_step(Stream& S, f32x16& s, int k0, int n, int lh, float scale) {
+// BAND: a key is valid for the lane's query iff key < n and it is within the band.  A tile inside the band of all 32 queries of
+// the wave and below n takes the unmasked path (wave-uniform).  A lane may meet a tile -- its first one too -- in which none of its
+// keys is valid: that tile leaves m and l as they are, gives p = 0 and multiplies o by exactly 1 (by 0 while m is still -inf: o is
+// still 0 then).
+template <bool BAND>
+__device__ __forceinline__ void softmax_step(Stream& S, f32x16& s, int k0, int n, int lh, float scale, const AttnBand<BAND>& band) {
   float mx = -INFINITY;
-  if (k0 + 32 <= n) {                              // (whole tile: no key mask -- wave-uniform)
+  bool whole;
+  if constexpr (BAND) whole = k0 + 32 <= n && k0 >= band.w_lo && k0 <= band.w_hi;
+  else whole = k0 + 32 <= n;
+  if (whole) {                                     // (whole tile: no key mask -- wave-uniform)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       s[r] = __fmul_rn(s[r], scale);
@@ -91,18 +139,23 @@ __device__ __forceinline__ void softmax_step(Stream& S, f32x16& s, int k0, int n
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      const float v = key < n ? __fmul_rn(s[r], scale) : -INFINITY;
+      bool valid;
+      if constexpr (BAND) valid = key < n && key >= band.q_lo && key <= band.q_hi;
+      else valid = key < n;
+      const float v = valid ? __fmul_rn(s[r], scale) : -INFINITY;
       s[r] = v;
       mx = fmaxf(mx, v);
     }
   }
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  const float m_new = fmaxf(S.m, mx);            // finite: every tile has >= 1 valid key
-  const float corr = __builtin_amdgcn_exp2f(S.m - m_new);        // exp2(-inf) = 0 on the first tile
+  const float m_new = fmaxf(S.m, mx);            // finite: every tile has >= 1 valid key (BAND: per lane it may have none)
+  // (BAND, no valid key so far: exp2(-inf - -inf) would be NaN; against a finite number every exponent below is exp2(-inf) = 0)
+  const float m_ref = BAND ? fmaxf(m_new, -FLT_MAX) : m_new;
+  const float corr = __builtin_amdgcn_exp2f(S.m - m_ref);        // exp2(-inf) = 0 on the first tile
   float psum = 0.f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const float p = __builtin_amdgcn_exp2f(s[r] - m_new);
+    const float p = __builtin_amdgcn_exp2f(s[r] - m_ref);
     s[r] = p;
     psum += p;
   }
@@ -172,14 +225,20 @@ __device__ __forceinline__ void attn_finish(Stream (&st)[3 - SPLIT], const AttnB
   }
 }
 
-// The launch both forms share: the base-2 scale and the rule that picks the kernel shape (4 waves per block either way).
+// The launch both forms share: the base-2 scale and the rule that picks the kernel shape (4 waves per block either way).  The banded
+// kernels take one argument more, the radius (`band`): same grid, same threshold.
 using AttnKernel = void (*)(const float* qkv, float* out, int n, int heads, float scale, const int* seg);
 
-static inline void launch_attention(AttnKernel split1, AttnKernel split2, const float* qkv, float* out, const int* seg, int batch,
-                                    int n, int heads, float scale, void* stream) {
+template <typename Kernel, typename... Band>
+static inline void launch_attention(Kernel split1, Kernel split2, const float* qkv, float* out, const int* seg, int batch,
+                                    int n, int heads, float scale, void* stream, Band... band) {
   scale *= 1.44269504088896340736f;        // the kernel's softmax runs in base 2: exp(x) = exp2(x log2(e))
   const bool large = (long long)fh_cdiv(n, 128) * heads * batch >= 512;
   const dim3 grid(fh_cdiv(n, large ? 128 : 64), heads, batch);      // queries per block: 32 WAVES / SPLIT
-  const AttnKernel kernel = large ? split1 : split2;
-  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, qkv, out, n, heads, scale, seg);
+  const Kernel kernel = large ? split1 : split2;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, qkv, out, n, heads, scale, seg, band...);
 }
+
+// The banded entries' radius as the kernels take it: clamped to the (longest) clip's rows -- every key is within n - 1 of every
+// query, so the band is the same, and query + radius stays far from INT_MAX.
+static inline int attn_clamp_radius(int radius, int n) { return radius < n ? radius : n; }

@@ -52,7 +52,7 @@ def pack_geglu(w, b):
 
 
 class FlowNet:
-    def __init__(self, sd, device, depth=2, heads=16, dim_head=64, store=None, bf=False, attn_form="f32"):
+    def __init__(self, sd, device, depth=2, heads=16, dim_head=64, store=None, bf=False, attn_form="f32", attn_window=None):
         if dim_head != 64:
             raise NotImplementedError("dim_head must be 64")
         self.device = hip.norm_device(device)
@@ -71,6 +71,12 @@ class FlowNet:
         self.attn_form = resolve_attn_form(attn_form)
         self._attn, self._attn_seg = (("fh_attention_bf16x6_f32", "fh_attention_bf16x6_seg_f32") if self.attn_form == "bf16x6"
                                       else ("fh_attention_f32", "fh_attention_seg_f32"))
+        # attn_window: None (full attention: the pair above, as always) | W >= 0: frame i attends to the frames j of its clip with
+        # |i - j| <= W (frames of 10 ms: 500 = +-5 s) -- the banded pair of the same form, with W as their radius
+        from .planner import resolve_attn_window
+        self.attn_window = resolve_attn_window(attn_window)
+        self._attn_band, self._attn_band_seg = (self._attn.replace("_f32", "_band_f32"), self._attn_seg.replace("_seg_f32", "_band_seg_f32"))
+        self._radius = None if self.attn_window is None else min(self.attn_window, 2 ** 31 - 1)      # (the entries take a C int)
         from .planner import use_gemm_bf16x6
         if getattr(W, "form", None) is not None and use_gemm_bf16x6(W.form) != self.bf:
             # (a blob holds the linears in ONE form: asking it for the other would fail on the first missing key)
@@ -234,13 +240,21 @@ class FlowNet:
                 hip.check(L.fh_qknorm_rope_f32(qkv.data_ptr(), lay["gq"].data_ptr(), lay["gk"].data_ptr(),
                                                ws["cos"].data_ptr(), ws["sin"].data_ptr(), batch, n, self.heads, st),
                           "fh_qknorm_rope_f32")
-                hip.check(getattr(L, self._attn)(qkv.data_ptr(), att.data_ptr(), batch, n, self.heads, 10.0, st), self._attn)
+                if self._radius is None:
+                    hip.check(getattr(L, self._attn)(qkv.data_ptr(), att.data_ptr(), batch, n, self.heads, 10.0, st), self._attn)
+                else:
+                    hip.check(getattr(L, self._attn_band)(qkv.data_ptr(), att.data_ptr(), batch, n, self.heads, self._radius, 10.0, st),
+                              self._attn_band)
             else:
                 hip.check(L.fh_qknorm_rope_seg_f32(qkv.data_ptr(), lay["gq"].data_ptr(), lay["gk"].data_ptr(),
                                                    ws["cos"].data_ptr(), ws["sin"].data_ptr(), seg, n_seg, max_n,
                                                    self.heads, st), "fh_qknorm_rope_seg_f32")
-                hip.check(getattr(L, self._attn_seg)(qkv.data_ptr(), att.data_ptr(), seg, n_seg, max_n, self.heads, 10.0, st),
-                          self._attn_seg)
+                if self._radius is None:
+                    hip.check(getattr(L, self._attn_seg)(qkv.data_ptr(), att.data_ptr(), seg, n_seg, max_n, self.heads, 10.0, st),
+                              self._attn_seg)
+                else:
+                    hip.check(getattr(L, self._attn_band_seg)(qkv.data_ptr(), att.data_ptr(), seg, n_seg, max_n, self.heads,
+                                                              self._radius, 10.0, st), self._attn_band_seg)
             self.gemm(att, lay["w_out"], other, M, D, D, R=cur)
             cur, other = other, cur
             hip.check(L.fh_rmsnorm_f32(cur.data_ptr(), g2.data_ptr(), b2.data_ptr(), a.data_ptr(), M, D, st),

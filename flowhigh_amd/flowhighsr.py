@@ -221,9 +221,10 @@ class FLowHigh:
     `FLowHigh` with `audio_enc_dec = MelVoco`, models/flow.py:54-142, models/melvoco.py:16-46)."""
 
     def __init__(self, state_dict, vocoder_config, device="cuda", depth=2, conv_bf16x6=None, store=None, conv_form=None,
-                 attn_form=None):
-        from .planner import resolve_attn_form
+                 attn_form=None, attn_window=None):
+        from .planner import resolve_attn_form, resolve_attn_window
         attn_form = resolve_attn_form(attn_form)          # (a wrong keyword is a ValueError before anything is loaded)
+        attn_window = resolve_attn_window(attn_window)
         device = torch.device(device)
         if device.type != "cuda":
             raise hip.HipError(f"flowhigh_amd runs on MI355X only (got device '{device}'); there is no CPU path")
@@ -246,9 +247,12 @@ class FLowHigh:
             # attn_form: None | 'f32' (default) | 'bf16x6' -- the arithmetic form of the two products of attention
             # (planner.resolve_attn_form; independent of conv_form, touches no weight).  fp32 kernel's time / bf16 x 6 kernel's at
             # (B, N) = (1, 50) (1, 1000) (8, 1000) (32, 1000) (1, 3000) (8, 3000): 1.00 1.02 1.41 1.36 1.23 1.44 (profiles/attention_bf16x6.md)
+            # attn_window: None (default: full attention, the reference's) | W >= 0 -- frame i attends to the frames j of its clip with
+            # |i - j| <= W.  The unit is frames of 10 ms: attn_window=500 is +-5 s.  O(N W) instead of O(N^2) for long clips
+            # (planner.resolve_attn_window; touches no weight, no part of a blob's format tag; profiles/attention_band.md)
             from .planner import resolve_conv_form, use_gemm_bf16x6
             self.net = FlowNet(state_dict, device, depth=depth, store=store, bf=use_gemm_bf16x6(resolve_conv_form(conv_form, conv_bf16x6)[0]),
-                               attn_form=attn_form)
+                               attn_form=attn_form, attn_window=attn_window)
             # conv_form: the arithmetic form of the vocoder's convs, 'auto' | 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6'
             # (planner.resolve_conv_form; None: FH_CONV_FORM / the older switches, else 'auto'.  conv_bf16x6: the boolean keyword
             # of rounds 2-5.)  'auto' = the default form, checked once against the direct form through THESE weights when the
@@ -268,6 +272,11 @@ class FLowHigh:
     @property
     def attn_form(self):
         return self.net.attn_form
+
+    @property
+    def attn_window(self):
+        """None (full attention) or the band's radius in frames (10 ms each): frame i attends to |i - j| <= attn_window."""
+        return self.net.attn_window
 
     def probe_conv_form(self, state_dict, frames=20, limit=None):
         """The load-time estimate behind conv_form='auto': the vocoder in its default form against the direct form (no Winograd
@@ -350,18 +359,22 @@ class FlowHighSR:
         pkg = _load_checkpoint(path)
         if strict:
             check_state_dict_keys(pkg['model'], self.flowhigh.vocoder_config)
-        self.flowhigh = FLowHigh(pkg['model'], self.flowhigh.vocoder_config, self.device, attn_form=self.flowhigh.attn_form)
+        self.flowhigh = FLowHigh(pkg['model'], self.flowhigh.vocoder_config, self.device, attn_form=self.flowhigh.attn_form,
+                                 attn_window=self.flowhigh.attn_window)
         return pkg
 
     @classmethod
-    def from_local(cls, ckpt_dir, device='cuda', conv_form=None, attn_form=None, **kwargs) -> 'FlowHighSR':
+    def from_local(cls, ckpt_dir, device='cuda', conv_form=None, attn_form=None, attn_window=None, **kwargs) -> 'FlowHighSR':
         """from_local of the reference (flowhighsr.py:110-137) + conv_form = 'auto' (default) | 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6': the
         arithmetic form of the vocoder's convs (planner.resolve_conv_form; the environment's
         FH_CONV_FORM overrides nothing a caller passes here); attn_form = None | 'f32' (default) | 'bf16x6': the form of the two
-        products of attention (planner.resolve_attn_form; no part of a weight blob)."""
-        from .planner import resolve_attn_form, resolve_conv_form
+        products of attention (planner.resolve_attn_form; no part of a weight blob); attn_window = None (default: full attention, as
+        the reference) | W >= 0: every frame attends to the frames within W of it, in frames of 10 ms -- attn_window=500 is +-5 s
+        (planner.resolve_attn_window; no part of a weight blob either)."""
+        from .planner import resolve_attn_form, resolve_attn_window, resolve_conv_form
         form, form_auto = resolve_conv_form(conv_form)
         attn_form = resolve_attn_form(attn_form)
+        attn_window = resolve_attn_window(attn_window)
         ckpt_dir = Path(ckpt_dir)
         dev = device if torch.device(device).type == 'cuda' else 'cuda'        # the reference always .cuda()s
         # A weight blob next to the checkpoints (python -m flowhigh_amd.convert <ckpt_dir>; FH_BLOB = another path, FH_BLOB=0 =
@@ -385,21 +398,26 @@ class FlowHighSR:
                 weights.WeightStore.why = why
             if store is not None:
                 try:
-                    return cls(flowhigh=FLowHigh(None, store.cfg, dev, store=store, conv_form=form, attn_form=attn_form), **kwargs)
+                    return cls(flowhigh=FLowHigh(None, store.cfg, dev, store=store, conv_form=form, attn_form=attn_form, attn_window=attn_window),
+                               **kwargs)
                 except (RuntimeError, KeyError, ValueError) as e:          # a damaged or stale blob must not stop the load
                     weights.WeightStore.why = f"{type(e).__name__}: {e}"
             import logging
             logging.getLogger("flowhigh_amd").warning("weight blob %s not used (%s): reading the checkpoints", blob, weights.WeightStore.why)
         sd, cfg = read_checkpoints(ckpt_dir)
-        return cls(flowhigh=FLowHigh(sd, cfg, dev, conv_form="auto" if form_auto else form, attn_form=attn_form), **kwargs)
+        return cls(flowhigh=FLowHigh(sd, cfg, dev, conv_form="auto" if form_auto else form, attn_form=attn_form, attn_window=attn_window),
+                   **kwargs)
 
     @classmethod
-    def from_pretrained(cls, device='cuda', conv_form=None, attn_form=None, **kwargs) -> 'FlowHighSR':
+    def from_pretrained(cls, device='cuda', conv_form=None, attn_form=None, attn_window=None, **kwargs) -> 'FlowHighSR':
+        """from_local on the published checkpoint.  attn_window = None (full attention) | W >= 0 frames of 10 ms (from_local)."""
+        from .planner import resolve_attn_window
+        attn_window = resolve_attn_window(attn_window)          # (a wrong keyword is a ValueError before anything is fetched)
         from huggingface_hub import hf_hub_download
         for fpath in ["FLowHigh_basic_400k.json", "bigvgan_48khz_256band.json",
                       "FLowHigh_basic_400k.pt", "bigvgan_48khz_256band.pt"]:
             local_path = hf_hub_download(repo_id=REPO_ID, filename=fpath)
-        return cls.from_local(Path(local_path).parent, device, conv_form=conv_form, attn_form=attn_form, **kwargs)
+        return cls.from_local(Path(local_path).parent, device, conv_form=conv_form, attn_form=attn_form, attn_window=attn_window, **kwargs)
 
     # ---- host pre-step (flowhighsr.py:59-86) -----------------------------------------------------
     def _upload(self, t):

@@ -126,6 +126,8 @@ _SIGS = {
     "fh_sum_multi_f32": [_P, _I, C.c_longlong, _P],
     "fh_attention_seg_f32": [_P, _P, _P, _I, _I, _I, _F, _P],
     "fh_attention_bf16x6_seg_f32": [_P, _P, _P, _I, _I, _I, _F, _P],
+    "fh_attention_band_seg_f32": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
+    "fh_attention_bf16x6_band_seg_f32": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
     "fh_dwconv_gelu_res_seg_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "fh_qknorm_rope_seg_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "fh_gemm_f32": [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _F, _I, _P],
@@ -137,6 +139,8 @@ _SIGS = {
     "fh_qknorm_rope_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "fh_attention_f32": [_P, _P, _I, _I, _I, _F, _P],
     "fh_attention_bf16x6_f32": [_P, _P, _I, _I, _I, _F, _P],
+    "fh_attention_band_f32": [_P, _P, _I, _I, _I, _I, _F, _P],
+    "fh_attention_bf16x6_band_f32": [_P, _P, _I, _I, _I, _I, _F, _P],
     "fh_rfft2048_f32": [_P, _P, _P, _I, _I, _P],
     "fh_irfft2048_f32": [_P, _P, _P, _I, _P],
     "fh_frame_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

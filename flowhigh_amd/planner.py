@@ -91,6 +91,22 @@ def resolve_attn_form(attn_form=None):
     return attn_form
 
 
+# ---- how far attention looks: a constructor keyword beside attn_form (it touches no weight either) -------------------------------
+#   None      full attention, the reference's: every frame of a clip attends to every other one (the default)
+#   W >= 0    a band: frame i attends to the frames j of its clip with |i - j| <= W.  The unit is frames of the transformer, 10 ms
+#             each: attn_window=500 is +-5 s.  Cost O(N W) instead of O(N^2) per clip of N frames; a window that spans the clip
+#             gives the bits of full attention (the fh_attention_*band* entries, attention_softmax.h: AttnBand)
+def resolve_attn_window(attn_window=None):
+    """-> None (full attention, the default) or the band's radius in frames (10 ms each) as an int >= 0.  A keyword only, no
+    environment switch."""
+    if attn_window is None:
+        return None
+    import numbers
+    if isinstance(attn_window, bool) or not isinstance(attn_window, numbers.Integral) or attn_window < 0:
+        raise ValueError(f"attn_window must be None (full attention) or an int >= 0 (frames, 10 ms each), got {attn_window!r}")
+    return int(attn_window)
+
+
 def _wino_on(form):
     """Winograd kernels allowed?  form None: the environment (FH_WINO=0 / FH_CONV_FORM=direct / direct_bf16x6 switch them off)."""
     return (resolve_conv_form()[0] if form is None else form) not in DIRECT_FORMS

@@ -460,6 +460,18 @@ int fh_attention_seg_f32(const float* qkv, float* out, const int* seg, int n_seg
 /* fh_attention_seg_f32 in the bf16 x 6 form (the key mask of attend.py:127-128). */
 int fh_attention_bf16x6_seg_f32(const float* qkv, float* out, const int* seg, int n_seg, int max_n, int heads,
                                 float scale, void* stream);
+/* Banded attention (attn_window = radius, in frames): the four entries above with a band.  Query i of a clip of n rows reads
+ * the keys j with 0 <= j < n and |i - j| <= radius; in the seg form i and j count from the clip's first row.  radius >= 0; any
+ * radius >= n - 1 (INT_MAX too) is full attention and gives the bits of the full entry of the same form.  Cost O(n radius): a block
+ * walks only the 64-key iterations that hold a key of its queries' bands.  A clip gives the same bits alone, inside any batch, and
+ * in the seg form.  Arguments and checks of the full entries otherwise; qkv and out must be 16-byte aligned in both forms.
+ * (The reference has no band: this is the mask sim.masked_fill(|i - j| > radius, -max) before the softmax of attend.py:131.) */
+int fh_attention_band_f32(const float* qkv, float* out, int batch, int n, int heads, int radius, float scale, void* stream);
+int fh_attention_band_seg_f32(const float* qkv, float* out, const int* seg, int n_seg, int max_n, int heads, int radius,
+                              float scale, void* stream);
+int fh_attention_bf16x6_band_f32(const float* qkv, float* out, int batch, int n, int heads, int radius, float scale, void* stream);
+int fh_attention_bf16x6_band_seg_f32(const float* qkv, float* out, const int* seg, int n_seg, int max_n, int heads, int radius,
+                                     float scale, void* stream);
 int fh_dwconv_gelu_res_seg_f32(const float* x, const float* w, const float* bias, float* y, const int* seg,
                                int n_seg, int max_n, int dim, int ksz, void* stream);
 int fh_qknorm_rope_seg_f32(float* qkv, const float* gq, const float* gk, const float* cos_t,

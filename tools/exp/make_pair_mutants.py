@@ -5,7 +5,7 @@ Per kernel (gemm = gemm_bf.hip, narrow = narrow_bf.hip, w43 = conv_wino.hip's BF
   <kernel>_pair_<ab>   the MFMA of pair (activation piece a, weight piece b) gets a zero activation operand (hh hm mh hl lh mm)
   <kernel>_split_l0    the device split writes l = 0
   <kernel>_split_trunc the device split truncates to bf16 instead of rounding to nearest even
-The attention kernel (attention_bf.hip) has two products, twelve pair MFMAs: attn_qk_pair_<ab> ((K piece, Q piece), the K operand
+The attention kernel (attention_bf_kernel.h, the full entries of attention_bf.hip) has two products, twelve pair MFMAs: attn_qk_pair_<ab> ((K piece, Q piece), the K operand
 zeroed), attn_pv_pair_<ab> ((V piece, P piece), the P operand zeroed, both output halves), and one split for all four operands:
 attn_qk_split_l0 / attn_qk_split_trunc.
 The split mutants edit a copy of the shared bf16x6.h next to the kernel's source: only that kernel is built against it.
@@ -91,18 +91,19 @@ def w54(kind, arg):
 
 
 def attn_qk(kind, arg):
-    t = (CSRC / "attention_bf.hip").read_text()
+    t = (CSRC / "attention_bf_kernel.h").read_text()          # (the kernel is in the header, as w54's: the full entries are built against it)
+    files = {"attention_bf.hip": (CSRC / "attention_bf.hip").read_text()}
     if kind == "split":
-        return {"attention_bf.hip": t, **split(arg)}
+        return {**files, "attention_bf_kernel.h": t, **split(arg)}
     pp = ["lh", "hl", "mm", "mh", "hm", "hh"].index(arg)          # kBf16x6SmallFirst as (K piece, Q piece)
     # (a zero the compiler cannot see, as in w43: with a constant zero the SPLIT = 1 kernel of some pairs spills 5 registers)
-    return {"attention_bf.hip": one(t, "        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[c.a],",
+    return {**files, "attention_bf_kernel.h": one(t, "        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[c.a],",
                                     f"        unsigned z = 0u;\n        if (pp == {pp}) asm volatile(\"\" : \"+v\"(z));\n"
                                     f"        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pp == {pp} ? as_bf((u32x4){{z, z, z, z}}) : kf[c.a],")}
 
 
 def attn_pv(kind, arg):
-    t = (CSRC / "attention_bf.hip").read_text()
+    t = (CSRC / "attention_bf_kernel.h").read_text()
     pp = ["lh", "hl", "mm", "mh", "hm", "hh"].index(arg)          # kBf16x6SmallFirst as (V piece, P piece)
     t = one(t, "        S.o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v0[c.a],",
             f"        unsigned z = 0u;\n        if (pp == {pp}) asm volatile(\"\" : \"+v\"(z));\n"
@@ -110,7 +111,7 @@ def attn_pv(kind, arg):
     for v in ("v0", "v1"):
         t = one(t, f"__builtin_amdgcn_mfma_f32_32x32x16_bf16({v}[c.a], as_bf(pq[c.b]),",
                 f"__builtin_amdgcn_mfma_f32_32x32x16_bf16({v}[c.a], pp == {pp} ? as_bf((u32x4){{z, z, z, z}}) : as_bf(pq[c.b]),")
-    return {"attention_bf.hip": t}
+    return {"attention_bf.hip": (CSRC / "attention_bf.hip").read_text(), "attention_bf_kernel.h": t}
 
 
 KERNELS = {"gemm": (gemm, "gemm_bf.hip"), "narrow": (narrow, "narrow_bf.hip"), "w43": (w43, "conv_wino.hip"),
