@@ -12,7 +12,7 @@ from pathlib import Path
 
 from . import weights
 from .flow import FlowNet
-from .flowhighsr import CKPT_FILES, read_checkpoints, weights_conv_form
+from .flowhighsr import CKPT_FILES, detect_architecture, read_checkpoints, weights_conv_form
 from .vocoder import Vocoder
 
 
@@ -32,6 +32,10 @@ def convert(ckpt_dir, blob=None, conv_form=None, probe=False):
     blob = Path(blob) if blob else ckpt_dir / weights.BLOB_NAME
     t0 = time.time()
     sd, cfg = read_checkpoints(ckpt_dir)
+    if detect_architecture(sd) != "transformer":
+        # (weight blobs hold the transformer backbone; from_local reads such a checkpoint from its files)
+        raise NotImplementedError(f"{ckpt_dir}: a checkpoint of the {detect_architecture(sd)} backbone: weight blobs are made for the "
+                                  "transformer backbone only; FlowHighSR.from_local reads this checkpoint from its files")
     t1 = time.time()
     form = weights_conv_form() if conv_form in (None, "auto") else conv_form
     if probe:
@@ -89,6 +93,9 @@ if __name__ == "__main__":
         print("\n".join(bad) if bad else "blob verified: sources, tensor digest and every tensor match a fresh packing")
         sys.exit(1 if bad else 0)
     form = next((f.split("=", 1)[1] for f in flags if f.startswith("--form=")), None)
-    r = convert(*args[:2], conv_form=form, probe="--probe" in flags)
+    try:
+        r = convert(*args[:2], conv_form=form, probe="--probe" in flags)
+    except NotImplementedError as e:
+        sys.exit(str(e))
     print(f"{r['blob']}: conv form {r['form']}, {r['tensors']} tensors, {r['bytes'] / 2 ** 20:.1f} MiB "
           f"(checkpoints read in {r['read_s']:.1f} s, packed in {r['pack_s']:.1f} s, written in {r['write_s']:.1f} s)")

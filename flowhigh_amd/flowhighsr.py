@@ -43,16 +43,18 @@ def weights_conv_form():
     return resolve_conv_form()[0]
 
 
-def read_checkpoints(ckpt_dir):
+def read_checkpoints(ckpt_dir, architecture=None):
     """(state dict with the wrapper's keys, vocoder JSON) from the reference's three checkpoint files: weight norm folded
-    (init_vocoder.py:13-17), key sets checked as load_state_dict(strict=True) would (flowhighsr.py:135)."""
+    (init_vocoder.py:13-17), key sets checked as load_state_dict(strict=True) would (flowhighsr.py:135).
+    architecture: None = the backbone the model file's keys show (detect_architecture), else the one they must be of."""
     ckpt_dir = Path(ckpt_dir)
     cfg = json.loads((ckpt_dir / "bigvgan_48khz_256band.json").read_text())
     gen = _load_checkpoint(ckpt_dir / "bigvgan_48khz_256band.pt")['generator']
     sd = {VOC + k: v for k, v in fold_weight_norm(gen).items()}            # init_vocoder.py:13-17
     model = _load_checkpoint(ckpt_dir / "FLowHigh_basic_400k.pt")['model']
     check_state_dict_keys(sd, cfg, only_prefix=VOC)                        # vocoder.load_state_dict (init_vocoder.py:16)
-    check_state_dict_keys(model, cfg)                                      # load_state_dict(strict=True), flowhighsr.py:135
+    # load_state_dict(strict=True), flowhighsr.py:135
+    check_state_dict_keys(model, cfg, architecture=resolve_architecture(architecture, model))
     sd.update(model)                                                       # wrapper checkpoint wins
     return sd, cfg
 _CFM_METHODS = ("basic_cfm", "independent_cfm_adaptive", "independent_cfm_constant", "independent_cfm_mix")
@@ -104,14 +106,46 @@ def _load_checkpoint(path):
         return torch.load(str(path), map_location='cpu', weights_only=False)
 
 
-def expected_state_keys(vocoder_cfg, depth=2):
+# the vector field's backbone (the reference's FLowHigh(architecture=), models/flow.py:74-139): the published checkpoint is a
+# transformer (flow.py: FlowNet); 'convnext' is the reference's second one (convnext.py: ConvNextNet)
+ARCHITECTURES = ("transformer", "convnext")
+CONVNEXT_BLOCKS = 8            # num_layers of the reference's convnext backbone (flow.py:126)
+
+
+def detect_architecture(sd):
+    """The backbone a state dict holds: 'convnext' if it has any `flowhigh.convnext.*` key, else 'transformer'."""
+    from .convnext import is_convnext_state_dict
+    return "convnext" if is_convnext_state_dict(sd) else "transformer"
+
+
+def resolve_architecture(architecture, sd=None):
+    """architecture= of FLowHigh / from_local / load: None = what the keys of `sd` show ('transformer' without a state dict),
+    else one of ARCHITECTURES (anything else is a ValueError)."""
+    if architecture is None:
+        return detect_architecture(sd) if sd is not None else "transformer"
+    if architecture not in ARCHITECTURES:
+        raise ValueError(f"architecture must be None or one of {ARCHITECTURES}, got {architecture!r}")
+    return architecture
+
+
+def expected_state_keys(vocoder_cfg, depth=2, architecture="transformer", blocks=CONVNEXT_BLOCKS):
     """Key set of the reference module's state_dict (SURVEY.md 8a "State-dict contract"): what
-    `load_state_dict(strict=True)` (flowhighsr.py:135, cfm_superresolution.py:125-131) accepts, no more, no less."""
+    `load_state_dict(strict=True)` (flowhighsr.py:135, cfm_superresolution.py:125-131) accepts, no more, no less.
+    architecture='convnext': the module built with that backbone (flow.py:124-139; `depth` is then unused, `blocks` is the
+    reference's 8): the same keys without any `transformer.*` one, the blocks' and `final_layer_norm`'s instead."""
+    resolve_architecture(architecture)
     fh = "flowhigh."
     keys = [fh + k for k in ("null_cond", "sinu_pos_emb.0.weights", "sinu_pos_emb.1.weight", "sinu_pos_emb.1.bias",
                              "to_embed.weight", "to_embed.bias", "conv_embed.dw_conv1d.0.weight",
                              "conv_embed.dw_conv1d.0.bias", "transformer.rotary_emb.inv_freq",
                              "transformer.final_norm.gamma", "to_pred.weight")]
+    if architecture == "convnext":
+        from .convnext import block_keys
+        keys = [k for k in keys if not k.startswith(fh + "transformer.")]
+        for i in range(blocks):
+            keys += block_keys(i)
+        keys += [fh + "final_layer_norm.weight", fh + "final_layer_norm.bias"]
+        depth = 0
     for layer in range(depth):
         p = f"{fh}transformer.layers.{layer}."
         for nidx in ("2", "4"):
@@ -143,11 +177,15 @@ def expected_state_keys(vocoder_cfg, depth=2):
     return keys
 
 
-def check_state_dict_keys(sd, vocoder_cfg, depth=2, only_prefix=None):
-    """load_state_dict(strict=True) semantics on the key set: missing AND unexpected keys raise RuntimeError."""
-    want = expected_state_keys(vocoder_cfg, depth)
+def check_state_dict_keys(sd, vocoder_cfg, depth=2, only_prefix=None, architecture="transformer", skip_prefix=None):
+    """load_state_dict(strict=True) semantics on the key set: missing AND unexpected keys raise RuntimeError.
+    skip_prefix: keys under it, wanted or present, are left out of the comparison."""
+    want = expected_state_keys(vocoder_cfg, depth, architecture)
     if only_prefix is not None:
         want = [k for k in want if k.startswith(only_prefix)]
+    if skip_prefix is not None:
+        want = [k for k in want if not k.startswith(skip_prefix)]
+        sd = [k for k in sd if not k.startswith(skip_prefix)]
     have = set(sd)
     missing = [k for k in want if k not in have]
     wset = set(want)
@@ -221,10 +259,22 @@ class FLowHigh:
     `FLowHigh` with `audio_enc_dec = MelVoco`, models/flow.py:54-142, models/melvoco.py:16-46)."""
 
     def __init__(self, state_dict, vocoder_config, device="cuda", depth=2, conv_bf16x6=None, store=None, conv_form=None,
-                 attn_form=None, attn_window=None):
+                 attn_form=None, attn_window=None, architecture=None):
         from .planner import resolve_attn_form, resolve_attn_window
+        # architecture: None (what the state dict's keys show; a weight blob holds a transformer) | 'transformer' | 'convnext'.
+        # A named architecture that the keys contradict fails as load_state_dict(strict=True) does.  The convnext backbone has
+        # no attention: an explicit attn_form='bf16x6' or attn_window= with it is a ValueError
+        named = architecture
+        architecture = resolve_architecture(architecture, state_dict)
+        if architecture == "convnext" and (attn_window is not None or attn_form == "bf16x6"):
+            raise ValueError("attn_form='bf16x6' / attn_window= choose a kernel of the transformer's attention: "
+                             "the convnext backbone has none")
         attn_form = resolve_attn_form(attn_form)          # (a wrong keyword is a ValueError before anything is loaded)
         attn_window = resolve_attn_window(attn_window)
+        if architecture == "convnext" and state_dict is None:
+            raise ValueError("architecture='convnext' needs the checkpoint's state dict: weight blobs hold the transformer backbone only")
+        if named is not None and state_dict is not None and detect_architecture(state_dict) != named:
+            check_state_dict_keys(state_dict, vocoder_config, depth, architecture=named, skip_prefix=VOC)
         device = torch.device(device)
         if device.type != "cuda":
             raise hip.HipError(f"flowhigh_amd runs on MI355X only (got device '{device}'); there is no CPU path")
@@ -235,6 +285,7 @@ class FLowHigh:
         # later: every public entry below runs under hip.on_device (the reference's from_local(ckpt_dir, device),
         # flowhighsr.py:110-137)
         self.device = device = hip.norm_device(device)
+        self.architecture = architecture
         self.vocoder_config = dict(vocoder_config)
         # store: a weights.WeightStore opened on a weight blob (state_dict may then be None), or a recording one (convert.py)
         if store is None or state_dict is not None:
@@ -251,8 +302,13 @@ class FLowHigh:
             # |i - j| <= W.  The unit is frames of 10 ms: attn_window=500 is +-5 s.  O(N W) instead of O(N^2) for long clips
             # (planner.resolve_attn_window; touches no weight, no part of a blob's format tag; profiles/attention_band.md)
             from .planner import resolve_conv_form, use_gemm_bf16x6
-            self.net = FlowNet(state_dict, device, depth=depth, store=store, bf=use_gemm_bf16x6(resolve_conv_form(conv_form, conv_bf16x6)[0]),
-                               attn_form=attn_form, attn_window=attn_window)
+            bf = use_gemm_bf16x6(resolve_conv_form(conv_form, conv_bf16x6)[0])
+            if architecture == "convnext":
+                # (blocks and inner width are read from the state dict; its linears follow conv_form as the transformer's do)
+                from .convnext import ConvNextNet
+                self.net = ConvNextNet(state_dict, device, bf=bf)
+            else:
+                self.net = FlowNet(state_dict, device, depth=depth, store=store, bf=bf, attn_form=attn_form, attn_window=attn_window)
             # conv_form: the arithmetic form of the vocoder's convs, 'auto' | 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6'
             # (planner.resolve_conv_form; None: FH_CONV_FORM / the older switches, else 'auto'.  conv_bf16x6: the boolean keyword
             # of rounds 2-5.)  'auto' = the default form, checked once against the direct form through THESE weights when the
@@ -271,12 +327,12 @@ class FLowHigh:
 
     @property
     def attn_form(self):
-        return self.net.attn_form
+        return getattr(self.net, "attn_form", None)       # (None: the convnext backbone, which has no attention)
 
     @property
     def attn_window(self):
         """None (full attention) or the band's radius in frames (10 ms each): frame i attends to |i - j| <= attn_window."""
-        return self.net.attn_window
+        return getattr(self.net, "attn_window", None)
 
     def probe_conv_form(self, state_dict, frames=20, limit=None):
         """The load-time estimate behind conv_form='auto': the vocoder in its default form against the direct form (no Winograd
@@ -353,26 +409,37 @@ class FlowHighSR:
         return self
 
     @hip.on_device
-    def load(self, path, strict=True):
+    def load(self, path, strict=True, architecture=None):
+        """architecture: None = the backbone the checkpoint's keys show, else the one they must be of (FLowHigh)."""
         path = Path(path)
         assert path.exists()
         pkg = _load_checkpoint(path)
+        arch = resolve_architecture(architecture, pkg['model'])
         if strict:
-            check_state_dict_keys(pkg['model'], self.flowhigh.vocoder_config)
-        self.flowhigh = FLowHigh(pkg['model'], self.flowhigh.vocoder_config, self.device, attn_form=self.flowhigh.attn_form,
-                                 attn_window=self.flowhigh.attn_window)
+            check_state_dict_keys(pkg['model'], self.flowhigh.vocoder_config, architecture=arch)
+        attn = dict(attn_form=self.flowhigh.attn_form, attn_window=self.flowhigh.attn_window) if arch == "transformer" else {}
+        self.flowhigh = FLowHigh(pkg['model'], self.flowhigh.vocoder_config, self.device, architecture=arch, **attn)
         return pkg
 
     @classmethod
-    def from_local(cls, ckpt_dir, device='cuda', conv_form=None, attn_form=None, attn_window=None, **kwargs) -> 'FlowHighSR':
+    def from_local(cls, ckpt_dir, device='cuda', conv_form=None, attn_form=None, attn_window=None, architecture=None,
+                   **kwargs) -> 'FlowHighSR':
         """from_local of the reference (flowhighsr.py:110-137) + conv_form = 'auto' (default) | 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6': the
         arithmetic form of the vocoder's convs (planner.resolve_conv_form; the environment's
         FH_CONV_FORM overrides nothing a caller passes here); attn_form = None | 'f32' (default) | 'bf16x6': the form of the two
         products of attention (planner.resolve_attn_form; no part of a weight blob); attn_window = None (default: full attention, as
         the reference) | W >= 0: every frame attends to the frames within W of it, in frames of 10 ms -- attn_window=500 is +-5 s
-        (planner.resolve_attn_window; no part of a weight blob either)."""
+        (planner.resolve_attn_window; no part of a weight blob either); architecture = None (default: the backbone the
+        checkpoint's keys show) | 'transformer' | 'convnext' (the reference's --architecture; FLowHigh).  Weight blobs hold the
+        transformer backbone only: a convnext checkpoint is always read from its files."""
         from .planner import resolve_attn_form, resolve_attn_window, resolve_conv_form
         form, form_auto = resolve_conv_form(conv_form)
+        if architecture is not None:
+            resolve_architecture(architecture)
+        if architecture == "convnext" and (attn_window is not None or attn_form == "bf16x6"):
+            raise ValueError("attn_form='bf16x6' / attn_window= choose a kernel of the transformer's attention: "
+                             "the convnext backbone has none")
+        explicit_attn = dict(attn_form=attn_form, attn_window=attn_window)
         attn_form = resolve_attn_form(attn_form)
         attn_window = resolve_attn_window(attn_window)
         ckpt_dir = Path(ckpt_dir)
@@ -382,7 +449,7 @@ class FlowHighSR:
         # checkpoint files (content digests) under the current layout switches.  Otherwise the checkpoints are read as always.
         from . import weights
         blob = os.environ.get("FH_BLOB", str(ckpt_dir / weights.BLOB_NAME))
-        if blob != "0" and Path(blob).exists():
+        if blob != "0" and Path(blob).exists() and architecture != "convnext":
             srcs = {f: weights.file_digest(ckpt_dir / f) for f in CKPT_FILES} if os.environ.get("FH_BLOB_VERIFY", "1") != "0" else None
             # ('auto': a blob of the default form is taken as it is -- the probe needs the checkpoint; a blob written by
             # `python -m flowhigh_amd.convert --probe` on a GPU box already holds the form the probe chose)
@@ -404,12 +471,14 @@ class FlowHighSR:
                     weights.WeightStore.why = f"{type(e).__name__}: {e}"
             import logging
             logging.getLogger("flowhigh_amd").warning("weight blob %s not used (%s): reading the checkpoints", blob, weights.WeightStore.why)
-        sd, cfg = read_checkpoints(ckpt_dir)
-        return cls(flowhigh=FLowHigh(sd, cfg, dev, conv_form="auto" if form_auto else form, attn_form=attn_form, attn_window=attn_window),
+        sd, cfg = read_checkpoints(ckpt_dir, architecture)
+        # (the keywords as the caller gave them: with a convnext checkpoint an explicit attention keyword is FLowHigh's ValueError)
+        return cls(flowhigh=FLowHigh(sd, cfg, dev, conv_form="auto" if form_auto else form, architecture=architecture, **explicit_attn),
                    **kwargs)
 
     @classmethod
-    def from_pretrained(cls, device='cuda', conv_form=None, attn_form=None, attn_window=None, **kwargs) -> 'FlowHighSR':
+    def from_pretrained(cls, device='cuda', conv_form=None, attn_form=None, attn_window=None, architecture=None,
+                        **kwargs) -> 'FlowHighSR':
         """from_local on the published checkpoint.  attn_window = None (full attention) | W >= 0 frames of 10 ms (from_local)."""
         from .planner import resolve_attn_window
         attn_window = resolve_attn_window(attn_window)          # (a wrong keyword is a ValueError before anything is fetched)
@@ -417,7 +486,8 @@ class FlowHighSR:
         for fpath in ["FLowHigh_basic_400k.json", "bigvgan_48khz_256band.json",
                       "FLowHigh_basic_400k.pt", "bigvgan_48khz_256band.pt"]:
             local_path = hf_hub_download(repo_id=REPO_ID, filename=fpath)
-        return cls.from_local(Path(local_path).parent, device, conv_form=conv_form, attn_form=attn_form, attn_window=attn_window, **kwargs)
+        return cls.from_local(Path(local_path).parent, device, conv_form=conv_form, attn_form=attn_form, attn_window=attn_window,
+                              architecture=architecture, **kwargs)
 
     # ---- host pre-step (flowhighsr.py:59-86) -----------------------------------------------------
     def _upload(self, t):

@@ -136,6 +136,9 @@ _SIGS = {
     "fh_time_fourier_f32": [_P, _F, _P, _I, _P],
     "fh_dwconv_gelu_res_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "fh_rmsnorm_f32": [_P, _P, _P, _P, _I, _I, _P],
+    "fh_dwconv_ln_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
+    "fh_dwconv_ln_seg_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
+    "fh_gelu_f32": [_P, _P, C.c_longlong, _P],
     "fh_qknorm_rope_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "fh_attention_f32": [_P, _P, _I, _I, _I, _F, _P],
     "fh_attention_bf16x6_f32": [_P, _P, _I, _I, _I, _F, _P],

@@ -208,6 +208,34 @@ def make_flow_state_dict(seed=0, dim=1024, dim_in=256, depth=2, heads=16, dim_he
     return sd
 
 
+def make_convnext_state_dict(seed, dim=1024, dim_in=256, blocks=8):
+    """FLowHigh tensors of the ConvNeXt backbone with reference shapes (flow.py:92-142 with architecture = 'convnext',
+    convnext.py:21-42,73-84): the transformer model's keys without any `transformer.*` one, `convnext.{i}.*` and
+    `final_layer_norm.*` instead.  torch-default inits (uniform +-1/sqrt(fan_in)), but: the norm's scale / shift projections,
+    which the reference initialises to zero weights (the time embedding would then not reach the output), are random with the
+    scale's bias around 1, and `gamma` (ones in the reference) is random in [0.5, 1.5]."""
+    sd = {k: v for k, v in make_flow_state_dict(seed, dim=dim, dim_in=dim_in, depth=0).items()
+          if not k.startswith(FH + "transformer.")}
+
+    def lin(name, out_f, in_f, wscale=1.0, bias_mean=0.0):
+        b = 1.0 / math.sqrt(in_f)
+        sd[name + ".weight"] = _uniform(name + ".weight", (out_f, in_f), b * wscale, seed)
+        sd[name + ".bias"] = _uniform(name + ".bias", (out_f,), b, seed) + bias_mean
+
+    for i in range(blocks):
+        p = f"{FH}convnext.{i}."
+        sd[p + "dwconv.weight"] = _uniform(p + "dwconv.weight", (dim, 1, 7), 1.0 / math.sqrt(7), seed)
+        sd[p + "dwconv.bias"] = _uniform(p + "dwconv.bias", (dim,), 1.0 / math.sqrt(7), seed)
+        lin(p + "norm.scale", dim, dim, wscale=0.3, bias_mean=1.0)
+        lin(p + "norm.shift", dim, dim, wscale=0.3)
+        lin(p + "pwconv1", 3 * dim, dim)                 # intermediate_dim = dim * 3 (flow.py:125)
+        lin(p + "pwconv2", dim, 3 * dim)
+        sd[p + "gamma"] = _uniform(p + "gamma", (dim,), 0.5, seed) + 1.0
+    sd[FH + "final_layer_norm.weight"] = 1.0 + _normal(FH + "final_layer_norm.weight", (dim,), 0.1, seed)
+    sd[FH + "final_layer_norm.bias"] = _normal(FH + "final_layer_norm.bias", (dim,), 0.1, seed)
+    return sd
+
+
 def make_state_dict(cfg=None, seed=0):
     """Full `FLowHigh_basic_400k.pt['model']`-shaped state dict."""
     cfg = cfg or SYNTH_CFG

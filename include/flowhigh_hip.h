@@ -478,6 +478,26 @@ int fh_qknorm_rope_seg_f32(float* qkv, const float* gq, const float* gk, const f
                            const float* sin_t, const int* seg, int n_seg, int max_n, int heads, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * ConvNeXt vector field (models/convnext.py:9-93, flow.py:247-253): csrc/convnext.hip.
+ * --------------------------------------------------------------------------------- */
+/* Depthwise conv + time-conditioned LayerNorm of a ConvNeXtBlock, rows [batch * n, dim] token-major:
+ *   u[r, c] = bias[c] + sum_{j < ksz} w[j, c] * x[r + j - ksz / 2, c]     zero padded at the CLIP's ends
+ *   y[r, c] = (u[r, c] - mean_c u[r]) / sqrt(var_c u[r] + eps) * scale[c] + shift[c]     biased variance over the dim channels
+ * w is tap-major [ksz, dim] as for fh_dwconv_gelu_res_f32, ksz odd and <= 7.  w == NULL: no conv, u = x (bias and ksz are not
+ * read): a plain LayerNorm with scale = its weight and shift = its bias.  dim % 256 == 0, dim <= 4096; every pointer 16-byte
+ * aligned; y must not overlap x.  FH_E_ARG otherwise, before anything is launched.  A block owns 16 consecutive rows of one clip.
+ * The statistics are two passes over values kept in registers (the mean, then the centred values' mean and sum of squares),
+ * summed in an order that does not depend on the row's place: a row's bits are a function of its own ksz input rows, the
+ * same alone, in any batch and in the segment form (seg: the table of fh_dwconv_gelu_res_seg_f32, int32 [n_seg][2] =
+ * (first row, rows); max_n = the longest clip's rows). */
+int fh_dwconv_ln_f32(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
+                     float* y, int batch, int n, int dim, int ksz, float eps, void* stream);
+int fh_dwconv_ln_seg_f32(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
+                         float* y, const int* seg, int n_seg, int max_n, int dim, int ksz, float eps, void* stream);
+/* y[i] = 0.5 x[i] (1 + erf(x[i] / sqrt 2)), i < n: nn.GELU as the GEGLU epilogue of the GEMMs evaluates it.  y may be x. */
+int fh_gelu_f32(const float* x, float* y, long long n, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * STFT framing, post-processing (postprocessing.py:5-41) and peak normalisation.
  * Packed spectrum layout ("P-layout") used between the DFT GEMMs: per frame 33 blocks of
  * 64 floats = 32 real parts then 32 imaginary parts of bins 32*blk .. 32*blk+31 (bins >= 1025
