@@ -4,7 +4,7 @@ Mirrors flowhighsr.py:21-149 of the reference's src/flowhigh/ (`FlowHighSR`: cto
 `generate`, `set_cfm_method`, `from_local`, `from_pretrained`) and the inference half of
 cfm_superresolution.py:94-284 (`ConditionalFlowMatcherWrapper`:
 `sample`, `load`, `device`, `odeint_kwargs`, `sigma`, `cfm_method`).  torchdiffeq's fixed-grid
-euler / midpoint steppers (call site cfm:243) are restated in `_integrate`.
+steppers (call site cfm:243; euler, midpoint, heun2, heun3, rk4) are tableaus in ode.py, run by `_integrate`.
 
 Everything numerical runs in the HIP kernels of libflowhigh_hip.so; this file only moves
 tensors, picks shapes and sequences launches.  There is no CPU path: constructing the model on
@@ -17,6 +17,7 @@ Extensions over the reference (all keyword-only, defaults keep reference behavio
   generate_batch(clips, sr, ...)      B equal-length clips, every per-clip normalisation kept per clip
   upsampling_method='hip'             resample_poly on the device instead of scipy on the host
 """
+import ctypes
 import json
 from pathlib import Path
 
@@ -25,7 +26,7 @@ import os
 import numpy as np
 import torch
 
-from . import hip
+from . import hip, ode
 from .flow import FlowNet
 from .frontend import LogMel, PostProcessor, Resampler, clip_rates
 from .prior import expand_seed, normalize_key
@@ -374,7 +375,7 @@ class FlowHighSR:
         ode_rtol=1e-5,
         use_torchode=False,
         cfm_method='basic_cfm',
-        torchdiffeq_ode_method='midpoint',   # [euler, midpoint]
+        torchdiffeq_ode_method='midpoint',   # ode.ODE_METHODS: [euler, midpoint, heun2, heun3, rk4]
         torchode_method_klass=None,
         cond_drop_prob=0.,
         #
@@ -600,17 +601,20 @@ class FlowHighSR:
         return out
 
     def _integrate(self, y0, cond_mel, batch, n, time_steps, cond_scale=1., ragged=None):
-        """Fixed-grid euler / midpoint (torchdiffeq semantics); y0, cond_mel [B*n, n_mels] on device.
-        Every update `out = base + h * v(x, t)` is the epilogue of the last GEMM of the vector field;
-        with classifier-free guidance v = null + s (cond - null) it is two chained epilogues."""
+        """Fixed-grid explicit Runge-Kutta methods (torchdiffeq semantics; ode.ODE_METHODS); y0, cond_mel [B*n, n_mels] on device.
+        One time step is the records of ode.step_plan(method).  Every update `out = base + h * v(x, t)` is the epilogue of the
+        last GEMM of the vector field (eval_fused; a raw k is the same with alpha = 1 and no base: eval); with classifier-free
+        guidance v = null + s (cond - null) it is two chained epilogues.  The stage arithmetic between the evaluations of heun2,
+        heun3 and rk4 is fh_rk_combine_f32 (combine).  euler and midpoint are one and two eval_fused and nothing else."""
         net = self.flowhigh.net
-        method = self.odeint_kwargs['method']
-        if method not in ('euler', 'midpoint'):
-            raise NotImplementedError(f"ode method '{method}'")
+        plan = ode.step_plan(self.odeint_kwargs['method'])          # (NotImplementedError for a name outside ODE_METHODS)
         net.set_cond(cond_mel, batch, n, ragged=ragged)
         t = torch.linspace(0, 1, time_steps + 1)
         y = y0
         bufs = [torch.empty_like(y0) for _ in range(4)]
+        names = {d for r in plan for d in (r[-1], getattr(r, "dst_a", None)) if d not in (None, "out", "x")}
+        stage = {"x": bufs[2], **{name: torch.empty_like(y0) for name in sorted(names)}}
+        L, st, n_el = hip.lib(), hip.stream(), y0.numel()
 
         def axpy_field(x, tt, out, h, base):           # out = base + h * v(x, tt)
             if cond_scale == 1.:
@@ -621,14 +625,22 @@ class FlowHighSR:
 
         for i in range(time_steps):
             t0, dt = t[i], t[i + 1] - t[i]
-            out = bufs[i % 2]
-            if method == 'euler':
-                axpy_field(y, float(t0), out, float(dt), y)
-            else:
-                half = 0.5 * dt
-                axpy_field(y, float(t0), bufs[2], float(half), y)
-                axpy_field(bufs[2], float(t0 + half), out, float(dt), y)
-            y = out
+            stage["y"], stage["out"] = y, bufs[i % 2]
+            for r in plan:
+                if isinstance(r, ode.Combine):
+                    ks = (ctypes.c_void_p * len(r.ks))(*[stage[k].data_ptr() for k in r.ks])
+                    wa = (ctypes.c_float * len(r.ks))(*r.wa)
+                    wb = None if r.wb is None else (ctypes.c_float * len(r.ks))(*r.wb)
+                    hip.check(L.fh_rk_combine_f32(y.data_ptr(), ks, len(r.ks), float(dt), wa, stage[r.dst_a].data_ptr(), wb,
+                                                  hip.ptr(None if r.dst_b is None else stage[r.dst_b]), n_el, st),
+                              "fh_rk_combine_f32")
+                    continue
+                tt = float(t0) if r.c == 0. else float(t0 + r.c * dt)          # float32, from the linspace grid
+                if isinstance(r, ode.Eval):
+                    axpy_field(stage[r.src], tt, stage[r.dst], 1., None)
+                else:
+                    axpy_field(stage[r.src], tt, stage[r.dst], float(r.weight * dt), stage[r.base])
+            y = stage["out"]
         return y
 
     def _cutoff_bins(self, cond_mel, n_seg, n, seg=None):

@@ -154,6 +154,7 @@ _SIGS = {
     "fh_mel_energy_seg_f32": [_P, _P, _P, _I, _I, _P],
     "fh_mel_splice_seg_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "fh_axpby_f32": [_P, _F, _P, _F, _P, C.c_longlong, _P],
+    "fh_rk_combine_f32": [_P, _P, _I, _F, _P, _P, _P, _P, C.c_longlong, _P],
     "fh_prior_normal_f32": [_P, _P, _P, _I, _I, _I, _P],
     "fh_spec_splice_f32": [_P, _P, _P, _P, _I, _I, _P],
     "fh_istft_ola_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],

@@ -541,6 +541,17 @@ int fh_mel_splice_seg_f32(const float* low, const float* high, const int32_t* cu
 int fh_axpby_f32(const float* x, float a, const float* y, float b, float* out, long long n,
                  void* stream);
 
+/* Stage arithmetic of the explicit Runge-Kutta methods of the sampler (flowhigh_amd/ode.py; heun2, heun3, rk4):
+ *   out_a = y + h * sum_j wa[j] ks[j]     and, where wb and out_b are given (both, or neither),     out_b = y + h * sum_j wb[j] ks[j]
+ * over n floats (n % 4 == 0, every pointer 16-byte aligned); every k and y is read once for both outputs.  ks, wa, wb are HOST
+ * arrays of n_k = 1..4 entries, read at call time into kernel arguments (graph-capturable).  Per element and output:
+ * s = w_j0 k_j0 for the first non-zero weight, then s = fmaf(w_j, k_j, s) in rising j, then out = fmaf(h, s, y); a term whose
+ * weight is exactly 0 is skipped, not multiplied; a row of zeros only is an error.  out_a / out_b may be y or one of ks (an
+ * element depends on its own index alone); out_a == out_b is an error.  No rows, no segment table: the batched and the ragged
+ * layout are the same call. */
+int fh_rk_combine_f32(const float* y, const float* const* ks, int n_k, float h, const float* wa, float* out_a,
+                      const float* wb, float* out_b, long long n, void* stream);
+
 /* eps ~ N(0,1) for the sampler's prior (cfm_superresolution.py:219-236), drawn on the device: counter-based Philox4x32-10 +
  * Box-Muller.  out [rows, d] token-major.  keys: DEVICE uint64 [n_seg][2] = (seed, stream) of every clip.
  * seg NULL: n_seg clips of n rows each; seg = device int32 [n_seg][2] = (first row, rows) as in the *_seg entries, n = longest clip.
