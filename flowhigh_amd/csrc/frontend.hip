@@ -364,7 +364,8 @@ extern "C" int fh_sizeof_rate(void) { return (int)sizeof(fh_rate); }
 extern "C" int fh_frame_f32(const float* audio, const float* window, float* frames, int batch,
                             int len, int n_frames, int nfft, int hop, int pad, int pad_mode,
                             void* stream) {
-  FH_CHECK_ARG(audio && window && frames && batch > 0 && len > 0 && n_frames > 0, "fh_frame_f32: bad args");
+  FH_CHECK_ARG(audio && window && frames && batch > 0 && len > 0 && n_frames > 0 && nfft > 0 && hop > 0 && pad >= 0 &&
+               (pad_mode == 0 || pad_mode == 1), "fh_frame_f32: bad args");
   FH_CHECK_ARG(pad_mode == 1 || pad < len, "fh_frame_f32: reflect pad %d needs len > pad", pad);
   FH_CHECK_ARG(hop * (n_frames - 1) + nfft <= len + 2 * pad, "fh_frame_f32: frames exceed padded signal");
   hipLaunchKernelGGL(frame_kernel<BatchedClips>, dim3(n_frames, batch), dim3(256), 0, (hipStream_t)stream,
@@ -478,7 +479,8 @@ extern "C" int fh_spec_splice_seg_f32(const float* pred, const float* src, const
 extern "C" int fh_istft_ola_f32(const float* frames, const float* window, float* y,
                                 uint32_t* peak_bits, int batch, int n_frames, int len, int nfft,
                                 int hop, void* stream) {
-  FH_CHECK_ARG(frames && window && y && peak_bits && batch > 0 && n_frames > 0 && len > 0, "fh_istft_ola_f32: bad args");
+  FH_CHECK_ARG(frames && window && y && peak_bits && batch > 0 && n_frames > 0 && len > 0 && nfft > 0 && hop > 0,
+               "fh_istft_ola_f32: bad args");
   dim3 grid(fh_cdiv(len, 256), batch);
   hipLaunchKernelGGL(istft_ola_kernel<BatchedClips>, grid, dim3(256), 0, (hipStream_t)stream,
                      BatchedClips{nullptr, y, 0, len, n_frames}, frames, window, peak_bits, nfft, hop);
