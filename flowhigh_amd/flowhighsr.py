@@ -16,6 +16,8 @@ Extensions over the reference (all keyword-only, defaults keep reference behavio
   sample(..., cond_scale=, mel_pp=)    as in the reference, evaluated on the device (no python bin loops)
   generate_batch(clips, sr, ...)      B equal-length clips, every per-clip normalisation kept per clip
   upsampling_method='hip'             resample_poly on the device instead of scipy on the host
+  generate*(..., channels=, level=)   multichannel clips ([C, T] / [T, C], one prior per clip) and output at the input's own
+                                      level instead of 0.99 peak (csrc/level.hip; DESIGN.md "Channels and level")
 """
 import ctypes
 import json
@@ -83,6 +85,84 @@ def resolve_rates(sr, n_clips):
     """sr= of generate_many as one input rate per clip: an int holds for every clip, a sequence gives one positive integer
     rate per clip.  Anything else is a ValueError (a wrong length names both counts), raised before any GPU work."""
     return clip_rates(sr, n_clips)
+
+
+# channels= of generate / generate_batch / generate_many / BatchingServer: the layout of a clip.  None: mono, 1-D or [1, T] (the
+# reference's contract).  'first': [C, T].  'last': [T, C] (gradio, soundfile).  Every channel runs as the mono path runs a clip;
+# the clip's channels share one prior draw and, at level='peak', one peak.
+_CHANNELS = (None, "first", "last")
+MAX_CHANNELS = 8
+# level= of the same entries: what the output is scaled to.  'peak' (default): 0.99 of the clip's own peak, as the reference.
+# 'input': the level of what came in -- the input's band as it was sent plus the generated high band beside it
+_LEVELS = ("peak", "input")
+
+
+def resolve_level(level):
+    if level not in _LEVELS:
+        raise ValueError(f"level must be one of {_LEVELS}, got {level!r}")
+    return level
+
+
+def resolve_channels(audio, channels=None):
+    """One clip as planar [C, T] (a numpy view where the input allows one; dtype and values untouched), 1 <= C <= 8.
+    channels=None: 1-D or [1, T].  'first': [C, T].  'last': [T, C].  A 1-D clip is one channel under every value.
+    Everything else is a ValueError: a 2-D clip without the keyword, more than 8 channels, an empty clip, 0-D or 3-D input."""
+    if channels not in _CHANNELS:
+        raise ValueError(f"channels must be one of {_CHANNELS}, got {channels!r}")
+    if isinstance(audio, torch.Tensor):
+        audio = audio.detach().cpu().numpy()
+    a = np.asarray(audio)
+    if a.ndim == 1:
+        a = a[None]
+    elif a.ndim != 2:
+        raise ValueError(f"a clip is 1-D, or 2-D with channels='first' ([C, T]) or channels='last' ([T, C]); got shape {a.shape}")
+    elif channels is None:
+        if a.shape[0] != 1:
+            raise ValueError(f"a clip of shape {a.shape} needs channels='first' ([C, T]) or channels='last' ([T, C]): "
+                             "without the channels keyword a clip is 1-D or [1, T]")
+    elif channels == "last":
+        a = a.T
+    if a.shape[1] < 1:
+        raise ValueError("empty clip")
+    if a.shape[0] > MAX_CHANNELS:
+        raise ValueError(f"channels={channels!r}: {a.shape[0]} channels, at most {MAX_CHANNELS} (is the layout the other one?)")
+    return a
+
+
+def channel_noise(noise, n_channels):
+    """noise= of one clip of n_channels channels as [C, N, n_mels]: [1, N, n_mels] is shared by the channels (a view), [C, N,
+    n_mels] is one draw per channel.  Any other leading dimension is a ValueError."""
+    if noise.ndim != 3 or noise.shape[0] not in (1, n_channels):
+        raise ValueError(f"noise of shape {tuple(noise.shape)} for a clip of {n_channels} channels: [1, N, n_mels] "
+                         f"(shared) or [{n_channels}, N, n_mels] (one per channel)")
+    return noise.expand(n_channels, -1, -1)
+
+
+def clip_noises(noise, chans):
+    """noise= of a call over clips of chans[i] channels as a list of [C_i, N, n_mels] (channel_noise): a list holds one tensor
+    per clip; a tensor is the one clip's, or [B, N, n_mels] with one shared draw per clip."""
+    if noise is None:
+        return None
+    if isinstance(noise, (list, tuple)):
+        noises = list(noise)
+    elif len(chans) == 1:
+        noises = [noise]
+    else:
+        noises = [noise[i:i + 1] for i in range(noise.shape[0])]
+    if len(noises) != len(chans):
+        raise ValueError(f"one noise tensor per clip: {len(noises)} for {len(chans)} clips")
+    return [channel_noise(z, c) for z, c in zip(noises, chans)]
+
+
+def resolve_clips(clips, channels=None, level="peak"):
+    """The clips of a call, layouts checked (resolve_channels; a ValueError before any GPU work) ->
+      (clips, None)     mono clips at level='peak': the default path takes them (as they came, or [1, T] views)
+      (None, planar)    anything else: float [C_i, T_i] arrays, the int16 rule (max > 1 -> / 32768) applied once per clip."""
+    level = resolve_level(level)
+    planar = [resolve_channels(a, channels) for a in clips]
+    if level == "peak" and all(a.shape[0] == 1 for a in planar):
+        return (clips if channels is None else planar), None
+    return None, [a / 32768.0 if a.max() > 1 else a for a in planar]
 
 
 def reference_prior_draw(n_frames, n_mels=256, generator=None):
@@ -537,6 +617,66 @@ class FlowHighSR:
             return self.resampler(x, sr, target_sampling_rate)
         raise UnboundLocalError(f"cond: unsupported upsampling_method '{self.upsampling_method}'")
 
+    def _prepare_rows(self, rows, sr, ragged=False):
+        """_prepare_cond for the rows of a channels= / level= call (1-D float arrays, one per channel, the int16 rule applied
+        already) -> (cond [R, T48], or with ragged the list of [T48_i] views; gains float32 [R] on the device: the peak p every
+        row was divided by).  A silent row is divided by 1 and has gain 0.  'hip': the peaks stay on the device
+        (fh_channel_peaks_f32); 'scipy': they are the host's np.max(np.abs(.)), uploaded with the rows."""
+        if self.upsampling_method == 'scipy':
+            import scipy.signal
+            conds, peaks = [], []
+            for audio, sr_i in zip(rows, resolve_rates(sr, len(rows)) if ragged else [sr] * len(rows)):
+                cond = scipy.signal.resample_poly(audio, 48000, sr_i)
+                p = np.max(np.abs(cond))
+                peaks.append(p)
+                conds.append(cond / p if p > 0 else cond)
+            gains = self._upload(torch.from_numpy(np.array(peaks, dtype=np.float32)))
+            if ragged:
+                return self.resampler.upload_packed(conds)[1], gains
+            return self._upload(torch.stack([torch.tensor(cond).float() for cond in conds])), gains
+        if self.upsampling_method == 'hip':
+            if ragged:
+                _, views, gains = self.resampler.ragged(rows, sr, 48000, gains=True)
+                return views, gains
+            x = self._upload(torch.from_numpy(np.stack([np.asarray(a, dtype=np.float32) for a in rows])))
+            return self.resampler(x, sr, 48000, gains=True)
+        raise UnboundLocalError(f"cond: unsupported upsampling_method '{self.upsampling_method}'")
+
+    def _level_args(self, chans, level, gains):
+        """The post-processor's gains= and groups= for rows that are chans[i] channels per clip.  level='input': the rows'
+        gains, no groups.  level='peak': every clip is a group; a mono clip among them takes gain 1, which makes its row gain
+        and its group peak the identity (w * 1, fl(q * 1)): it keeps the bits of the default path."""
+        if level != "peak":
+            return dict(gains=gains, groups=None)
+        group = np.repeat(np.arange(len(chans), dtype=np.int32), chans)
+        if 1 in chans:
+            mono = self._upload(torch.from_numpy(np.repeat(np.array(chans) == 1, chans)))
+            gains = gains.masked_fill(mono, 1.0)
+        return dict(gains=gains, groups=self._upload(torch.from_numpy(group)))
+
+    def _generate_rows(self, planar, sr, timestep, noises, keys, generator, level, return_stages=False):
+        """generate_batch for clips of equal length with channels= / level=: planar = float [C_i, T] arrays (resolve_clips),
+        noises = None or one [C_i, N, n_mels] per clip (clip_noises), keys = None or one key per clip.  Every channel is a row of
+        the batch and runs as a mono clip does; the rows of a clip share its prior.  -> [sum C_i, T48] (rows in clip order),
+        with return_stages also the stages of the rows (and their gains)."""
+        chans = [a.shape[0] for a in planar]
+        row_keys = None
+        if keys is not None:
+            noise = None
+            row_keys = [k for k, c in zip(keys, chans) for _ in range(c)]
+        else:
+            if noises is None:                               # one draw per CLIP: the generator moves as for mono clips
+                n = resample_out_len(planar[0].shape[1], 48000, sr) // 480
+                noises = [channel_noise(self._draw_noise(1, n, generator), c) for c in chans]
+            noise = torch.cat(list(noises), 0)
+        cond, gains = self._prepare_rows([row for a in planar for row in a], sr)
+        kw = dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
+        wav = self._sample(cond=cond, time_steps=timestep, cfm_method=self.cfm_method, noise=noise, keys=row_keys, **kw).squeeze(1)
+        out = self.postproc(wav, cond, cond.size(-1), return_cr=return_stages, **self._level_args(chans, level, gains))
+        if return_stages:
+            return out[0], dict(cond=cond, wav=wav.clone(), cr=out[1].clone(), gains=gains)
+        return out
+
     # ---- sampler (cfm_superresolution.py:162-284) ------------------------------------------------
     def _draw_noise(self, batch, n_frames, generator):
         n_mels = self.flowhigh.n_mels
@@ -799,9 +939,30 @@ class FlowHighSR:
     @torch.no_grad()
     @hip.on_device
     def generate_batch(self, clips, sr, target_sampling_rate=48000, timestep=1, *, noise=None,
-                       generator=None, return_stages=False, seed=None, _keys=None):
-        clips = list(clips)
-        keys = _keys if _keys is not None else self._prior_keys(seed, len(clips), generator, noise)
+                       generator=None, return_stages=False, seed=None, _keys=None, channels=None, level='peak'):
+        """B clips of equal length as one batch -> [B, T48], every clip what generate() returns for it alone.
+        channels=, level= (generate): with channels= every clip may have its own number of channels and the result is a list
+        of [C_i, T48]; noise= is then one tensor per clip in a list ([1, N, n_mels] shared by the clip's channels, or
+        [C_i, N, n_mels]), or [B, N, n_mels]: one shared draw per clip."""
+        clips, planar = resolve_clips(list(clips), channels, level)
+        n_clips = len(clips if planar is None else planar)
+        keys = _keys if _keys is not None else self._prior_keys(seed, n_clips, generator, noise)
+        if planar is not None:
+            if target_sampling_rate != 48000:
+                raise NotImplementedError("the mel codec is fixed at 48 kHz")
+            chans = [a.shape[0] for a in planar]
+            out = self._generate_rows(planar, sr, timestep, clip_noises(noise, chans), keys, generator, level, return_stages)
+            if channels is None:
+                return out
+            rows, stages = out if return_stages else (out, None)
+            rows = list(rows.split(chans))
+            return (rows, stages) if return_stages else rows
+        if channels is not None:                 # mono clips given as [1, T]: the default path, the list form of the result
+            out = self.generate_batch(clips, sr, target_sampling_rate, timestep, noise=noise, generator=generator,
+                                      return_stages=return_stages, _keys=keys)
+            rows, stages = out if return_stages else (out, None)
+            rows = [rows[i:i + 1] for i in range(n_clips)]
+            return (rows, stages) if return_stages else rows
         cond = self._prepare_cond(clips, sr, target_sampling_rate)
         kw = dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
         HR_audio = self._sample(cond=cond, time_steps=timestep, cfm_method=self.cfm_method, noise=noise,
@@ -815,7 +976,8 @@ class FlowHighSR:
     @torch.no_grad()
     @hip.on_device
     def generate_many(self, clips, sr, target_sampling_rate=48000, timestep=1, *, noise=None, generator=None,
-                      max_batch=64, streams=None, ragged=None, max_frames=None, seed=None, ends=None):
+                      max_batch=64, streams=None, ragged=None, max_frames=None, seed=None, ends=None, channels=None,
+                      level='peak'):
         """Serving-side entry (the gradio caller of app.py:8-26, many requests at once): clips of ANY lengths,
         int16 or float.  Clips of equal length run as one batch (at most max_batch rows), so every result is
         what generate() returns for that clip alone; the prior noise is drawn in the order of `clips`, as a loop
@@ -841,10 +1003,23 @@ class FlowHighSR:
         same frame count (6000 and 6001 samples at 12 kHz: 50 frames both) share them, so every bucket of one frame
         count runs on the same stream, in order; results do not depend on `streams`.  Measured on a
         mix of 0.5-4 s clips: between -15 % and +40 % of the single-stream time from run to run (the host enqueues
-        ~120 launches per clip and is the bottleneck either way), hence off by default."""
+        ~120 launches per clip and is the bottleneck either way), hence off by default.
+        channels=, level= (generate): every clip may have its own number of channels; the result list then holds one [C_i, T48_i]
+        per clip.  A clip's channels are rows of the same batch or ragged sequence (a clip of C channels costs what C clips
+        cost), share the clip's prior -- noise[i] is [1, N_i, n_mels], or [C_i, N_i, n_mels] for a draw per channel -- and a
+        clip gives the same bits alone, in a batch, in a ragged group and under either `ends`."""
         clips = list(clips)
         ends = resolve_ends(ends)
         rates = resolve_rates(sr, len(clips))
+        clips, planar = resolve_clips(clips, channels, level)
+        chans = None
+        if planar is not None:
+            if target_sampling_rate != 48000:
+                raise NotImplementedError("the mel codec is fixed at 48 kHz")
+            clips, chans = planar, [a.shape[0] for a in planar]
+            if noise is not None:
+                for z, c in zip(noise, chans):
+                    channel_noise(z, c)                  # (a wrong leading dimension: a ValueError before any GPU work)
         keys = self._prior_keys(seed, len(clips), generator, noise)
         lengths = [int(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).shape[-1]) for a in clips]
         if noise is None:
@@ -860,7 +1035,7 @@ class FlowHighSR:
         if ragged and len(set(zip(lengths, rates))) > 1 and target_sampling_rate == 48000:
             try:
                 return self._generate_many_ragged(clips, lengths, rates, timestep, noise, max_frames, keys=keys,
-                                                  frames=[sh[1] for sh in shapes], ends=ends)
+                                                  frames=[sh[1] for sh in shapes], ends=ends, chans=chans, level=level)
             except NotImplementedError as e:
                 # a vocoder configuration whose launch positions cannot be merged: one batch per length (said once)
                 if not getattr(self, "_ragged_fallback_logged", False):
@@ -888,6 +1063,16 @@ class FlowHighSR:
             with torch.cuda.stream(st):
                 for k in range(0, len(idx), max_batch):
                     part = idx[k:k + max_batch]
+                    if chans is not None:                    # (max_batch counts clips: a clip's channels stay in one batch)
+                        part_ch = [chans[i] for i in part]
+                        y = self._generate_rows([clips[i] for i in part], key[1], timestep,
+                                                clip_noises([noise[i] for i in part], part_ch) if keys is None else None,
+                                                [keys[i] for i in part] if keys is not None else None, None, level)
+                        for i, rows in zip(part, y.split(part_ch)):
+                            out[i] = rows.clone()
+                            if st is not main:
+                                out[i].record_stream(main)
+                        continue
                     if keys is not None:
                         prior = dict(_keys=[keys[i] for i in part])
                     else:
@@ -902,8 +1087,10 @@ class FlowHighSR:
                 main.wait_stream(s_)
         return out
 
-    def _generate_many_ragged(self, clips, lengths, rates, timestep, noise, max_frames, keys=None, frames=None, ends="per_clip"):
-        """rates: the input rate of every clip (resolve_rates)."""
+    def _generate_many_ragged(self, clips, lengths, rates, timestep, noise, max_frames, keys=None, frames=None, ends="per_clip",
+                              chans=None, level="peak"):
+        """rates: the input rate of every clip (resolve_rates).  chans (a channels= / level= call): clips are float [C_i, T_i]
+        arrays (resolve_clips) of chans[i] channels, each C_i rows of n frames in its sequence."""
         if max_frames is None:
             max_frames = int(os.environ.get("FH_RAGGED_MAX_FRAMES", "12000"))
         chunk_limit = int(os.environ.get("FH_VOCODER_CHUNK_FRAMES", "6000"))
@@ -912,24 +1099,38 @@ class FlowHighSR:
 
         def prior_of(i):              # one clip on its own: its noise, or its key
             return dict(_keys=[keys[i]]) if keys is not None else dict(noise=noise[i])
+
+        def alone(i):
+            if chans is None:
+                return self.generate_batch([clips[i]], rates[i], 48000, timestep, **prior_of(i)).clone()
+            return self._generate_rows([clips[i]], rates[i], timestep, clip_noises(noise[i], [chans[i]]) if keys is None else None,
+                                       [keys[i]] if keys is not None else None, None, level)
+        width = chans if chans is not None else [1] * len(clips)
         out = [None] * len(clips)
         kw = dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
         # greedy packing in list order; a clip that does not fit a sequence of its own runs through generate()
         groups, cur, tot = [], [], 0
         for i, n in enumerate(frames):
-            if n > max_frames or (chunk_limit > 0 and n > chunk_limit):
-                out[i] = self.generate_batch([clips[i]], rates[i], 48000, timestep, **prior_of(i)).clone()
+            if n * width[i] > max_frames or (chunk_limit > 0 and n > chunk_limit):
+                out[i] = alone(i)
                 continue
-            if cur and tot + n > max_frames:
+            if cur and tot + n * width[i] > max_frames:
                 groups.append(cur)
                 cur, tot = [], 0
             cur.append(i)
-            tot += n
+            tot += n * width[i]
         if cur:
             groups.append(cur)
         for idx in groups:
             if len(idx) == 1:
-                out[idx[0]] = self.generate_batch([clips[idx[0]]], rates[idx[0]], 48000, timestep, **prior_of(idx[0])).clone()
+                out[idx[0]] = alone(idx[0])
+                continue
+            if chans is not None:
+                ys = self._ragged_group_rows([clips[i] for i in idx], [rates[i] for i in idx], timestep,
+                                             [noise[i] for i in idx] if keys is None else None,
+                                             [keys[i] for i in idx] if keys is not None else None, ends, level, kw)
+                for i, y in zip(idx, ys):
+                    out[i] = y
                 continue
             prior = dict(keys=[keys[i] for i in idx]) if keys is not None else dict(noises=[noise[i] for i in idx])
             if ends == "ragged":
@@ -952,6 +1153,36 @@ class FlowHighSR:
                 out[i] = self.postproc(wav, cond[None], cond.shape[0]).clone()
         return out
 
+    def _ragged_group_rows(self, planar, rates, timestep, noises, keys, ends, level, kw):
+        """One ragged group of a channels= / level= call: every channel of every clip is a row of the sequence, the rows of
+        a clip are adjacent and share its prior, and the post-processor gets the rows' gains and (level='peak') their clip as
+        their group.  -> list of [C_i, T48_i], each the bits of _generate_rows on that clip alone."""
+        chans = [a.shape[0] for a in planar]
+        if keys is not None:
+            prior = dict(keys=[k for k, c in zip(keys, chans) for _ in range(c)])
+        else:
+            prior = dict(noises=[z[None] for zs, c in zip(noises, chans) for z in channel_noise(zs, c)])
+        if ends == "ragged":
+            rows = [row for a in planar for row in a]
+            conds, gains = self._prepare_rows(rows, [r for r, c in zip(rates, chans) for _ in range(c)], ragged=True)
+            cond_mel, mels = self.flowhigh.logmel.ragged(conds)
+            wavs = self._sample_ragged(conds, timestep, self.cfm_method, mels=mels, cond_mel=cond_mel, **prior, **kw)
+            packed, _ = self.postproc.ragged(wavs, conds, [c.shape[0] for c in conds], **self._level_args(chans, level, gains))
+            packed = packed.clone()                          # (the caller's own: one copy for the group, handed out as views)
+            out, start, r = [], 0, 0
+            for c in chans:                                  # (a clip's rows are adjacent and of one length)
+                t48 = conds[r].shape[0]
+                out.append(packed[start:start + c * t48].view(c, t48))
+                start, r = start + c * t48, r + c
+            return out
+        prepared = [self._prepare_rows(list(a), rate) for a, rate in zip(planar, rates)]          # (cond [C_i, T48_i], gains [C_i])
+        wavs = self._sample_ragged([row for cond, _ in prepared for row in cond], timestep, self.cfm_method, **prior, **kw)
+        out, r = [], 0
+        for (cond, gains), c in zip(prepared, chans):
+            out.append(self.postproc(torch.cat(list(wavs[r:r + c]), 0), cond, cond.shape[1], **self._level_args([c], level, gains)))
+            r += c
+        return out
+
     def _serve_streams(self, n):
         pool = getattr(self, "_side_streams", None)
         if pool is None or len(pool) < n:
@@ -963,7 +1194,9 @@ class FlowHighSR:
     def generate_from_device(self, x, sr, timestep=1, *, noise=None, seed=None, generator=None):
         """Device-resident variant (no host work, no sync; graph-capturable): x [B, T_in] float32
         low-rate clips already in HBM (|x| <= 1), noise [B, N, n_mels] -> [B, T48].  Same
-        arithmetic as generate_batch with upsampling_method='hip'.  On a prior='device' model `noise` may be left out:
+        arithmetic as generate_batch with upsampling_method='hip'.  Mono clips at 0.99 peak only: channels= and level= are
+        keywords of generate / generate_batch / generate_many (a multichannel clip can go in as its channels, [C, T_in]; they
+        then come back as C independent clips).  On a prior='device' model `noise` may be left out:
         the prior is drawn on the device from seed= (or from keys taken from the generator: _prior_keys); a
         prior='reference' model has no device-side draw and needs `noise`."""
         keys = self._prior_keys(seed, x.shape[0], generator, noise)
@@ -985,12 +1218,24 @@ class FlowHighSR:
         and replayed with a single enqueue (short clips are launch-bound from Python).  Returns a `GraphedGenerate`
         with static buffers `.x` [batch, n_in] and `.noise` [batch * N, n_mels]; fill them and call `.replay()`.
         On a prior='device' model the graph records the prior launch and has `.keys` (device int64 [batch, 2] = the clips'
-        (seed, stream)) in place of `.noise`: a replay draws from the keys that are there."""
+        (seed, stream)) in place of `.noise`: a replay draws from the keys that are there.
+        The captured call is generate_from_device: mono [batch, n_in] clips at 0.99 peak, no channels= or level=."""
         return GraphedGenerate(self, batch, n_in, sr, timestep)
 
     @torch.no_grad()
     @hip.on_device
-    def generate(self, audio, sr: int, target_sampling_rate=48000, timestep=1, *, noise=None, generator=None, seed=None):
+    def generate(self, audio, sr: int, target_sampling_rate=48000, timestep=1, *, noise=None, generator=None, seed=None,
+                 channels=None, level='peak'):
         """One clip, reference contract: returns float32 [1, T48] on the model device.  seed= (prior='device' models): the
-        clip's noise is that of the key (seed, 0), or of a (seed, stream) pair given as [(seed, stream)]."""
-        return self.generate_batch([audio], sr, target_sampling_rate, timestep, noise=noise, generator=generator, seed=seed)
+        clip's noise is that of the key (seed, 0), or of a (seed, stream) pair given as [(seed, stream)].
+        channels = None (default: a mono clip, 1-D or [1, T]; a 2-D clip is then a ValueError) | 'first' ([C, T]) | 'last'
+        ([T, C], what gradio and soundfile hand over), 1 <= C <= 8: returns [C, T48] in every layout.  Each channel runs as a
+        mono clip does (resampled, divided by its own peak p_c, its own cutoff); the channels share ONE prior draw (noise=
+        [1, N, n_mels]; [C, N, n_mels] gives every channel its own) or the clip's one (seed, stream) key, and one final
+        scaling, so the balance between them is kept.  A silent channel comes back as exact zeros.
+        level = 'peak' (default: 0.99 of the clip's peak -- over all its channels --, as the reference) | 'input': the
+        output at the level of the input, w_c * p_c: below the cutoff it is the 48 kHz input itself, not its normalised copy.
+        A mono clip with neither keyword runs what it always ran (DESIGN.md "Channels and level")."""
+        out = self.generate_batch([audio], sr, target_sampling_rate, timestep, noise=noise, generator=generator, seed=seed,
+                                  channels=channels, level=level)
+        return out if channels is None else out[0]

@@ -264,6 +264,9 @@ class _BatchedPost:
     def peak_scale(self, peak):
         _launch("fh_peak_scale_f32", _ptr(self.out), _ptr(peak), self.B, self.out.shape[1], 0.99)
 
+    def row_gain(self, gains):
+        _launch("fh_row_gain_f32", _ptr(self.out), _ptr(gains), self.B, self.out.shape[1])
+
 
 class _SegmentPost:
     """The same launches for n clips of different lengths: w holds the device tables (c_pred, c_src: fh_clip arrays, seg: the
@@ -289,6 +292,9 @@ class _SegmentPost:
     def peak_scale(self, peak):
         _launch("fh_peak_scale_seg_f32", self.clips["src"], self.n, self.max_len, _ptr(peak), 0.99)
 
+    def row_gain(self, gains):
+        _launch("fh_row_gain_seg_f32", self.clips["src"], self.n, self.max_len, _ptr(gains))
+
 
 class PostProcessor:
     def __init__(self, device):
@@ -306,8 +312,21 @@ class PostProcessor:
                                  peak=torch.empty(n, dtype=torch.int32, device=self.device), **more)
         return self._ws[key]
 
-    def _run(self, w, form, rows, n):
-        """The launch sequence of both forms: per-clip cutoff, splice, iSTFT, 0.99 peak.  form: _BatchedPost or _SegmentPost."""
+    def _level_args(self, n, gains, groups):
+        """gains= / groups= of __call__ and ragged, checked: device float32 [n] / int32 [n] of this device."""
+        if gains is None:
+            if groups is not None:
+                raise ValueError("groups= goes with gains=: the joint peak of a group is that of its rows at their own levels")
+            return
+        for name, t, dtype in (("gains", gains, torch.float32), ("groups", groups, torch.int32)):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (n,)
+                                  or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f"{name} must be a contiguous {dtype} [{n}] on {self.device}")
+
+    def _run(self, w, form, rows, n, gains=None, groups=None):
+        """The launch sequence of both forms: per-clip cutoff, splice, iSTFT, 0.99 peak.  form: _BatchedPost or _SegmentPost.
+        gains (float32 [n], every row's input peak): the iSTFT output times its row's gain instead, the signal at the input's
+        level; with groups (int32 [n], non-decreasing) then scaled to 0.99 of the joint peak of every group of rows."""
         hann = _ptr(self.c["hann"])
         for which, spec in (("pred", w["sp"]), ("src", w["ss"])):
             form.frame(which, hann, w["frames"])
@@ -318,28 +337,38 @@ class PostProcessor:
         _irfft(self.c, w["sp"], w["frames"], rows)
         w["peak"].zero_()
         form.istft_ola(w["frames"], hann, w["peak"])
-        form.peak_scale(w["peak"])
+        if gains is None:
+            form.peak_scale(w["peak"])
+            return
+        form.row_gain(gains)
+        if groups is not None:
+            _launch("fh_group_peak_f32", _ptr(w["peak"]), _ptr(gains), _ptr(groups), n)
+            form.peak_scale(w["peak"])
 
     @hip.on_device
-    def __call__(self, pred, src, length, return_cr=False):
-        """pred [B, Tp], src [B, T] -> [B, length]; per-clip cutoff, splice, iSTFT, 0.99 peak."""
+    def __call__(self, pred, src, length, return_cr=False, gains=None, groups=None):
+        """pred [B, Tp], src [B, T] -> [B, length]; per-clip cutoff, splice, iSTFT, 0.99 peak.
+        gains=, groups= (_run): the rows at their inputs' levels, or at 0.99 of their group's joint peak."""
         B, Tp = pred.shape
+        self._level_args(B, gains, groups)
         T = src.shape[1]
         F = min(1 + Tp // HOP, 1 + T // HOP)
         w = self._workspace((B, Tp, T, length), B * F, B)
         out = torch.empty(B, length, dtype=torch.float32, device=self.device)
-        self._run(w, _BatchedPost(pred.contiguous(), src.contiguous(), out, F), B * F, B)
+        self._run(w, _BatchedPost(pred.contiguous(), src.contiguous(), out, F), B * F, B, gains, groups)
         return (out, w["cr"]) if return_cr else out
 
     @hip.on_device
-    def ragged(self, preds, srcs, lengths, return_cr=False):
+    def ragged(self, preds, srcs, lengths, return_cr=False, gains=None, groups=None):
         """preds: list of [Tp_i] (or [1, Tp_i]) vocoder waveforms, srcs: list of [T_i] conditioning clips, lengths: samples to
         return per clip -> (output packed [sum length_i], list of the clips' [length_i] views[, cr int32 [n]]), every clip the
         bits of __call__(pred_i[None], src_i[None], length_i): per-clip cutoff, splice, iSTFT, 0.99 peak.  11 launches for the
-        list.  The results belong to the workspace of this mix of lengths: a caller that keeps them clones them."""
+        list.  The results belong to the workspace of this mix of lengths: a caller that keeps them clones them.
+        gains=, groups= as in __call__ (one launch more than the 11, or two)."""
         preds, srcs = _flat(preds), _flat(srcs)
         lengths = [int(n) for n in lengths]
         n = len(preds)
+        self._level_args(n, gains, groups)
         if len(srcs) != n or len(lengths) != n or n < 1:
             raise ValueError("one pred, one src and one length per clip")
         Tp, T = [p.shape[0] for p in preds], [s_.shape[0] for s_ in srcs]
@@ -358,7 +387,7 @@ class PostProcessor:
                 [clip_array(src=ptrs[:n], len_in=Tp, row0=row0, rows=F),
                  clip_array(src=ptrs[n:], len_in=T, row0=row0, rows=F, dst=outs, len_out=lengths), seg_table(row0, F)], self.device)
             w["ptrs"] = ptrs
-        self._run(w, _SegmentPost(w, Tp, T, F, lengths), sum(F), n)
+        self._run(w, _SegmentPost(w, Tp, T, F, lengths), sum(F), n, gains, groups)
         return (w["out"], w["views"], w["cr"]) if return_cr else (w["out"], w["views"])
 
 
@@ -390,9 +419,18 @@ class Resampler:
             self._banks[key] = (torch.from_numpy(bank).to(self.device), rows)
         return self._banks[key]
 
+    def _gains(self, peak, n):
+        """fh_channel_peaks_f32 between the peak and the division: float32 [n] = the peaks (the caller's own tensor); a silent
+        clip's slot becomes 1.0, so its samples stay exact zeros."""
+        gains = torch.empty(n, dtype=torch.float32, device=self.device)
+        _launch("fh_channel_peaks_f32", _ptr(peak), _ptr(gains), n)
+        return gains
+
     @hip.on_device
-    def __call__(self, x, sr_in, sr_out=48000):
-        """x [B, T_in] float32 on device -> [B, T_out], each clip divided by its max |.|."""
+    def __call__(self, x, sr_in, sr_out=48000, gains=False):
+        """x [B, T_in] float32 on device -> [B, T_out], each clip divided by its max |.|.
+        gains=True -> (that, float32 [B] on the device: the peaks the clips were divided by), with a silent clip left as zeros
+        (its gain is 0) where the default divides 0 by 0."""
         B, n_in = x.shape
         flt = self._filter(sr_out, sr_in)
         if flt is None:
@@ -405,8 +443,9 @@ class Resampler:
             _launch("fh_resample_poly_f32", _ptr(x), taps, _ptr(y), B, n_in, n_out, up, down, n_taps, pre)
         peak = torch.zeros(B, dtype=torch.int32, device=self.device)
         _launch("fh_peak_abs_f32", _ptr(y), _ptr(peak), B, y.shape[1])
+        g = self._gains(peak, B) if gains else None
         _launch("fh_peak_scale_f32", _ptr(y), _ptr(peak), B, y.shape[1], 1.0)
-        return y
+        return (y, g) if gains else y
 
     def _fill(self, buf, xs):
         """list of 1-D float32 clips -> the packed device buffer `buf`.  Host arrays go up as one pinned buffer and one copy."""
@@ -418,7 +457,7 @@ class Resampler:
         buf.copy_(host.pin_memory() if buf.is_cuda else host, non_blocking=True)
 
     @hip.on_device
-    def ragged(self, xs, sr_in, sr_out=48000):
+    def ragged(self, xs, sr_in, sr_out=48000, gains=False):
         """xs: list of 1-D float32 clips at sr_in (host arrays: packed and uploaded with one copy; or device tensors) ->
         (the 48 kHz clips packed back to back [sum T_i], list of their [T_i] views), each resampled and divided by its
         max |.| with the bits of __call__ on that clip alone.  Four launches for the list.  The result belongs to the
@@ -426,7 +465,8 @@ class Resampler:
         sr_in may be one rate per clip: clips of different rates still run as one resampling launch, every clip with the
         polyphase filter of its own rate (fh_resample_poly_rates_seg_f32: the filter rows and every clip's row index go up
         with the clip descriptors, the tap bank is kept per tuple of distinct rates); the workspace then belongs to the mix
-        of (length, rate) pairs."""
+        of (length, rate) pairs.
+        gains=True -> (packed, views, float32 [n] on the device) as in __call__; the gains are the caller's own tensor."""
         rates = clip_rates(sr_in, len(xs))
         tab = ragged_clip_tables([int(np.prod(x.shape)) for x in xs], rates, sr_out, check_mel=False)
         n, max_len = len(xs), max(tab["len_out"])
@@ -451,8 +491,9 @@ class Resampler:
             _launch("fh_resample_poly_seg_f32", w["clips"], n, max_len, taps, up, down, n_taps, pre)
         w["peak"].zero_()
         _launch("fh_peak_abs_seg_f32", w["clips"], n, max_len, _ptr(w["peak"]))
+        g = self._gains(w["peak"], n) if gains else None
         _launch("fh_peak_scale_seg_f32", w["clips"], n, max_len, _ptr(w["peak"]), 1.0)
-        return w["y"], w["views"]
+        return (w["y"], w["views"], g) if gains else (w["y"], w["views"])
 
     @hip.on_device
     def upload_packed(self, conds):

@@ -172,6 +172,10 @@ _SIGS = {
     "fh_spec_splice_seg_f32": [_P, _P, _P, _P, _P, _I, _I, _P],
     "fh_istft_ola_seg_f32": [_P, _P, _P, _I, _I, _P, _I, _I, _P],
     "fh_rows_to_channels_seg_f32": [_P, _P, _I, _I, _I, _P],
+    "fh_channel_peaks_f32": [_P, _P, _I, _P],
+    "fh_group_peak_f32": [_P, _P, _P, _I, _P],
+    "fh_row_gain_f32": [_P, _P, _I, _I, _P],
+    "fh_row_gain_seg_f32": [_P, _I, _I, _P, _P],
 }
 EXPORTS = sorted(_SIGS) + ["fh_last_error"]
 

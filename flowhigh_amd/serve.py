@@ -55,23 +55,33 @@ class BatchingServer:
         self._worker.start()
 
     # ---- caller side -------------------------------------------------------------------------------
-    def submit(self, audio, sr_in, timestep=1, seed=None):
-        """Queue one clip (int16 or float, 1-D or [1, T]); returns a Future of a float32 numpy array [T48]."""
+    def submit(self, audio, sr_in, timestep=1, seed=None, *, channels=None, level='peak'):
+        """Queue one clip (int16 or float, 1-D or [1, T]); returns a Future of a float32 numpy array [T48].
+        channels = 'first' ([C, T]) | 'last' ([T, C]): a multichannel clip (FlowHighSR.generate), the Future's array is
+        [C, T48].  level = 'peak' | 'input' as in generate.  A shape that fits no layout is a ValueError here."""
         if self._closed:
             raise RuntimeError("server is closed")
+        from .flowhighsr import resolve_channels, resolve_level
+        level = resolve_level(level)
         a = np.asarray(audio.detach().cpu() if isinstance(audio, torch.Tensor) else audio)
-        if a.ndim == 2:
+        planar = resolve_channels(a, channels)
+        if channels is not None:
+            a = planar                            # [C, T]
+        elif a.ndim == 2:
             a = a.squeeze(0)
         fut = Future()
-        self._q.put((a, int(sr_in), int(timestep), seed, fut))
+        self._q.put((a, int(sr_in), int(timestep), seed, fut, level))
         return fut
 
-    def generate(self, audio, sr_out=48000, timestep=1):
-        """Drop-in for app.py's `generate(audio, sr_out, timestep)`: audio = (sr_in, numpy array)."""
+    def generate(self, audio, sr_out=48000, timestep=1, *, level='peak'):
+        """Drop-in for app.py's `generate(audio, sr_out, timestep)`: audio = (sr_in, numpy array).  A 2-D array [T, C] with
+        C <= 8 < T is gradio's multichannel clip (gr.Audio(type="numpy")): it runs with channels='last' and comes back [T48, C]."""
         if int(sr_out) != 48000:
             raise NotImplementedError("the mel codec is fixed at 48 kHz")
         sr_in, a = audio
-        return 48000, self.submit(a, sr_in, timestep).result()
+        if np.ndim(a) == 2 and np.shape(a)[1] <= 8 < np.shape(a)[0]:
+            return 48000, self.submit(a, sr_in, timestep, channels='last', level=level).result().T
+        return 48000, self.submit(a, sr_in, timestep, level=level).result()
 
     def close(self):
         self._closed = True
@@ -109,10 +119,16 @@ class BatchingServer:
                 return
             groups = {}
             for item in batch:
-                # same step count; mix_rates off: same input rate too
-                groups.setdefault((None if self.mix_rates else item[1], item[2]), []).append(item)
-            for (sr_in, steps), items in groups.items():
+                # same step count and level; mix_rates off: same input rate too
+                groups.setdefault((None if self.mix_rates else item[1], item[2], item[5]), []).append(item)
+            for (sr_in, steps, level), items in groups.items():
                 try:
+                    # (handed on only where a request asked: a model whose generate_many predates the keywords keeps working.
+                    # One [C, T] clip makes the call a channels='first' one, the mono clips beside it going as [1, T])
+                    planar = any(it[0].ndim == 2 for it in items)
+                    level_kw = dict(channels='first') if planar else {}
+                    if level != 'peak':
+                        level_kw["level"] = level
                     if sr_in is None:
                         sr_in = [it[1] for it in items]
                         if len(set(sr_in)) == 1:          # (one rate in the window: the call it has always been)
@@ -124,14 +140,16 @@ class BatchingServer:
                             prior = dict(seed=[0 if it[3] is None else int(it[3]) for it in items])
                     elif any(it[3] is not None for it in items):
                         noise = []
-                        for a, sr_i, _, seed, _ in items:
+                        for a, sr_i, _, seed, *_ in items:
                             g = torch.Generator().manual_seed(0 if seed is None else int(seed))
                             t48 = -(-a.shape[-1] * 48000 // sr_i)
                             noise.append(self.model._draw_noise(1, t48 // 480, g))
-                    outs = self.model.generate_many([it[0] for it in items], sr_in, 48000, steps, noise=noise,
-                                                    max_batch=self.max_batch, **self._ends_kw, **prior)
+                    outs = self.model.generate_many([it[0][None] if planar and it[0].ndim == 1 else it[0] for it in items], sr_in,
+                                                    48000, steps, noise=noise, max_batch=self.max_batch, **self._ends_kw, **prior,
+                                                    **level_kw)
                     for it, y in zip(items, outs):
-                        it[4].set_result(y.detach().cpu().squeeze(0).numpy())
+                        y = y.detach().cpu()
+                        it[4].set_result((y if it[0].ndim == 2 else y.squeeze(0)).numpy())
                 except Exception as e:            # noqa: BLE001  (every waiting caller must be released)
                     for it in items:
                         if not it[4].done():

@@ -649,6 +649,24 @@ int fh_istft_ola_seg_f32(const float* frames, const float* window, const fh_clip
  * channel-major [d, rows] buffer (the vocoder's input), a plain copy. */
 int fh_rows_to_channels_seg_f32(const float* mel, const fh_clip* clips, int n_clips, int max_rows, int d, void* stream);
 
+/* -----------------------------------------------------------------------------------
+ * Level-true output and multichannel clips (csrc/level.hip; FlowHighSR.generate*(channels=, level=)).  A row is one
+ * channel of a clip run as a mono clip; its gain is the peak p its 48 kHz input was divided by.  Peak slots hold
+ * non-negative float bits, as fh_peak_abs_f32 and fh_istft_ola_f32 leave them.
+ * --------------------------------------------------------------------------------- */
+/* gains[i] = the float in peak_bits[i]; a slot that holds +-0 becomes the bits of 1.0f (a silent row: the
+ * fh_peak_scale_f32 that follows leaves its zeros as they are).  It goes between fh_peak_abs_f32 and fh_peak_scale_f32, or
+ * between their segment forms. */
+int fh_channel_peaks_f32(uint32_t* peak_bits, float* gains, int n, void* stream);
+/* q_bits[i] = bits(max over the rows r of i's group, gains[r] != 0, of fl(q[r] * gains[r])); a maximum of 0 (every row
+ * silent) becomes 1.0f.  group: device int32 [n], non-decreasing (rows of a group are adjacent).  One thread walks a
+ * group: meant for a clip's channels, not for thousands of rows per group. */
+int fh_group_peak_f32(uint32_t* q_bits, const float* gains, const int32_t* group, int n, void* stream);
+/* y[b, :] *= gains[b] (one float32 multiply per sample), y [batch, len] at any 4-byte alignment; batch <= 65535. */
+int fh_row_gain_f32(float* y, const float* gains, int batch, int len, void* stream);
+/* The same over dst[0 .. len_out) of every clip (the table fh_peak_scale_seg_f32 takes); max_len: the longest len_out. */
+int fh_row_gain_seg_f32(const fh_clip* clips, int n_clips, int max_len, const float* gains, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
