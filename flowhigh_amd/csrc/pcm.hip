@@ -1,0 +1,214 @@
+// The last step of delivery (FlowHighSR.generate*(pcm='int16', dither=, interleaved=)): float32 rows -> int16 PCM on the device,
+// quantised, optionally dithered, planar or interleaved.  flowhigh_amd/pcm.py is the definition; the kernel gives its bits.
+//   fh_pcm_i16_f32       n_clips clips of `channels` planar rows of `len` floats, back to back
+//   fh_pcm_i16_seg_f32   a device table of clips, each with its own channels, len, source rows (pointer + pitch) and destination
+// Both are instantiations of one kernel body that differ in the clip locator, so a clip gets the same bits from either.
+//   sample x -> v = fl(x * 32768) [exact] -> v = fl(v + d) when dithering -> rint (ties to even) -> clamp to [-32768, 32767];
+//   NaN -> 0.
+//   d of (channel c, sample t) under the clip's key (seed, stream): Philox4x32-10 of the counter (t >> 1, stream) under the key
+//   (seed.lo ^ 'PCM1', seed.hi ^ c); even t takes (r0, r1), odd t (r2, r3); d = ((ra >> 8) - (rb >> 8)) 2^-24: triangular on
+//   (-1, 1) LSB, exact in fp32.  It depends on (key, c, t) only -- not on the batch, the layout or the number of channels.
+// Grid: (blocks of 256 runs, clip, channel).  A thread owns a run of 8 consecutive samples of one channel.  Planar output: run s
+// is the 16-byte word s of the row's memory counted from the aligned address at or below the row (as level.hip's row gain),
+// so a run wholly inside the row is one 16-byte store and the (at most two) runs over an end go element by element.  Interleaved
+// output: runs start at the row's first sample.  With C = 2, 4 or 8 and the clip's destination aligned to a frame (2 C bytes) the
+// blocks of channel 0 encode every channel and store each sample frame as one 4-, 8- or 16-byte word (pcm_frames); otherwise
+// every sample is a 2-byte store at its place in its frame.  Loads are two 16-byte reads where the run's first float is 16-byte
+// aligned, else eight 4-byte reads.  Which stores are used never changes a value.
+#include "fh_common.h"
+#include "philox.h"
+
+namespace {
+
+constexpr int RUN = 8;                          // samples per thread = one 16-byte store of int16
+constexpr unsigned KEY_TAG = 0x50434D31u;       // 'PCM1': keeps the dither's blocks apart from the prior's under the same key
+
+typedef short i16x8 __attribute__((ext_vector_type(8)));
+
+struct pcm_view {          // one clip as the kernel body sees it
+  const float* src;        // row c at src + c * pitch
+  int16_t* dst;
+  long long pitch;
+  int channels, len;
+};
+
+struct BatchedPcm {        // equal clips back to back: clip b is computed
+  const float* x;
+  int16_t* y;
+  int channels, len;
+  __device__ pcm_view operator()(int b) const {
+    const size_t per = (size_t)channels * len;
+    return {x + b * per, y + b * per, (long long)len, channels, len};
+  }
+};
+struct PcmTable {          // one fh_pcm_clip per clip on the device
+  const fh_pcm_clip* clips;
+  __device__ pcm_view operator()(int b) const {
+    const fh_pcm_clip c = clips[b];
+    return {c.src, c.dst, (long long)c.pitch, c.channels, c.len};
+  }
+};
+
+__device__ __forceinline__ short encode(float x, float d) {
+  float v = __fmul_rn(x, 32768.f);
+  v = __fadd_rn(v, d);
+  float q = rintf(v);
+  q = fminf(fmaxf(q, -32768.f), 32767.f);
+  return (v != v) ? (short)0 : (short)(int)q;
+}
+
+// x[k] = sample first + k of the row at src, 0 outside [0, len): two 16-byte reads where the run is whole and aligned
+__device__ __forceinline__ void load_run(const float* __restrict__ src, long long first, int len, bool whole, float (&x)[RUN]) {
+  if (whole && (((size_t)(src + first)) & 15) == 0) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(src + first), b = *reinterpret_cast<const f32x4*>(src + first + 4);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      x[k] = a[k];
+      x[4 + k] = b[k];
+    }
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < RUN; ++k) {
+    const long long t = first + k;
+    x[k] = (t >= 0 && t < len) ? src[t] : 0.f;
+  }
+}
+
+// d[k] = the dither of sample first + k of channel ch under the key (seed, strm).  A run of 8 samples touches 4 Philox blocks
+// when it starts on an even sample, 5 when on an odd one; with first < 0 the run's samples before t = 0 are never stored.
+__device__ __forceinline__ void dither_run(unsigned long long seed, unsigned long long strm, int ch, long long first,
+                                           float (&d)[RUN]) {
+  const unsigned k0 = (unsigned)seed ^ KEY_TAG, k1 = (unsigned)(seed >> 32) ^ (unsigned)ch;
+  const long long t0 = first < 0 ? 0 : first;
+  const long long q0 = t0 >> 1;
+  u32x4 r[RUN / 2 + 1];
+#pragma unroll
+  for (int j = 0; j <= RUN / 2; ++j) {
+    const unsigned long long q = (unsigned long long)(q0 + j);
+    if (j < RUN / 2 || (first & 1))
+      r[j] = philox4x32_10(u32x4{(unsigned)q, (unsigned)(q >> 32), (unsigned)strm, (unsigned)(strm >> 32)}, k0, k1);
+    else
+      r[j] = u32x4{0u, 0u, 0u, 0u};
+  }
+  const int odd = (int)(first & 1);            // (first may be negative: & 1 is its parity all the same)
+#pragma unroll
+  for (int k = 0; k < RUN; ++k) {
+    const long long t = first + k;              // sample t lies in block (t >> 1) - q0
+    const int j = (int)((t >> 1) - q0);
+    u32x4 rr = r[0];
+#pragma unroll
+    for (int m = 1; m <= RUN / 2; ++m) rr = (j == m) ? r[m] : rr;
+    const bool hi = ((k + odd) & 1) != 0;
+    const unsigned ra = hi ? rr[2] : rr[0], rb = hi ? rr[3] : rr[1];
+    d[k] = (float)((int)(ra >> 8) - (int)(rb >> 8)) * 0x1p-24f;
+  }
+}
+
+// Interleaved output of a clip of C = 2, 4 or 8 channels whose destination is aligned to a frame (2 C bytes): the thread encodes
+// its run of every channel and stores each sample frame as ONE 4-, 8- or 16-byte word.
+template <int C>
+__device__ __forceinline__ void pcm_frames(const pcm_view& c, const unsigned long long* __restrict__ keys) {
+  typedef short frame_t __attribute__((ext_vector_type(C)));
+  const long long first = ((long long)blockIdx.x * 256 + threadIdx.x) * RUN;
+  if (first >= c.len) return;
+  const bool whole = first + RUN <= c.len;
+  unsigned long long seed = 0, strm = 0;
+  if (keys) {
+    seed = keys[2 * blockIdx.y];
+    strm = keys[2 * blockIdx.y + 1];
+  }
+  frame_t o[RUN];
+#pragma unroll
+  for (int ch = 0; ch < C; ++ch) {
+    float x[RUN], d[RUN];
+    load_run(c.src + (long long)ch * c.pitch, first, c.len, whole, x);
+#pragma unroll
+    for (int k = 0; k < RUN; ++k) d[k] = 0.f;
+    if (keys) dither_run(seed, strm, ch, first, d);
+#pragma unroll
+    for (int k = 0; k < RUN; ++k) o[k][ch] = encode(x[k], d[k]);
+  }
+  frame_t* __restrict__ frames = reinterpret_cast<frame_t*>(c.dst);
+#pragma unroll
+  for (int k = 0; k < RUN; ++k)
+    if (first + k < c.len) frames[first + k] = o[k];
+}
+
+template <class Loc>
+__global__ __launch_bounds__(256) void pcm_i16_kernel(Loc loc, const unsigned long long* __restrict__ keys, int interleaved) {
+  const pcm_view c = loc(blockIdx.y);
+  const int ch = blockIdx.z;
+  if (c.channels < 1 || c.channels > 8 || c.len < 1 || ch >= c.channels) return;      // (a table lives on the device: checked)
+  if (interleaved && (c.channels == 2 || c.channels == 4 || c.channels == 8) && ((size_t)c.dst & (2 * c.channels - 1)) == 0) {
+    if (ch != 0) return;                        // (the blocks of channel 0 write whole frames)
+    if (c.channels == 2)
+      pcm_frames<2>(c, keys);
+    else if (c.channels == 4)
+      pcm_frames<4>(c, keys);
+    else
+      pcm_frames<8>(c, keys);
+    return;
+  }
+  const float* __restrict__ src = c.src + (long long)ch * c.pitch;
+  int16_t* __restrict__ row = interleaved ? c.dst : c.dst + (size_t)ch * c.len;
+  const int lead = interleaved ? 0 : (int)(((size_t)row >> 1) & (RUN - 1));      // elements between the aligned address and the row
+  const long long first = ((long long)blockIdx.x * 256 + threadIdx.x) * RUN - lead;   // the run's first sample
+  if (first >= c.len) return;
+  const bool whole = first >= 0 && first + RUN <= c.len;
+
+  float x[RUN], d[RUN];
+  load_run(src, first, c.len, whole, x);
+#pragma unroll
+  for (int k = 0; k < RUN; ++k) d[k] = 0.f;
+  if (keys) dither_run(keys[2 * blockIdx.y], keys[2 * blockIdx.y + 1], ch, first, d);
+
+  if (whole && !interleaved) {
+    i16x8 o;
+#pragma unroll
+    for (int k = 0; k < RUN; ++k) o[k] = encode(x[k], d[k]);
+    *reinterpret_cast<i16x8*>(row + first) = o;
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < RUN; ++k) {
+    const long long t = first + k;
+    if (t < 0 || t >= c.len) continue;
+    const short o = encode(x[k], d[k]);
+    if (interleaved)
+      row[(size_t)t * c.channels + ch] = o;
+    else
+      row[t] = o;
+  }
+}
+
+int pcm_blocks(int len) { return fh_cdiv(((long long)len + RUN - 1) / RUN + 1, 256); }      // runs of a row at any alignment
+
+}  // namespace
+
+extern "C" int fh_sizeof_pcm_clip(void) { return (int)sizeof(fh_pcm_clip); }
+
+extern "C" int fh_pcm_i16_f32(const float* x, int16_t* y, const uint64_t* keys, int n_clips, int channels, int len,
+                              int interleaved, void* stream) {
+  FH_CHECK_ARG(x && y, "fh_pcm_i16_f32: null pointer (x %p, y %p)", (const void*)x, (void*)y);
+  FH_CHECK_ARG(n_clips > 0 && n_clips < 65536, "fh_pcm_i16_f32: %d clips (1 .. 65535)", n_clips);
+  FH_CHECK_ARG(channels >= 1 && channels <= 8, "fh_pcm_i16_f32: %d channels (1 .. 8)", channels);
+  FH_CHECK_ARG(len > 0, "fh_pcm_i16_f32: len %d must be positive", len);
+  FH_CHECK_ARG((((size_t)x) & 3) == 0 && (((size_t)y) & 1) == 0, "fh_pcm_i16_f32: x must be 4-byte, y 2-byte aligned");
+  hipLaunchKernelGGL(pcm_i16_kernel<BatchedPcm>, dim3(pcm_blocks(len), n_clips, channels), dim3(256), 0, (hipStream_t)stream,
+                     BatchedPcm{x, y, channels, len}, (const unsigned long long*)keys, interleaved ? 1 : 0);
+  FH_CHECK_LAUNCH("fh_pcm_i16_f32");
+  return FH_OK;
+}
+
+extern "C" int fh_pcm_i16_seg_f32(const fh_pcm_clip* clips, int n_clips, int max_channels, int max_len, const uint64_t* keys,
+                                  int interleaved, void* stream) {
+  FH_CHECK_ARG(clips, "fh_pcm_i16_seg_f32: null clip table");
+  FH_CHECK_ARG(n_clips > 0 && n_clips < 65536, "fh_pcm_i16_seg_f32: %d clips (1 .. 65535)", n_clips);
+  FH_CHECK_ARG(max_channels >= 1 && max_channels <= 8, "fh_pcm_i16_seg_f32: %d channels (1 .. 8)", max_channels);
+  FH_CHECK_ARG(max_len > 0, "fh_pcm_i16_seg_f32: max_len %d must be positive", max_len);
+  hipLaunchKernelGGL(pcm_i16_kernel<PcmTable>, dim3(pcm_blocks(max_len), n_clips, max_channels), dim3(256), 0,
+                     (hipStream_t)stream, PcmTable{clips}, (const unsigned long long*)keys, interleaved ? 1 : 0);
+  FH_CHECK_LAUNCH("fh_pcm_i16_seg_f32");
+  return FH_OK;
+}

@@ -1,0 +1,184 @@
+"""Delivery: what generate*(output_rate=, pcm=, dither=, interleaved=) do to the post-processed 48 kHz result, on the device.
+
+  48 kHz rows -> resample_poly to the output rate (the input side's kernels with the (R, 48000) plan)
+              -> level='peak': 0.99 of the clip's own peak again, jointly over its channels (the 48 kHz path's peak kernels)
+              -> pcm='int16': one launch of fh_pcm_i16_f32 / fh_pcm_i16_seg_f32 (csrc/pcm.hip; pcm.py is the definition)
+
+`batch` runs the batched entries over clips of one length, `ragged` the segment forms over a group of clips of different
+lengths; rows are read where the post-processor left them, and a clip gets the same bits from either.  With every keyword at
+its default nothing here runs.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import hip, tables
+from .frontend import _launch, _ptr, clip_array, upload_tables
+from .prior import expand_seed
+
+MAX_RATE_FACTOR = 640             # max(up, down) of the reduced output_rate / 48000: the filter has 20 * that + 1 taps
+_PCM = (None, "int16")
+_DITHER = (None, "tpdf")
+
+
+def resolve_output_rate(output_rate):
+    """output_rate= -> None (48 kHz: nothing to do) or the rate R as an int.  R is a positive integer whose reduced ratio
+    up / down = R / 48000 has max(up, down) <= 640 (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 88200, 96000, ...)."""
+    if output_rate is None:
+        return None
+    r = output_rate
+    if isinstance(r, (bool, str, bytes)) or not isinstance(r, (int, np.integer, float)) or r != r or int(r) != r or int(r) <= 0:
+        raise ValueError(f"output_rate must be None or a positive integer, got {output_rate!r}")
+    r = int(r)
+    if r == 48000:
+        return None
+    g = math.gcd(r, 48000)
+    if max(r // g, 48000 // g) > MAX_RATE_FACTOR:
+        raise ValueError(f"output_rate={r}: {r} / 48000 reduces to {r // g} / {48000 // g}; the larger of the two must be "
+                         f"at most {MAX_RATE_FACTOR} (e.g. 8000, 16000, 22050, 32000, 44100, 96000)")
+    return r
+
+
+def resolve_delivery(n_clips, output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False):
+    """The delivery keywords of a call over n_clips clips, checked (ValueError, before any GPU work) ->
+    None when they are all at their defaults, else dict(rate: None | R, pcm, keys: None | one (seed, stream) per clip,
+    interleaved)."""
+    rate = resolve_output_rate(output_rate)
+    if pcm not in _PCM:
+        raise ValueError(f"pcm must be one of {_PCM}, got {pcm!r}")
+    if dither not in _DITHER:
+        raise ValueError(f"dither must be one of {_DITHER}, got {dither!r}")
+    if dither is not None and pcm is None:
+        raise ValueError("dither= goes with pcm=: a float result is not quantised")
+    if interleaved not in (False, True):
+        raise ValueError(f"interleaved must be a bool, got {interleaved!r}")
+    if interleaved and pcm is None:
+        raise ValueError("interleaved=True goes with pcm=: the float result is planar")
+    keys = None
+    if dither is not None:
+        try:
+            keys = expand_seed(dither_seed, n_clips)
+        except TypeError as e:
+            raise ValueError(f"dither_seed: {e}") from e
+    if rate is None and pcm is None:
+        return None
+    return dict(rate=rate, pcm=pcm, keys=keys, interleaved=bool(interleaved))
+
+
+def delivered_len(t48, output_rate=None):
+    """Samples per channel of a delivered clip whose 48 kHz result has t48."""
+    rate = resolve_output_rate(output_rate)
+    return int(t48) if rate is None else tables.resample_out_len(int(t48), rate, 48000)
+
+
+class Delivery:
+    def __init__(self, device, resampler):
+        self.device = hip.norm_device(device)
+        self.resampler = resampler            # its tap cache holds the (R, 48000) filters beside the input side's
+
+    def _keys(self, opt, which):
+        """Device int64 [n, 2] of the clips `which` of the call, or None without dither."""
+        if opt["keys"] is None:
+            return None
+        host = np.array([[opt["keys"][i][0], opt["keys"][i][1]] for i in which], dtype=np.uint64).view(np.int64)
+        return torch.from_numpy(host).pin_memory().to(self.device, non_blocking=True)
+
+    def _rows(self, t):
+        if t.dtype != torch.float32 or t.ndim != 2 or t.device != self.device:
+            raise ValueError(f"delivery takes float32 [rows, T] on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t if t.stride(1) == 1 or t.shape[1] == 1 else t.contiguous()
+
+    @hip.on_device
+    def batch(self, rows, chans, level, opt, which, packed=False):
+        """rows [R, T48]: the channels of len(chans) clips of one length, in clip order; which: the clips' indices in the
+        call (their dither keys).  -> list of the clips' results, [C_i, T] float32 / int16, or [T, C_i] int16 interleaved:
+        views of one buffer in clip order.  packed (mono clips only): that buffer instead, [R, T], or [R, T, 1] interleaved."""
+        rows = self._rows(rows).contiguous()
+        R, n = rows.shape[0], len(chans)
+        if sum(chans) != R or (packed and R != n):
+            raise ValueError(f"{R} rows for clips of {chans} channels")
+        y = rows
+        if opt["rate"] is not None:
+            taps, n_taps, pre, up, down = self.resampler._filter(opt["rate"], 48000)
+            T = tables.resample_out_len(rows.shape[1], opt["rate"], 48000)
+            y = torch.empty(R, T, dtype=torch.float32, device=self.device)
+            _launch("fh_resample_poly_f32", _ptr(rows), taps, _ptr(y), R, rows.shape[1], T, up, down, n_taps, pre)
+            if level == "peak":
+                peak = torch.zeros(R, dtype=torch.int32, device=self.device)
+                _launch("fh_peak_abs_f32", _ptr(y), _ptr(peak), R, T)
+                self._group_peak(peak, chans)
+                _launch("fh_peak_scale_f32", _ptr(y), _ptr(peak), R, T, 0.99)
+        T = y.shape[1]
+        if opt["pcm"] is None:
+            return y if packed else list(y.split(chans))
+        out = torch.empty(R * T, dtype=torch.int16, device=self.device)
+        keys = self._keys(opt, which)
+        if len(set(chans)) == 1:
+            _launch("fh_pcm_i16_f32", _ptr(y), _ptr(out), hip.ptr(keys), n, chans[0], T, int(opt["interleaved"]))
+        else:                      # clips of different channel counts: the segment form, the rows still where they are
+            self._pcm_seg([y.data_ptr() + 4 * T * r for r in _starts(chans)], [T] * n, chans, [T] * n, out, keys, opt)
+        if packed:
+            return out.view(R, T, 1) if opt["interleaved"] else out.view(R, T)
+        return _clip_views(out, chans, [T] * n, opt["interleaved"])
+
+    def _group_peak(self, peak, chans):
+        """The rows' peak slots -> the joint peak of every clip in all of its rows' slots; a silent clip's becomes 1.0, so the
+        scaling leaves its zeros (fh_group_peak_f32 with every gain 1: fl(q * 1) = q)."""
+        R = sum(chans)
+        group = torch.from_numpy(np.repeat(np.arange(len(chans), dtype=np.int32), chans)).pin_memory().to(self.device, non_blocking=True)
+        _launch("fh_group_peak_f32", _ptr(peak), _ptr(torch.ones(R, dtype=torch.float32, device=self.device)), _ptr(group), R)
+
+    def _pcm_seg(self, srcs, pitches, chans, lens, out, keys, opt):
+        off = _starts([c * t for c, t in zip(chans, lens)])
+        table = (hip.PcmClip * len(chans))(*[hip.PcmClip(int(s), out.data_ptr() + 2 * o, int(p), int(c), int(t))
+                                            for s, o, p, c, t in zip(srcs, off, pitches, chans, lens)])
+        desc, (clips,) = upload_tables([table], self.device)
+        _launch("fh_pcm_i16_seg_f32", clips, len(chans), max(chans), max(lens), hip.ptr(keys), int(opt["interleaved"]))
+
+    @hip.on_device
+    def ragged(self, clips, level, opt, which):
+        """clips: list of [C_i, T48_i] device tensors (any row pitch: views of the post-processor's buffers) -> list of the
+        clips' results as in `batch`, each the bits of batch() on that clip alone.  One launch per step for the group."""
+        clips = [self._rows(c) for c in clips]
+        chans, n = [c.shape[0] for c in clips], len(clips)
+        srcs, pitches, lens = [c.data_ptr() for c in clips], [c.stride(0) for c in clips], [c.shape[1] for c in clips]
+        if opt["rate"] is not None:
+            flt = self.resampler._filter(opt["rate"], 48000)
+            taps, n_taps, pre, up, down = flt
+            out_lens = [tables.resample_out_len(t, opt["rate"], 48000) for t in lens]
+            row_in = [s + 4 * p * r for s, p, c in zip(srcs, pitches, chans) for r in range(c)]
+            row_len_in = [t for t, c in zip(lens, chans) for _ in range(c)]
+            row_len = [t for t, c in zip(out_lens, chans) for _ in range(c)]
+            y = torch.empty(sum(row_len), dtype=torch.float32, device=self.device)
+            row_off = _starts(row_len)
+            desc, (table,) = upload_tables([clip_array(src=row_in, len_in=row_len_in, len_out=row_len,
+                                                       dst=[y.data_ptr() + 4 * o for o in row_off])], self.device)
+            R, max_len = len(row_len), max(row_len)
+            _launch("fh_resample_poly_seg_f32", table, R, max_len, taps, up, down, n_taps, pre)
+            if level == "peak":
+                peak = torch.zeros(R, dtype=torch.int32, device=self.device)
+                _launch("fh_peak_abs_seg_f32", table, R, max_len, _ptr(peak))
+                self._group_peak(peak, chans)
+                _launch("fh_peak_scale_seg_f32", table, R, max_len, _ptr(peak), 0.99)
+            first = _starts(chans)
+            srcs, pitches, lens = [y.data_ptr() + 4 * row_off[r] for r in first], out_lens, out_lens
+            if opt["pcm"] is None:
+                return [y[row_off[r]:row_off[r] + c * t].view(c, t) for r, c, t in zip(first, chans, lens)]
+        out = torch.empty(sum(c * t for c, t in zip(chans, lens)), dtype=torch.int16, device=self.device)
+        self._pcm_seg(srcs, pitches, chans, lens, out, self._keys(opt, which), opt)
+        return _clip_views(out, chans, lens, opt["interleaved"])
+
+
+def _starts(lens):
+    return [int(x) for x in np.cumsum([0] + list(lens[:-1]))]
+
+
+def _clip_views(out, chans, lens, interleaved):
+    """The clips of a packed int16 buffer: [C, T] planar, [T, C] interleaved."""
+    views, o = [], 0
+    for c, t in zip(chans, lens):
+        v = out[o:o + c * t]
+        views.append(v.view(t, c) if interleaved else v.view(c, t))
+        o += c * t
+    return views

@@ -18,6 +18,8 @@ Extensions over the reference (all keyword-only, defaults keep reference behavio
   upsampling_method='hip'             resample_poly on the device instead of scipy on the host
   generate*(..., channels=, level=)   multichannel clips ([C, T] / [T, C], one prior per clip) and output at the input's own
                                       level instead of 0.99 peak (csrc/level.hip; DESIGN.md "Channels and level")
+  generate*(..., output_rate=, pcm=, dither=, dither_seed=, interleaved=)   the result delivered on the device: resampled to
+                                      another rate, as int16 PCM (TPDF dither), interleaved [T, C] (delivery.py, csrc/pcm.hip)
 """
 import ctypes
 import json
@@ -30,6 +32,7 @@ import torch
 
 from . import hip, ode
 from .flow import FlowNet
+from .delivery import Delivery, resolve_delivery
 from .frontend import LogMel, PostProcessor, Resampler, clip_rates
 from .prior import expand_seed, normalize_key
 from .tables import HOP, resample_out_len
@@ -477,6 +480,7 @@ class FlowHighSR:
         self.upsampling_method = upsampling_method
         self.postproc = PostProcessor(flowhigh.device)
         self.resampler = Resampler(flowhigh.device)
+        self.delivery = Delivery(flowhigh.device, self.resampler)
 
     # ---- reference surface -----------------------------------------------------------------
     @property
@@ -939,45 +943,55 @@ class FlowHighSR:
     @torch.no_grad()
     @hip.on_device
     def generate_batch(self, clips, sr, target_sampling_rate=48000, timestep=1, *, noise=None,
-                       generator=None, return_stages=False, seed=None, _keys=None, channels=None, level='peak'):
+                       generator=None, return_stages=False, seed=None, _keys=None, channels=None, level='peak',
+                       output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False):
         """B clips of equal length as one batch -> [B, T48], every clip what generate() returns for it alone.
         channels=, level= (generate): with channels= every clip may have its own number of channels and the result is a list
         of [C_i, T48]; noise= is then one tensor per clip in a list ([1, N, n_mels] shared by the clip's channels, or
-        [C_i, N, n_mels]), or [B, N, n_mels]: one shared draw per clip."""
+        [C_i, N, n_mels]), or [B, N, n_mels]: one shared draw per clip.
+        output_rate=, pcm=, dither=, dither_seed=, interleaved= (generate): the same shapes at the output rate, int16 with
+        pcm=; interleaved=True gives [B, T, 1] without channels=, a list of [T, C_i] with it."""
         clips, planar = resolve_clips(list(clips), channels, level)
         n_clips = len(clips if planar is None else planar)
+        opt = resolve_delivery(n_clips, output_rate, pcm, dither, dither_seed, interleaved)
+        if opt is not None and return_stages:
+            raise ValueError("return_stages=True returns the 48 kHz stages: it does not go with output_rate= / pcm=")
         keys = _keys if _keys is not None else self._prior_keys(seed, n_clips, generator, noise)
+        rows, chans, stages = self._batch_rows(clips, planar, keys, sr, target_sampling_rate, timestep, noise, generator, level,
+                                               return_stages)
+        if opt is not None:
+            # (without channels= every clip is one row: the delivered buffer itself is the [B, T] result)
+            return self.delivery.batch(rows, chans, level, opt, range(n_clips), packed=channels is None)
+        if channels is not None:
+            rows = list(rows.split(chans))
+        return (rows, stages) if return_stages else rows
+
+    def _batch_rows(self, clips, planar, keys, sr, target_sampling_rate, timestep, noise, generator, level, return_stages=False):
+        """The 48 kHz result of a batch of equal-length clips (resolve_clips' pair) -> ([R, T48]: the clips' channels as rows,
+        in clip order; channels per clip; the stages or None).  Mono clips at level='peak' run the default path."""
         if planar is not None:
             if target_sampling_rate != 48000:
                 raise NotImplementedError("the mel codec is fixed at 48 kHz")
             chans = [a.shape[0] for a in planar]
             out = self._generate_rows(planar, sr, timestep, clip_noises(noise, chans), keys, generator, level, return_stages)
-            if channels is None:
-                return out
             rows, stages = out if return_stages else (out, None)
-            rows = list(rows.split(chans))
-            return (rows, stages) if return_stages else rows
-        if channels is not None:                 # mono clips given as [1, T]: the default path, the list form of the result
-            out = self.generate_batch(clips, sr, target_sampling_rate, timestep, noise=noise, generator=generator,
-                                      return_stages=return_stages, _keys=keys)
-            rows, stages = out if return_stages else (out, None)
-            rows = [rows[i:i + 1] for i in range(n_clips)]
-            return (rows, stages) if return_stages else rows
+            return rows, chans, stages
         cond = self._prepare_cond(clips, sr, target_sampling_rate)
         kw = dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
         HR_audio = self._sample(cond=cond, time_steps=timestep, cfm_method=self.cfm_method, noise=noise,
                                 generator=generator, keys=keys, **kw)
         HR_audio = HR_audio.squeeze(1)
         out = self.postproc(HR_audio, cond, cond.size(-1), return_cr=return_stages)
+        chans = [1] * len(clips)
         if return_stages:
-            return out[0], dict(cond=cond, wav=HR_audio.clone(), cr=out[1].clone())      # (plan-owned buffers)
-        return out
+            return out[0], chans, dict(cond=cond, wav=HR_audio.clone(), cr=out[1].clone())      # (plan-owned buffers)
+        return out, chans, None
 
     @torch.no_grad()
     @hip.on_device
     def generate_many(self, clips, sr, target_sampling_rate=48000, timestep=1, *, noise=None, generator=None,
                       max_batch=64, streams=None, ragged=None, max_frames=None, seed=None, ends=None, channels=None,
-                      level='peak'):
+                      level='peak', output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False):
         """Serving-side entry (the gradio caller of app.py:8-26, many requests at once): clips of ANY lengths,
         int16 or float.  Clips of equal length run as one batch (at most max_batch rows), so every result is
         what generate() returns for that clip alone; the prior noise is drawn in the order of `clips`, as a loop
@@ -1007,10 +1021,16 @@ class FlowHighSR:
         channels=, level= (generate): every clip may have its own number of channels; the result list then holds one [C_i, T48_i]
         per clip.  A clip's channels are rows of the same batch or ragged sequence (a clip of C channels costs what C clips
         cost), share the clip's prior -- noise[i] is [1, N_i, n_mels], or [C_i, N_i, n_mels] for a draw per channel -- and a
-        clip gives the same bits alone, in a batch, in a ragged group and under either `ends`."""
+        clip gives the same bits alone, in a batch, in a ragged group and under either `ends`.
+        output_rate=, pcm=, dither=, dither_seed=, interleaved= (generate): every result delivered at the output rate / as
+        int16 ([C_i, T_i], or [T_i, C_i] interleaved).  A batch of equal clips goes through the batched entries, a ragged group
+        through their segment forms, one launch per step over the group, reading the rows where the post-processor left
+        them; dither_seed=s gives clip i the key (s, i), or it holds one int / (seed, stream) pair per clip.  A clip's result
+        does not depend on how it ran."""
         clips = list(clips)
         ends = resolve_ends(ends)
         rates = resolve_rates(sr, len(clips))
+        opt = resolve_delivery(len(clips), output_rate, pcm, dither, dither_seed, interleaved)
         clips, planar = resolve_clips(clips, channels, level)
         chans = None
         if planar is not None:
@@ -1035,7 +1055,7 @@ class FlowHighSR:
         if ragged and len(set(zip(lengths, rates))) > 1 and target_sampling_rate == 48000:
             try:
                 return self._generate_many_ragged(clips, lengths, rates, timestep, noise, max_frames, keys=keys,
-                                                  frames=[sh[1] for sh in shapes], ends=ends, chans=chans, level=level)
+                                                  frames=[sh[1] for sh in shapes], ends=ends, chans=chans, level=level, opt=opt)
             except NotImplementedError as e:
                 # a vocoder configuration whose launch positions cannot be merged: one batch per length (said once)
                 if not getattr(self, "_ragged_fallback_logged", False):
@@ -1068,8 +1088,9 @@ class FlowHighSR:
                         y = self._generate_rows([clips[i] for i in part], key[1], timestep,
                                                 clip_noises([noise[i] for i in part], part_ch) if keys is None else None,
                                                 [keys[i] for i in part] if keys is not None else None, None, level)
-                        for i, rows in zip(part, y.split(part_ch)):
-                            out[i] = rows.clone()
+                        ys = y.split(part_ch) if opt is None else self.delivery.batch(y, part_ch, level, opt, part)
+                        for i, rows in zip(part, ys):
+                            out[i] = rows.clone() if opt is None else rows
                             if st is not main:
                                 out[i].record_stream(main)
                         continue
@@ -1078,8 +1099,9 @@ class FlowHighSR:
                     else:
                         prior = dict(noise=noise[part[0]] if len(part) == 1 else torch.cat([noise[i] for i in part], 0))
                     y = self.generate_batch([clips[i] for i in part], key[1], target_sampling_rate, timestep, **prior)
+                    ys = None if opt is None else self.delivery.batch(y, [1] * len(part), level, opt, part)
                     for r, i in enumerate(part):
-                        out[i] = y[r:r + 1].clone()
+                        out[i] = y[r:r + 1].clone() if ys is None else ys[r]
                         if st is not main:
                             out[i].record_stream(main)
         for s_ in side:
@@ -1088,9 +1110,10 @@ class FlowHighSR:
         return out
 
     def _generate_many_ragged(self, clips, lengths, rates, timestep, noise, max_frames, keys=None, frames=None, ends="per_clip",
-                              chans=None, level="peak"):
+                              chans=None, level="peak", opt=None):
         """rates: the input rate of every clip (resolve_rates).  chans (a channels= / level= call): clips are float [C_i, T_i]
-        arrays (resolve_clips) of chans[i] channels, each C_i rows of n frames in its sequence."""
+        arrays (resolve_clips) of chans[i] channels, each C_i rows of n frames in its sequence.  opt: resolve_delivery's
+        result; a clip that runs alone is delivered by the batched entries, a group by the segment forms."""
         if max_frames is None:
             max_frames = int(os.environ.get("FH_RAGGED_MAX_FRAMES", "12000"))
         chunk_limit = int(os.environ.get("FH_VOCODER_CHUNK_FRAMES", "6000"))
@@ -1102,9 +1125,17 @@ class FlowHighSR:
 
         def alone(i):
             if chans is None:
-                return self.generate_batch([clips[i]], rates[i], 48000, timestep, **prior_of(i)).clone()
-            return self._generate_rows([clips[i]], rates[i], timestep, clip_noises(noise[i], [chans[i]]) if keys is None else None,
-                                       [keys[i]] if keys is not None else None, None, level)
+                y = self.generate_batch([clips[i]], rates[i], 48000, timestep, **prior_of(i))
+                return y.clone() if opt is None else self.delivery.batch(y, [1], level, opt, [i])[0]
+            y = self._generate_rows([clips[i]], rates[i], timestep, clip_noises(noise[i], [chans[i]]) if keys is None else None,
+                                    [keys[i]] if keys is not None else None, None, level)
+            return y if opt is None else self.delivery.batch(y, [chans[i]], level, opt, [i])[0]
+
+        def deliver(idx, ys):          # a group's 48 kHz results (still plan- or workspace-owned) -> the caller's own
+            if opt is not None:
+                ys = self.delivery.ragged([y if y.ndim == 2 else y[None] for y in ys], level, opt, idx)
+            for i, y in zip(idx, ys):
+                out[i] = y
         width = chans if chans is not None else [1] * len(clips)
         out = [None] * len(clips)
         kw = dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
@@ -1128,9 +1159,9 @@ class FlowHighSR:
             if chans is not None:
                 ys = self._ragged_group_rows([clips[i] for i in idx], [rates[i] for i in idx], timestep,
                                              [noise[i] for i in idx] if keys is None else None,
-                                             [keys[i] for i in idx] if keys is not None else None, ends, level, kw)
-                for i, y in zip(idx, ys):
-                    out[i] = y
+                                             [keys[i] for i in idx] if keys is not None else None, ends, level, kw,
+                                             own=opt is None)
+                deliver(idx, ys)
                 continue
             prior = dict(keys=[keys[i] for i in idx]) if keys is not None else dict(noises=[noise[i] for i in idx])
             if ends == "ragged":
@@ -1139,21 +1170,22 @@ class FlowHighSR:
                 cond_mel, mels = self.flowhigh.logmel.ragged(conds)
                 wavs = self._sample_ragged(conds, timestep, self.cfm_method, mels=mels, cond_mel=cond_mel, **prior, **kw)
                 packed, views = self.postproc.ragged(wavs, conds, [c.shape[0] for c in conds])
-                packed = packed.clone()                      # (the caller's own: one copy for the group, handed out as views)
-                start = 0
-                for i, v in zip(idx, views):
-                    out[i] = packed[start:start + v.shape[0]][None]
+                if opt is None:
+                    packed = packed.clone()                  # (the caller's own: one copy for the group, handed out as views)
+                start, ys = 0, []
+                for v in views:
+                    ys.append(packed[start:start + v.shape[0]][None])
                     start += v.shape[0]
+                deliver(idx, ys)
                 continue
             # (the per-clip front and back ends -- ~8 + ~12 small launches per clip -- on up to 4 side streams measured
             # 121.5 ms against 121.3 ms on one stream for the 24-clip mix: not worth the cross-stream bookkeeping)
             conds = [self._prepare_cond([clips[i]], rates[i], 48000)[0] for i in idx]
             wavs = self._sample_ragged(conds, timestep, self.cfm_method, **prior, **kw)
-            for i, cond, wav in zip(idx, conds, wavs):
-                out[i] = self.postproc(wav, cond[None], cond.shape[0]).clone()
+            deliver(idx, [self.postproc(wav, cond[None], cond.shape[0]).clone() for cond, wav in zip(conds, wavs)])
         return out
 
-    def _ragged_group_rows(self, planar, rates, timestep, noises, keys, ends, level, kw):
+    def _ragged_group_rows(self, planar, rates, timestep, noises, keys, ends, level, kw, own=True):
         """One ragged group of a channels= / level= call: every channel of every clip is a row of the sequence, the rows of
         a clip are adjacent and share its prior, and the post-processor gets the rows' gains and (level='peak') their clip as
         their group.  -> list of [C_i, T48_i], each the bits of _generate_rows on that clip alone."""
@@ -1168,7 +1200,8 @@ class FlowHighSR:
             cond_mel, mels = self.flowhigh.logmel.ragged(conds)
             wavs = self._sample_ragged(conds, timestep, self.cfm_method, mels=mels, cond_mel=cond_mel, **prior, **kw)
             packed, _ = self.postproc.ragged(wavs, conds, [c.shape[0] for c in conds], **self._level_args(chans, level, gains))
-            packed = packed.clone()                          # (the caller's own: one copy for the group, handed out as views)
+            if own:
+                packed = packed.clone()                      # (the caller's own: one copy for the group, handed out as views)
             out, start, r = [], 0, 0
             for c in chans:                                  # (a clip's rows are adjacent and of one length)
                 t48 = conds[r].shape[0]
@@ -1225,7 +1258,7 @@ class FlowHighSR:
     @torch.no_grad()
     @hip.on_device
     def generate(self, audio, sr: int, target_sampling_rate=48000, timestep=1, *, noise=None, generator=None, seed=None,
-                 channels=None, level='peak'):
+                 channels=None, level='peak', output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False):
         """One clip, reference contract: returns float32 [1, T48] on the model device.  seed= (prior='device' models): the
         clip's noise is that of the key (seed, 0), or of a (seed, stream) pair given as [(seed, stream)].
         channels = None (default: a mono clip, 1-D or [1, T]; a 2-D clip is then a ValueError) | 'first' ([C, T]) | 'last'
@@ -1235,7 +1268,20 @@ class FlowHighSR:
         scaling, so the balance between them is kept.  A silent channel comes back as exact zeros.
         level = 'peak' (default: 0.99 of the clip's peak -- over all its channels --, as the reference) | 'input': the
         output at the level of the input, w_c * p_c: below the cutoff it is the 48 kHz input itself, not its normalised copy.
-        A mono clip with neither keyword runs what it always ran (DESIGN.md "Channels and level")."""
+        A mono clip with neither keyword runs what it always ran (DESIGN.md "Channels and level").
+        Delivery (DESIGN.md "Delivery"; all on the device, every default leaves the call as it was):
+        output_rate = None | 48000 (as it is) | R, a positive integer whose reduced R / 48000 has no term above 640 (8000, 11025,
+        12000, 16000, 22050, 24000, 32000, 44100, 88200, 96000; anything else is a ValueError): the result is
+        scipy.signal.resample_poly(y48, R, 48000) of every row, tables.resample_out_len(T48, R, 48000) samples; at level='peak'
+        it is put at 0.99 of its own peak (over the clip's channels) again, at level='input' it is left as resampled.
+        target_sampling_rate keeps its meaning (the rate of the mel codec: 48000 or NotImplementedError).
+        pcm = None | 'int16': torch.int16 in the float result's shape, pcm.py's encoding of it (round to nearest even, clamp).
+        dither = None | 'tpdf' (pcm only): +-1 LSB triangular dither from the key (dither_seed, 0) -- dither_seed an int, or
+        [(seed, stream)]; a function of the key, the channel and the sample index alone.
+        interleaved = True (pcm only): [T, C] ([T, 1] for a mono clip), written in that order by the kernel."""
         out = self.generate_batch([audio], sr, target_sampling_rate, timestep, noise=noise, generator=generator, seed=seed,
-                                  channels=channels, level=level)
-        return out if channels is None else out[0]
+                                  channels=channels, level=level, output_rate=output_rate, pcm=pcm, dither=dither,
+                                  dither_seed=dither_seed, interleaved=interleaved)
+        if channels is not None or (interleaved and pcm is not None):
+            return out[0]
+        return out

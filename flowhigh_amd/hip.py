@@ -79,6 +79,11 @@ class Rate(C.Structure):
                 ("n_pre_remove", C.c_int32)]
 
 
+class PcmClip(C.Structure):
+    """fh_pcm_clip: one clip of fh_pcm_i16_seg_f32 (csrc/pcm.hip)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("pitch", C.c_int64), ("channels", C.c_int32), ("len", C.c_int32)]
+
+
 class HipError(RuntimeError):
     pass
 
@@ -176,6 +181,9 @@ _SIGS = {
     "fh_group_peak_f32": [_P, _P, _P, _I, _P],
     "fh_row_gain_f32": [_P, _P, _I, _I, _P],
     "fh_row_gain_seg_f32": [_P, _I, _I, _P, _P],
+    "fh_pcm_i16_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "fh_sizeof_pcm_clip": [],
+    "fh_pcm_i16_seg_f32": [_P, _I, _I, _I, _P, _I, _P],
 }
 EXPORTS = sorted(_SIGS) + ["fh_last_error"]
 
@@ -207,7 +215,7 @@ def lib():
     if L.fh_sizeof_conv_group() != C.sizeof(ConvGroup) or L.fh_sizeof_act_group() != C.sizeof(ActGroup) \
             or L.fh_sizeof_wino_group() != C.sizeof(WinoGroup) or L.fh_sizeof_sum_job() != C.sizeof(SumJob) \
             or L.fh_sizeof_amp_group() != C.sizeof(AmpGroup) or L.fh_sizeof_clip() != C.sizeof(Clip) \
-            or L.fh_sizeof_rate() != C.sizeof(Rate):
+            or L.fh_sizeof_rate() != C.sizeof(Rate) or L.fh_sizeof_pcm_clip() != C.sizeof(PcmClip):
         raise HipError("descriptor struct layout mismatch between hip.py and flowhigh_hip.h")
     _lib = L
     return L

@@ -9,6 +9,7 @@ clip's key (seed, 0) and the noise is drawn on the device).  Host logic only: no
 no sockets (the reference's UI / network layers are out of scope); `generate()` below has the signature of
 the function `app.py` hands to `gr.Interface`.
 """
+import inspect
 import os
 import queue
 import threading
@@ -55,14 +56,27 @@ class BatchingServer:
         self._worker.start()
 
     # ---- caller side -------------------------------------------------------------------------------
-    def submit(self, audio, sr_in, timestep=1, seed=None, *, channels=None, level='peak'):
+    def submit(self, audio, sr_in, timestep=1, seed=None, *, channels=None, level='peak', output_rate=None, pcm=None,
+               dither=None, dither_seed=0):
         """Queue one clip (int16 or float, 1-D or [1, T]); returns a Future of a float32 numpy array [T48].
         channels = 'first' ([C, T]) | 'last' ([T, C]): a multichannel clip (FlowHighSR.generate), the Future's array is
-        [C, T48].  level = 'peak' | 'input' as in generate.  A shape that fits no layout is a ValueError here."""
+        [C, T48].  level = 'peak' | 'input' as in generate.  A shape that fits no layout is a ValueError here.
+        output_rate=, pcm=, dither=, dither_seed= as in generate (dither_seed: an int s = the key (s, 0), or a (seed, stream)
+        pair), checked here; requests are grouped by them too.  With pcm= the Future's array is int16, and a channels='last'
+        request gets it in its own layout, [T, C], written that way on the device."""
         if self._closed:
             raise RuntimeError("server is closed")
+        from .delivery import resolve_delivery
         from .flowhighsr import resolve_channels, resolve_level
         level = resolve_level(level)
+        if isinstance(dither_seed, (tuple, list)):
+            dither_seed = tuple(dither_seed)
+            if len(dither_seed) != 2:
+                raise ValueError(f"dither_seed of a request is an int or a (seed, stream) pair, got {dither_seed!r}")
+        opt = resolve_delivery(1, output_rate, pcm, dither, [dither_seed])
+        deliv = None
+        if opt is not None:
+            deliv = (opt["rate"], opt["pcm"], dither, bool(pcm is not None and channels == 'last'), dither_seed)
         a = np.asarray(audio.detach().cpu() if isinstance(audio, torch.Tensor) else audio)
         planar = resolve_channels(a, channels)
         if channels is not None:
@@ -70,18 +84,26 @@ class BatchingServer:
         elif a.ndim == 2:
             a = a.squeeze(0)
         fut = Future()
-        self._q.put((a, int(sr_in), int(timestep), seed, fut, level))
+        self._q.put((a, int(sr_in), int(timestep), seed, fut, level, deliv))
         return fut
 
-    def generate(self, audio, sr_out=48000, timestep=1, *, level='peak'):
+    def generate(self, audio, sr_out=48000, timestep=1, *, level='peak', pcm=None, dither=None):
         """Drop-in for app.py's `generate(audio, sr_out, timestep)`: audio = (sr_in, numpy array).  A 2-D array [T, C] with
-        C <= 8 < T is gradio's multichannel clip (gr.Audio(type="numpy")): it runs with channels='last' and comes back [T48, C]."""
+        C <= 8 < T is gradio's multichannel clip (gr.Audio(type="numpy")): it runs with channels='last' and comes back [T48, C].
+        sr_out other than 48000 goes on as output_rate= where the model's generate_many takes it; pcm='int16' (dither='tpdf')
+        returns the int16 array a WAV writer or a socket takes, a [T, C] clip in that layout from the device."""
+        kw = {}
         if int(sr_out) != 48000:
-            raise NotImplementedError("the mel codec is fixed at 48 kHz")
+            if "output_rate" not in inspect.signature(self.model.generate_many).parameters:
+                raise NotImplementedError("the mel codec is fixed at 48 kHz")
+            kw["output_rate"] = int(sr_out)
+        if pcm is not None or dither is not None:
+            kw.update(pcm=pcm, dither=dither)
         sr_in, a = audio
         if np.ndim(a) == 2 and np.shape(a)[1] <= 8 < np.shape(a)[0]:
-            return 48000, self.submit(a, sr_in, timestep, channels='last', level=level).result().T
-        return 48000, self.submit(a, sr_in, timestep, level=level).result()
+            y = self.submit(a, sr_in, timestep, channels='last', level=level, **kw).result()
+            return int(sr_out), (y if pcm is not None else y.T)
+        return int(sr_out), self.submit(a, sr_in, timestep, level=level, **kw).result()
 
     def close(self):
         self._closed = True
@@ -120,8 +142,9 @@ class BatchingServer:
             groups = {}
             for item in batch:
                 # same step count and level; mix_rates off: same input rate too
-                groups.setdefault((None if self.mix_rates else item[1], item[2], item[5]), []).append(item)
-            for (sr_in, steps, level), items in groups.items():
+                # ... and the same delivery (output rate, sample format, dither, layout; the dither seed is the request's own)
+                groups.setdefault((None if self.mix_rates else item[1], item[2], item[5], item[6] and item[6][:4]), []).append(item)
+            for (sr_in, steps, level, deliv), items in groups.items():
                 try:
                     # (handed on only where a request asked: a model whose generate_many predates the keywords keeps working.
                     # One [C, T] clip makes the call a channels='first' one, the mono clips beside it going as [1, T])
@@ -129,6 +152,13 @@ class BatchingServer:
                     level_kw = dict(channels='first') if planar else {}
                     if level != 'peak':
                         level_kw["level"] = level
+                    if deliv is not None:
+                        rate, pcm, dither, interleaved = deliv
+                        level_kw.update({k: v for k, v in (("output_rate", rate), ("pcm", pcm), ("dither", dither)) if v is not None})
+                        if dither is not None:
+                            level_kw["dither_seed"] = [it[6][4] for it in items]
+                        if interleaved:
+                            level_kw["interleaved"] = True
                     if sr_in is None:
                         sr_in = [it[1] for it in items]
                         if len(set(sr_in)) == 1:          # (one rate in the window: the call it has always been)
@@ -149,6 +179,9 @@ class BatchingServer:
                                                     **level_kw)
                     for it, y in zip(items, outs):
                         y = y.detach().cpu()
+                        if deliv is not None and deliv[3]:          # [T, C] from the device; a 1-D request's is [T, 1]
+                            it[4].set_result((y if it[0].ndim == 2 else y.squeeze(1)).numpy())
+                            continue
                         it[4].set_result((y if it[0].ndim == 2 else y.squeeze(0)).numpy())
                 except Exception as e:            # noqa: BLE001  (every waiting caller must be released)
                     for it in items:

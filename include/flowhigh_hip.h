@@ -667,6 +667,36 @@ int fh_row_gain_f32(float* y, const float* gains, int batch, int len, void* stre
 /* The same over dst[0 .. len_out) of every clip (the table fh_peak_scale_seg_f32 takes); max_len: the longest len_out. */
 int fh_row_gain_seg_f32(const fh_clip* clips, int n_clips, int max_len, const float* gains, void* stream);
 
+/* -----------------------------------------------------------------------------------
+ * int16 PCM on the device (csrc/pcm.hip; FlowHighSR.generate*(pcm='int16', dither=, interleaved=)): the last step of
+ * delivery.  flowhigh_amd/pcm.py is the definition, the entries give its bits.
+ *   sample x -> v = fl(x * 32768) (exact) -> v = fl(v + d) when dithering -> rint, ties to even -> clamp to
+ *   [-32768, 32767]; NaN -> 0, +-inf saturates.
+ *   d of channel c, sample t under the clip's key (seed, stream): (r0 .. r3) = Philox4x32-10 of the counter
+ *   (q & 0xffffffff, q >> 32, stream & 0xffffffff, stream >> 32), q = t >> 1, under the key ((seed & 0xffffffff) ^ 0x50434D31,
+ *   (seed >> 32) ^ c); even t takes (ra, rb) = (r0, r1), odd t (r2, r3); d = (ra >> 8) 2^-24 - (rb >> 8) 2^-24: triangular on
+ *   (-1, 1) LSB, exact in fp32, a function of (key, c, t) only.
+ * keys: DEVICE uint64 [n_clips][2] = (seed, stream) of every clip, or NULL: no dither.
+ * interleaved 0: clip b's output is [channels][len] (planar, as its input); 1: [len][channels], written in that order.
+ * --------------------------------------------------------------------------------- */
+/* x [n_clips][channels][len] float32 (4-byte aligned) -> y, n_clips * channels * len int16 at any 2-byte alignment.
+ * channels 1 .. 8, n_clips <= 65535. */
+int fh_pcm_i16_f32(const float* x, int16_t* y, const uint64_t* keys, int n_clips, int channels, int len, int interleaved,
+                   void* stream);
+/* The same for clips of different shapes in one launch; clip c gets the bits of fh_pcm_i16_f32 on that clip alone with
+ * keys[c].  Rows are read where they are: row r of a clip starts at src + r * pitch. */
+typedef struct {
+  const float* src;    /* the clip's first row */
+  int16_t* dst;        /* channels * len int16, any 2-byte alignment */
+  int64_t pitch;       /* floats from one row of the clip to the next */
+  int32_t channels;    /* 1 .. 8 (a clip outside that range, or with len < 1, is left unwritten) */
+  int32_t len;         /* samples per row */
+} fh_pcm_clip;
+int fh_sizeof_pcm_clip(void);
+/* max_channels, max_len: the largest channels / len of the table. */
+int fh_pcm_i16_seg_f32(const fh_pcm_clip* clips, int n_clips, int max_channels, int max_len, const uint64_t* keys,
+                       int interleaved, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
