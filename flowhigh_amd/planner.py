@@ -990,6 +990,45 @@ def _classes(items, key):
     return out.items()
 
 
+def wino_run_map(lengths, wcfg, wpad, dil, pm):
+    """Run list of a ragged Winograd launch (fh_conv_wino_ragged_f32 / fh_conv_wino54_ragged_f32: run_map) whose groups have
+    `lengths`, in launch order, with plan tile id `wcfg`: the runs (consecutive tiles of one (group, co tile) panel, dealt to one
+    XCD; numbered panel * runs per panel + run, the grid being the longest group's) that hold real tiles."""
+    bm, bt = _WINO_TILES[wcfg]
+    cot = wpad // bm
+    n_tiles = wino_n_tiles(wcfg, max(lengths), dil, pm)
+    run_len = wino_run_len(n_tiles)
+    rpp = -(-n_tiles // run_len)
+    runs = []
+    for gi, length in enumerate(lengths):
+        # tile index = (block of bt outputs within the phase) * dil + phase: real while its first
+        # output (phase + dil * bt * block) lies inside the row
+        # (blocks per phase differ by at most one, so the real tiles are 0 .. t_last without holes)
+        if wcfg & WINO_F54 and pm:          # (the F(5,4) kernel's concatenated tiling: a group's real tiles are the first ones)
+            t_last = wino_n_tiles(wcfg, length, dil, pm) - 1
+        else:
+            nb = [max(0, -(-(length - ph) // (dil * bt))) for ph in range(dil)]
+            t_last = dil * (nb[0] - 1) + sum(1 for v in nb if v == nb[0]) - 1
+        own = range(t_last // run_len + 1)
+        for ct in range(cot):
+            runs += [(gi * cot + ct) * rpp + r for r in own]
+    return runs
+
+
+def act_ragged_groups(groups, lengths, channels):
+    """Descriptors of a ragged activation launch (fh_act1d_ragged_f32) from per-clip ones: a copy of each of `groups` with its
+    length and tile_base -- the prefix of channels x tiles per row, fh_act_tile_len() outputs each -- filled in.
+    -> (the copies, the launch's total_tiles, its mult4 flag: every length a multiple of 4)."""
+    tt = hip.lib().fh_act_tile_len()
+    out, base = [], 0
+    for g, length in zip(groups, lengths):
+        g2 = hip.ActGroup.from_buffer_copy(g)
+        g2.len, g2.tile_base = length, base
+        base += channels * -(-length // tt)
+        out.append(g2)
+    return out, base, int(all(g.len % 4 == 0 for g in out))
+
+
 # ---- one merge per step kind: (voc, [(clip, step, host structs)] of one position, blobs) -> the merged steps ------------------
 def _merge_wino(voc, items, blobs):
     assert all(s.batch == 1 and s.ng == len(groups) for _, s, groups in items)
@@ -1006,25 +1045,7 @@ def _merge_wino(voc, items, blobs):
         novl = 0 if (pm or all(t[1] % 4 == 0 for t in allg)) else 2
         if any(s.wcfg & WINO_NOVL for s, _ in lst):             # (segments with xlen: odd-(k - u) upsamplers)
             novl = 2
-        # runs (consecutive tiles of one (group, co tile) panel, dealt to one XCD) that hold real tiles
-        bm, bt = _WINO_TILES[wcfg]
-        cot = wpad // bm
-        n_tiles = wino_n_tiles(wcfg, maxlen, dil, pm)
-        run_len = wino_run_len(n_tiles)
-        rpp = -(-n_tiles // run_len)
-        runs = []
-        for gi, (_, length, _) in enumerate(allg):
-            # tile index = (block of bt outputs within the phase) * dil + phase: real while its first
-            # output (phase + dil * bt * block) lies inside the row
-            # (blocks per phase differ by at most one, so the real tiles are 0 .. t_last without holes)
-            if fam and pm:                  # (the F(5,4) kernel's concatenated tiling: a group's real tiles are the first ones)
-                t_last = wino_n_tiles(wcfg, length, dil, pm) - 1
-            else:
-                nb = [max(0, -(-(length - ph) // (dil * bt))) for ph in range(dil)]
-                t_last = dil * (nb[0] - 1) + sum(1 for v in nb if v == nb[0]) - 1
-            own = range(t_last // run_len + 1)
-            for ct in range(cot):
-                runs += [(gi * cot + ct) * rpp + r for r in own]
+        runs = wino_run_map([t[1] for t in allg], wcfg, wpad, dil, pm)
         off_map = _append(blobs, (C.c_int32 * len(runs))(*runs))
         yield make_step("rwino", _append(blobs, [t[2] for t in allg]), len(allg), wpad, maxlen, dil, wcfg, int(pm) | novl,
                         off_map, len(runs))
@@ -1057,16 +1078,10 @@ def _merge_amp(voc, items, blobs):
 
 
 def _merge_act(voc, items, blobs):
-    tt = hip.lib().fh_act_tile_len()
     for (c, din, dout), lst in _classes(items, lambda s: (s.c, s.din, s.dout)):
-        out, base = [], 0
-        for s, groups in sorted(lst, key=lambda t: -t[0].length):
-            for g in groups:
-                g2 = hip.ActGroup.from_buffer_copy(g)
-                g2.len, g2.tile_base = s.length, base
-                base += c * -(-s.length // tt)
-                out.append(g2)
-        yield make_step("ract", _append(blobs, out), len(out), c, din, dout, base, int(all(g.len % 4 == 0 for g in out)))
+        pairs = [(g, s.length) for s, groups in sorted(lst, key=lambda t: -t[0].length) for g in groups]
+        out, tiles, mult4 = act_ragged_groups([g for g, _ in pairs], [n for _, n in pairs], c)
+        yield make_step("ract", _append(blobs, out), len(out), c, din, dout, tiles, mult4)
 
 
 def _merge_sum(voc, items, blobs):

@@ -9,8 +9,8 @@ import torch
 
 from . import hip
 from .packing import pack_wino54_weight_any, pack_wino_weight_any
-from .planner import (AMP_DIRECT, WINO_BF16X6, WINO_F54, amp_max_center, amp_tile_list, make_act_group, make_wino_group, make_wino_seg, pick_wino54_tile,
-                      pick_wino_tile, use_wino54)
+from .planner import (AMP_DIRECT, WINO_BF16X6, WINO_F54, WINO_NOVL, act_ragged_groups, amp_max_center, amp_tile_list, make_act_group, make_wino_group,
+                      make_wino_seg, pick_wino54_tile, pick_wino_tile, use_wino54, wino_run_map)
 
 def amp_actconv(groups, batch, channels, dilation, device, direct=False):
     """Upload descriptors and enqueue one narrow-stage launch (test / one-off use).  direct: the bf16 x 6 form (groups made with
@@ -33,6 +33,25 @@ def conv_wino(groups, batch, cout_pad, length, dilation, device, tile_cfg=0, pha
     return d
 
 
+def conv_wino_ragged(groups, lengths, cout_pad, dilation, device, tile_cfg=0, phase_major=False):
+    """Upload descriptors and run map and enqueue one ragged Winograd conv launch (test / one-off use): group i is one clip's
+    [C, lengths[i]] tensors (g.len = lengths[i], batch 1), the groups in launch order.  tile_cfg: plan tile id, F(4,3) or
+    WINO_F54 | id, | WINO_BF16X6 for three-piece weights; the vector loader is ruled out as planner._merge_wino does it.
+    -> (descriptors, run map): keep both until the launch has run."""
+    if any(g.len != n for g, n in zip(groups, lengths)) or len(groups) != len(lengths):
+        raise ValueError("conv_wino_ragged: lengths must be the groups' own")
+    if tile_cfg & WINO_F54 and any(g.out_stride > 1 or g.out_len or g.seg[i].ngrp > 3 or g.seg[i].xlen for g in groups for i in range(g.nseg)):
+        raise NotImplementedError("the F(5,4) kernel takes plain convs of at most 12 taps (no strided outputs, xlen, out_len)")
+    wcfg = tile_cfg & (15 | WINO_F54)
+    novl = 0 if ((phase_major or all(n % 4 == 0 for n in lengths)) and not tile_cfg & WINO_NOVL) else 2
+    runs = torch.tensor(wino_run_map(list(lengths), wcfg, cout_pad, dilation, bool(phase_major)), dtype=torch.int32).to(device)
+    d = hip.to_device_struct_array(groups, device)
+    name, cfg = wino_entry(wcfg, tile_cfg & WINO_BF16X6, ragged=True)
+    enqueue(getattr(hip.lib(), name), (d.data_ptr(), len(groups), cout_pad, max(lengths), dilation, int(bool(phase_major)) | novl, cfg,
+                                       runs.data_ptr(), runs.numel(), hip.stream()))
+    return d, runs
+
+
 def conv_grouped(groups, batch, cout_pad, n_len, tile_cfg, device, ck=8, bf=False):
     """Upload descriptors and enqueue one grouped conv launch (test / one-off use).  bf: the bf16 x 6 entry (the groups' weights
     are pack_conv_bf_weight's; every cin a multiple of 16)."""
@@ -45,6 +64,15 @@ def conv_grouped(groups, batch, cout_pad, n_len, tile_cfg, device, ck=8, bf=Fals
 def act1d_grouped(groups, batch, channels, length, device, din=1, dout=1):
     d = hip.to_device_struct_array(groups, device)
     enqueue(hip.lib().fh_act1d_grouped_pm_f32, (d.data_ptr(), len(groups), batch, channels, length, din, dout, hip.stream()))
+    return d
+
+
+def act1d_ragged(groups, lengths, channels, device, din=1, dout=1):
+    """Upload descriptors and enqueue one ragged activation launch (test / one-off use): group i (make_act_group) is one clip's
+    [channels, lengths[i]] tensors, in launch order; length, tile prefix and the mult4 flag as planner._merge_act makes them."""
+    ragged, tiles, mult4 = act_ragged_groups(groups, lengths, channels)
+    d = hip.to_device_struct_array(ragged, device)
+    enqueue(hip.lib().fh_act1d_ragged_f32, (d.data_ptr(), len(ragged), channels, din, dout, tiles, mult4, hip.stream()))
     return d
 
 

@@ -30,14 +30,14 @@ from .packing import (  # noqa: F401
 from .planner import (  # noqa: F401
     AMP_DIRECT, AMP_MAX_D, WINO54_MIN_C, WINO_BF16X6, WINO_BM, WINO_F54, WINO_MAX_K, WINO_MIN_C, WINO_NARROW, WINO_NOVL,
     WINO_UPS_MIN_CIN, WINO_UPS_MIN_CIN_BF, WINO_XCD_RANGES, _PlanBuilder, _TILE_PREF, _WINO_BF_SPEED, _WINO_COST, _WINO_RUN,
-    _WINO_TILES, _WINO_TILES_OFF, _WINO_WIDE_PANEL_MAX, _addr, _choose_wino_cfg, amp_max_center,
+    _WINO_TILES, _WINO_TILES_OFF, _WINO_WIDE_PANEL_MAX, _addr, _choose_wino_cfg, act_ragged_groups, amp_max_center,
     amp_tile_len, amp_tile_list, choose_wino_cfg, make_act_group, make_amp_group, make_amp_seg, make_conv_group,
     make_conv_seg, make_wino_group, make_wino_seg, merge_ragged, pick_tile_cfg, pick_wino54_tile,
     pick_wino_tile, plan_switches, resolve_conv_form, ups_fused_ok, use_amp, use_amp_bf16x6, use_bf16x6, use_direct_bf16x6, wino_ups_min_cin, use_wino, use_wino54, wino_block_mapping,
-    wino_conv_ok, wino_launch_cost, wino_n_tiles, wino_split_k, wino_split_steps, wino_taps)
+    wino_conv_ok, wino_launch_cost, wino_n_tiles, wino_run_len, wino_run_map, wino_split_k, wino_split_steps, wino_taps)
 from .runtime import (  # noqa: F401
-    ACT_BLOCKS_CHOICES, _act_blocks, _act_choice, act1d_grouped, amp_actconv, calibrate_act_occupancy, conv_grouped, ensure_act_blocks,
-    conv_wino, decide_act_blocks, launch_step, measure_act_conv_pair, parse_act_blocks, pick_act_blocks,
+    ACT_BLOCKS_CHOICES, _act_blocks, _act_choice, act1d_grouped, act1d_ragged, amp_actconv, calibrate_act_occupancy, conv_grouped, ensure_act_blocks,
+    conv_wino, conv_wino_ragged, decide_act_blocks, launch_step, measure_act_conv_pair, parse_act_blocks, pick_act_blocks,
     run_ragged_steps, run_steps, sync_act_blocks)
 
 VOC = "flowhigh.audio_enc_dec.vocoder."
