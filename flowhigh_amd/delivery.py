@@ -2,18 +2,22 @@
 
   48 kHz rows -> resample_poly to the output rate (the input side's kernels with the (R, 48000) plan)
               -> level='peak': 0.99 of the clip's own peak again, jointly over its channels (the 48 kHz path's peak kernels)
+              -> loudness=L:  the clip put at L LUFS at the delivered rate (csrc/loudness.hip; loudness.py is the definition):
+                              the rows' peaks, the K-weighted sub-block energies, the gate and gain, the row gain
               -> pcm='int16': one launch of fh_pcm_i16_f32 / fh_pcm_i16_seg_f32 (csrc/pcm.hip; pcm.py is the definition)
 
 `batch` runs the batched entries over clips of one length, `ragged` the segment forms over a group of clips of different
 lengths; rows are read where the post-processor left them, and a clip gets the same bits from either.  With every keyword at
 its default nothing here runs.
 """
+import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import hip, tables
+from . import loudness as _loudness
 from .frontend import _launch, _ptr, clip_array, upload_tables
 from .prior import expand_seed
 
@@ -40,11 +44,18 @@ def resolve_output_rate(output_rate):
     return r
 
 
-def resolve_delivery(n_clips, output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False):
+def resolve_delivery(n_clips, output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False, *, loudness=None,
+                     level="peak"):
     """The delivery keywords of a call over n_clips clips, checked (ValueError, before any GPU work) ->
     None when they are all at their defaults, else dict(rate: None | R, pcm, keys: None | one (seed, stream) per clip,
-    interleaved)."""
+    interleaved), with the key "loudness" (the target in LUFS) only when loudness= is given.  level: the call's level=, which
+    loudness= has to agree with."""
     rate = resolve_output_rate(output_rate)
+    target = _loudness.resolve_loudness(loudness)
+    if target is not None:
+        if level == "input":
+            raise ValueError("loudness= and level='input' are two rules for one gain: loudness= goes with level='peak'")
+        _loudness.geometry(48000 if rate is None else rate)
     if pcm not in _PCM:
         raise ValueError(f"pcm must be one of {_PCM}, got {pcm!r}")
     if dither not in _DITHER:
@@ -61,9 +72,12 @@ def resolve_delivery(n_clips, output_rate=None, pcm=None, dither=None, dither_se
             keys = expand_seed(dither_seed, n_clips)
         except TypeError as e:
             raise ValueError(f"dither_seed: {e}") from e
-    if rate is None and pcm is None:
+    if rate is None and pcm is None and target is None:
         return None
-    return dict(rate=rate, pcm=pcm, keys=keys, interleaved=bool(interleaved))
+    opt = dict(rate=rate, pcm=pcm, keys=keys, interleaved=bool(interleaved))
+    if target is not None:
+        opt["loudness"] = target
+    return opt
 
 
 def delivered_len(t48, output_rate=None):
@@ -110,6 +124,16 @@ class Delivery:
                 self._group_peak(peak, chans)
                 _launch("fh_peak_scale_f32", _ptr(y), _ptr(peak), R, T, 0.99)
         T = y.shape[1]
+        if opt.get("loudness") is not None:
+            if y is rows:
+                y = rows.clone()             # (the rows belong to the post-processor's plan: the gain goes onto the caller's own copy)
+            rate = opt["rate"] or 48000
+            peak = torch.zeros(R, dtype=torch.int32, device=self.device)
+            _launch("fh_peak_abs_f32", _ptr(y), _ptr(peak), R, T)
+            hop, energies = self._energies(rate, R, T)
+            _launch("fh_kweight_energy_f32", _ptr(y), _coef(rate), _ptr(energies), R, T, hop)
+            _, gains = self._gate(energies, [T] * R, chans, hop, opt["loudness"], peak)
+            _launch("fh_row_gain_f32", _ptr(y), _ptr(gains), R, T)
         if opt["pcm"] is None:
             return y if packed else list(y.split(chans))
         out = torch.empty(R * T, dtype=torch.int16, device=self.device)
@@ -128,6 +152,66 @@ class Delivery:
         R = sum(chans)
         group = torch.from_numpy(np.repeat(np.arange(len(chans), dtype=np.int32), chans)).pin_memory().to(self.device, non_blocking=True)
         _launch("fh_group_peak_f32", _ptr(peak), _ptr(torch.ones(R, dtype=torch.float32, device=self.device)), _ptr(group), R)
+
+    def _energies(self, rate, rows, max_len):
+        hop, _ = _loudness.geometry(rate)
+        return hop, torch.empty(rows, -(-max_len // hop), dtype=torch.float64, device=self.device)
+
+    def _gate(self, energies, row_len, chans, hop, target, peak):
+        """fh_loudness_gate_f32 over rows that are chans[i] per clip -> (lufs [n_clips], gains [rows]); target None: measure."""
+        R, n = len(row_len), len(chans)
+        host = np.concatenate([np.asarray(row_len, dtype=np.int32), np.repeat(np.arange(n, dtype=np.int32), chans)])
+        tab = torch.from_numpy(host).pin_memory().to(self.device, non_blocking=True)
+        lufs = torch.empty(n, dtype=torch.float32, device=self.device)
+        gains = torch.empty(R, dtype=torch.float32, device=self.device)
+        _launch("fh_loudness_gate_f32", _ptr(energies), energies.shape[1], _ptr(tab[:R]), _ptr(tab[R:]), R, n, hop,
+                float("nan") if target is None else float(target), _ptr(peak), _ptr(lufs), _ptr(gains))
+        return lufs, gains
+
+    def _loudness_seg(self, srcs, pitches, chans, lens, rate, target, row_table=None):
+        """The segment forms over clips read where they are (clip i: chans[i] rows of lens[i] floats, pitches[i] apart, from
+        srcs[i]) -> (lufs, gains); row_table: the fh_clip per row (dst, len_out) the peak entry takes, made here when None."""
+        R, n, max_len = sum(chans), len(chans), max(lens)
+        row_len = [t for t, c in zip(lens, chans) for _ in range(c)]
+        group = np.repeat(np.arange(n, dtype=np.int32), chans)
+        pcm_table = (hip.PcmClip * n)(*[hip.PcmClip(int(s), 0, int(p), int(c), int(t))
+                                        for s, p, c, t in zip(srcs, pitches, chans, lens)])
+        tables_ = [pcm_table, group]
+        if row_table is None:
+            tables_.append(clip_array(dst=[s + 4 * p * r for s, p, c in zip(srcs, pitches, chans) for r in range(c)], len_out=row_len))
+        desc, ptrs = upload_tables(tables_, self.device)
+        row_table = ptrs[2] if len(ptrs) == 3 else row_table
+        peak = torch.zeros(R, dtype=torch.int32, device=self.device)
+        _launch("fh_peak_abs_seg_f32", row_table, R, max_len, _ptr(peak))
+        hop, energies = self._energies(rate, R, max_len)
+        _launch("fh_kweight_energy_seg_f32", ptrs[0], ptrs[1], n, R, max_len, _coef(rate), _ptr(energies), hop)
+        return self._gate(energies, row_len, chans, hop, target, peak), row_table
+
+    @hip.on_device
+    def measure(self, rows, chans=None, rate=48000):
+        """FlowHighSR.measure_loudness: float32 [R, T] rows (chans[i] per clip; None: every row a clip) or a list of [C_i, T_i]
+        tensors -> float32 [n_clips] LUFS on the device: the kernels of loudness= with no target."""
+        hop, _ = _loudness.geometry(rate)            # (any integer rate with a sub-block of 16 samples or more, not only output rates)
+        rate = int(rate)
+        if isinstance(rows, torch.Tensor):
+            rows = self._rows(rows).contiguous()
+            R, T = rows.shape
+            chans = [1] * R if chans is None else [int(c) for c in chans]
+            if sum(chans) != R or min(chans, default=0) < 1 or T < 1:
+                raise ValueError(f"{R} rows of {T} samples for clips of {chans} channels")
+            peak = torch.zeros(R, dtype=torch.int32, device=self.device)
+            _launch("fh_peak_abs_f32", _ptr(rows), _ptr(peak), R, T)
+            hop, energies = self._energies(rate, R, T)
+            _launch("fh_kweight_energy_f32", _ptr(rows), _coef(rate), _ptr(energies), R, T, hop)
+            return self._gate(energies, [T] * R, chans, hop, None, peak)[0]
+        if chans is not None:
+            raise ValueError("chans= goes with one [R, T] tensor: a list holds one [C_i, T_i] tensor per clip")
+        clips = [self._rows(c) for c in rows]
+        if not clips or min(min(c.shape) for c in clips) < 1:
+            raise ValueError("measure_loudness takes at least one clip, every clip at least one sample")
+        (lufs, _), _ = self._loudness_seg([c.data_ptr() for c in clips], [c.stride(0) for c in clips], [c.shape[0] for c in clips],
+                                         [c.shape[1] for c in clips], rate, None)
+        return lufs
 
     def _pcm_seg(self, srcs, pitches, chans, lens, out, keys, opt):
         off = _starts([c * t for c, t in zip(chans, lens)])
@@ -163,11 +247,32 @@ class Delivery:
                 _launch("fh_peak_scale_seg_f32", table, R, max_len, _ptr(peak), 0.99)
             first = _starts(chans)
             srcs, pitches, lens = [y.data_ptr() + 4 * row_off[r] for r in first], out_lens, out_lens
+        if opt.get("loudness") is not None:
+            if opt["rate"] is None:
+                # (views of the post-processor's buffers: the gain goes onto the caller's own copy, one buffer for the group)
+                y = torch.cat([c.reshape(-1) for c in clips])
+                row_off = _starts([t for t, c in zip(lens, chans) for _ in range(c)])
+                first = _starts(chans)
+                srcs, pitches, table = [y.data_ptr() + 4 * row_off[r] for r in first], lens, None
+            R, max_len = sum(chans), max(lens)
+            (_, gains), table = self._loudness_seg(srcs, pitches, chans, lens, opt["rate"] or 48000, opt["loudness"], table)
+            _launch("fh_row_gain_seg_f32", table, R, max_len, _ptr(gains))
+        if opt["rate"] is not None or opt.get("loudness") is not None:
             if opt["pcm"] is None:
                 return [y[row_off[r]:row_off[r] + c * t].view(c, t) for r, c, t in zip(first, chans, lens)]
         out = torch.empty(sum(c * t for c, t in zip(chans, lens)), dtype=torch.int16, device=self.device)
         self._pcm_seg(srcs, pitches, chans, lens, out, self._keys(opt, which), opt)
         return _clip_views(out, chans, lens, opt["interleaved"])
+
+
+_COEF = {}
+
+
+def _coef(rate):
+    """The K-weighting of `rate` as the host double [10] the energy entries read during the call (kept: the address is passed)."""
+    if rate not in _COEF:
+        _COEF[rate] = (ctypes.c_double * 10)(*_loudness.coefficients(rate))
+    return ctypes.addressof(_COEF[rate])
 
 
 def _starts(lens):

@@ -20,6 +20,8 @@ Extensions over the reference (all keyword-only, defaults keep reference behavio
                                       level instead of 0.99 peak (csrc/level.hip; DESIGN.md "Channels and level")
   generate*(..., output_rate=, pcm=, dither=, dither_seed=, interleaved=)   the result delivered on the device: resampled to
                                       another rate, as int16 PCM (TPDF dither), interleaved [T, C] (delivery.py, csrc/pcm.hip)
+  generate*(..., loudness=L)          the result at L LUFS (ITU-R BS.1770-4) on the device; measure_loudness reads it back
+                                     (loudness.py is the definition, csrc/loudness.hip the kernels; DESIGN.md "Loudness")
 """
 import ctypes
 import json
@@ -944,18 +946,19 @@ class FlowHighSR:
     @hip.on_device
     def generate_batch(self, clips, sr, target_sampling_rate=48000, timestep=1, *, noise=None,
                        generator=None, return_stages=False, seed=None, _keys=None, channels=None, level='peak',
-                       output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False):
+                       output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False, loudness=None):
         """B clips of equal length as one batch -> [B, T48], every clip what generate() returns for it alone.
         channels=, level= (generate): with channels= every clip may have its own number of channels and the result is a list
         of [C_i, T48]; noise= is then one tensor per clip in a list ([1, N, n_mels] shared by the clip's channels, or
         [C_i, N, n_mels]), or [B, N, n_mels]: one shared draw per clip.
         output_rate=, pcm=, dither=, dither_seed=, interleaved= (generate): the same shapes at the output rate, int16 with
-        pcm=; interleaved=True gives [B, T, 1] without channels=, a list of [T, C_i] with it."""
+        pcm=; interleaved=True gives [B, T, 1] without channels=, a list of [T, C_i] with it.  loudness= (generate): every clip
+        at that many LUFS, each by its own gain."""
         clips, planar = resolve_clips(list(clips), channels, level)
         n_clips = len(clips if planar is None else planar)
-        opt = resolve_delivery(n_clips, output_rate, pcm, dither, dither_seed, interleaved)
+        opt = resolve_delivery(n_clips, output_rate, pcm, dither, dither_seed, interleaved, loudness=loudness, level=level)
         if opt is not None and return_stages:
-            raise ValueError("return_stages=True returns the 48 kHz stages: it does not go with output_rate= / pcm=")
+            raise ValueError("return_stages=True returns the 48 kHz stages: it does not go with output_rate= / pcm= / loudness=")
         keys = _keys if _keys is not None else self._prior_keys(seed, n_clips, generator, noise)
         rows, chans, stages = self._batch_rows(clips, planar, keys, sr, target_sampling_rate, timestep, noise, generator, level,
                                                return_stages)
@@ -991,7 +994,7 @@ class FlowHighSR:
     @hip.on_device
     def generate_many(self, clips, sr, target_sampling_rate=48000, timestep=1, *, noise=None, generator=None,
                       max_batch=64, streams=None, ragged=None, max_frames=None, seed=None, ends=None, channels=None,
-                      level='peak', output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False):
+                      level='peak', output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False, loudness=None):
         """Serving-side entry (the gradio caller of app.py:8-26, many requests at once): clips of ANY lengths,
         int16 or float.  Clips of equal length run as one batch (at most max_batch rows), so every result is
         what generate() returns for that clip alone; the prior noise is drawn in the order of `clips`, as a loop
@@ -1026,11 +1029,13 @@ class FlowHighSR:
         int16 ([C_i, T_i], or [T_i, C_i] interleaved).  A batch of equal clips goes through the batched entries, a ragged group
         through their segment forms, one launch per step over the group, reading the rows where the post-processor left
         them; dither_seed=s gives clip i the key (s, i), or it holds one int / (seed, stream) pair per clip.  A clip's result
-        does not depend on how it ran."""
+        does not depend on how it ran.
+        loudness= (generate): every clip at that many LUFS at the delivered rate, each by its own gain; a batch of equal clips
+        through the batched entries of csrc/loudness.hip, a ragged group through their segment forms, the same bits either way."""
         clips = list(clips)
         ends = resolve_ends(ends)
         rates = resolve_rates(sr, len(clips))
-        opt = resolve_delivery(len(clips), output_rate, pcm, dither, dither_seed, interleaved)
+        opt = resolve_delivery(len(clips), output_rate, pcm, dither, dither_seed, interleaved, loudness=loudness, level=level)
         clips, planar = resolve_clips(clips, channels, level)
         chans = None
         if planar is not None:
@@ -1216,6 +1221,14 @@ class FlowHighSR:
             r += c
         return out
 
+    @torch.no_grad()
+    def measure_loudness(self, rows, chans=None, rate=48000):
+        """Integrated loudness on the device: rows = float32 [R, T] on the model's device (chans: channels per clip, summing to
+        R; None: every row is a clip) or a list of [C_i, T_i] tensors; rate: their sample rate -> float32 [n_clips] LUFS on the
+        device, -inf for a clip no block of which passes the gates.  The kernels of loudness= with no target: it reads what a
+        loudness= call delivered, and whether the peak cap bound (flowhigh_amd/loudness.py is the definition)."""
+        return self.delivery.measure(rows, chans, rate)
+
     def _serve_streams(self, n):
         pool = getattr(self, "_side_streams", None)
         if pool is None or len(pool) < n:
@@ -1258,7 +1271,8 @@ class FlowHighSR:
     @torch.no_grad()
     @hip.on_device
     def generate(self, audio, sr: int, target_sampling_rate=48000, timestep=1, *, noise=None, generator=None, seed=None,
-                 channels=None, level='peak', output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False):
+                 channels=None, level='peak', output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False,
+                 loudness=None):
         """One clip, reference contract: returns float32 [1, T48] on the model device.  seed= (prior='device' models): the
         clip's noise is that of the key (seed, 0), or of a (seed, stream) pair given as [(seed, stream)].
         channels = None (default: a mono clip, 1-D or [1, T]; a 2-D clip is then a ValueError) | 'first' ([C, T]) | 'last'
@@ -1278,10 +1292,17 @@ class FlowHighSR:
         pcm = None | 'int16': torch.int16 in the float result's shape, pcm.py's encoding of it (round to nearest even, clamp).
         dither = None | 'tpdf' (pcm only): +-1 LSB triangular dither from the key (dither_seed, 0) -- dither_seed an int, or
         [(seed, stream)]; a function of the key, the channel and the sample index alone.
-        interleaved = True (pcm only): [T, C] ([T, 1] for a mono clip), written in that order by the kernel."""
+        interleaved = True (pcm only): [T, C] ([T, 1] for a mono clip), written in that order by the kernel.
+        loudness = None | L, a finite target in LUFS, -70 <= L <= 0 (-16: streaming and podcasts, -23: EBU R 128): the clip at
+        that integrated loudness (ITU-R BS.1770-4 as loudness.py states it: K-weighting in float64, 400 ms blocks, both gates),
+        measured at the delivered rate after the resampling and before the PCM encoding, one gain for all channels:
+        g = min(10^((L - measured) / 20), 0.99 / peak).  The peak stays at or below 0.99 and there is no limiter, so a clip
+        that would need more comes out below the target (measure_loudness reads what was delivered).  A clip shorter than
+        400 ms is measured as one block of its own length; channel weights are 1 (exact for mono and stereo).  It goes with
+        level='peak' only (level='input' is a ValueError: two rules for one gain); a silent clip stays zeros."""
         out = self.generate_batch([audio], sr, target_sampling_rate, timestep, noise=noise, generator=generator, seed=seed,
                                   channels=channels, level=level, output_rate=output_rate, pcm=pcm, dither=dither,
-                                  dither_seed=dither_seed, interleaved=interleaved)
+                                  dither_seed=dither_seed, interleaved=interleaved, loudness=loudness)
         if channels is not None or (interleaved and pcm is not None):
             return out[0]
         return out

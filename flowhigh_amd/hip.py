@@ -88,7 +88,7 @@ class HipError(RuntimeError):
     pass
 
 
-_P, _I, _F = C.c_void_p, C.c_int, C.c_float
+_P, _I, _F, _D = C.c_void_p, C.c_int, C.c_float, C.c_double
 _SIGS = {
     "fh_abi_version": [],
     "fh_sizeof_conv_group": [],
@@ -184,6 +184,10 @@ _SIGS = {
     "fh_pcm_i16_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
     "fh_sizeof_pcm_clip": [],
     "fh_pcm_i16_seg_f32": [_P, _I, _I, _I, _P, _I, _P],
+    "fh_loudness_span_len": [],
+    "fh_kweight_energy_f32": [_P, _P, _P, _I, _I, _I, _P],
+    "fh_kweight_energy_seg_f32": [_P, _P, _I, _I, _I, _P, _P, _I, _P],
+    "fh_loudness_gate_f32": [_P, _I, _P, _P, _I, _I, _I, _D, _P, _P, _P, _P],
 }
 EXPORTS = sorted(_SIGS) + ["fh_last_error"]
 

@@ -57,13 +57,15 @@ class BatchingServer:
 
     # ---- caller side -------------------------------------------------------------------------------
     def submit(self, audio, sr_in, timestep=1, seed=None, *, channels=None, level='peak', output_rate=None, pcm=None,
-               dither=None, dither_seed=0):
+               dither=None, dither_seed=0, loudness=None):
         """Queue one clip (int16 or float, 1-D or [1, T]); returns a Future of a float32 numpy array [T48].
         channels = 'first' ([C, T]) | 'last' ([T, C]): a multichannel clip (FlowHighSR.generate), the Future's array is
         [C, T48].  level = 'peak' | 'input' as in generate.  A shape that fits no layout is a ValueError here.
         output_rate=, pcm=, dither=, dither_seed= as in generate (dither_seed: an int s = the key (s, 0), or a (seed, stream)
         pair), checked here; requests are grouped by them too.  With pcm= the Future's array is int16, and a channels='last'
-        request gets it in its own layout, [T, C], written that way on the device."""
+        request gets it in its own layout, [T, C], written that way on the device.
+        loudness = None | a target in LUFS as in generate: requests are grouped by it, and it is handed to generate_many only
+        where a request gave it."""
         if self._closed:
             raise RuntimeError("server is closed")
         from .delivery import resolve_delivery
@@ -73,10 +75,10 @@ class BatchingServer:
             dither_seed = tuple(dither_seed)
             if len(dither_seed) != 2:
                 raise ValueError(f"dither_seed of a request is an int or a (seed, stream) pair, got {dither_seed!r}")
-        opt = resolve_delivery(1, output_rate, pcm, dither, [dither_seed])
+        opt = resolve_delivery(1, output_rate, pcm, dither, [dither_seed], loudness=loudness, level=level)
         deliv = None
         if opt is not None:
-            deliv = (opt["rate"], opt["pcm"], dither, bool(pcm is not None and channels == 'last'), dither_seed)
+            deliv = (opt["rate"], opt["pcm"], dither, bool(pcm is not None and channels == 'last'), opt.get("loudness"), dither_seed)
         a = np.asarray(audio.detach().cpu() if isinstance(audio, torch.Tensor) else audio)
         planar = resolve_channels(a, channels)
         if channels is not None:
@@ -142,8 +144,8 @@ class BatchingServer:
             groups = {}
             for item in batch:
                 # same step count and level; mix_rates off: same input rate too
-                # ... and the same delivery (output rate, sample format, dither, layout; the dither seed is the request's own)
-                groups.setdefault((None if self.mix_rates else item[1], item[2], item[5], item[6] and item[6][:4]), []).append(item)
+                # ... and the same delivery (output rate, sample format, dither, layout, loudness; the dither seed is the request's own)
+                groups.setdefault((None if self.mix_rates else item[1], item[2], item[5], item[6] and item[6][:5]), []).append(item)
             for (sr_in, steps, level, deliv), items in groups.items():
                 try:
                     # (handed on only where a request asked: a model whose generate_many predates the keywords keeps working.
@@ -153,10 +155,11 @@ class BatchingServer:
                     if level != 'peak':
                         level_kw["level"] = level
                     if deliv is not None:
-                        rate, pcm, dither, interleaved = deliv
-                        level_kw.update({k: v for k, v in (("output_rate", rate), ("pcm", pcm), ("dither", dither)) if v is not None})
+                        rate, pcm, dither, interleaved, target = deliv
+                        level_kw.update({k: v for k, v in (("output_rate", rate), ("pcm", pcm), ("dither", dither),
+                                                           ("loudness", target)) if v is not None})
                         if dither is not None:
-                            level_kw["dither_seed"] = [it[6][4] for it in items]
+                            level_kw["dither_seed"] = [it[6][5] for it in items]
                         if interleaved:
                             level_kw["interleaved"] = True
                     if sr_in is None:

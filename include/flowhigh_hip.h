@@ -697,6 +697,36 @@ int fh_sizeof_pcm_clip(void);
 int fh_pcm_i16_seg_f32(const fh_pcm_clip* clips, int n_clips, int max_channels, int max_len, const uint64_t* keys,
                        int interleaved, void* stream);
 
+/* -----------------------------------------------------------------------------------
+ * Integrated loudness on the device (csrc/loudness.hip; FlowHighSR.generate*(loudness=L), FlowHighSR.measure_loudness): ITU-R
+ * BS.1770-4 as flowhigh_amd/loudness.py defines it -- K-weighting, 100 ms sub-block energies, 400 ms blocks at 75 % overlap,
+ * the absolute gate at -70 LUFS and the relative gate 10 LU below the absolute-gated mean, both strict.  Everything behind the
+ * float32 load is float64.  A clip shorter than one block is one block of its whole length; every channel weight is 1.0.
+ * --------------------------------------------------------------------------------- */
+/* Samples per span of the K-weighting recursion: one workgroup walks the spans of a row in order (tests stand either side). */
+int fh_loudness_span_len(void);
+/* energies[r, i] = sum over n in [i hop, min((i + 1) hop, len)) of y[r, n]^2, i < n_sub = ceil(len / hop), y = the K-weighted
+ * row r of x [rows, len] (float32, 4-byte aligned); energies: DEVICE double [rows, n_sub].
+ * coef: HOST double [10] = shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 (a0 = 1), read before the call returns.
+ * hop >= 16 (a rate of 155 Hz or more); rows <= 65535; len <= 2^30.  A row's result depends on that row alone. */
+int fh_kweight_energy_f32(const float* x, const double* coef, double* energies, int rows, int len, int hop, void* stream);
+/* The same over clips read where they are: row r is channel r - (first row of its clip) of clip group[r] of the table (src,
+ * pitch, channels, len are read; dst is not).  group: device int32 [rows], non-decreasing, with values in [0, n_clips).
+ * energies: DEVICE double [rows, ceil(max_len / hop)], row r written up to its own ceil(len / hop); max_len: the largest len
+ * of the table (a clip longer than that, or with len < 1, is left unwritten).  Row r gets the bits of
+ * fh_kweight_energy_f32 on that row alone. */
+int fh_kweight_energy_seg_f32(const fh_pcm_clip* clips, const int32_t* group, int n_clips, int rows, int max_len,
+                              const double* coef, double* energies, int hop, void* stream);
+/* One workgroup per clip: lufs[c] = the gated loudness of clip c (float32; -inf when no block passes a gate), whose rows are
+ * those r with group[r] == c (group as above; every row of a clip has the clip's length lens[r]); energies: DEVICE double
+ * [rows, n_sub] as the entries above leave it.  gains[r] = the clip's gain in each of its rows:
+ *   fl32(min(10^((target - lufs[c]) / 20), 0.99 / peak)), peak = the largest of the rows' peak_bits (non-negative float bits, as
+ *   fh_peak_abs_f32 leaves them); 1 when lufs[c] is not finite or the peak is 0 or not finite.
+ * The gain is a function of the float32 lufs[c] that is written.  target: -70 .. 0 LUFS, or NaN: measure only, every gain 1.
+ * Double arithmetic, blocks summed in ascending order. */
+int fh_loudness_gate_f32(const double* energies, int n_sub, const int32_t* lens, const int32_t* group, int rows, int n_clips,
+                         int hop, double target, const uint32_t* peak_bits, float* lufs, float* gains, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
