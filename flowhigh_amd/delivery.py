@@ -4,6 +4,9 @@
               -> level='peak': 0.99 of the clip's own peak again, jointly over its channels (the 48 kHz path's peak kernels)
               -> loudness=L:  the clip put at L LUFS at the delivered rate (csrc/loudness.hip; loudness.py is the definition):
                               the rows' peaks, the K-weighted sub-block energies, the gate and gain, the row gain
+              -> true_peak=T: the clip held under T dBTP (csrc/truepeak.hip; truepeak.py is the definition): one gain from its
+                              4x oversampled peak, or with limiter='lookahead' the oversampled envelope and the look-ahead
+                              limiter (behind the UNCAPPED loudness gain where loudness= is given as well)
               -> pcm='int16': one launch of fh_pcm_i16_f32 / fh_pcm_i16_seg_f32 (csrc/pcm.hip; pcm.py is the definition)
 
 `batch` runs the batched entries over clips of one length, `ragged` the segment forms over a group of clips of different
@@ -18,6 +21,7 @@ import torch
 
 from . import hip, tables
 from . import loudness as _loudness
+from . import truepeak as _truepeak
 from .frontend import _launch, _ptr, clip_array, upload_tables
 from .prior import expand_seed
 
@@ -45,13 +49,15 @@ def resolve_output_rate(output_rate):
 
 
 def resolve_delivery(n_clips, output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False, *, loudness=None,
-                     level="peak"):
+                     level="peak", true_peak=None, limiter=None):
     """The delivery keywords of a call over n_clips clips, checked (ValueError, before any GPU work) ->
     None when they are all at their defaults, else dict(rate: None | R, pcm, keys: None | one (seed, stream) per clip,
-    interleaved), with the key "loudness" (the target in LUFS) only when loudness= is given.  level: the call's level=, which
-    loudness= has to agree with."""
+    interleaved), with the key "loudness" (the target in LUFS) only when loudness= is given, and the keys "true_peak" (the ceiling
+    in dBTP) and "limiter" only when true_peak= is given.  level: the call's level=, which loudness= has to agree with
+    (true_peak= goes with either level: its rule only attenuates)."""
     rate = resolve_output_rate(output_rate)
     target = _loudness.resolve_loudness(loudness)
+    ceiling, limiter = _truepeak.resolve_true_peak(true_peak, limiter, 48000 if rate is None else rate)
     if target is not None:
         if level == "input":
             raise ValueError("loudness= and level='input' are two rules for one gain: loudness= goes with level='peak'")
@@ -72,11 +78,14 @@ def resolve_delivery(n_clips, output_rate=None, pcm=None, dither=None, dither_se
             keys = expand_seed(dither_seed, n_clips)
         except TypeError as e:
             raise ValueError(f"dither_seed: {e}") from e
-    if rate is None and pcm is None and target is None:
+    if rate is None and pcm is None and target is None and ceiling is None:
         return None
     opt = dict(rate=rate, pcm=pcm, keys=keys, interleaved=bool(interleaved))
     if target is not None:
         opt["loudness"] = target
+    if ceiling is not None:
+        opt["true_peak"] = ceiling
+        opt["limiter"] = limiter
     return opt
 
 
@@ -90,6 +99,7 @@ class Delivery:
     def __init__(self, device, resampler):
         self.device = hip.norm_device(device)
         self.resampler = resampler            # its tap cache holds the (R, 48000) filters beside the input side's
+        self._windows = {}                    # half window H -> the limiter's device double [2 H + 1]
 
     def _keys(self, opt, which):
         """Device int64 [n, 2] of the clips `which` of the call, or None without dither."""
@@ -124,16 +134,41 @@ class Delivery:
                 self._group_peak(peak, chans)
                 _launch("fh_peak_scale_f32", _ptr(y), _ptr(peak), R, T, 0.99)
         T = y.shape[1]
-        if opt.get("loudness") is not None:
-            if y is rows:
-                y = rows.clone()             # (the rows belong to the post-processor's plan: the gain goes onto the caller's own copy)
-            rate = opt["rate"] or 48000
+        target, ceiling = opt.get("loudness"), opt.get("true_peak")
+        if (target is not None or ceiling is not None) and y is rows:
+            y = rows.clone()                 # (the rows belong to the post-processor's plan: the gain goes onto the caller's own copy)
+        rate = opt["rate"] or 48000
+        lufs = peak = None
+        if target is not None:
             peak = torch.zeros(R, dtype=torch.int32, device=self.device)
             _launch("fh_peak_abs_f32", _ptr(y), _ptr(peak), R, T)
             hop, energies = self._energies(rate, R, T)
             _launch("fh_kweight_energy_f32", _ptr(y), _coef(rate), _ptr(energies), R, T, hop)
-            _, gains = self._gate(energies, [T] * R, chans, hop, opt["loudness"], peak)
-            _launch("fh_row_gain_f32", _ptr(y), _ptr(gains), R, T)
+            # (with true_peak= the gate only measures: the gain is composed by fh_delivery_gain_f32)
+            lufs, gains = self._gate(energies, [T] * R, chans, hop, None if ceiling is not None else target, peak)
+            if ceiling is None:
+                _launch("fh_row_gain_f32", _ptr(y), _ptr(gains), R, T)
+        if ceiling is not None:
+            group = self._group(chans)
+            if opt["limiter"] is None:
+                tp = torch.zeros(R, dtype=torch.int32, device=self.device)
+                _launch("fh_true_peak_f32", _ptr(y), self._tp_taps(), _ptr(tp), R, T)
+                gains = self._delivery_gain(lufs, target, peak, tp, group, R, n, ceiling, False)
+                _launch("fh_row_gain_f32", _ptr(y), _ptr(gains), R, T)
+            else:
+                if target is not None:
+                    gains = self._delivery_gain(lufs, target, None, None, group, R, n, ceiling, True)
+                    _launch("fh_row_gain_f32", _ptr(y), _ptr(gains), R, T)
+                H, c32 = _truepeak.half_window(rate), float(np.float32(_truepeak.ceiling(ceiling)))
+                m = torch.empty(n, T, dtype=torch.float32, device=self.device)
+                if len(set(chans)) == 1:
+                    _launch("fh_tp_envelope_f32", _ptr(y), self._tp_taps(), _ptr(m), n, chans[0], T)
+                    _launch("fh_limit_f32", _ptr(y), _ptr(y), _ptr(m), self._window(H), 0, n, chans[0], T, H, c32)
+                else:                  # clips of different channel counts: the segment forms, in place
+                    table = (hip.PcmClip * n)(*[hip.PcmClip(y.data_ptr() + 4 * T * r, 0, T, c, T) for r, c in zip(_starts(chans), chans)])
+                    desc, (clips,) = upload_tables([table], self.device)
+                    _launch("fh_tp_envelope_seg_f32", clips, n, T, self._tp_taps(), _ptr(m))
+                    _launch("fh_limit_seg_f32", clips, n, T, _ptr(m), self._window(H), 0, H, c32)
         if opt["pcm"] is None:
             return y if packed else list(y.split(chans))
         out = torch.empty(R * T, dtype=torch.int16, device=self.device)
@@ -150,8 +185,33 @@ class Delivery:
         """The rows' peak slots -> the joint peak of every clip in all of its rows' slots; a silent clip's becomes 1.0, so the
         scaling leaves its zeros (fh_group_peak_f32 with every gain 1: fl(q * 1) = q)."""
         R = sum(chans)
-        group = torch.from_numpy(np.repeat(np.arange(len(chans), dtype=np.int32), chans)).pin_memory().to(self.device, non_blocking=True)
+        group = self._group(chans)
         _launch("fh_group_peak_f32", _ptr(peak), _ptr(torch.ones(R, dtype=torch.float32, device=self.device)), _ptr(group), R)
+
+    def _group(self, chans):
+        """Device int32 [rows]: the clip of every row."""
+        return torch.from_numpy(np.repeat(np.arange(len(chans), dtype=np.int32), chans)).pin_memory().to(self.device, non_blocking=True)
+
+    def _tp_taps(self):
+        """The device taps of the 4x oversampling: the resampler's own (4, 1) filter, from its tap cache."""
+        taps, n_taps, pre, up, down = self.resampler._filter(4 * 48000, 48000)
+        assert (n_taps, pre, up, down) == (_truepeak.N_TAPS + 1, 4 * _truepeak.HALF + 1, 4, 1)
+        return taps
+
+    def _window(self, H):
+        """The limiter's Hann weights for the half window H as a device double [2 H + 1], made once per H."""
+        if H not in self._windows:
+            self._windows[H] = torch.from_numpy(_truepeak.window(H)).to(self.device)
+        return self._windows[H].data_ptr()
+
+    def _delivery_gain(self, lufs, target, peak, tp, group, R, n, ceiling, uncapped, dbtp=None):
+        """fh_delivery_gain_f32 -> gains [R] (None when only dbtp is asked for); ceiling in dBTP; group: a device int32 [R] tensor or
+        its address."""
+        gains = None if dbtp is not None else torch.empty(R, dtype=torch.float32, device=self.device)
+        _launch("fh_delivery_gain_f32", hip.ptr(lufs), float("nan") if target is None else float(target), hip.ptr(peak), hip.ptr(tp),
+                group if isinstance(group, int) else _ptr(group), R, n, 1.0 if ceiling is None else _truepeak.ceiling(ceiling),
+                int(uncapped), hip.ptr(gains), hip.ptr(dbtp))
+        return gains
 
     def _energies(self, rate, rows, max_len):
         hop, _ = _loudness.geometry(rate)
@@ -171,7 +231,14 @@ class Delivery:
     def _loudness_seg(self, srcs, pitches, chans, lens, rate, target, row_table=None):
         """The segment forms over clips read where they are (clip i: chans[i] rows of lens[i] floats, pitches[i] apart, from
         srcs[i]) -> (lufs, gains); row_table: the fh_clip per row (dst, len_out) the peak entry takes, made here when None."""
-        R, n, max_len = sum(chans), len(chans), max(lens)
+        seg = self._seg_tables(srcs, pitches, chans, lens, row_table)
+        lufs, gains, _ = self._loudness_on(seg, chans, lens, rate, target)
+        return (lufs, gains), seg["rows"]
+
+    def _seg_tables(self, srcs, pitches, chans, lens, row_table=None):
+        """The device tables of a group of clips read where they are -> dict(keep, clips: the fh_pcm_clip table (dst NULL), group:
+        int32 [rows], rows: the fh_clip per row, row_len)."""
+        n = len(chans)
         row_len = [t for t, c in zip(lens, chans) for _ in range(c)]
         group = np.repeat(np.arange(n, dtype=np.int32), chans)
         pcm_table = (hip.PcmClip * n)(*[hip.PcmClip(int(s), 0, int(p), int(c), int(t))
@@ -180,12 +247,16 @@ class Delivery:
         if row_table is None:
             tables_.append(clip_array(dst=[s + 4 * p * r for s, p, c in zip(srcs, pitches, chans) for r in range(c)], len_out=row_len))
         desc, ptrs = upload_tables(tables_, self.device)
-        row_table = ptrs[2] if len(ptrs) == 3 else row_table
+        return dict(keep=desc, clips=ptrs[0], group=ptrs[1], rows=ptrs[2] if len(ptrs) == 3 else row_table, row_len=row_len)
+
+    def _loudness_on(self, seg, chans, lens, rate, target):
+        """The loudness launches over _seg_tables' tables -> (lufs, gains, the rows' peak slots)."""
+        R, n, max_len = sum(chans), len(chans), max(lens)
         peak = torch.zeros(R, dtype=torch.int32, device=self.device)
-        _launch("fh_peak_abs_seg_f32", row_table, R, max_len, _ptr(peak))
+        _launch("fh_peak_abs_seg_f32", seg["rows"], R, max_len, _ptr(peak))
         hop, energies = self._energies(rate, R, max_len)
-        _launch("fh_kweight_energy_seg_f32", ptrs[0], ptrs[1], n, R, max_len, _coef(rate), _ptr(energies), hop)
-        return self._gate(energies, row_len, chans, hop, target, peak), row_table
+        _launch("fh_kweight_energy_seg_f32", seg["clips"], seg["group"], n, R, max_len, _coef(rate), _ptr(energies), hop)
+        return (*self._gate(energies, seg["row_len"], chans, hop, target, peak), peak)
 
     @hip.on_device
     def measure(self, rows, chans=None, rate=48000):
@@ -212,6 +283,37 @@ class Delivery:
         (lufs, _), _ = self._loudness_seg([c.data_ptr() for c in clips], [c.stride(0) for c in clips], [c.shape[0] for c in clips],
                                          [c.shape[1] for c in clips], rate, None)
         return lufs
+
+    @hip.on_device
+    def measure_true_peak(self, rows, chans=None, rate=48000):
+        """FlowHighSR.measure_true_peak: rows as measure() takes them -> float32 [n_clips] dBTP on the device (-inf for silence):
+        fh_true_peak_f32 / fh_true_peak_seg_f32 and the joint maximum of fh_delivery_gain_f32."""
+        if isinstance(rate, (bool, str, bytes)) or int(rate) != rate or int(rate) <= 0:
+            raise ValueError(f"rate must be a positive integer, got {rate!r}")          # (the factor is 4 at every rate)
+        if isinstance(rows, torch.Tensor):
+            rows = self._rows(rows).contiguous()
+            R, T = rows.shape
+            chans = [1] * R if chans is None else [int(c) for c in chans]
+            if sum(chans) != R or min(chans, default=0) < 1 or T < 1:
+                raise ValueError(f"{R} rows of {T} samples for clips of {chans} channels")
+            tp = torch.zeros(R, dtype=torch.int32, device=self.device)
+            _launch("fh_true_peak_f32", _ptr(rows), self._tp_taps(), _ptr(tp), R, T)
+            group = self._group(chans)
+        else:
+            if chans is not None:
+                raise ValueError("chans= goes with one [R, T] tensor: a list holds one [C_i, T_i] tensor per clip")
+            clips = [self._rows(c) for c in rows]
+            if not clips or min(min(c.shape) for c in clips) < 1:
+                raise ValueError("measure_true_peak takes at least one clip, every clip at least one sample")
+            chans, lens = [c.shape[0] for c in clips], [c.shape[1] for c in clips]
+            R = sum(chans)
+            seg = self._seg_tables([c.data_ptr() for c in clips], [c.stride(0) for c in clips], chans, lens, row_table=0)
+            tp = torch.zeros(R, dtype=torch.int32, device=self.device)
+            _launch("fh_true_peak_seg_f32", seg["clips"], seg["group"], len(chans), R, max(lens), self._tp_taps(), _ptr(tp))
+            group = seg["group"]
+        dbtp = torch.empty(len(chans), dtype=torch.float32, device=self.device)
+        self._delivery_gain(None, None, None, tp, group, R, len(chans), None, False, dbtp=dbtp)
+        return dbtp
 
     def _pcm_seg(self, srcs, pitches, chans, lens, out, keys, opt):
         off = _starts([c * t for c, t in zip(chans, lens)])
@@ -247,17 +349,35 @@ class Delivery:
                 _launch("fh_peak_scale_seg_f32", table, R, max_len, _ptr(peak), 0.99)
             first = _starts(chans)
             srcs, pitches, lens = [y.data_ptr() + 4 * row_off[r] for r in first], out_lens, out_lens
-        if opt.get("loudness") is not None:
+        target, ceiling = opt.get("loudness"), opt.get("true_peak")
+        if target is not None or ceiling is not None:
             if opt["rate"] is None:
                 # (views of the post-processor's buffers: the gain goes onto the caller's own copy, one buffer for the group)
                 y = torch.cat([c.reshape(-1) for c in clips])
                 row_off = _starts([t for t, c in zip(lens, chans) for _ in range(c)])
                 first = _starts(chans)
                 srcs, pitches, table = [y.data_ptr() + 4 * row_off[r] for r in first], lens, None
-            R, max_len = sum(chans), max(lens)
-            (_, gains), table = self._loudness_seg(srcs, pitches, chans, lens, opt["rate"] or 48000, opt["loudness"], table)
-            _launch("fh_row_gain_seg_f32", table, R, max_len, _ptr(gains))
-        if opt["rate"] is not None or opt.get("loudness") is not None:
+            R, max_len, rate = sum(chans), max(lens), opt["rate"] or 48000
+            seg = self._seg_tables(srcs, pitches, chans, lens, table)
+            lufs = peak = None
+            if target is not None:
+                lufs, gains, peak = self._loudness_on(seg, chans, lens, rate, None if ceiling is not None else target)
+                if ceiling is None:
+                    _launch("fh_row_gain_seg_f32", seg["rows"], R, max_len, _ptr(gains))
+            if ceiling is not None and opt["limiter"] is None:
+                tp = torch.zeros(R, dtype=torch.int32, device=self.device)
+                _launch("fh_true_peak_seg_f32", seg["clips"], seg["group"], n, R, max_len, self._tp_taps(), _ptr(tp))
+                gains = self._delivery_gain(lufs, target, peak, tp, seg["group"], R, n, ceiling, False)
+                _launch("fh_row_gain_seg_f32", seg["rows"], R, max_len, _ptr(gains))
+            elif ceiling is not None:
+                if target is not None:
+                    gains = self._delivery_gain(lufs, target, None, None, seg["group"], R, n, ceiling, True)
+                    _launch("fh_row_gain_seg_f32", seg["rows"], R, max_len, _ptr(gains))
+                H, c32 = _truepeak.half_window(rate), float(np.float32(_truepeak.ceiling(ceiling)))
+                m = torch.empty(n, max_len, dtype=torch.float32, device=self.device)
+                _launch("fh_tp_envelope_seg_f32", seg["clips"], n, max_len, self._tp_taps(), _ptr(m))
+                _launch("fh_limit_seg_f32", seg["clips"], n, max_len, _ptr(m), self._window(H), 0, H, c32)
+        if opt["rate"] is not None or target is not None or ceiling is not None:
             if opt["pcm"] is None:
                 return [y[row_off[r]:row_off[r] + c * t].view(c, t) for r, c, t in zip(first, chans, lens)]
         out = torch.empty(sum(c * t for c, t in zip(chans, lens)), dtype=torch.int16, device=self.device)

@@ -22,6 +22,8 @@ Extensions over the reference (all keyword-only, defaults keep reference behavio
                                       another rate, as int16 PCM (TPDF dither), interleaved [T, C] (delivery.py, csrc/pcm.hip)
   generate*(..., loudness=L)          the result at L LUFS (ITU-R BS.1770-4) on the device; measure_loudness reads it back
                                      (loudness.py is the definition, csrc/loudness.hip the kernels; DESIGN.md "Loudness")
+  generate*(..., true_peak=T, limiter=)   the result under T dBTP, by one gain or by a look-ahead limiter; measure_true_peak reads it
+                                     back (truepeak.py is the definition, csrc/truepeak.hip the kernels; DESIGN.md "True peak and limiter")
 """
 import ctypes
 import json
@@ -946,19 +948,23 @@ class FlowHighSR:
     @hip.on_device
     def generate_batch(self, clips, sr, target_sampling_rate=48000, timestep=1, *, noise=None,
                        generator=None, return_stages=False, seed=None, _keys=None, channels=None, level='peak',
-                       output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False, loudness=None):
+                       output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False, loudness=None,
+                       true_peak=None, limiter=None):
         """B clips of equal length as one batch -> [B, T48], every clip what generate() returns for it alone.
         channels=, level= (generate): with channels= every clip may have its own number of channels and the result is a list
         of [C_i, T48]; noise= is then one tensor per clip in a list ([1, N, n_mels] shared by the clip's channels, or
         [C_i, N, n_mels]), or [B, N, n_mels]: one shared draw per clip.
         output_rate=, pcm=, dither=, dither_seed=, interleaved= (generate): the same shapes at the output rate, int16 with
         pcm=; interleaved=True gives [B, T, 1] without channels=, a list of [T, C_i] with it.  loudness= (generate): every clip
-        at that many LUFS, each by its own gain."""
+        at that many LUFS, each by its own gain.  true_peak=, limiter= (generate): every clip under that ceiling in dBTP, each by
+        its own gain or its own limiter gain."""
         clips, planar = resolve_clips(list(clips), channels, level)
         n_clips = len(clips if planar is None else planar)
-        opt = resolve_delivery(n_clips, output_rate, pcm, dither, dither_seed, interleaved, loudness=loudness, level=level)
+        opt = resolve_delivery(n_clips, output_rate, pcm, dither, dither_seed, interleaved, loudness=loudness, level=level,
+                               true_peak=true_peak, limiter=limiter)
         if opt is not None and return_stages:
-            raise ValueError("return_stages=True returns the 48 kHz stages: it does not go with output_rate= / pcm= / loudness=")
+            raise ValueError("return_stages=True returns the 48 kHz stages: it does not go with output_rate= / pcm= / loudness= / "
+                             "true_peak=")
         keys = _keys if _keys is not None else self._prior_keys(seed, n_clips, generator, noise)
         rows, chans, stages = self._batch_rows(clips, planar, keys, sr, target_sampling_rate, timestep, noise, generator, level,
                                                return_stages)
@@ -994,7 +1000,8 @@ class FlowHighSR:
     @hip.on_device
     def generate_many(self, clips, sr, target_sampling_rate=48000, timestep=1, *, noise=None, generator=None,
                       max_batch=64, streams=None, ragged=None, max_frames=None, seed=None, ends=None, channels=None,
-                      level='peak', output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False, loudness=None):
+                      level='peak', output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False, loudness=None,
+                      true_peak=None, limiter=None):
         """Serving-side entry (the gradio caller of app.py:8-26, many requests at once): clips of ANY lengths,
         int16 or float.  Clips of equal length run as one batch (at most max_batch rows), so every result is
         what generate() returns for that clip alone; the prior noise is drawn in the order of `clips`, as a loop
@@ -1031,11 +1038,14 @@ class FlowHighSR:
         them; dither_seed=s gives clip i the key (s, i), or it holds one int / (seed, stream) pair per clip.  A clip's result
         does not depend on how it ran.
         loudness= (generate): every clip at that many LUFS at the delivered rate, each by its own gain; a batch of equal clips
-        through the batched entries of csrc/loudness.hip, a ragged group through their segment forms, the same bits either way."""
+        through the batched entries of csrc/loudness.hip, a ragged group through their segment forms, the same bits either way.
+        true_peak=, limiter= (generate): every clip under that ceiling in dBTP, through the batched entries of csrc/truepeak.hip or
+        their segment forms, the same bits either way."""
         clips = list(clips)
         ends = resolve_ends(ends)
         rates = resolve_rates(sr, len(clips))
-        opt = resolve_delivery(len(clips), output_rate, pcm, dither, dither_seed, interleaved, loudness=loudness, level=level)
+        opt = resolve_delivery(len(clips), output_rate, pcm, dither, dither_seed, interleaved, loudness=loudness, level=level,
+                               true_peak=true_peak, limiter=limiter)
         clips, planar = resolve_clips(clips, channels, level)
         chans = None
         if planar is not None:
@@ -1229,6 +1239,14 @@ class FlowHighSR:
         loudness= call delivered, and whether the peak cap bound (flowhigh_amd/loudness.py is the definition)."""
         return self.delivery.measure(rows, chans, rate)
 
+    @torch.no_grad()
+    def measure_true_peak(self, rows, chans=None, rate=48000):
+        """True peak on the device: rows, chans and rate as measure_loudness takes them -> float32 [n_clips] dBTP on the device,
+        -inf for a silent clip: the largest of the samples and of their 4x oversampling (81 taps, the same at every rate) over
+        the clip's channels.  The kernels of true_peak=: it reads what a true_peak= call delivered (flowhigh_amd/truepeak.py is
+        the definition)."""
+        return self.delivery.measure_true_peak(rows, chans, rate)
+
     def _serve_streams(self, n):
         pool = getattr(self, "_side_streams", None)
         if pool is None or len(pool) < n:
@@ -1272,7 +1290,7 @@ class FlowHighSR:
     @hip.on_device
     def generate(self, audio, sr: int, target_sampling_rate=48000, timestep=1, *, noise=None, generator=None, seed=None,
                  channels=None, level='peak', output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False,
-                 loudness=None):
+                 loudness=None, true_peak=None, limiter=None):
         """One clip, reference contract: returns float32 [1, T48] on the model device.  seed= (prior='device' models): the
         clip's noise is that of the key (seed, 0), or of a (seed, stream) pair given as [(seed, stream)].
         channels = None (default: a mono clip, 1-D or [1, T]; a 2-D clip is then a ValueError) | 'first' ([C, T]) | 'last'
@@ -1296,13 +1314,24 @@ class FlowHighSR:
         loudness = None | L, a finite target in LUFS, -70 <= L <= 0 (-16: streaming and podcasts, -23: EBU R 128): the clip at
         that integrated loudness (ITU-R BS.1770-4 as loudness.py states it: K-weighting in float64, 400 ms blocks, both gates),
         measured at the delivered rate after the resampling and before the PCM encoding, one gain for all channels:
-        g = min(10^((L - measured) / 20), 0.99 / peak).  The peak stays at or below 0.99 and there is no limiter, so a clip
+        g = min(10^((L - measured) / 20), 0.99 / peak).  The peak stays at or below 0.99, so without limiter= a clip
         that would need more comes out below the target (measure_loudness reads what was delivered).  A clip shorter than
         400 ms is measured as one block of its own length; channel weights are 1 (exact for mono and stereo).  It goes with
-        level='peak' only (level='input' is a ValueError: two rules for one gain); a silent clip stays zeros."""
+        level='peak' only (level='input' is a ValueError: two rules for one gain); a silent clip stays zeros.
+        true_peak = None | T, a finite ceiling in dBTP, -20 <= T <= 0 (-1: the usual delivery spec): the true peak of the result --
+        the largest of its samples and of their 4x oversampling (ITU-R BS.1770-4 Annex 2 as truepeak.py states it: 81 taps, factor
+        4 at every rate), over the clip's channels, at the delivered rate -- is held at or under T, behind the resampling and the
+        loudness measurement and before the PCM encoding.  It only attenuates, so it goes with either level=.
+        limiter = None: one gain for the clip, g = min(g_L, 10^(T / 20) / TP), g_L the gain of loudness= (1 without it) |
+        'lookahead' (with true_peak= only): a zero-delay look-ahead limiter, 5 ms either side, one gain curve for all channels
+        (the stereo image stays), no sample above the ceiling; with loudness= the loudness gain is then NOT capped at the 0.99
+        peak, the limiter takes what is over, and the delivered loudness ends slightly under the target (nothing iterates;
+        measure_loudness reads it).  A delivered rate above 102 499 Hz is a ValueError (the limiter's window).  Non-finite samples
+        are outside the contract.  measure_true_peak reads what was delivered."""
         out = self.generate_batch([audio], sr, target_sampling_rate, timestep, noise=noise, generator=generator, seed=seed,
                                   channels=channels, level=level, output_rate=output_rate, pcm=pcm, dither=dither,
-                                  dither_seed=dither_seed, interleaved=interleaved, loudness=loudness)
+                                  dither_seed=dither_seed, interleaved=interleaved, loudness=loudness, true_peak=true_peak,
+                                  limiter=limiter)
         if channels is not None or (interleaved and pcm is not None):
             return out[0]
         return out

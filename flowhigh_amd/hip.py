@@ -188,6 +188,14 @@ _SIGS = {
     "fh_kweight_energy_f32": [_P, _P, _P, _I, _I, _I, _P],
     "fh_kweight_energy_seg_f32": [_P, _P, _I, _I, _I, _P, _P, _I, _P],
     "fh_loudness_gate_f32": [_P, _I, _P, _P, _I, _I, _I, _D, _P, _P, _P, _P],
+    "fh_tp_tile_len": [],
+    "fh_true_peak_f32": [_P, _P, _P, _I, _I, _P],
+    "fh_true_peak_seg_f32": [_P, _P, _I, _I, _I, _P, _P, _P],
+    "fh_tp_envelope_f32": [_P, _P, _P, _I, _I, _I, _P],
+    "fh_tp_envelope_seg_f32": [_P, _I, _I, _P, _P, _P],
+    "fh_limit_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
+    "fh_limit_seg_f32": [_P, _I, _I, _P, _P, _P, _I, _F, _P],
+    "fh_delivery_gain_f32": [_P, _D, _P, _P, _P, _I, _I, _D, _I, _P, _P, _P],
 }
 EXPORTS = sorted(_SIGS) + ["fh_last_error"]
 

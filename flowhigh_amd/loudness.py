@@ -16,8 +16,9 @@ Departures from the Recommendation, all stated in DESIGN.md "Loudness":
   * a clip shorter than one block is ONE block of its whole length, z[0] = sum_c sum_i e[c, i] / T (serving traffic has 0.3 s clips;
     the Recommendation leaves them unmeasured);
   * every channel weight is 1.0: exact for mono and stereo, 1.5 dB low per surround channel of a 5.1 layout;
-  * the gain is capped so that the peak stays at or below 0.99, the project's convention; there is no limiter, so a clip whose
-    target needs more than the cap allows comes out quieter than the target (measure_loudness reads what was delivered).
+  * the gain is capped so that the peak stays at or below 0.99, the project's convention, so with loudness= alone a clip whose
+    target needs more than the cap allows comes out quieter than the target (measure_loudness reads what was delivered); with
+    true_peak= and limiter='lookahead' the gain is not capped and the limiter of truepeak.py takes what is over.
 
 numpy (and scipy.signal.lfilter for the recursion): nothing here touches torch or the GPU.
 """

@@ -57,7 +57,7 @@ class BatchingServer:
 
     # ---- caller side -------------------------------------------------------------------------------
     def submit(self, audio, sr_in, timestep=1, seed=None, *, channels=None, level='peak', output_rate=None, pcm=None,
-               dither=None, dither_seed=0, loudness=None):
+               dither=None, dither_seed=0, loudness=None, true_peak=None, limiter=None):
         """Queue one clip (int16 or float, 1-D or [1, T]); returns a Future of a float32 numpy array [T48].
         channels = 'first' ([C, T]) | 'last' ([T, C]): a multichannel clip (FlowHighSR.generate), the Future's array is
         [C, T48].  level = 'peak' | 'input' as in generate.  A shape that fits no layout is a ValueError here.
@@ -65,7 +65,7 @@ class BatchingServer:
         pair), checked here; requests are grouped by them too.  With pcm= the Future's array is int16, and a channels='last'
         request gets it in its own layout, [T, C], written that way on the device.
         loudness = None | a target in LUFS as in generate: requests are grouped by it, and it is handed to generate_many only
-        where a request gave it."""
+        where a request gave it.  true_peak = None | a ceiling in dBTP, limiter = None | 'lookahead' as in generate: the same."""
         if self._closed:
             raise RuntimeError("server is closed")
         from .delivery import resolve_delivery
@@ -75,10 +75,12 @@ class BatchingServer:
             dither_seed = tuple(dither_seed)
             if len(dither_seed) != 2:
                 raise ValueError(f"dither_seed of a request is an int or a (seed, stream) pair, got {dither_seed!r}")
-        opt = resolve_delivery(1, output_rate, pcm, dither, [dither_seed], loudness=loudness, level=level)
+        opt = resolve_delivery(1, output_rate, pcm, dither, [dither_seed], loudness=loudness, level=level, true_peak=true_peak,
+                               limiter=limiter)
         deliv = None
         if opt is not None:
-            deliv = (opt["rate"], opt["pcm"], dither, bool(pcm is not None and channels == 'last'), opt.get("loudness"), dither_seed)
+            deliv = (opt["rate"], opt["pcm"], dither, bool(pcm is not None and channels == 'last'), opt.get("loudness"),
+                     opt.get("true_peak"), opt.get("limiter"), dither_seed)
         a = np.asarray(audio.detach().cpu() if isinstance(audio, torch.Tensor) else audio)
         planar = resolve_channels(a, channels)
         if channels is not None:
@@ -89,12 +91,15 @@ class BatchingServer:
         self._q.put((a, int(sr_in), int(timestep), seed, fut, level, deliv))
         return fut
 
-    def generate(self, audio, sr_out=48000, timestep=1, *, level='peak', pcm=None, dither=None):
+    def generate(self, audio, sr_out=48000, timestep=1, *, level='peak', pcm=None, dither=None, true_peak=None, limiter=None):
         """Drop-in for app.py's `generate(audio, sr_out, timestep)`: audio = (sr_in, numpy array).  A 2-D array [T, C] with
         C <= 8 < T is gradio's multichannel clip (gr.Audio(type="numpy")): it runs with channels='last' and comes back [T48, C].
         sr_out other than 48000 goes on as output_rate= where the model's generate_many takes it; pcm='int16' (dither='tpdf')
-        returns the int16 array a WAV writer or a socket takes, a [T, C] clip in that layout from the device."""
+        returns the int16 array a WAV writer or a socket takes, a [T, C] clip in that layout from the device.  true_peak=,
+        limiter= go on to submit where they are given."""
         kw = {}
+        if true_peak is not None or limiter is not None:
+            kw.update(true_peak=true_peak, limiter=limiter)
         if int(sr_out) != 48000:
             if "output_rate" not in inspect.signature(self.model.generate_many).parameters:
                 raise NotImplementedError("the mel codec is fixed at 48 kHz")
@@ -144,8 +149,9 @@ class BatchingServer:
             groups = {}
             for item in batch:
                 # same step count and level; mix_rates off: same input rate too
-                # ... and the same delivery (output rate, sample format, dither, layout, loudness; the dither seed is the request's own)
-                groups.setdefault((None if self.mix_rates else item[1], item[2], item[5], item[6] and item[6][:5]), []).append(item)
+                # ... and the same delivery (output rate, sample format, dither, layout, loudness, true peak, limiter; the dither seed
+                # is the request's own)
+                groups.setdefault((None if self.mix_rates else item[1], item[2], item[5], item[6] and item[6][:7]), []).append(item)
             for (sr_in, steps, level, deliv), items in groups.items():
                 try:
                     # (handed on only where a request asked: a model whose generate_many predates the keywords keeps working.
@@ -155,11 +161,12 @@ class BatchingServer:
                     if level != 'peak':
                         level_kw["level"] = level
                     if deliv is not None:
-                        rate, pcm, dither, interleaved, target = deliv
+                        rate, pcm, dither, interleaved, target, ceiling, limiter = deliv
                         level_kw.update({k: v for k, v in (("output_rate", rate), ("pcm", pcm), ("dither", dither),
-                                                           ("loudness", target)) if v is not None})
+                                                           ("loudness", target), ("true_peak", ceiling), ("limiter", limiter))
+                                         if v is not None})
                         if dither is not None:
-                            level_kw["dither_seed"] = [it[6][5] for it in items]
+                            level_kw["dither_seed"] = [it[6][7] for it in items]
                         if interleaved:
                             level_kw["interleaved"] = True
                     if sr_in is None:

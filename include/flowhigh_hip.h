@@ -727,6 +727,55 @@ int fh_kweight_energy_seg_f32(const fh_pcm_clip* clips, const int32_t* group, in
 int fh_loudness_gate_f32(const double* energies, int n_sub, const int32_t* lens, const int32_t* group, int rows, int n_clips,
                          int hop, double target, const uint32_t* peak_bits, float* lufs, float* gains, void* stream);
 
+/* -----------------------------------------------------------------------------------
+ * True peak and the look-ahead limiter on the device (csrc/truepeak.hip; FlowHighSR.generate*(true_peak=, limiter=),
+ * FlowHighSR.measure_true_peak): ITU-R BS.1770-4 Annex 2 as flowhigh_amd/truepeak.py defines it.  Oversampling is by 4 at every
+ * rate with the 81 taps of scipy.signal.resample_poly(x, 4, 1), zeros outside the clip, in float32 FMA chains in ascending tap order:
+ *   x4[4 n + p] = sum_i h[p + 4 i] x[n + 10 - i]   (21 taps at p = 0, 20 at p = 1 .. 3)
+ * taps: DEVICE float [82], the polyphase plan of (4, 1) as fh_resample_poly_f32 takes it: one leading zero, then h[0 .. 81).
+ * A batched entry and its segment form give a clip the same bits; tiles are counted from the clip's sample 0.
+ * --------------------------------------------------------------------------------- */
+/* Frames per workgroup of the true-peak and envelope entries (tests stand either side). */
+int fh_tp_tile_len(void);
+/* peak_bits[r] = max(peak_bits[r], bits(max_n max(|x[r, n]|, |x4[r, 4 n + p]|, p = 0 .. 3))) over x [rows, len] float32 (4-byte
+ * aligned): an integer atomic maximum of non-negative float bits into slots the caller zeroes, as fh_peak_abs_f32.
+ * rows <= 65535; len <= 2^30. */
+int fh_true_peak_f32(const float* x, const float* taps, uint32_t* peak_bits, int rows, int len, void* stream);
+/* The same over clips read where they are: row r is channel r - (first row of its clip) of clip group[r] of the table (src, pitch,
+ * channels, len are read; dst is not), group as fh_kweight_energy_seg_f32 takes it; max_len: the largest len of the table. */
+int fh_true_peak_seg_f32(const fh_pcm_clip* clips, const int32_t* group, int n_clips, int rows, int max_len, const float* taps,
+                         uint32_t* peak_bits, void* stream);
+/* m[b, n] = max over the channels c of clip b of max(|x[b, c, n]|, |x4[b, c, 4 n + p]|): x [n_clips][channels][len], m [n_clips][len]
+ * float32.  channels 1 .. 8, n_clips <= 65535. */
+int fh_tp_envelope_f32(const float* x, const float* taps, float* m, int n_clips, int channels, int len, void* stream);
+/* The same over a table of clips (src, pitch, channels, len are read); m [n_clips][max_len], clip b written up to its len. */
+int fh_tp_envelope_seg_f32(const fh_pcm_clip* clips, int n_clips, int max_len, const float* taps, float* m, void* stream);
+/* The look-ahead limiter with half window H (1 .. 512) under the ceiling c (float32, 0 < c <= 1), from the clip's envelope m:
+ *   r[n] = c / m[n] where m[n] > c, else 1; 1 outside [0, len)        (float32 division, correctly rounded)
+ *   q[n] = min r[n - H .. n + H]
+ *   g[n] = fl32(sum_k w[k] q[n - H + k], k = 0 .. 2 H ascending, in float64)     w: DEVICE double [2 H + 1]
+ *   y[b, c, n] = clamp(fl32(x[b, c, n] g[n]), -c, c)
+ * x, y [n_clips][channels][len] at any 4-byte alignment, y == x: in place; m [n_clips][len]; gain: NULL, or [n_clips][len], g is
+ * written there as well.  Grid (tiles of 1024 frames, clips). */
+int fh_limit_f32(const float* x, float* y, const float* m, const double* w, float* gain, int n_clips, int channels, int len, int H,
+                 float ceiling, void* stream);
+/* The same over a table of clips: dst NULL: the clip's rows are limited in place; else dst is the clip's output, FLOAT32
+ * [channels][len] behind the table's int16_t*.  m and gain [n_clips][max_len]. */
+int fh_limit_seg_f32(const fh_pcm_clip* clips, int n_clips, int max_len, const float* m, const double* w, float* gain, int H,
+                     float ceiling, void* stream);
+/* The gain of a delivery in every row of every clip (group as above), joint over the clip's rows:
+ *   g_L = 1 when target is NaN, else from the clip's float32 loudness lufs[c]:
+ *         uncapped 0: fl32(min(10^((target - lufs[c]) / 20), 0.99 / peak)), peak the largest of the rows' peak_bits (fh_loudness_gate_f32's gain)
+ *         uncapped 1: fl32(10^((target - lufs[c]) / 20))                    (what a limiter follows)
+ *         1 when lufs[c] is not finite (capped: or the peak is 0)
+ *   gains[r] = g_L, or with uncapped 0 and tp_bits: fl32(min(g_L, ceiling / TP)), TP the largest of the rows' tp_bits (as
+ *         fh_true_peak_f32 leaves them); g_L when TP is 0.  ceiling: linear, 0 < c <= 1.
+ *   dbtp[c] = fl32(20 log10(TP)), -inf for TP = 0 (NULL: not written; gains may be NULL then).
+ * lufs, peak_bits, tp_bits may be NULL where the rule does not read them.  Double arithmetic. */
+int fh_delivery_gain_f32(const float* lufs, double target, const uint32_t* peak_bits, const uint32_t* tp_bits,
+                         const int32_t* group, int rows, int n_clips, double ceiling, int uncapped, float* gains, float* dbtp,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
