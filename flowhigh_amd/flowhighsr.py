@@ -24,6 +24,9 @@ Extensions over the reference (all keyword-only, defaults keep reference behavio
                                      (loudness.py is the definition, csrc/loudness.hip the kernels; DESIGN.md "Loudness")
   generate*(..., true_peak=T, limiter=)   the result under T dBTP, by one gain or by a look-ahead limiter; measure_true_peak reads it
                                      back (truepeak.py is the definition, csrc/truepeak.hip the kernels; DESIGN.md "True peak and limiter")
+  stream(sr, ...) -> push / flush, stream_push(sessions, blocks), generate_long(audio, sr, ...)   streaming sessions: overlapping
+                                     windows that share one keyed prior at their absolute frames, cross-faded on the device
+                                     (stream.py is the definition, streaming.py the host side, csrc/stream.hip the seam; DESIGN.md "Streaming")
 """
 import ctypes
 import json
@@ -662,16 +665,19 @@ class FlowHighSR:
             gains = gains.masked_fill(mono, 1.0)
         return dict(gains=gains, groups=self._upload(torch.from_numpy(group)))
 
-    def _generate_rows(self, planar, sr, timestep, noises, keys, generator, level, return_stages=False):
+    def _generate_rows(self, planar, sr, timestep, noises, keys, generator, level, return_stages=False, first_frames=None):
         """generate_batch for clips of equal length with channels= / level=: planar = float [C_i, T] arrays (resolve_clips),
         noises = None or one [C_i, N, n_mels] per clip (clip_noises), keys = None or one key per clip.  Every channel is a row of
-        the batch and runs as a mono clip does; the rows of a clip share its prior.  -> [sum C_i, T48] (rows in clip order),
+        the batch and runs as a mono clip does; the rows of a clip share its prior (first_frames, with keys: the absolute frame every clip's prior starts at, _device_prior).
+        -> [sum C_i, T48] (rows in clip order),
         with return_stages also the stages of the rows (and their gains)."""
         chans = [a.shape[0] for a in planar]
         row_keys = None
         if keys is not None:
             noise = None
             row_keys = [k for k, c in zip(keys, chans) for _ in range(c)]
+            if first_frames is not None:
+                first_frames = [f for f, c in zip(first_frames, chans) for _ in range(c)]
         else:
             if noises is None:                               # one draw per CLIP: the generator moves as for mono clips
                 n = resample_out_len(planar[0].shape[1], 48000, sr) // 480
@@ -679,7 +685,8 @@ class FlowHighSR:
             noise = torch.cat(list(noises), 0)
         cond, gains = self._prepare_rows([row for a in planar for row in a], sr)
         kw = dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
-        wav = self._sample(cond=cond, time_steps=timestep, cfm_method=self.cfm_method, noise=noise, keys=row_keys, **kw).squeeze(1)
+        wav = self._sample(cond=cond, time_steps=timestep, cfm_method=self.cfm_method, noise=noise, keys=row_keys,
+                           first_frames=first_frames if keys is not None else None, **kw).squeeze(1)
         out = self.postproc(wav, cond, cond.size(-1), return_cr=return_stages, **self._level_args(chans, level, gains))
         if return_stages:
             return out[0], dict(cond=cond, wav=wav.clone(), cr=out[1].clone(), gains=gains)
@@ -707,9 +714,10 @@ class FlowHighSR:
             keys = [normalize_key(int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator)), 0) for _ in range(n_clips)]
         return keys
 
-    def _device_prior(self, keys, n_seg, n, seg=None, rows=None):
+    def _device_prior(self, keys, n_seg, n, seg=None, rows=None, first_frames=None):
         """fh_prior_normal_f32: [n_seg * n, n_mels] noise rows of the keys (a list of (seed, stream), or a device int64
-        [n_seg, 2]); seg: the ragged segment table, rows = its total."""
+        [n_seg, 2]); seg: the ragged segment table, rows = its total.  first_frames (a list of ints, or a device int64 [n_seg]):
+        clip b's rows are rows first_frames[b] .. of its key's stream (fh_prior_normal_at_f32; the windows of a streaming session)."""
         if not isinstance(keys, torch.Tensor):
             host = np.array([[k[0], k[1]] for k in keys], dtype=np.uint64).view(np.int64)
             keys = self._upload(torch.from_numpy(host))
@@ -717,19 +725,31 @@ class FlowHighSR:
             raise ValueError(f"keys must be a contiguous int64 [{n_seg}, 2], got {keys.dtype} {tuple(keys.shape)}")
         d = self.flowhigh.n_mels
         out = torch.empty(n_seg * n if rows is None else rows, d, dtype=torch.float32, device=self.device)
-        hip.check(hip.lib().fh_prior_normal_f32(out.data_ptr(), keys.data_ptr(), hip.ptr(seg), n_seg, n, d, hip.stream()),
-                  "fh_prior_normal_f32")
+        if first_frames is None:
+            hip.check(hip.lib().fh_prior_normal_f32(out.data_ptr(), keys.data_ptr(), hip.ptr(seg), n_seg, n, d, hip.stream()),
+                      "fh_prior_normal_f32")
+            return out
+        if not isinstance(first_frames, torch.Tensor):
+            if min(int(f) for f in first_frames) < 0:
+                raise ValueError(f"first_frames must be non-negative, got {list(first_frames)}")
+            first_frames = self._upload(torch.tensor([int(f) for f in first_frames], dtype=torch.int64))
+        if first_frames.shape != (n_seg,) or first_frames.dtype != torch.int64 or not first_frames.is_contiguous():
+            raise ValueError(f"first_frames must be a contiguous int64 [{n_seg}], got {first_frames.dtype} {tuple(first_frames.shape)}")
+        hip.check(hip.lib().fh_prior_normal_at_f32(out.data_ptr(), keys.data_ptr(), first_frames.data_ptr(), hip.ptr(seg), n_seg, n, d,
+                                                   hip.stream()), "fh_prior_normal_at_f32")
         return out
 
     @torch.no_grad()
     @hip.on_device
-    def draw_prior(self, frames, seed, *, stream=0):
+    def draw_prior(self, frames, seed, *, stream=0, first_frame=0):
         """The noise a prior='device' call with that key uses, as a device tensor (read it back to rebuild a call with noise=,
         or to hand it to the oracle; prior.prior_normal_host gives the same values without a GPU).
         frames = N, seed = s            -> [1, N, n_mels]: key (s, stream)
         frames = N, seed = [s_0, ...]   -> [len(seed), N, n_mels]: clip i's key (an int s_i = (s_i, stream), or a pair)
         frames = [N_0, N_1, ...]        -> a list of [1, N_i, n_mels] (the ragged form, one launch); seed an int s = keys
-                                           (s, stream + i) as seed=s gives a call over the list, or one item per clip."""
+                                           (s, stream + i) as seed=s gives a call over the list, or one item per clip.
+        first_frame = f (the uniform forms): rows f .. f + N of the keys' streams, what window i of a streaming session draws
+        at f = its first absolute frame (stream.py)."""
         ragged = not isinstance(frames, (int, np.integer))
         count = len(frames) if ragged else (1 if isinstance(seed, (int, np.integer)) else len(seed))
         if isinstance(seed, (int, np.integer)):
@@ -738,7 +758,10 @@ class FlowHighSR:
             keys = [normalize_key(s_, stream) if isinstance(s_, (int, np.integer)) else k
                     for k, s_ in zip(expand_seed(seed, count), seed)]
         if not ragged:
-            return self._device_prior(keys, count, int(frames)).view(count, int(frames), -1)
+            at = None if not first_frame else [int(first_frame)] * count
+            return self._device_prior(keys, count, int(frames), first_frames=at).view(count, int(frames), -1)
+        if first_frame:
+            raise ValueError("first_frame= goes with one frame count, not with a list of them")
         frames = [int(n) for n in frames]
         seg = self.flowhigh.net.ragged_workspace(frames)["seg"]
         z = self._device_prior(keys, count, max(frames), seg=seg, rows=sum(frames))
@@ -822,16 +845,17 @@ class FlowHighSR:
             hip.check(L.fh_mel_splice_seg_f32(*args, seg.data_ptr(), n_seg, n, high.shape[-1], st), "fh_mel_splice_seg_f32")
         return out
 
-    def _sample_rows(self, cond_mel, noise, keys, n_seg, n, time_steps, cfm_method, std_1, std_2, cond_scale, mel_pp, ragged=None):
+    def _sample_rows(self, cond_mel, noise, keys, n_seg, n, time_steps, cfm_method, std_1, std_2, cond_scale, mel_pp, ragged=None,
+                     first_frames=None):
         """The sampler behind the log-mel (cfm:176-279) on token-major rows: n_seg clips of n rows, or (ragged: the net's
         ragged workspace) clips of different lengths packed back to back, n = the longest.  cond_mel, noise [rows, n_mels] on
-        the device; noise None: drawn on the device from the clips' keys.  Returns the mel rows."""
+        the device; noise None: drawn on the device from the clips' keys (first_frames: _device_prior).  Returns the mel rows."""
         if cfm_method in _CFM_METHODS[1:]:
             if std_1 is None or std_2 is None:          # cfm:180-183 (resets BOTH; generate() never passes std_1)
                 std_1, std_2 = 1.0, self.sigma
         seg = ragged["seg"] if ragged is not None else None
         if noise is None:                               # prior='device': drawn where it is used
-            noise = self._device_prior(keys, n_seg, n, seg=seg, rows=cond_mel.shape[0])
+            noise = self._device_prior(keys, n_seg, n, seg=seg, rows=cond_mel.shape[0], first_frames=first_frames)
         cut = None
         if cfm_method == 'basic_cfm':
             y0 = noise
@@ -862,7 +886,7 @@ class FlowHighSR:
         return out.clone() if decode_to_audio else out
 
     def _sample(self, *, cond=None, cond_mask=None, time_steps=4, cond_scale=1., decode_to_audio=True,
-                std_1=None, std_2=None, mel_pp=False, cfm_method=None, noise=None, generator=None, keys=None):
+                std_1=None, std_2=None, mel_pp=False, cfm_method=None, noise=None, generator=None, keys=None, first_frames=None):
         if cfm_method not in _CFM_METHODS:
             cfm_method = self.cfm_method
         if cond_mask is not None:
@@ -882,7 +906,8 @@ class FlowHighSR:
             if noise is None:
                 noise = self._draw_noise(batch, n, generator)
             noise = self._upload(noise.to(torch.float32)).reshape(batch * n, -1).contiguous()
-        mel = self._sample_rows(cond_mel, noise, keys, batch, n, time_steps, cfm_method, std_1, std_2, cond_scale, mel_pp)
+        mel = self._sample_rows(cond_mel, noise, keys, batch, n, time_steps, cfm_method, std_1, std_2, cond_scale, mel_pp,
+                                first_frames=first_frames)
         mel = mel.view(batch, n, -1)
         if not decode_to_audio:
             return mel
@@ -1230,6 +1255,51 @@ class FlowHighSR:
             out.append(self.postproc(torch.cat(list(wavs[r:r + c]), 0), cond, cond.shape[1], **self._level_args([c], level, gains)))
             r += c
         return out
+
+    # ---- streaming sessions (stream.py is the definition, streaming.py the host side, csrc/stream.hip the seam) ------------------
+    def stream(self, sr, *, window_ms=1000, overlap_ms=200, guard_ms=50, timestep=1, seed=None, stream=0, pcm=None,
+               channels=None, dither=None, output_rate=None, loudness=None, true_peak=None):
+        """A streaming session at the input rate `sr` (prior='device' models): push(block) returns the samples that block made
+        final, float32 [1, n] on the device at 48 kHz (n may be 0), flush() the rest; the blocks of a stream of T input samples
+        add up to tables.resample_out_len(T, 48000, sr) samples, equal to stream.stitch of its windows' results bit for bit.
+        window_ms / overlap_ms / guard_ms: the StreamPlan (multiples of stream.grain_ms(sr): 10 ms at most rates; overlap >= 20 ms,
+        2 overlap <= window, 2 guard < overlap).  Window i is what generate(window_i, sr, level='input') returns with the noise
+        of the session's key (seed, stream) at rows i * hop frames on (draw_prior(first_frame=)): consecutive windows share
+        their prior where they overlap and are cross-faded there (fh_xfade_seg_f32).  seed=None draws one from torch's generator.
+        Latency: a sample is final once the window that holds it left of its right overlap has arrived, at most window_ms after it
+        came in, plus one batched run.  The sample format is fixed by the session's first block: an integer dtype is divided by
+        32768, a float dtype taken as it is.  pcm='int16' encodes every emitted block (no dither: the encoding is stateless).
+        Not built, each a ValueError: channels=, dither=, output_rate=, loudness=, true_peak=."""
+        from .streaming import open_session
+        return open_session(self, sr, window_ms, overlap_ms, guard_ms, timestep, seed, stream, pcm,
+                            dict(channels=channels, dither=dither, output_rate=output_rate, loudness=loudness, true_peak=true_peak))
+
+    def stream_push(self, sessions, blocks):
+        """One block per session -> one output block per session (StreamSession.push).  Every window that became runnable, of
+        every session with the same (sr, window, overlap, guard, timestep), goes through ONE batched run and one
+        fh_xfade_seg_f32 launch -- several windows of one session included; sessions with other plans form further batches.
+        A session's output does not depend on what it was pushed with."""
+        sessions, blocks = list(sessions), list(blocks)
+        if len(sessions) != len(blocks):
+            raise ValueError(f"one block per session: {len(blocks)} blocks for {len(sessions)} sessions")
+        from .streaming import check_sessions
+        check_sessions(self, sessions)                      # (before any block is taken: a refused push leaves every session as it was)
+        for s, b in zip(sessions, blocks):
+            s._take(b)
+        return self._stream_run(sessions, final=False)
+
+    @torch.no_grad()
+    @hip.on_device
+    def _stream_run(self, sessions, final):
+        from .streaming import run
+        return run(self, sessions, final)
+
+    def generate_long(self, audio, sr, **stream_keywords):
+        """A clip of any length through a streaming session: push everything, then flush -> [1, T48] (int16 with pcm='int16').
+        Keywords: those of stream().  Memory and attention cost are those of one push's windows, whatever the clip's length."""
+        s = self.stream(sr, **stream_keywords)
+        first = s.push(audio)
+        return torch.cat([first, s.flush()], 1)
 
     @torch.no_grad()
     def measure_loudness(self, rows, chans=None, rate=48000):

@@ -84,6 +84,11 @@ class PcmClip(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("pitch", C.c_int64), ("channels", C.c_int32), ("len", C.c_int32)]
 
 
+class XfadeJob(C.Structure):
+    """fh_xfade_job: one seam of fh_xfade_seg_f32 (csrc/stream.hip)."""
+    _fields_ = [("head", C.c_void_p), ("tail", C.c_void_p)]
+
+
 class HipError(RuntimeError):
     pass
 
@@ -161,6 +166,7 @@ _SIGS = {
     "fh_axpby_f32": [_P, _F, _P, _F, _P, C.c_longlong, _P],
     "fh_rk_combine_f32": [_P, _P, _I, _F, _P, _P, _P, _P, C.c_longlong, _P],
     "fh_prior_normal_f32": [_P, _P, _P, _I, _I, _I, _P],
+    "fh_prior_normal_at_f32": [_P, _P, _P, _P, _I, _I, _I, _P],
     "fh_spec_splice_f32": [_P, _P, _P, _P, _I, _I, _P],
     "fh_istft_ola_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "fh_peak_scale_f32": [_P, _P, _I, _I, _F, _P],
@@ -196,6 +202,8 @@ _SIGS = {
     "fh_limit_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "fh_limit_seg_f32": [_P, _I, _I, _P, _P, _P, _I, _F, _P],
     "fh_delivery_gain_f32": [_P, _D, _P, _P, _P, _I, _I, _D, _I, _P, _P, _P],
+    "fh_sizeof_xfade_job": [],
+    "fh_xfade_seg_f32": [_P, _I, _P, _P, _I, _P],
 }
 EXPORTS = sorted(_SIGS) + ["fh_last_error"]
 
@@ -227,7 +235,8 @@ def lib():
     if L.fh_sizeof_conv_group() != C.sizeof(ConvGroup) or L.fh_sizeof_act_group() != C.sizeof(ActGroup) \
             or L.fh_sizeof_wino_group() != C.sizeof(WinoGroup) or L.fh_sizeof_sum_job() != C.sizeof(SumJob) \
             or L.fh_sizeof_amp_group() != C.sizeof(AmpGroup) or L.fh_sizeof_clip() != C.sizeof(Clip) \
-            or L.fh_sizeof_rate() != C.sizeof(Rate) or L.fh_sizeof_pcm_clip() != C.sizeof(PcmClip):
+            or L.fh_sizeof_rate() != C.sizeof(Rate) or L.fh_sizeof_pcm_clip() != C.sizeof(PcmClip) \
+            or L.fh_sizeof_xfade_job() != C.sizeof(XfadeJob):
         raise HipError("descriptor struct layout mismatch between hip.py and flowhigh_hip.h")
     _lib = L
     return L

@@ -40,13 +40,18 @@ def normalize_key(seed, stream=0):
     return int(seed) & _MASK64, int(stream) & _MASK64
 
 
-def prior_normal_host(seed, stream, n_frames, n_mels=256, dtype=np.float64):
-    """[n_frames, n_mels] prior noise of the key (seed, stream): the formulas above, evaluated in float64 and cast to `dtype`."""
+def prior_normal_host(seed, stream, n_frames, n_mels=256, dtype=np.float64, first_frame=0):
+    """[n_frames, n_mels] prior noise of the key (seed, stream): the formulas above, evaluated in float64 and cast to `dtype`.
+    first_frame=f: rows f .. f + n_frames of the key's stream (the quad counter starts at f * n_mels / 4, in 64 bits): what
+    fh_prior_normal_at_f32 draws for a window of a streaming session that starts at absolute frame f (stream.py)."""
     seed, stream = normalize_key(seed, stream)
     n_frames, n_mels = int(n_frames), int(n_mels)
     if n_mels % 4 or n_mels <= 0 or n_frames < 0:
         raise ValueError(f"n_mels {n_mels} must be a positive multiple of 4 and n_frames {n_frames} >= 0")
-    q = np.arange(n_frames * n_mels // 4, dtype=np.uint64)
+    first_frame = int(first_frame)
+    if first_frame < 0 or (first_frame + n_frames) * (n_mels // 4) > _MASK64:
+        raise ValueError(f"first_frame {first_frame} must be >= 0 and leave the quad counter within 64 bits")
+    q = np.arange(n_frames * n_mels // 4, dtype=np.uint64) + np.uint64(first_frame * (n_mels // 4))
     ctr = np.empty((q.size, 4), dtype=np.uint64)
     ctr[:, 0], ctr[:, 1] = q & np.uint64(_MASK32), q >> np.uint64(32)
     ctr[:, 2], ctr[:, 3] = stream & _MASK32, stream >> 32

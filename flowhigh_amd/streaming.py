@@ -1,0 +1,192 @@
+"""Streaming sessions on the device: FlowHighSR.stream / stream_push / generate_long (stream.py is the definition of what they compute).
+
+A session cuts its stream into the windows of its StreamPlan.  Window i runs exactly as generate(window_i, sr, level='input')
+runs, with its prior drawn by fh_prior_normal_at_f32 from the session's key at the window's absolute first frame; consecutive
+windows are joined over their overlap by fh_xfade_seg_f32.  Every runnable window of every session of a push that shares a plan
+and a number of time steps is a row of ONE batch (rows of a batch have the bits of a clip alone) and a job of ONE seam launch.
+Pending input samples live on the host, the previous window's last O48 output samples on the device, in a buffer of the session's own.
+"""
+import numpy as np
+import torch
+
+from . import hip
+from .frontend import upload_tables
+from .stream import StreamPlan
+
+# keywords of generate() that a session does not take, and why
+_NOT_BUILT = dict(channels="a session is one mono stream", dither="dither needs a sample-index offset across blocks (csrc/pcm.hip)",
+                  output_rate="resampling a stream needs resampler state across blocks",
+                  loudness="loudness is a statistic of a whole clip", true_peak="the true peak is a statistic of a whole clip")
+
+
+def check_not_built(**kw):
+    for name, value in kw.items():
+        if value is not None:
+            raise ValueError(f"{name}= is not built for streaming sessions: {_NOT_BUILT[name]}")
+
+
+class StreamSession:
+    """One stream of a FlowHighSR.stream() call.  push(block) -> the newly final samples, flush() -> the rest."""
+
+    def __init__(self, model, plan, timestep, key, pcm):
+        self.model, self.plan, self.timestep, self.key, self.pcm = model, plan, int(timestep), key, pcm
+        self.closed = False
+        self.integer = None                     # the sample format, fixed by the first block: integer dtype (/ 32768) or float
+        self.dtype = None
+        self.pending = None                     # input samples from window `done`'s first one on (host)
+        self.arrived = 0                        # input samples pushed so far
+        self.done = 0                           # windows run so far
+        self.tail = None                        # the last window's final O48 output samples (device, the session's own)
+
+    # ---- host side ---------------------------------------------------------------------------------------------------
+    def _take(self, block):
+        """A pushed block as 1-D samples in the session's format, appended to the pending input."""
+        if isinstance(block, torch.Tensor):
+            block = block.detach().cpu().numpy()
+        a = np.asarray(block)
+        if a.ndim == 2 and a.shape[0] == 1:
+            a = a[0]
+        if a.ndim != 1:
+            raise ValueError(f"a block is 1-D or [1, n] (one mono stream), got shape {a.shape}")
+        if a.size == 0:
+            return
+        integer = np.issubdtype(a.dtype, np.integer)
+        if not integer and not np.issubdtype(a.dtype, np.floating):
+            raise ValueError(f"a block holds integer or float samples, got dtype {a.dtype}")
+        if self.integer is None:
+            self.integer = bool(integer)
+            self.dtype = np.float64 if integer else a.dtype
+            self.pending = np.empty(0, dtype=self.dtype)
+        elif integer != self.integer:
+            raise ValueError(f"the session's sample format is fixed by its first block ({'integer' if self.integer else 'float'}): "
+                             f"got a block of dtype {a.dtype}")
+        # (an integer block is int16 full scale whatever its largest sample: no block is guessed from its own peak)
+        a = a / 32768.0 if integer else a.astype(self.dtype, copy=False)
+        self.pending = np.concatenate([self.pending, a])
+        self.arrived += a.size
+
+    def _cut(self, final):
+        """The windows that can run now as (index, [1, n] samples, last of the stream); the pending input moves on.
+        final: the stream ends here -- what is left past the last full window is the last window, if it is more than the overlap
+        it shares with that window (or the stream's only window); -> (windows, whether the kept tail is the stream's end)."""
+        p = self.plan
+        out = []
+        if self.pending is None:
+            return out, False
+        while self.pending.size >= p.W:
+            out.append([self.done + len(out), self.pending[None, :p.W], False])
+            self.pending = self.pending[p.H:]
+        if not final:
+            return out, False
+        k, left = self.done + len(out), self.pending
+        self.pending = None
+        if left.size > (p.O if k else 0):
+            out.append([k, left[None], True])
+        elif out:
+            out[-1][2] = True                   # the stream ends with this window's last sample
+        return out, bool(k) and not out
+
+    def push(self, block):
+        """float32 (int16 with pcm=) [1, n] on the device: the samples this block made final; n may be 0."""
+        return self.model.stream_push([self], [block])[0]
+
+    def flush(self):
+        """Runs the last, partial window and returns what is left; the session is closed afterwards."""
+        return self.model._stream_run([self], final=True)[0]
+
+
+def open_session(model, sr, window_ms, overlap_ms, guard_ms, timestep, seed, stream, pcm, not_built):
+    from .prior import normalize_key
+    check_not_built(**not_built)
+    if model.prior != 'device':
+        raise ValueError("a streaming session shares one keyed prior between its windows: construct the model with prior='device' "
+                         "(a prior='reference' model draws from a generator, window by window)")
+    if pcm not in (None, "int16"):
+        raise ValueError(f"pcm must be None or 'int16', got {pcm!r}")
+    if isinstance(timestep, bool) or int(timestep) != timestep or timestep < 1:
+        raise ValueError(f"timestep must be a positive integer, got {timestep!r}")
+    plan = StreamPlan(sr, window_ms, overlap_ms, guard_ms)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,)))
+    elif isinstance(seed, (bool, float)) or not isinstance(seed, (int, np.integer)):
+        raise TypeError(f"seed must be an int, got {seed!r}")
+    return StreamSession(model, plan, timestep, normalize_key(seed, stream), pcm)
+
+
+def _ramp(model, plan):
+    """(w_in, w_out) of the plan on the device, kept per (O48, G48)."""
+    cache = model.__dict__.setdefault("_stream_ramps", {})
+    k = (plan.O48, plan.G48)
+    if k not in cache:
+        cache[k] = tuple(model._upload(torch.from_numpy(w)) for w in plan.ramp())
+    return cache[k]
+
+
+def _encode(model, block):
+    """float32 [1, n] -> int16 [1, n]: pcm.py's encoding without dither, which is stateless (fh_pcm_i16_f32)."""
+    out = torch.empty(block.shape, dtype=torch.int16, device=block.device)
+    if block.shape[1]:
+        hip.check(hip.lib().fh_pcm_i16_f32(block.data_ptr(), out.data_ptr(), 0, 1, 1, block.shape[1], 0, hip.stream()), "fh_pcm_i16_f32")
+    return out
+
+
+def check_sessions(model, sessions):
+    if len({id(s) for s in sessions}) != len(sessions):
+        raise ValueError("a session is in the list twice")
+    for s in sessions:
+        if s.model is not model:
+            raise ValueError("a session of another model")
+        if s.closed:
+            raise RuntimeError("the session is closed: flush() ends a stream")
+
+
+def run(model, sessions, final):
+    """Every runnable window of `sessions` (final: and their last ones; the sessions then close) -> one output block per session."""
+    sessions = list(sessions)
+    check_sessions(model, sessions)
+    work = {}                 # (plan key, time steps, samples of a window) -> [(session index, window index, [1, n], last)]
+    ends_in_tail = []
+    for si, s in enumerate(sessions):
+        windows, tail_ends = s._cut(final)
+        ends_in_tail.append(tail_ends)
+        for wi, x, last in windows:
+            work.setdefault((s.plan.key, s.timestep, x.shape[1]), []).append((si, wi, x, last))
+    if final:
+        for s in sessions:
+            s.closed = True                      # (whatever the last run raises: a flush ends the stream)
+    parts = [[] for _ in sessions]
+    # full windows first: a last, shorter window reads the tail its predecessor leaves
+    for key in sorted(work, key=lambda k: k[2] != sessions[work[k][0][0]].plan.W):
+        items = work[key]
+        p = sessions[items[0][0]].plan
+        y = model._generate_rows([x for _, _, x, _ in items], p.sr, key[1], None, [sessions[si].key for si, _, _, _ in items], None,
+                                 "input", first_frames=[p.first_frame(wi) for _, wi, _, _ in items])
+        o, esz = p.O48, y.element_size()
+        jobs, row_of = [], {}
+        for r, (si, wi, _, _) in enumerate(items):
+            if wi:                               # the older window: a row of this batch, or the tail the session kept
+                prev = row_of.get((si, wi - 1))
+                tail = sessions[si].tail.data_ptr() if prev is None else y[prev].data_ptr() + (p.W48 - o) * esz
+                jobs.append(hip.XfadeJob(y[r].data_ptr(), tail))
+            row_of[(si, wi)] = r
+        if jobs:
+            w_in, w_out = _ramp(model, p)
+            keep, (jp,) = upload_tables([(hip.XfadeJob * len(jobs))(*jobs)], model.device)
+            hip.check(hip.lib().fh_xfade_seg_f32(jp, len(jobs), w_in.data_ptr(), w_out.data_ptr(), o, hip.stream()), "fh_xfade_seg_f32")
+        # (y belongs to the post-processor's workspace: what is emitted and the kept tail are copied out before the next batch)
+        for r, (si, wi, _, last) in enumerate(items):
+            s = sessions[si]
+            parts[si].append(y[r] if last else y[r, :p.H48])
+            s.tail = None if last else y[r, p.W48 - o:].clone()
+            s.done = wi + 1
+        for si in {si for si, _, _, _ in items}:
+            parts[si] = [torch.cat(parts[si], 0)]
+    out = []
+    for si, s in enumerate(sessions):
+        if final:
+            if ends_in_tail[si]:
+                parts[si].append(s.tail)         # the stream ended with the last window's right overlap: it is final as it is
+            s.tail = None
+        block = torch.cat(parts[si], 0)[None] if parts[si] else torch.empty(1, 0, dtype=torch.float32, device=model.device)
+        out.append(_encode(model, block) if s.pcm == "int16" else block)
+    return out

@@ -561,6 +561,12 @@ int fh_rk_combine_f32(const float* y, const float* const* ks, int n_k, float h, 
  * u1 = ((r >> 8) + 1) 2^-24 and u2 = (r' >> 8) 2^-24, lanes 0, 1 = sqrt(-2 ln u1) (cos, sin)(2 pi u2) of (r0, r1), lanes 2, 3 the same
  * of (r2, r3); within 1e-5 of the float64 evaluation (flowhigh_amd/prior.py: prior_normal_host).  n_seg <= 65535, n d < 2^33. */
 int fh_prior_normal_f32(float* out, const uint64_t* keys, const int32_t* seg, int n_seg, int n, int d, void* stream);
+/* The same draw with clip b's rows counted from first_frames[b] (DEVICE int64 [n_seg], non-negative; a captured launch reads what
+ * is there): quad q of clip b takes the counter first_frames[b] * d / 4 + q in 64 bits, so its n rows are rows first_frames[b] ..
+ * first_frames[b] + n of a draw from 0 under the same key, bit for bit (the windows of a streaming session: flowhigh_amd/stream.py).
+ * One kernel body with fh_prior_normal_f32, which is the case of no first_frames. */
+int fh_prior_normal_at_f32(float* out, const uint64_t* keys, const int64_t* first_frames, const int32_t* seg, int n_seg, int n, int d,
+                           void* stream);
 
 /* out[b,t,:] = bins < cr[b] ? src : pred  (P-layout, postprocessing.py:36-37). */
 int fh_spec_splice_f32(const float* pred, const float* src, const int32_t* cr, float* out,
@@ -775,6 +781,21 @@ int fh_limit_seg_f32(const fh_pcm_clip* clips, int n_clips, int max_len, const f
 int fh_delivery_gain_f32(const float* lufs, double target, const uint32_t* peak_bits, const uint32_t* tp_bits,
                          const int32_t* group, int rows, int n_clips, double ceiling, int uncapped, float* gains, float* dbtp,
                          void* stream);
+
+/* ---- streaming sessions (csrc/stream.hip; flowhigh_amd/stream.py is the definition) ---- */
+/* The seam between two consecutive windows of a stream, for every seam of a push in one launch.  Job j blends the first o48
+ * samples of the newer window (head, in place) with the last o48 of the older one (tail):
+ *   head[u] = fmaf(w_in[u], head[u], fl(w_out[u] * tail[u]))            float32, u = 0 .. o48 - 1
+ * a term whose weight is exactly 0 is skipped, not multiplied (w_out[u] == 0: fl(w_in[u] * head[u]); w_in[u] == 0: fl(w_out[u] *
+ * tail[u]); both: 0), so behind a weight 0 nothing is read into the result.  jobs: DEVICE array; w_in, w_out: DEVICE float32
+ * [o48]; heads and tails at any 4-byte alignment.  No job's head may overlap any job's tail or another head (2 * overlap <=
+ * window); the jobs are then independent and one session's consecutive seams go in one launch.  n_jobs <= 65535. */
+typedef struct {
+  float* head;
+  const float* tail;
+} fh_xfade_job;
+int fh_sizeof_xfade_job(void);
+int fh_xfade_seg_f32(const fh_xfade_job* jobs, int n_jobs, const float* w_in, const float* w_out, int o48, void* stream);
 
 #ifdef __cplusplus
 }
