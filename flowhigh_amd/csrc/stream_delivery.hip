@@ -1,0 +1,225 @@
+// Streaming delivery (FlowHighSR.stream(delivery=), FlowHighSR.delivery_stream; flowhigh_amd/stream_delivery.py is the schedule
+// and the definition): the delivery of a stream block by block, with the bits of the one-shot delivery of the whole stream.
+//   fh_stream_resample_f32   the polyphase resampler (frontend.hip: resample_poly_kernel's loop and order) on absolute indices
+//   fh_stream_limit_f32      the oversampled envelope and the look-ahead limiter of a mono stream in one launch
+//                            (truepeak.hip: tp_envelope_kernel + limit_kernel, their arithmetic and order)
+//   fh_stream_pcm_i16_f32    pcm.hip's encoder with the dither at the sample's absolute index
+// One fh_stream_job per stream and launch.  A job's source is TWO spans, the carry the stream kept and the fresh block, read as
+// one run of samples whose first has the absolute index `base`; nothing is concatenated.  The last block column of a launch
+// copies the last n_keep source samples into the stream's other carry buffer (the two ping-pong, so the copy never writes
+// what the launch reads).
+//
+// The job table lives on the device: a kernel returns at once on a job with a negative count or a null pointer it would use,
+// reads the source only through sd_src::at (0 outside the two spans) and writes only dst[0 .. n_out) and carry_out[0 .. n_keep).
+//
+// Limiter: a workgroup owns TILE outputs from `first` on.  The samples of tile +- (2 H + HALO) go to LDS (0 before the stream's
+// sample 0, and past its last one when it has ended), m and r over tile +- 2 H are computed from there (r = 1 outside the
+// stream), then the sliding minimum by doubling and the float64 Hann sum in ascending k as limit_kernel has them.  The
+// envelope work is (TILE + 4 H) / TILE of that of the two launches on a clip: the price of one launch and no m round trip.
+#include "fh_common.h"
+#include "pcm_common.h"
+#include "truepeak_common.h"
+
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int TILE = 1024;                      // outputs per workgroup of the limiter
+constexpr int PER = TILE / THREADS;
+constexpr int HALO = tp::HALO, PHASE_TAPS = tp::PHASE_TAPS, MAX_H = tp::MAX_H;
+constexpr int LIM_N = TILE + 4 * MAX_H;
+using tp::limit_sample;
+using tp::load_taps;
+using tp::tp_phase;
+
+struct sd_src {                                 // the two spans as one run of samples
+  const float* carry;
+  const float* fresh;
+  long long base;
+  int n_carry, n_fresh;
+  __device__ long long end() const { return base + n_carry + n_fresh; }
+  __device__ float at(long long a) const {      // sample a of the stream; 0 outside the spans
+    const long long s = a - base;
+    if (s < 0) return 0.f;
+    if (s < n_carry) return carry[s];
+    const long long f = s - n_carry;
+    return f < n_fresh ? fresh[f] : 0.f;
+  }
+};
+
+__device__ __forceinline__ bool job_ok(const fh_stream_job& J) {
+  return J.n_carry >= 0 && J.n_fresh >= 0 && J.n_out >= 0 && J.n_keep >= 0 && J.base >= 0 && J.first >= 0 &&
+         (J.n_carry == 0 || J.carry) && (J.n_fresh == 0 || J.fresh) && (J.n_out == 0 || J.dst) && (J.n_keep == 0 || J.carry_out) &&
+         (long long)J.n_keep <= (long long)J.n_carry + J.n_fresh;
+}
+
+__device__ __forceinline__ sd_src source(const fh_stream_job& J) {
+  return {(const float*)J.carry, (const float*)J.fresh, J.base, J.n_carry, J.n_fresh};
+}
+
+// carry_out[s] = the source's sample end - n_keep + s, by one workgroup
+__device__ __forceinline__ void keep_tail(const fh_stream_job& J, const sd_src& S) {
+  float* __restrict__ out = (float*)J.carry_out;
+  const long long from = S.end() - J.n_keep;
+  for (int s = threadIdx.x; s < J.n_keep; s += THREADS) out[s] = S.at(from + s);
+}
+
+// out[i] = sum_j x[j] * h[(i + pre) * down - j * up] for i = first + o: resample_poly_kernel's loop on 64-bit indices, its j_hi
+// clamped to the last sample that is there (the stream's last one when it has ended; the schedule asks for no other output)
+__global__ __launch_bounds__(THREADS) void stream_resample_kernel(const fh_stream_job* __restrict__ jobs, const float* __restrict__ h,
+                                                                  int up, int down, int n_taps, int pre) {
+  const fh_stream_job J = jobs[blockIdx.y];
+  if (!job_ok(J)) return;
+  const sd_src S = source(J);
+  if (blockIdx.x == gridDim.x - 1) {
+    keep_tail(J, S);
+    return;
+  }
+  const long long o = (long long)blockIdx.x * THREADS + threadIdx.x;
+  if (o >= J.n_out) return;
+  const long long pos = (J.first + o + pre) * down;
+  long long j_hi = pos / up;
+  if (j_hi > S.end() - 1) j_hi = S.end() - 1;
+  float acc = 0.f;
+  for (long long j = j_hi; j >= 0; --j) {
+    const long long k = pos - j * up;
+    if (k >= n_taps) break;
+    acc = fmaf(S.at(j), h[k], acc);
+  }
+  ((float*)J.dst)[o] = acc;
+}
+
+__global__ __launch_bounds__(THREADS) void stream_limit_kernel(const fh_stream_job* __restrict__ jobs, const float* __restrict__ taps,
+                                                               const double* __restrict__ w, int H, float c32) {
+  __shared__ float xs[LIM_N + 2 * HALO];
+  __shared__ float hs[4][PHASE_TAPS];
+  __shared__ float a[2][LIM_N];
+  __shared__ double ws[2 * MAX_H + 1];
+  const fh_stream_job J = jobs[blockIdx.y];
+  if (!job_ok(J)) return;
+  const sd_src S = source(J);
+  if (blockIdx.x == gridDim.x - 1) {
+    keep_tail(J, S);
+    return;
+  }
+  const long long rel0 = (long long)blockIdx.x * TILE;               // the tile's first output in dst
+  if (rel0 >= J.n_out) return;
+  const long long tile0 = J.first + rel0, end = S.end();
+  const int t = threadIdx.x, W = 2 * H + 1, N = TILE + 4 * H;
+  load_taps(taps, hs);
+  for (int j = t; j < N + 2 * HALO; j += THREADS) xs[j] = S.at(tile0 - 2 * H - HALO + j);      // (0 before sample 0 and past `end`)
+  for (int j = t; j < W; j += THREADS) ws[j] = w[j];
+  __syncthreads();
+  for (int j = t; j < N; j += THREADS) {                            // a[0][j] = r[tile0 - 2 H + j]
+    const long long n = tile0 - 2 * H + j;
+    float r = 1.f;
+    if (n >= 0 && n < end) {
+      float mv = fabsf(xs[j + HALO]);
+      mv = fmaxf(mv, tp_phase<0>(xs, hs, j));
+      mv = fmaxf(mv, tp_phase<1>(xs, hs, j));
+      mv = fmaxf(mv, tp_phase<2>(xs, hs, j));
+      mv = fmaxf(mv, tp_phase<3>(xs, hs, j));
+      if (mv > c32) r = __fdiv_rn(c32, mv);
+    }
+    a[0][j] = r;
+  }
+  __syncthreads();
+  int cur = 0, P = 1;
+  for (; 2 * P <= W; P *= 2) {                                      // a[cur][j] = min r[j .. j + P) -> ... + 2 P)
+    for (int j = t; j < N; j += THREADS) a[cur ^ 1][j] = j + P < N ? fminf(a[cur][j], a[cur][j + P]) : a[cur][j];
+    cur ^= 1;
+    __syncthreads();
+  }
+  // q[i] = min r[i .. i + W): the sample tile0 - H + i, i < TILE + 2 H (i + W - 1 <= N - 1)
+  float* __restrict__ q = a[cur ^ 1];
+  for (int i = t; i < TILE + 2 * H; i += THREADS) q[i] = fminf(a[cur][i], a[cur][i + W - P]);
+  __syncthreads();
+  double acc[PER];
+#pragma unroll
+  for (int k = 0; k < PER; ++k) acc[k] = 0.0;
+  for (int kk = 0; kk < W; ++kk) {                                  // g[tile0 + i] = sum_kk w[kk] q[i + kk], ascending
+    const double wv = ws[kk];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) acc[k] = fma(wv, (double)q[t + k * THREADS + kk], acc[k]);
+  }
+  float* __restrict__ dst = (float*)J.dst + rel0;
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    const int i = t + k * THREADS;
+    if (rel0 + i < J.n_out) dst[i] = limit_sample(xs[i + 2 * H + HALO], (float)acc[k], c32);
+  }
+}
+
+// dst[o] = pcm.hip's encode of the source's sample first + o with the dither of channel 0 at the index first + o.  A thread owns
+// the 16-byte word of 8 outputs counted from the aligned address at or below dst, as pcm_i16_kernel does for a planar row.
+__global__ __launch_bounds__(THREADS) void stream_pcm_kernel(const fh_stream_job* __restrict__ jobs,
+                                                             const unsigned long long* __restrict__ keys) {
+  const fh_stream_job J = jobs[blockIdx.y];
+  if (!job_ok(J) || (((size_t)J.dst) & 1)) return;                  // (an odd dst would misalign every 16-byte store)
+  const sd_src S = source(J);
+  int16_t* __restrict__ row = (int16_t*)J.dst;
+  const int lead = (int)(((size_t)row >> 1) & (RUN - 1));
+  const long long first = ((long long)blockIdx.x * THREADS + threadIdx.x) * RUN - lead;      // the run's first output
+  if (J.n_out == 0 || first >= J.n_out) return;
+  float x[RUN], d[RUN];
+#pragma unroll
+  for (int k = 0; k < RUN; ++k) {
+    const long long o = first + k;
+    x[k] = (o >= 0 && o < J.n_out) ? S.at(J.first + o) : 0.f;
+    d[k] = 0.f;
+  }
+  if (keys) dither_run(keys[2 * blockIdx.y], keys[2 * blockIdx.y + 1], 0, J.first + first, d);
+  if (first >= 0 && first + RUN <= J.n_out) {
+    i16x8 v;
+#pragma unroll
+    for (int k = 0; k < RUN; ++k) v[k] = encode(x[k], d[k]);
+    *reinterpret_cast<i16x8*>(row + first) = v;
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < RUN; ++k) {
+    const long long o = first + k;
+    if (o >= 0 && o < J.n_out) row[o] = encode(x[k], d[k]);
+  }
+}
+
+}  // namespace
+
+extern "C" int fh_sizeof_stream_job(void) { return (int)sizeof(fh_stream_job); }
+
+#define FH_CHECK_STREAM_JOBS(name)                                                                   \
+  FH_CHECK_ARG(jobs, name ": null job table");                                                       \
+  FH_CHECK_ARG(n_jobs > 0 && n_jobs < 65536, name ": %d jobs (1 .. 65535)", n_jobs);                 \
+  FH_CHECK_ARG(max_out >= 0, name ": max_out %d must not be negative", max_out)
+
+extern "C" int fh_stream_resample_f32(const fh_stream_job* jobs, int n_jobs, int max_out, const float* taps, int up, int down,
+                                      int n_taps, int pre, void* stream) {
+  FH_CHECK_STREAM_JOBS("fh_stream_resample_f32");
+  FH_CHECK_ARG(taps, "fh_stream_resample_f32: null taps");
+  FH_CHECK_ARG(up > 0 && down > 0 && n_taps > 0 && pre >= 0, "fh_stream_resample_f32: up %d, down %d, n_taps %d must be positive, "
+               "pre %d not negative", up, down, n_taps, pre);
+  hipLaunchKernelGGL(stream_resample_kernel, dim3(fh_cdiv(max_out, THREADS) + 1, n_jobs), dim3(THREADS), 0, (hipStream_t)stream, jobs,
+                     taps, up, down, n_taps, pre);
+  FH_CHECK_LAUNCH("fh_stream_resample_f32");
+  return FH_OK;
+}
+
+extern "C" int fh_stream_limit_f32(const fh_stream_job* jobs, int n_jobs, int max_out, const float* taps4, const double* w, int H,
+                                   float ceiling, void* stream) {
+  FH_CHECK_STREAM_JOBS("fh_stream_limit_f32");
+  FH_CHECK_ARG(taps4 && w, "fh_stream_limit_f32: null pointer (taps4 %p, w %p)", (const void*)taps4, (const void*)w);
+  FH_CHECK_ARG(H >= 1 && H <= MAX_H, "fh_stream_limit_f32: H %d (1 .. %d)", H, MAX_H);
+  FH_CHECK_ARG(ceiling > 0.f && ceiling <= 1.f, "fh_stream_limit_f32: ceiling %g (0 < c <= 1)", (double)ceiling);
+  FH_CHECK_ARG((((size_t)taps4) & 3) == 0 && (((size_t)w) & 7) == 0, "fh_stream_limit_f32: taps4 must be 4-byte, w 8-byte aligned");
+  hipLaunchKernelGGL(stream_limit_kernel, dim3(fh_cdiv(max_out, TILE) + 1, n_jobs), dim3(THREADS), 0, (hipStream_t)stream, jobs, taps4,
+                     w, H, ceiling);
+  FH_CHECK_LAUNCH("fh_stream_limit_f32");
+  return FH_OK;
+}
+
+extern "C" int fh_stream_pcm_i16_f32(const fh_stream_job* jobs, int n_jobs, int max_out, const uint64_t* keys, void* stream) {
+  FH_CHECK_STREAM_JOBS("fh_stream_pcm_i16_f32");
+  hipLaunchKernelGGL(stream_pcm_kernel, dim3(fh_cdiv(((long long)max_out + RUN - 1) / RUN + 1, THREADS), n_jobs), dim3(THREADS), 0,
+                     (hipStream_t)stream, jobs, (const unsigned long long*)keys);
+  FH_CHECK_LAUNCH("fh_stream_pcm_i16_f32");
+  return FH_OK;
+}

@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "fh_common.h"
+#include "truepeak_common.h"
 
 namespace {
 
@@ -30,6 +31,11 @@ constexpr int PLAN_TAPS = 8 * HALO + 2;         // tables.resample_poly_plan(4, 
 constexpr int MAX_H = 512;
 constexpr int MAX_LEN = 1 << 30;
 constexpr int LIM_N = TILE + 4 * MAX_H;
+// (load_taps, tp_phase and limit_sample are in truepeak_common.h, shared with stream_delivery.hip; the constants are one statement)
+static_assert(HALO == tp::HALO && PHASE_TAPS == tp::PHASE_TAPS && PLAN_TAPS == tp::PLAN_TAPS && MAX_H == tp::MAX_H, "truepeak_common.h");
+using tp::limit_sample;
+using tp::load_taps;
+using tp::tp_phase;
 
 struct tp_row {                                 // one row as the true-peak body sees it
   const float* x;
@@ -81,23 +87,6 @@ struct ClipTable {                              // one fh_pcm_clip per clip on t
             c.len};
   }
 };
-
-// hs[p][i] = h[p + 4 i], h = taps + 1 (the plan's taps behind its leading pad); phases 1 .. 3 have 20 taps
-__device__ __forceinline__ void load_taps(const float* __restrict__ taps, float (*hs)[PHASE_TAPS]) {
-  const int t = threadIdx.x;
-  if (t < 4 * PHASE_TAPS) {
-    const int p = t / PHASE_TAPS, i = t % PHASE_TAPS, j = p + 4 * i;
-    hs[p][i] = j < PLAN_TAPS - 1 ? taps[1 + j] : 0.f;
-  }
-}
-
-template <int P>
-__device__ __forceinline__ float tp_phase(const float* __restrict__ xs, const float (*hs)[PHASE_TAPS], int i) {
-  float acc = 0.f;
-#pragma unroll
-  for (int k = 0; k < (P == 0 ? PHASE_TAPS : PHASE_TAPS - 1); ++k) acc = fmaf(hs[P][k], xs[i + 2 * HALO - k], acc);
-  return fabsf(acc);
-}
 
 // v[k] = max(|x[n]|, |x4[4 n + p]|, p = 0 .. 3) of frame n = tile0 + threadIdx.x + k * THREADS of the row x[0 .. len), 0 past its end.
 // Ends with a barrier: xs may be staged again at once.  (hs is ready: the barrier behind the staging comes before its first read.)
@@ -169,10 +158,6 @@ __global__ __launch_bounds__(THREADS) void tp_envelope_kernel(Loc loc, const flo
     const int i = threadIdx.x + k * THREADS;
     if (tile0 + i < c.len) out[i] = best[k];
   }
-}
-
-__device__ __forceinline__ float limit_sample(float x, float g, float c32) {
-  return fminf(fmaxf(__fmul_rn(x, g), -c32), c32);
 }
 
 template <class Loc>

@@ -1,0 +1,181 @@
+"""Streaming delivery on the device: FlowHighSR.stream(delivery=) / delivery_stream / delivery_push (stream_delivery.py is the
+schedule and the definition, csrc/stream_delivery.hip the kernels).
+
+A DeliveryStream takes the 48 kHz float32 blocks of one mono stream and returns them delivered -- resampled to output_rate, held
+under true_peak by the look-ahead limiter, encoded to int16 with dither -- with the bits of Delivery.batch(whole stream, [1],
+'input', ...).  Each stage keeps its counters (stream_delivery.Stage) and two device carry buffers that take turns; a push is
+at most three launches for all of its streams that share a plan, each launch one job per stream, and one upload of that plan's
+job tables.  Nothing is read back: what a push emits follows from the lengths of the blocks alone.  The blocks a push returns are
+views of one buffer per plan.
+"""
+import numpy as np
+import torch
+
+from . import delivery as _delivery
+from . import hip
+from . import stream_delivery as SD
+from . import truepeak as _truepeak
+from .frontend import upload_tables
+
+KEYWORDS = ("output_rate", "pcm", "dither", "dither_seed", "true_peak", "limiter")
+_REFUSED = dict(loudness="loudness is a statistic of the whole stream", channels="a stream is mono",
+                interleaved="a stream is mono: there is nothing to interleave")
+
+
+def resolve(delivery, session_pcm=None):
+    """delivery= of stream() / the keywords of delivery_stream(), checked (ValueError, before any GPU work) -> None when every
+    value is a default, else dict(rate: None | R, true_peak: None | the ceiling in dBTP, pcm, key: None | the dither's (seed, stream))."""
+    if delivery is None:
+        return None
+    if not isinstance(delivery, dict):
+        raise ValueError(f"delivery must be None or a dict of {', '.join(KEYWORDS)}, got {delivery!r}")
+    for name in delivery:
+        if name in _REFUSED:
+            raise ValueError(f"delivery= does not take {name}=: {_REFUSED[name]}")
+        if name not in KEYWORDS:
+            raise ValueError(f"delivery= has no key {name!r}: it takes {', '.join(KEYWORDS)}")
+    kw = {k: delivery.get(k) for k in KEYWORDS if k != "dither_seed"}
+    if kw["true_peak"] is not None and kw["limiter"] is None:
+        raise ValueError("true_peak= without limiter='lookahead' is one gain from the whole stream's peak: a stream takes "
+                         "true_peak= with limiter='lookahead'")
+    opt = _delivery.resolve_delivery(1, dither_seed=delivery.get("dither_seed", 0), level="input", **kw)
+    if opt is None:
+        return None
+    if session_pcm is not None:
+        raise ValueError("delivery= and the session's pcm= are two encoders for one stream: give pcm in delivery=")
+    return SD.make_plan(opt["rate"], opt.get("true_peak"), opt["pcm"], None if opt["keys"] is None else opt["keys"][0])
+
+
+class _StageState:
+    """One stage of one stream on the device: the schedule's counters and two carry buffers of `capacity` samples."""
+
+    def __init__(self, counters, capacity):
+        self.counters, self.capacity = counters, int(capacity)
+        self.buffers, self.cur = None, 0
+
+    def job(self, fresh, n_fresh, dst, ended, device):
+        """The fh_stream_job of this push; the counters move on and the carry buffers change places."""
+        step = self.counters.step(n_fresh, ended)
+        if self.buffers is None and self.capacity:
+            self.buffers = [torch.empty(self.capacity, dtype=torch.float32, device=device) for _ in range(2)]
+        c = self.counters
+        assert step["n_carry"] <= self.capacity and step["n_keep"] <= self.capacity, (step, self.capacity)
+        assert step["base"] + step["n_carry"] + n_fresh == c.arrived and step["first"] + step["n_out"] == c.emitted
+        assert step["n_out"] == 0 or step["base"] <= c._lowest(step["first"])
+        carry = self.buffers[self.cur].data_ptr() if step["n_carry"] else 0
+        keep = self.buffers[self.cur ^ 1].data_ptr() if step["n_keep"] else 0
+        self.cur ^= 1                            # (with n_keep == 0 the next carry is empty: either buffer will do)
+        return hip.StreamJob(carry, fresh if n_fresh else 0, dst if step["n_out"] else 0, keep, step["base"], step["first"],
+                             step["n_carry"], n_fresh, step["n_out"], step["n_keep"], int(ended), 0), step["n_out"]
+
+
+class DeliveryStream:
+    """One stream of FlowHighSR.delivery_stream().  push(block48) -> the delivered samples that block made final, float32
+    (int16 with pcm) [1, n] on the device, n may be 0; flush() -> the rest, and the stream is closed."""
+
+    def __init__(self, plan, owner=None):
+        if plan is None:
+            raise ValueError("every delivery keyword is at its default: there is nothing to deliver")
+        self.plan, self.owner, self.closed = plan, owner, False
+        self.key = (plan["rate"], plan["true_peak"], plan["pcm"], plan["key"] is not None)          # streams of one key share launches
+        self.stages = {}
+        if plan["rate"] is not None:
+            flt = SD.ResampleFilter(plan["rate"])
+            self.stages["resample"] = _StageState(SD.ResampleStage(flt), flt.carry_bound)
+        if plan["true_peak"] is not None:
+            H = _truepeak.half_window(plan["rate"] or 48000)
+            self.stages["limit"] = _StageState(SD.LimitStage(H), 2 * (2 * H + _truepeak.HALF))
+        if plan["pcm"] is not None:
+            self.stages["encode"] = _StageState(SD.EncodeStage(), 0)
+
+    def push(self, block48):
+        return self.owner.delivery_push([self], [block48])[0]
+
+    def flush(self):
+        return self.owner.delivery_push([self], [None], final=True)[0]
+
+
+def _block(b, device):
+    """A pushed block as float32 [n] on the device (None: nothing)."""
+    if b is None:
+        return torch.empty(0, dtype=torch.float32, device=device)
+    if not isinstance(b, torch.Tensor) or b.dtype != torch.float32 or b.device != device or b.ndim not in (1, 2) \
+            or (b.ndim == 2 and b.shape[0] != 1):
+        raise ValueError(f"a block is a float32 [1, n] tensor on {device} at 48 kHz, got {getattr(b, 'dtype', type(b))} "
+                         f"{tuple(getattr(b, 'shape', ()))} on {getattr(b, 'device', 'the host')}")
+    return b.reshape(-1).contiguous()
+
+
+def push(delivery, streams, blocks, final=False):
+    """One 48 kHz block per stream (None: nothing this time) -> one delivered block per stream, [1, n].  delivery: the model's
+    Delivery (its device, its tap cache and limiter windows).  final: the streams end here; they are closed afterwards.
+    Every stage is ONE launch for all the streams that share a plan; a stream's result does not depend on its company."""
+    with hip.device_guard(delivery.device):
+        return _push(delivery, streams, blocks, final)
+
+
+def _push(delivery, streams, blocks, final):
+    streams, blocks = list(streams), list(blocks)
+    if len(streams) != len(blocks):
+        raise ValueError(f"one block per stream: {len(blocks)} blocks for {len(streams)} streams")
+    if len({id(s) for s in streams}) != len(streams):
+        raise ValueError("a stream is in the list twice")
+    for s in streams:
+        if s.closed:
+            raise RuntimeError("the stream is closed: flush() ends a stream")
+    dev = delivery.device
+    cur = [_block(b, dev) for b in blocks]             # (every block is checked before any stream moves)
+    if final:
+        for s in streams:
+            s.closed = True
+    groups = {}
+    for i, s in enumerate(streams):
+        groups.setdefault(s.key, []).append(i)
+    for key, idx in groups.items():
+        rate, ceiling_db, pcm, dithered = key
+        # What every stage emits follows from the blocks' lengths, so the jobs of all stages are made first and go up as ONE
+        # buffer; a stage's outputs are one buffer too, a stream's part of it the next stage's fresh block.
+        n_in = {i: cur[i].numel() for i in idx}
+        src = {i: cur[i].data_ptr() for i in idx}
+        stages, tables_ = [], []
+        for name in ("resample", "limit", "encode"):
+            if name not in streams[idx[0]].stages:
+                continue
+            # (a stream with nothing new and nothing to end stays as it is: its job would write and move nothing)
+            live = [i for i in idx if final or n_in[i]]
+            if not live:
+                continue
+            rooms = [streams[i].stages[name].counters.peek(n_in[i], final) for i in live]
+            offs = [int(o) for o in np.cumsum([0] + [-(-r // 8) * 8 for r in rooms[:-1]])]          # (16-byte aligned parts)
+            buf = torch.empty(offs[-1] + rooms[-1], dtype=torch.int16 if name == "encode" else torch.float32, device=dev)
+            jobs = []
+            for i, off, room in zip(live, offs, rooms):
+                dst = buf.data_ptr() + off * buf.element_size()
+                job, n_out = streams[i].stages[name].job(src[i], n_in[i], dst, final, dev)
+                assert n_out == room
+                jobs.append(job)
+                cur[i], src[i], n_in[i] = buf[off:off + room], dst, room
+            stages.append((name, live, max(rooms), buf))
+            tables_.append((hip.StreamJob * len(jobs))(*jobs))
+        if not stages:
+            continue
+        if dithered and stages[-1][0] == "encode":
+            tables_.append(np.array([streams[i].plan["key"] for i in stages[-1][1]], dtype=np.uint64).view(np.int64))
+        keep, ptrs = upload_tables(tables_, dev)
+        L = hip.lib()
+        for (name, live, max_out, _), jp in zip(stages, ptrs):
+            if name == "resample":
+                taps, n_taps, pre, up, down = delivery.resampler._filter(rate, 48000)
+                hip.check(L.fh_stream_resample_f32(jp, len(live), max_out, taps, up, down, n_taps, pre, hip.stream()), "fh_stream_resample_f32")
+            elif name == "limit":
+                H = streams[live[0]].stages[name].counters.H
+                c32 = float(np.float32(_truepeak.ceiling(ceiling_db)))
+                hip.check(L.fh_stream_limit_f32(jp, len(live), max_out, delivery._tp_taps(), delivery._window(H), H, c32, hip.stream()),
+                          "fh_stream_limit_f32")
+            elif max_out:
+                hip.check(L.fh_stream_pcm_i16_f32(jp, len(live), max_out, ptrs[-1] if dithered else 0, hip.stream()), "fh_stream_pcm_i16_f32")
+    out = []
+    for s, c in zip(streams, cur):                       # (what stood still at some stage emits an empty block of the result's type)
+        want = torch.float32 if s.plan["pcm"] is None else torch.int16
+        out.append(c[None] if c.numel() else torch.empty(1, 0, dtype=want, device=dev))
+    return out

@@ -1258,7 +1258,7 @@ class FlowHighSR:
 
     # ---- streaming sessions (stream.py is the definition, streaming.py the host side, csrc/stream.hip the seam) ------------------
     def stream(self, sr, *, window_ms=1000, overlap_ms=200, guard_ms=50, timestep=1, seed=None, stream=0, pcm=None,
-               channels=None, dither=None, output_rate=None, loudness=None, true_peak=None):
+               channels=None, dither=None, output_rate=None, loudness=None, true_peak=None, delivery=None):
         """A streaming session at the input rate `sr` (prior='device' models): push(block) returns the samples that block made
         final, float32 [1, n] on the device at 48 kHz (n may be 0), flush() the rest; the blocks of a stream of T input samples
         add up to tables.resample_out_len(T, 48000, sr) samples, equal to stream.stitch of its windows' results bit for bit.
@@ -1269,10 +1269,18 @@ class FlowHighSR:
         Latency: a sample is final once the window that holds it left of its right overlap has arrived, at most window_ms after it
         came in, plus one batched run.  The sample format is fixed by the session's first block: an integer dtype is divided by
         32768, a float dtype taken as it is.  pcm='int16' encodes every emitted block (no dither: the encoding is stateless).
-        Not built, each a ValueError: channels=, dither=, output_rate=, loudness=, true_peak=."""
+        delivery=dict(output_rate=, pcm=, dither=, dither_seed=, true_peak=, limiter='lookahead'): what the session emits goes
+        through a DeliveryStream (delivery_stream()): the keywords mean what they mean to generate(level='input'), and the blocks
+        of the stream add up to the bits of that delivery of the whole 48 kHz stream, delivery.delivered_len(T48, output_rate)
+        samples.  The resampler withholds about 10 max(up, down) / up samples at 48 kHz and the limiter 2 H + 10 delivered
+        samples (about 10.2 ms) until the flush.  The dither's key is (dither_seed, 0).  delivery= excludes the session's own pcm=;
+        it does not take loudness= (a statistic of the whole stream), true_peak= without the limiter (the same), channels= or
+        interleaved= (a session is mono); a dict of defaults is None.
+        Not built as keywords of their own, each a ValueError: channels=, dither=, output_rate=, loudness=, true_peak=."""
         from .streaming import open_session
         return open_session(self, sr, window_ms, overlap_ms, guard_ms, timestep, seed, stream, pcm,
-                            dict(channels=channels, dither=dither, output_rate=output_rate, loudness=loudness, true_peak=true_peak))
+                            dict(channels=channels, dither=dither, output_rate=output_rate, loudness=loudness, true_peak=true_peak),
+                            delivery)
 
     def stream_push(self, sessions, blocks):
         """One block per session -> one output block per session (StreamSession.push).  Every window that became runnable, of
@@ -1294,8 +1302,23 @@ class FlowHighSR:
         from .streaming import run
         return run(self, sessions, final)
 
+    def delivery_stream(self, **keywords):
+        """The delivery of a stream on its own: output_rate=, pcm=, dither=, dither_seed=, true_peak=, limiter= as stream(delivery=)
+        takes them -> a DeliveryStream: push(block48) takes float32 [1, n] on the device at 48 kHz and returns the delivered
+        samples it made final, flush() the rest.  The blocks add up to Delivery.batch of the whole stream at level='input'."""
+        from .delivery_stream import DeliveryStream, resolve
+        return DeliveryStream(resolve(keywords), self)
+
+    @torch.no_grad()
+    def delivery_push(self, streams, blocks, final=False):
+        """One 48 kHz block per DeliveryStream (None: nothing) -> one delivered block per stream; every stage is one launch for
+        all the streams that share a plan.  final: the streams end here."""
+        from .delivery_stream import push
+        return push(self.delivery, streams, blocks, final)
+
     def generate_long(self, audio, sr, **stream_keywords):
-        """A clip of any length through a streaming session: push everything, then flush -> [1, T48] (int16 with pcm='int16').
+        """A clip of any length through a streaming session: push everything, then flush -> [1, T48] (int16 with pcm='int16');
+        with delivery=: [1, delivery.delivered_len(T48, output_rate)] at the delivered rate, int16 with delivery's pcm.
         Keywords: those of stream().  Memory and attention cost are those of one push's windows, whatever the clip's length."""
         s = self.stream(sr, **stream_keywords)
         first = s.push(audio)

@@ -89,6 +89,13 @@ class XfadeJob(C.Structure):
     _fields_ = [("head", C.c_void_p), ("tail", C.c_void_p)]
 
 
+class StreamJob(C.Structure):
+    """fh_stream_job: one stream of a fh_stream_*_f32 launch (csrc/stream_delivery.hip)."""
+    _fields_ = [("carry", C.c_void_p), ("fresh", C.c_void_p), ("dst", C.c_void_p), ("carry_out", C.c_void_p),
+                ("base", C.c_int64), ("first", C.c_int64), ("n_carry", C.c_int32), ("n_fresh", C.c_int32),
+                ("n_out", C.c_int32), ("n_keep", C.c_int32), ("ended", C.c_int32), ("pad_", C.c_int32)]
+
+
 class HipError(RuntimeError):
     pass
 
@@ -204,6 +211,10 @@ _SIGS = {
     "fh_delivery_gain_f32": [_P, _D, _P, _P, _P, _I, _I, _D, _I, _P, _P, _P],
     "fh_sizeof_xfade_job": [],
     "fh_xfade_seg_f32": [_P, _I, _P, _P, _I, _P],
+    "fh_sizeof_stream_job": [],
+    "fh_stream_resample_f32": [_P, _I, _I, _P, _I, _I, _I, _I, _P],
+    "fh_stream_limit_f32": [_P, _I, _I, _P, _P, _I, _F, _P],
+    "fh_stream_pcm_i16_f32": [_P, _I, _I, _P, _P],
 }
 EXPORTS = sorted(_SIGS) + ["fh_last_error"]
 
@@ -236,7 +247,7 @@ def lib():
             or L.fh_sizeof_wino_group() != C.sizeof(WinoGroup) or L.fh_sizeof_sum_job() != C.sizeof(SumJob) \
             or L.fh_sizeof_amp_group() != C.sizeof(AmpGroup) or L.fh_sizeof_clip() != C.sizeof(Clip) \
             or L.fh_sizeof_rate() != C.sizeof(Rate) or L.fh_sizeof_pcm_clip() != C.sizeof(PcmClip) \
-            or L.fh_sizeof_xfade_job() != C.sizeof(XfadeJob):
+            or L.fh_sizeof_xfade_job() != C.sizeof(XfadeJob) or L.fh_sizeof_stream_job() != C.sizeof(StreamJob):
         raise HipError("descriptor struct layout mismatch between hip.py and flowhigh_hip.h")
     _lib = L
     return L

@@ -24,25 +24,29 @@ KEY_TAG = 0x50434D31            # 'PCM1'
 FULL_SCALE = 32768.0
 
 
-def dither_uniforms(seed, stream, channel, n):
-    """(ra >> 8, rb >> 8) of samples 0 .. n - 1 of one channel: two uint32 arrays [n] of 24-bit integers."""
+def dither_uniforms(seed, stream, channel, n, first=0):
+    """(ra >> 8, rb >> 8) of samples first .. first + n - 1 of one channel: two uint32 arrays [n] of 24-bit integers.
+    first: the absolute index of the first sample (a block of a stream, stream_delivery.py); the counter has 64 bits."""
     seed, stream = normalize_key(seed, stream)
-    n = int(n)
+    n, first = int(n), int(first)
     if n < 0 or not 0 <= int(channel) < 2 ** 32:
         raise ValueError(f"n {n} must be >= 0 and channel {channel} a 32-bit index")
-    q = np.arange((n + 1) // 2, dtype=np.uint64)
+    if first < 0 or first + n > 2 ** 64:
+        raise ValueError(f"first {first} must be >= 0 and leave the sample index within 64 bits")
+    q = np.arange(first >> 1, (first + n + 1) >> 1, dtype=np.uint64)         # the blocks that hold the samples
+    odd = first & 1
     ctr = np.empty((q.size, 4), dtype=np.uint64)
     ctr[:, 0], ctr[:, 1] = q & np.uint64(_MASK32), q >> np.uint64(32)
     ctr[:, 2], ctr[:, 3] = stream & _MASK32, stream >> 32
     r = philox4x32_10(ctr, ((seed & _MASK32) ^ KEY_TAG, ((seed >> 32) ^ int(channel)) & _MASK32))
-    ra = r[:, 0::2].reshape(-1)[:n] >> np.uint32(8)          # (r0, r2) of every block = samples 2q, 2q + 1
-    rb = r[:, 1::2].reshape(-1)[:n] >> np.uint32(8)
+    ra = r[:, 0::2].reshape(-1)[odd:odd + n] >> np.uint32(8)          # (r0, r2) of every block = samples 2q, 2q + 1
+    rb = r[:, 1::2].reshape(-1)[odd:odd + n] >> np.uint32(8)
     return ra, rb
 
 
-def tpdf_dither(seed, stream, channel, n):
-    """float32 [n]: the dither of samples 0 .. n - 1 of channel `channel` under the key (seed, stream), in LSB."""
-    ra, rb = dither_uniforms(seed, stream, channel, n)
+def tpdf_dither(seed, stream, channel, n, first=0):
+    """float32 [n]: the dither of samples first .. first + n - 1 of channel `channel` under the key (seed, stream), in LSB."""
+    ra, rb = dither_uniforms(seed, stream, channel, n, first)
     d = (ra.astype(np.int64) - rb.astype(np.int64)).astype(np.float64) * 2.0 ** -24
     out = d.astype(np.float32)
     assert np.array_equal(out.astype(np.float64), d)          # exact by construction

@@ -5,6 +5,8 @@ runs, with its prior drawn by fh_prior_normal_at_f32 from the session's key at t
 windows are joined over their overlap by fh_xfade_seg_f32.  Every runnable window of every session of a push that shares a plan
 and a number of time steps is a row of ONE batch (rows of a batch have the bits of a clip alone) and a job of ONE seam launch.
 Pending input samples live on the host, the previous window's last O48 output samples on the device, in a buffer of the session's own.
+A session opened with delivery= hands what it emits to a DeliveryStream of its own (delivery_stream.py): all such sessions of a push
+go through one launch sequence there.
 """
 import numpy as np
 import torch
@@ -14,9 +16,12 @@ from .frontend import upload_tables
 from .stream import StreamPlan
 
 # keywords of generate() that a session does not take, and why
-_NOT_BUILT = dict(channels="a session is one mono stream", dither="dither needs a sample-index offset across blocks (csrc/pcm.hip)",
-                  output_rate="resampling a stream needs resampler state across blocks",
-                  loudness="loudness is a statistic of a whole clip", true_peak="the true peak is a statistic of a whole clip")
+_CARRIED = "delivery=dict(...) carries it across pushes"
+_NOT_BUILT = dict(channels="a session is one mono stream",
+                  dither=f"dither needs a sample-index offset across blocks (csrc/pcm.hip): {_CARRIED}",
+                  output_rate=f"resampling a stream needs resampler state across blocks: {_CARRIED}",
+                  loudness="loudness is a statistic of a whole clip",
+                  true_peak=f"the true peak is a statistic of a whole clip: {_CARRIED} with limiter='lookahead'")
 
 
 def check_not_built(**kw):
@@ -28,8 +33,9 @@ def check_not_built(**kw):
 class StreamSession:
     """One stream of a FlowHighSR.stream() call.  push(block) -> the newly final samples, flush() -> the rest."""
 
-    def __init__(self, model, plan, timestep, key, pcm):
+    def __init__(self, model, plan, timestep, key, pcm, delivery=None):
         self.model, self.plan, self.timestep, self.key, self.pcm = model, plan, int(timestep), key, pcm
+        self.delivery = delivery                # None | the session's DeliveryStream: what it emits goes through it
         self.closed = False
         self.integer = None                     # the sample format, fixed by the first block: integer dtype (/ 32768) or float
         self.dtype = None
@@ -87,7 +93,8 @@ class StreamSession:
         return out, bool(k) and not out
 
     def push(self, block):
-        """float32 (int16 with pcm=) [1, n] on the device: the samples this block made final; n may be 0."""
+        """float32 (int16 with pcm=) [1, n] on the device: the samples this block made final (with delivery=: at the delivered
+        rate, those its delivery made final); n may be 0."""
         return self.model.stream_push([self], [block])[0]
 
     def flush(self):
@@ -95,7 +102,8 @@ class StreamSession:
         return self.model._stream_run([self], final=True)[0]
 
 
-def open_session(model, sr, window_ms, overlap_ms, guard_ms, timestep, seed, stream, pcm, not_built):
+def open_session(model, sr, window_ms, overlap_ms, guard_ms, timestep, seed, stream, pcm, not_built, delivery=None):
+    from .delivery_stream import DeliveryStream, resolve
     from .prior import normalize_key
     check_not_built(**not_built)
     if model.prior != 'device':
@@ -110,7 +118,8 @@ def open_session(model, sr, window_ms, overlap_ms, guard_ms, timestep, seed, str
         seed = int(torch.randint(0, 2 ** 63 - 1, (1,)))
     elif isinstance(seed, (bool, float)) or not isinstance(seed, (int, np.integer)):
         raise TypeError(f"seed must be an int, got {seed!r}")
-    return StreamSession(model, plan, timestep, normalize_key(seed, stream), pcm)
+    opt = resolve(delivery, pcm)
+    return StreamSession(model, plan, timestep, normalize_key(seed, stream), pcm, None if opt is None else DeliveryStream(opt, model))
 
 
 def _ramp(model, plan):
@@ -189,4 +198,10 @@ def run(model, sessions, final):
             s.tail = None
         block = torch.cat(parts[si], 0)[None] if parts[si] else torch.empty(1, 0, dtype=torch.float32, device=model.device)
         out.append(_encode(model, block) if s.pcm == "int16" else block)
+    # every delivering session's block of this push through one launch sequence (delivery_stream.py)
+    carried = [si for si, s in enumerate(sessions) if s.delivery is not None]
+    if carried:
+        from .delivery_stream import push
+        for si, y in zip(carried, push(model.delivery, [sessions[si].delivery for si in carried], [out[si] for si in carried], final)):
+            out[si] = y
     return out

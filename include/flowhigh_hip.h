@@ -797,6 +797,45 @@ typedef struct {
 int fh_sizeof_xfade_job(void);
 int fh_xfade_seg_f32(const fh_xfade_job* jobs, int n_jobs, const float* w_in, const float* w_out, int o48, void* stream);
 
+/* -----------------------------------------------------------------------------------
+ * Streaming delivery (csrc/stream_delivery.hip; FlowHighSR.stream(delivery=), FlowHighSR.delivery_stream): the resampler, the
+ * look-ahead limiter and the int16 encoder of delivery run block by block over a stream, with the bits of the one-shot entries on
+ * the whole stream (flowhigh_amd/stream_delivery.py is the schedule and the definition).  One job per stream and launch, jobs:
+ * DEVICE array.  A job's source is two spans read as one run of float32 samples -- the carry the stream kept, then the fresh
+ * block -- whose first sample has the absolute index `base`; a sample outside the spans reads as 0.  The job writes the outputs
+ * with the absolute indices [first, first + n_out) to dst[0 .. n_out) and copies the last n_keep source samples to
+ * carry_out[0 .. n_keep) (a buffer that is neither span: a stream's two carry buffers take turns).  A job with a negative count,
+ * a negative base or first, n_keep > n_carry + n_fresh, a null pointer to something it would use or (fh_stream_pcm_i16_f32) a dst
+ * at an odd address is left unwritten; no job
+ * reads outside its spans or writes outside dst[0 .. n_out) and carry_out[0 .. n_keep).  n_jobs <= 65535; max_out: the largest
+ * n_out of the table (0: only carries move). */
+typedef struct {
+  const void* carry;   /* n_carry float32: the carried samples */
+  const void* fresh;   /* n_fresh float32: the new block */
+  void* dst;           /* n_out outputs: float32, int16 for fh_stream_pcm_i16_f32 */
+  void* carry_out;     /* n_keep float32 (fh_stream_pcm_i16_f32 keeps nothing and does not read it) */
+  int64_t base;        /* absolute index of carry[0] (of fresh[0] when n_carry is 0) */
+  int64_t first;       /* absolute index of dst[0] */
+  int32_t n_carry, n_fresh, n_out, n_keep;
+  int32_t ended;       /* NOT READ BY THE KERNELS: the host's record that the stream ends at base + n_carry + n_fresh.  What lies
+                          past the spans reads as the zeros (and r = 1) past a clip's end whether it is set or not; it is the
+                          schedule that asks for outputs that read there only when the stream has ended */
+  int32_t pad_;
+} fh_stream_job;
+int fh_sizeof_stream_job(void);
+/* out[i] = sum_j x[j] taps[(i + pre) down - j up], fh_resample_poly_f32's loop and order with 64-bit indices; j runs down from
+ * min((i + pre) down / up, the source's last sample). */
+int fh_stream_resample_f32(const fh_stream_job* jobs, int n_jobs, int max_out, const float* taps, int up, int down, int n_taps,
+                           int pre, void* stream);
+/* fh_tp_envelope_f32 + fh_limit_f32 of a mono stream in one launch: y[n] for n in [first, first + n_out) from the samples
+ * n - 2 H - 10 .. n + 2 H + 10, zeros and r = 1 before sample 0 and past the source's end.  taps4: fh_tp_envelope_f32's taps;
+ * w: DEVICE double [2 H + 1]; H 1 .. 512; 0 < ceiling <= 1.  Grid (tiles of 1024 outputs + 1, jobs). */
+int fh_stream_limit_f32(const fh_stream_job* jobs, int n_jobs, int max_out, const float* taps4, const double* w, int H,
+                        float ceiling, void* stream);
+/* fh_pcm_i16_f32's encoding of one channel: output o of a job encodes the source's sample first + o with the dither of channel 0
+ * at the 64-bit sample index first + o under the job's key.  keys: DEVICE uint64 [n_jobs][2], NULL: no dither. */
+int fh_stream_pcm_i16_f32(const fh_stream_job* jobs, int n_jobs, int max_out, const uint64_t* keys, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
