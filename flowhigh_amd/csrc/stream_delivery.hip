@@ -4,6 +4,8 @@
 //   fh_stream_limit_f32      the oversampled envelope and the look-ahead limiter of a mono stream in one launch
 //                            (truepeak.hip: tp_envelope_kernel + limit_kernel, their arithmetic and order)
 //   fh_stream_pcm_i16_f32    pcm.hip's encoder with the dither at the sample's absolute index
+//   fh_stream_limit_linked_f32   the limiter of streams of 1 .. 8 channels: one envelope and one gain for a stream's channels
+//   fh_stream_pcm_i16_rows_f32   the encoder of such streams: channel c's dither, planar rows or interleaved sample frames
 // One fh_stream_job per stream and launch.  A job's source is TWO spans, the carry the stream kept and the fresh block, read as
 // one run of samples whose first has the absolute index `base`; nothing is concatenated.  The last block column of a launch
 // copies the last n_keep source samples into the stream's other carry buffer (the two ping-pong, so the copy never writes
@@ -16,6 +18,13 @@
 // sample 0, and past its last one when it has ended), m and r over tile +- 2 H are computed from there (r = 1 outside the
 // stream), then the sliding minimum by doubling and the float64 Hann sum in ascending k as limit_kernel has them.  The
 // envelope work is (TILE + 4 H) / TILE of that of the two launches on a clip: the price of one launch and no m round trip.
+//
+// Channels: a stream of C channels is C consecutive jobs, one per channel row, with equal base, first and counts; a device table
+// `groups` of int32 [n_groups + 1] gives every stream's first job.  The resampler runs a row per job as it is.  The linked limiter's
+// workgroup owns one tile of one STREAM: it stages each channel in turn through the one xs buffer and folds the channels' peaks
+// with fmaxf in tp_envelope_kernel's order (best = 0, then channel 0, 1, ...) into one m per sample; r, the sliding minimum and
+// the Hann sum then run once per tile, and every channel's x (read again from its source) takes the one g.  LDS is the mono
+// kernel's.  A group whose size is not 1 .. 8, whose jobs differ in a counter or one of whose jobs fails job_ok is left unwritten.
 #include "fh_common.h"
 #include "pcm_common.h"
 #include "truepeak_common.h"
@@ -27,6 +36,7 @@ constexpr int TILE = 1024;                      // outputs per workgroup of the 
 constexpr int PER = TILE / THREADS;
 constexpr int HALO = tp::HALO, PHASE_TAPS = tp::PHASE_TAPS, MAX_H = tp::MAX_H;
 constexpr int LIM_N = TILE + 4 * MAX_H;
+constexpr int MAX_CH = 8;                       // channels of a stream
 using tp::limit_sample;
 using tp::load_taps;
 using tp::tp_phase;
@@ -88,6 +98,39 @@ __global__ __launch_bounds__(THREADS) void stream_resample_kernel(const fh_strea
   ((float*)J.dst)[o] = acc;
 }
 
+// max(|x[n]|, |x4[4 n + p]|, p = 0 .. 3) of the sample staged at xs[j + HALO]: tp_tile's chain
+__device__ __forceinline__ float peak_at(const float* __restrict__ xs, const float (*hs)[PHASE_TAPS], int j) {
+  float mv = fabsf(xs[j + HALO]);
+  mv = fmaxf(mv, tp_phase<0>(xs, hs, j));
+  mv = fmaxf(mv, tp_phase<1>(xs, hs, j));
+  mv = fmaxf(mv, tp_phase<2>(xs, hs, j));
+  mv = fmaxf(mv, tp_phase<3>(xs, hs, j));
+  return mv;
+}
+
+// a[0][j] = r[tile0 - 2 H + j], j < N = TILE + 4 H (behind a barrier) -> acc[k] = g[tile0 + t + k THREADS] in float64: the sliding
+// minimum by doubling and the Hann sum in ascending k, as limit_kernel has them
+__device__ __forceinline__ void gain_tile(float (*a)[LIM_N], const double* __restrict__ ws, int H, double (&acc)[PER]) {
+  const int t = threadIdx.x, W = 2 * H + 1, N = TILE + 4 * H;
+  int cur = 0, P = 1;
+  for (; 2 * P <= W; P *= 2) {                                      // a[cur][j] = min r[j .. j + P) -> ... + 2 P)
+    for (int j = t; j < N; j += THREADS) a[cur ^ 1][j] = j + P < N ? fminf(a[cur][j], a[cur][j + P]) : a[cur][j];
+    cur ^= 1;
+    __syncthreads();
+  }
+  // q[i] = min r[i .. i + W): the sample tile0 - H + i, i < TILE + 2 H (i + W - 1 <= N - 1)
+  float* __restrict__ q = a[cur ^ 1];
+  for (int i = t; i < TILE + 2 * H; i += THREADS) q[i] = fminf(a[cur][i], a[cur][i + W - P]);
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < PER; ++k) acc[k] = 0.0;
+  for (int kk = 0; kk < W; ++kk) {                                  // g[tile0 + i] = sum_kk w[kk] q[i + kk], ascending
+    const double wv = ws[kk];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) acc[k] = fma(wv, (double)q[t + k * THREADS + kk], acc[k]);
+  }
+}
+
 __global__ __launch_bounds__(THREADS) void stream_limit_kernel(const fh_stream_job* __restrict__ jobs, const float* __restrict__ taps,
                                                                const double* __restrict__ w, int H, float c32) {
   __shared__ float xs[LIM_N + 2 * HALO];
@@ -113,34 +156,14 @@ __global__ __launch_bounds__(THREADS) void stream_limit_kernel(const fh_stream_j
     const long long n = tile0 - 2 * H + j;
     float r = 1.f;
     if (n >= 0 && n < end) {
-      float mv = fabsf(xs[j + HALO]);
-      mv = fmaxf(mv, tp_phase<0>(xs, hs, j));
-      mv = fmaxf(mv, tp_phase<1>(xs, hs, j));
-      mv = fmaxf(mv, tp_phase<2>(xs, hs, j));
-      mv = fmaxf(mv, tp_phase<3>(xs, hs, j));
+      const float mv = peak_at(xs, hs, j);
       if (mv > c32) r = __fdiv_rn(c32, mv);
     }
     a[0][j] = r;
   }
   __syncthreads();
-  int cur = 0, P = 1;
-  for (; 2 * P <= W; P *= 2) {                                      // a[cur][j] = min r[j .. j + P) -> ... + 2 P)
-    for (int j = t; j < N; j += THREADS) a[cur ^ 1][j] = j + P < N ? fminf(a[cur][j], a[cur][j + P]) : a[cur][j];
-    cur ^= 1;
-    __syncthreads();
-  }
-  // q[i] = min r[i .. i + W): the sample tile0 - H + i, i < TILE + 2 H (i + W - 1 <= N - 1)
-  float* __restrict__ q = a[cur ^ 1];
-  for (int i = t; i < TILE + 2 * H; i += THREADS) q[i] = fminf(a[cur][i], a[cur][i + W - P]);
-  __syncthreads();
   double acc[PER];
-#pragma unroll
-  for (int k = 0; k < PER; ++k) acc[k] = 0.0;
-  for (int kk = 0; kk < W; ++kk) {                                  // g[tile0 + i] = sum_kk w[kk] q[i + kk], ascending
-    const double wv = ws[kk];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) acc[k] = fma(wv, (double)q[t + k * THREADS + kk], acc[k]);
-  }
+  gain_tile(a, ws, H, acc);
   float* __restrict__ dst = (float*)J.dst + rel0;
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
@@ -149,25 +172,107 @@ __global__ __launch_bounds__(THREADS) void stream_limit_kernel(const fh_stream_j
   }
 }
 
-// dst[o] = pcm.hip's encode of the source's sample first + o with the dither of channel 0 at the index first + o.  A thread owns
-// the 16-byte word of 8 outputs counted from the aligned address at or below dst, as pcm_i16_kernel does for a planar row.
-__global__ __launch_bounds__(THREADS) void stream_pcm_kernel(const fh_stream_job* __restrict__ jobs,
-                                                             const unsigned long long* __restrict__ keys) {
-  const fh_stream_job J = jobs[blockIdx.y];
-  if (!job_ok(J) || (((size_t)J.dst) & 1)) return;                  // (an odd dst would misalign every 16-byte store)
+// The jobs [j0, j0 + n) of one stream: one per channel row
+struct sd_group {
+  int j0, n;
+};
+
+// group g of the table, checked (the tables live on the device): 1 .. 8 jobs inside the job table, each job_ok, all with the
+// counters of the first
+__device__ __forceinline__ bool group_ok(const fh_stream_job* __restrict__ jobs, int n_jobs, const int32_t* __restrict__ groups, int g,
+                                         sd_group& G) {
+  const int j0 = groups[g], j1 = groups[g + 1];
+  if (j0 < 0 || j1 > n_jobs || j1 <= j0 || j1 - j0 > MAX_CH) return false;
+  const fh_stream_job A = jobs[j0];
+  for (int j = j0; j < j1; ++j) {
+    const fh_stream_job J = jobs[j];
+    if (!job_ok(J) || J.base != A.base || J.first != A.first || J.n_carry != A.n_carry || J.n_fresh != A.n_fresh ||
+        J.n_out != A.n_out || J.n_keep != A.n_keep)
+      return false;
+  }
+  G = {j0, j1 - j0};
+  return true;
+}
+
+// stream_limit_kernel for streams of channels: a workgroup owns one tile of one group.  a[0][j] collects m over the channels (the
+// thread that owns j is the same for every channel), then becomes r; from there on the tile is the mono kernel's.
+__global__ __launch_bounds__(THREADS) void stream_limit_linked_kernel(const fh_stream_job* __restrict__ jobs, int n_jobs,
+                                                                      const int32_t* __restrict__ groups, const float* __restrict__ taps,
+                                                                      const double* __restrict__ w, int H, float c32) {
+  __shared__ float xs[LIM_N + 2 * HALO];
+  __shared__ float hs[4][PHASE_TAPS];
+  __shared__ float a[2][LIM_N];
+  __shared__ double ws[2 * MAX_H + 1];
+  sd_group G;
+  if (!group_ok(jobs, n_jobs, groups, blockIdx.y, G)) return;
+  jobs += G.j0;
+  if (blockIdx.x == gridDim.x - 1) {
+    for (int c = 0; c < G.n; ++c) {
+      const fh_stream_job J = jobs[c];
+      keep_tail(J, source(J));
+    }
+    return;
+  }
+  const fh_stream_job J0 = jobs[0];                                  // (the counters are the group's)
+  const long long rel0 = (long long)blockIdx.x * TILE;               // the tile's first output in every dst
+  if (rel0 >= J0.n_out) return;
+  const long long tile0 = J0.first + rel0, end = source(J0).end();
+  const int t = threadIdx.x, W = 2 * H + 1, N = TILE + 4 * H;
+  load_taps(taps, hs);
+  for (int j = t; j < W; j += THREADS) ws[j] = w[j];
+  for (int c = 0; c < G.n; ++c) {                                    // a[0][j] = m[tile0 - 2 H + j]: best = 0, then channel by channel
+    const sd_src S = source(jobs[c]);
+    for (int j = t; j < N + 2 * HALO; j += THREADS) xs[j] = S.at(tile0 - 2 * H - HALO + j);
+    __syncthreads();
+    for (int j = t; j < N; j += THREADS) {
+      const long long n = tile0 - 2 * H + j;
+      const float best = c ? a[0][j] : 0.f;
+      a[0][j] = (n >= 0 && n < end) ? fmaxf(best, peak_at(xs, hs, j)) : best;
+    }
+    __syncthreads();                                                 // (xs is staged again)
+  }
+  for (int j = t; j < N; j += THREADS) {                             // a[0][j] = r[tile0 - 2 H + j]; 1 outside the stream
+    const long long n = tile0 - 2 * H + j;
+    const float mv = a[0][j];
+    a[0][j] = (n >= 0 && n < end && mv > c32) ? __fdiv_rn(c32, mv) : 1.f;
+  }
+  __syncthreads();
+  double acc[PER];
+  gain_tile(a, ws, H, acc);
+  for (int c = 0; c < G.n; ++c) {                                    // (x is read again from the source: LDS holds one channel)
+    const fh_stream_job J = jobs[c];
+    const sd_src S = source(J);
+    float* __restrict__ dst = (float*)J.dst + rel0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const int i = t + k * THREADS;
+      if (rel0 + i < J.n_out) dst[i] = limit_sample(S.at(tile0 + i), (float)acc[k], c32);
+    }
+  }
+}
+
+// x[k], d[k] = the source's sample and channel ch's dither at the output first + k of the job (the absolute index J.first + first + k)
+__device__ __forceinline__ void pcm_run(const fh_stream_job& J, const unsigned long long* __restrict__ key, int ch, long long first,
+                                        float (&x)[RUN], float (&d)[RUN]) {
   const sd_src S = source(J);
-  int16_t* __restrict__ row = (int16_t*)J.dst;
-  const int lead = (int)(((size_t)row >> 1) & (RUN - 1));
-  const long long first = ((long long)blockIdx.x * THREADS + threadIdx.x) * RUN - lead;      // the run's first output
-  if (J.n_out == 0 || first >= J.n_out) return;
-  float x[RUN], d[RUN];
 #pragma unroll
   for (int k = 0; k < RUN; ++k) {
     const long long o = first + k;
     x[k] = (o >= 0 && o < J.n_out) ? S.at(J.first + o) : 0.f;
     d[k] = 0.f;
   }
-  if (keys) dither_run(keys[2 * blockIdx.y], keys[2 * blockIdx.y + 1], 0, J.first + first, d);
+  if (key) dither_run(key[0], key[1], ch, J.first + first, d);
+}
+
+// dst[o] = pcm.hip's encode of the source's sample first + o with the dither of channel ch at the index first + o.  A thread owns
+// the 16-byte word of 8 outputs counted from the aligned address at or below dst, as pcm_i16_kernel does for a planar row.
+__device__ __forceinline__ void pcm_row(const fh_stream_job& J, const unsigned long long* __restrict__ key, int ch) {
+  int16_t* __restrict__ row = (int16_t*)J.dst;
+  const int lead = (int)(((size_t)row >> 1) & (RUN - 1));
+  const long long first = ((long long)blockIdx.x * THREADS + threadIdx.x) * RUN - lead;      // the run's first output
+  if (J.n_out == 0 || first >= J.n_out) return;
+  float x[RUN], d[RUN];
+  pcm_run(J, key, ch, first, x, d);
   if (first >= 0 && first + RUN <= J.n_out) {
     i16x8 v;
 #pragma unroll
@@ -180,6 +285,84 @@ __global__ __launch_bounds__(THREADS) void stream_pcm_kernel(const fh_stream_job
     const long long o = first + k;
     if (o >= 0 && o < J.n_out) row[o] = encode(x[k], d[k]);
   }
+}
+
+__global__ __launch_bounds__(THREADS) void stream_pcm_kernel(const fh_stream_job* __restrict__ jobs,
+                                                             const unsigned long long* __restrict__ keys) {
+  const fh_stream_job J = jobs[blockIdx.y];
+  if (!job_ok(J) || (((size_t)J.dst) & 1)) return;                  // (an odd dst would misalign every 16-byte store)
+  pcm_row(J, keys ? keys + 2 * blockIdx.y : nullptr, 0);
+}
+
+// Interleaved output of a stream of C = 2, 4 or 8 channels whose frame buffer is aligned to a frame (2 C bytes): the thread
+// encodes its run of every channel and stores each sample frame as ONE 4-, 8- or 16-byte word, as pcm.hip's pcm_frames does.
+template <int C>
+__device__ __forceinline__ void stream_frames(const fh_stream_job* __restrict__ jobs, const unsigned long long* __restrict__ key) {
+  typedef short frame_t __attribute__((ext_vector_type(C)));
+  const long long first = ((long long)blockIdx.x * THREADS + threadIdx.x) * RUN;
+  const int n_out = jobs[0].n_out;
+  if (first >= n_out) return;
+  frame_t o[RUN];
+#pragma unroll
+  for (int ch = 0; ch < C; ++ch) {
+    const fh_stream_job J = jobs[ch];
+    float x[RUN], d[RUN];
+    pcm_run(J, key, ch, first, x, d);
+#pragma unroll
+    for (int k = 0; k < RUN; ++k) o[k][ch] = encode(x[k], d[k]);
+  }
+  frame_t* __restrict__ frames = reinterpret_cast<frame_t*>(jobs[0].dst);
+#pragma unroll
+  for (int k = 0; k < RUN; ++k)
+    if (first + k < n_out) frames[first + k] = o[k];
+}
+
+// The encoder of streams of channels.  Grid (blocks of 256 runs, jobs): job j is channel j - groups[g] of the group g that
+// holds it, found by bisection (a job no group holds, or whose group fails group_ok, is left unwritten).  Planar: every job
+// writes its own dst as stream_pcm_kernel does.  Interleaved: the group's first dst is the frame buffer int16 [n_out, C]; with
+// whole-frame stores the blocks of channel 0 write for the group, otherwise every job stores its samples at their places.
+__global__ __launch_bounds__(THREADS) void stream_pcm_rows_kernel(const fh_stream_job* __restrict__ jobs, int n_jobs,
+                                                                  const int32_t* __restrict__ groups, int n_groups,
+                                                                  const unsigned long long* __restrict__ keys, int interleaved) {
+  const int job = blockIdx.y;
+  int g = 0, hi = n_groups;
+  while (hi - g > 1) {                                               // the last group that starts at or below the job
+    const int mid = (g + hi) >> 1;
+    if (groups[mid] <= job)
+      g = mid;
+    else
+      hi = mid;
+  }
+  sd_group G;
+  if (!group_ok(jobs, n_jobs, groups, g, G) || job < G.j0 || job >= G.j0 + G.n) return;
+  const int ch = job - G.j0;
+  const unsigned long long* __restrict__ key = keys ? keys + 2 * g : nullptr;
+  if (!interleaved) {
+    for (int c = 0; c < G.n; ++c)
+      if (((size_t)jobs[G.j0 + c].dst) & 1) return;                  // (an odd dst anywhere: the group is left unwritten)
+    pcm_row(jobs[job], key, ch);
+    return;
+  }
+  int16_t* __restrict__ frames = (int16_t*)jobs[G.j0].dst;
+  if (((size_t)frames) & 1) return;
+  if ((G.n == 2 || G.n == 4 || G.n == 8) && (((size_t)frames) & (2 * G.n - 1)) == 0) {
+    if (ch != 0) return;                                             // (the blocks of channel 0 write whole frames)
+    if (G.n == 2)
+      stream_frames<2>(jobs + G.j0, key);
+    else if (G.n == 4)
+      stream_frames<4>(jobs + G.j0, key);
+    else
+      stream_frames<8>(jobs + G.j0, key);
+    return;
+  }
+  const fh_stream_job J = jobs[job];
+  const long long first = ((long long)blockIdx.x * THREADS + threadIdx.x) * RUN;
+  if (first >= J.n_out) return;
+  float x[RUN], d[RUN];
+  pcm_run(J, key, ch, first, x, d);
+#pragma unroll
+  for (int k = 0; k < RUN; ++k)
+    if (first + k < J.n_out) frames[(size_t)(first + k) * G.n + ch] = encode(x[k], d[k]);
 }
 
 }  // namespace
@@ -221,5 +404,35 @@ extern "C" int fh_stream_pcm_i16_f32(const fh_stream_job* jobs, int n_jobs, int 
   hipLaunchKernelGGL(stream_pcm_kernel, dim3(fh_cdiv(((long long)max_out + RUN - 1) / RUN + 1, THREADS), n_jobs), dim3(THREADS), 0,
                      (hipStream_t)stream, jobs, (const unsigned long long*)keys);
   FH_CHECK_LAUNCH("fh_stream_pcm_i16_f32");
+  return FH_OK;
+}
+
+#define FH_CHECK_STREAM_GROUPS(name)                                                                                       \
+  FH_CHECK_ARG(groups, name ": null group table");                                                                        \
+  FH_CHECK_ARG(n_groups > 0 && n_groups < 65536, name ": %d groups (1 .. 65535)", n_groups);                              \
+  FH_CHECK_ARG((((size_t)groups) & 3) == 0, name ": groups must be 4-byte aligned")
+
+extern "C" int fh_stream_limit_linked_f32(const fh_stream_job* jobs, int n_jobs, const int32_t* groups, int n_groups, int max_out,
+                                          const float* taps4, const double* w, int H, float ceiling, void* stream) {
+  FH_CHECK_STREAM_JOBS("fh_stream_limit_linked_f32");
+  FH_CHECK_STREAM_GROUPS("fh_stream_limit_linked_f32");
+  FH_CHECK_ARG(taps4 && w, "fh_stream_limit_linked_f32: null pointer (taps4 %p, w %p)", (const void*)taps4, (const void*)w);
+  FH_CHECK_ARG(H >= 1 && H <= MAX_H, "fh_stream_limit_linked_f32: H %d (1 .. %d)", H, MAX_H);
+  FH_CHECK_ARG(ceiling > 0.f && ceiling <= 1.f, "fh_stream_limit_linked_f32: ceiling %g (0 < c <= 1)", (double)ceiling);
+  FH_CHECK_ARG((((size_t)taps4) & 3) == 0 && (((size_t)w) & 7) == 0,
+               "fh_stream_limit_linked_f32: taps4 must be 4-byte, w 8-byte aligned");
+  hipLaunchKernelGGL(stream_limit_linked_kernel, dim3(fh_cdiv(max_out, TILE) + 1, n_groups), dim3(THREADS), 0, (hipStream_t)stream,
+                     jobs, n_jobs, groups, taps4, w, H, ceiling);
+  FH_CHECK_LAUNCH("fh_stream_limit_linked_f32");
+  return FH_OK;
+}
+
+extern "C" int fh_stream_pcm_i16_rows_f32(const fh_stream_job* jobs, int n_jobs, const int32_t* groups, int n_groups, int max_out,
+                                          const uint64_t* keys, int interleaved, void* stream) {
+  FH_CHECK_STREAM_JOBS("fh_stream_pcm_i16_rows_f32");
+  FH_CHECK_STREAM_GROUPS("fh_stream_pcm_i16_rows_f32");
+  hipLaunchKernelGGL(stream_pcm_rows_kernel, dim3(fh_cdiv(((long long)max_out + RUN - 1) / RUN + 1, THREADS), n_jobs), dim3(THREADS), 0,
+                     (hipStream_t)stream, jobs, n_jobs, groups, n_groups, (const unsigned long long*)keys, interleaved ? 1 : 0);
+  FH_CHECK_LAUNCH("fh_stream_pcm_i16_rows_f32");
   return FH_OK;
 }

@@ -1258,7 +1258,7 @@ class FlowHighSR:
 
     # ---- streaming sessions (stream.py is the definition, streaming.py the host side, csrc/stream.hip the seam) ------------------
     def stream(self, sr, *, window_ms=1000, overlap_ms=200, guard_ms=50, timestep=1, seed=None, stream=0, pcm=None,
-               channels=None, dither=None, output_rate=None, loudness=None, true_peak=None, delivery=None):
+               channels=None, dither=None, output_rate=None, loudness=None, true_peak=None, delivery=None, n_channels=None):
         """A streaming session at the input rate `sr` (prior='device' models): push(block) returns the samples that block made
         final, float32 [1, n] on the device at 48 kHz (n may be 0), flush() the rest; the blocks of a stream of T input samples
         add up to tables.resample_out_len(T, 48000, sr) samples, equal to stream.stitch of its windows' results bit for bit.
@@ -1274,13 +1274,21 @@ class FlowHighSR:
         of the stream add up to the bits of that delivery of the whole 48 kHz stream, delivery.delivered_len(T48, output_rate)
         samples.  The resampler withholds about 10 max(up, down) / up samples at 48 kHz and the limiter 2 H + 10 delivered
         samples (about 10.2 ms) until the flush.  The dither's key is (dither_seed, 0).  delivery= excludes the session's own pcm=;
-        it does not take loudness= (a statistic of the whole stream), true_peak= without the limiter (the same), channels= or
-        interleaved= (a session is mono); a dict of defaults is None.
-        Not built as keywords of their own, each a ValueError: channels=, dither=, output_rate=, loudness=, true_peak=."""
+        it does not take loudness= (a statistic of the whole stream), true_peak= without the limiter (the same), channels=, or,
+        in a mono session, interleaved=; a dict of defaults is None.
+        n_channels=C (an int 1 .. 8; None: one mono stream): the stream has C channels, fixed here and never read from a block's
+        shape.  Blocks are [C, n] (a block of another row count is a ValueError that leaves the session as it was), push() and
+        flush() return [C, m].  Window i is what generate(window_i [C, n], sr, channels='first', level='input') returns under
+        the session's prior: the channels share it, each is cross-faded on its own with the one ramp.  pcm='int16' encodes
+        planar.  delivery= then delivers C channels (delivery_stream(n_channels=C)): the limiter is channel-linked, channel c
+        takes its own dither, and delivery=dict(interleaved=True, pcm='int16', ...) returns sample frames, int16 [m, C].
+        n_channels=1 gives [1, n] blocks with the bits of the mono session.
+        Not built as keywords of their own, each a ValueError: channels= (the count goes by n_channels=), dither=, output_rate=,
+        loudness=, true_peak=."""
         from .streaming import open_session
         return open_session(self, sr, window_ms, overlap_ms, guard_ms, timestep, seed, stream, pcm,
                             dict(channels=channels, dither=dither, output_rate=output_rate, loudness=loudness, true_peak=true_peak),
-                            delivery)
+                            delivery, n_channels)
 
     def stream_push(self, sessions, blocks):
         """One block per session -> one output block per session (StreamSession.push).  Every window that became runnable, of
@@ -1302,27 +1310,35 @@ class FlowHighSR:
         from .streaming import run
         return run(self, sessions, final)
 
-    def delivery_stream(self, **keywords):
+    def delivery_stream(self, n_channels=None, **keywords):
         """The delivery of a stream on its own: output_rate=, pcm=, dither=, dither_seed=, true_peak=, limiter= as stream(delivery=)
         takes them -> a DeliveryStream: push(block48) takes float32 [1, n] on the device at 48 kHz and returns the delivered
-        samples it made final, flush() the rest.  The blocks add up to Delivery.batch of the whole stream at level='input'."""
+        samples it made final, flush() the rest.  The blocks add up to Delivery.batch of the whole stream at level='input'.
+        n_channels=C (an int 1 .. 8; None: the mono stream): push takes [C, n] and returns [C, m], the blocks add up to
+        Delivery.batch of the whole [C, T] stream as one clip: the limiter's envelope and gain are one for all channels, channel c
+        takes its own dither.  interleaved=True (with n_channels and pcm): int16 sample frames [m, C].  Refused: channels= (the
+        count goes by n_channels=), loudness=, true_peak= without limiter='lookahead', and interleaved= without n_channels."""
         from .delivery_stream import DeliveryStream, resolve
-        return DeliveryStream(resolve(keywords), self)
+        return DeliveryStream(resolve(keywords, None, n_channels), self)
 
     @torch.no_grad()
     def delivery_push(self, streams, blocks, final=False):
         """One 48 kHz block per DeliveryStream (None: nothing) -> one delivered block per stream; every stage is one launch for
-        all the streams that share a plan.  final: the streams end here."""
+        all the streams that share a plan, whatever their channel counts (streams opened with n_channels= form one plan, mono
+        streams opened without it another).  final: the streams end here."""
         from .delivery_stream import push
         return push(self.delivery, streams, blocks, final)
 
     def generate_long(self, audio, sr, **stream_keywords):
         """A clip of any length through a streaming session: push everything, then flush -> [1, T48] (int16 with pcm='int16');
         with delivery=: [1, delivery.delivered_len(T48, output_rate)] at the delivered rate, int16 with delivery's pcm.
-        Keywords: those of stream().  Memory and attention cost are those of one push's windows, whatever the clip's length."""
+        Keywords: those of stream().  Memory and attention cost are those of one push's windows, whatever the clip's length.
+        With n_channels=C: audio is [C, T], the result [C, T48] (or what delivery= makes of it: [C, n], int16 [n, C] with its
+        interleaved=)."""
         s = self.stream(sr, **stream_keywords)
         first = s.push(audio)
-        return torch.cat([first, s.flush()], 1)
+        frames = s.delivery is not None and s.delivery.interleaved
+        return torch.cat([first, s.flush()], 0 if frames else 1)
 
     @torch.no_grad()
     def measure_loudness(self, rows, chans=None, rate=48000):

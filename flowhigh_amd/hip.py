@@ -215,6 +215,8 @@ _SIGS = {
     "fh_stream_resample_f32": [_P, _I, _I, _P, _I, _I, _I, _I, _P],
     "fh_stream_limit_f32": [_P, _I, _I, _P, _P, _I, _F, _P],
     "fh_stream_pcm_i16_f32": [_P, _I, _I, _P, _P],
+    "fh_stream_limit_linked_f32": [_P, _I, _P, _I, _I, _P, _P, _I, _F, _P],
+    "fh_stream_pcm_i16_rows_f32": [_P, _I, _P, _I, _I, _P, _I, _P],
 }
 EXPORTS = sorted(_SIGS) + ["fh_last_error"]
 

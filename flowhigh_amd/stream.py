@@ -21,6 +21,9 @@ both rounded to float32 once.  The seam, in float32:
 where a term whose weight is exactly 0 is skipped, not multiplied: in a guard the result is the other window's bits, and a NaN
 behind a zero weight does not pass.
 
+A session opened with n_channels=C cuts [C, n] blocks into [C, n] windows on the same schedule; every row is joined with the one
+ramp (stitch(..., channels=C)).
+
 numpy only: nothing here touches torch or the GPU.
 """
 import math
@@ -176,8 +179,15 @@ def seam(prev, cur, w_in, w_out):
     return np.where(zi & zo, F32(0), out).astype(F32)
 
 
-def stitch(windows, plan):
-    """The stream's output, float32 [T48], from its windows' outputs (window i: 1-D, W48 samples, the last one what is left)."""
+def stitch(windows, plan, channels=None):
+    """The stream's output, float32 [T48], from its windows' outputs (window i: 1-D, W48 samples, the last one what is left).
+    channels=C (a session opened with n_channels=C): the windows are [C, n] and the output [C, T48]; every row is stitched on
+    its own with the one ramp."""
+    if channels is not None:
+        windows = [np.asarray(w, dtype=F32) for w in windows]
+        if not windows or any(w.ndim != 2 or w.shape[0] != channels for w in windows):
+            raise ValueError(f"a stream of {channels} channels has at least one window and every window is [{channels}, n]")
+        return np.stack([stitch([w[c] for w in windows], plan) for c in range(channels)])
     windows = [np.asarray(w, dtype=F32).reshape(-1) for w in windows]
     if not windows:
         raise ValueError("a stream has at least one window")

@@ -16,6 +16,11 @@ the past in a carry and gives the bits of the one-shot delivery of the whole str
               oversampling, r = 1 outside, q extended by H) hold at the stream's first and last sample and nowhere else.
   encoder     sample t of the stream takes pcm.py's dither of channel 0 at the absolute index t: no carry, one counter.
 
+A stream of C channels (1 <= C <= 8, fixed when it opens) is C rows [C, T] that move together: ONE set of counters per stage, the
+resampler per row, the limiter channel-linked as truepeak.limit is on a [C, T] clip (m is the maximum over the rows of what a
+row alone gives, one gain for every row), the encoder with channel c's dither at the absolute index, planar [C, n] or sample
+frames [n, C] (interleaved).  A [T] stream is the one row it always was.
+
 A stage's step is (base, first, n_out, n_keep): its source is carry + fresh block, `base` the absolute index of the carry's first
 sample; it writes the outputs [first, first + n_out) and keeps the last n_keep source samples as the next carry.  `chunked` walks
 these steps in numpy and equals the whole-stream definitions (`whole`: the fma loop below, truepeak.limit, pcm.encode).
@@ -146,14 +151,15 @@ def _fma32(a, b, c):
 
 def resample_span(flt, src, base, E, first, n_out, reads=None):
     """Outputs [first, first + n_out) from src = the inputs [base, base + len(src)), E = base + len(src) inputs there: the
-    kernel's loop (j descending from min(j_hi, E - 1), break at k >= n_taps), vectorised over the outputs.
+    kernel's loop (j descending from min(j_hi, E - 1), break at k >= n_taps), vectorised over the outputs (and over the rows
+    of src [C, n], each row a stream of its own under the one schedule).
     reads: a dict that gets the lowest and highest input index read (min, max)."""
     src = np.asarray(src, dtype=F32)
-    assert base + src.size == E
+    assert base + src.shape[-1] == E
     i = first + np.arange(int(n_out), dtype=np.int64)
     pos = (i + flt.pre) * flt.down
     j = np.minimum(pos // flt.up, E - 1)
-    acc = np.zeros(i.size, dtype=F32)
+    acc = np.zeros(src.shape[:-1] + (i.size,), dtype=F32)
     live = np.ones(i.size, dtype=bool)
     while True:
         k = pos - j * flt.up
@@ -164,7 +170,7 @@ def resample_span(flt, src, base, E, first, n_out, reads=None):
         assert jj.min() >= base and jj.max() < E, "an output reads outside the two spans"
         if reads is not None:
             reads["min"], reads["max"] = min(reads.get("min", E), int(jj.min())), max(reads.get("max", -1), int(jj.max()))
-        acc[live] = _fma32(src[jj - base], flt.taps[kk], acc[live])
+        acc[..., live] = _fma32(src[..., jj - base], flt.taps[kk], acc[..., live])
         j = j - 1
     return acc
 
@@ -178,30 +184,33 @@ def resample_whole(x48, rate):
 
 # ---- limiter ---------------------------------------------------------------------------------------------------------------
 def envelope_span(src, base, E, lo, hi, ended):
-    """m[lo .. hi) of a mono stream from src = its samples [base, E): truepeak.envelope's values, every sum in float64 in
-    ascending tap order whatever the span; zeros before sample 0, and past E (read only when the stream ends there)."""
+    """m[lo .. hi) of a stream from src = its samples [base, E), one row or rows [C, n]: truepeak.envelope's values (the
+    maximum over the rows of a row's own), every sum in float64 in ascending tap order whatever the span; zeros before sample 0,
+    and past E (read only when the stream ends there)."""
+    src = np.asarray(src, dtype=F32)
     HALF, FACTOR = _truepeak.HALF, _truepeak.FACTOR
     h = _truepeak.taps().astype(np.float64)
-    n = np.arange(lo, hi, dtype=np.int64)
+    n = hi - lo
     assert lo >= 0 and (ended or hi + HALF <= E) and (lo - HALF >= base or base == 0)
-    pad = np.zeros(hi - lo + 2 * HALF, dtype=np.float64)                 # x[lo - HALF .. hi + HALF)
+    pad = np.zeros(src.shape[:-1] + (n + 2 * HALF,), dtype=np.float64)   # x[lo - HALF .. hi + HALF)
     a, b = max(lo - HALF, base, 0), min(hi + HALF, E)
-    pad[a - (lo - HALF):b - (lo - HALF)] = np.asarray(src, dtype=F32)[a - base:b - base]
-    best = np.abs(pad[HALF:HALF + n.size])
+    pad[..., a - (lo - HALF):b - (lo - HALF)] = src[..., a - base:b - base]
+    best = np.abs(pad[..., HALF:HALF + n])
     for p in range(FACTOR):
-        acc = np.zeros(n.size)
+        acc = np.zeros(best.shape)
         for i in range(2 * HALF + 1):
             if p + FACTOR * i < h.size:
-                acc += h[p + FACTOR * i] * pad[2 * HALF - i:2 * HALF - i + n.size]          # x[n + 10 - i]
+                acc += h[p + FACTOR * i] * pad[..., 2 * HALF - i:2 * HALF - i + n]          # x[n + 10 - i]
         best = np.maximum(best, np.abs(acc))
-    return best.astype(F32)
+    best = best.astype(F32)
+    return best.max(0) if src.ndim == 2 else best
 
 
 def limit_span(src, base, E, first, n_out, ended, H, true_peak_db):
-    """The limiter's outputs [first, first + n_out) from src = the samples [base, E)."""
-    if n_out == 0:
-        return np.zeros(0, F32)
+    """The limiter's outputs [first, first + n_out) from src = the samples [base, E), one row or rows [C, n] under one gain."""
     src = np.asarray(src, dtype=F32)
+    if n_out == 0:
+        return np.zeros(src.shape[:-1] + (0,), F32)
     a, b = first, first + n_out
     lo, hi = max(0, a - 2 * H), (min(b + 2 * H, E) if ended else b + 2 * H)
     assert ended or hi + _truepeak.HALF <= E
@@ -209,65 +218,100 @@ def limit_span(src, base, E, first, n_out, ended, H, true_peak_db):
     # limiter_gain's own ends (r = 1 outside, q extended by H) fall on the stream's ends or outside what [a, b) reads
     g = _truepeak.limiter_gain(m, H, true_peak_db)[0][a - lo:b - lo]
     c32 = F32(_truepeak.ceiling(true_peak_db))
-    return np.clip((src[a - base:b - base] * g).astype(F32), -c32, c32)
+    return np.clip((src[..., a - base:b - base] * g).astype(F32), -c32, c32)
 
 
 # ---- the chain -------------------------------------------------------------------------------------------------------------
-def make_plan(rate=None, true_peak=None, pcm=None, key=None):
+MAX_CHANNELS = 8
+
+
+def make_plan(rate=None, true_peak=None, pcm=None, key=None, channels=None, interleaved=False):
     """The stages of a delivery, as delivery_stream.resolve gives them: rate None | R, true_peak None | the ceiling in dBTP
-    (limiter='lookahead'), pcm None | 'int16', key None | the dither's (seed, stream)."""
-    return dict(rate=rate, true_peak=true_peak, pcm=pcm, key=key)
+    (limiter='lookahead'), pcm None | 'int16', key None | the dither's (seed, stream); channels None (one mono stream: the plan
+    it always was) | C rows that move together, 1 .. 8; interleaved: the encoder's output as sample frames [n, C]."""
+    plan = dict(rate=rate, true_peak=true_peak, pcm=pcm, key=key)
+    if channels is None:
+        if interleaved:
+            raise ValueError("interleaved goes with channels: a mono stream has nothing to interleave")
+        return plan
+    if isinstance(channels, (bool, float)) or not isinstance(channels, (int, np.integer)) or not 1 <= channels <= MAX_CHANNELS:
+        raise ValueError(f"channels must be None or an int 1 .. {MAX_CHANNELS}, got {channels!r}")
+    if interleaved and pcm is None:
+        raise ValueError("interleaved is the int16 encoder's layout: it goes with pcm")
+    plan.update(channels=int(channels), interleaved=bool(interleaved))
+    return plan
+
+
+def _rows(x48, plan):
+    """x48 [T] or [C, T] -> (float32 [C, T], whether it came as [T]), checked against the plan's channels."""
+    x = np.asarray(x48, dtype=F32)
+    flat = x.ndim == 1
+    x = x[None] if flat else x
+    if x.ndim != 2 or not 1 <= x.shape[0] <= MAX_CHANNELS:
+        raise ValueError(f"a stream is [T] or [C, T] with 1 <= C <= {MAX_CHANNELS}, got shape {np.shape(x48)}")
+    C = plan.get("channels")
+    if C is not None and x.shape[0] != C:
+        raise ValueError(f"the plan's channels {C!r} and a stream of shape {np.shape(x48)}")
+    return x, flat
 
 
 def chunked(x48, cuts, plan, stats=None, first=0):
-    """x48 float32 [T48] pushed in the blocks x48[c_{k-1}:c_k] for c in cuts (ascending, the last one T48), then flushed ->
-    the concatenated delivery.  first: the encoder's first absolute index.
+    """x48 float32 [T48] or [C, T48] pushed in the blocks x48[..., c_{k-1}:c_k] for c in cuts (ascending, the last one T48), then
+    flushed -> the concatenated delivery: [n] for [T48], else [C, n], or [n, C] from an interleaved plan.  first: the encoder's
+    first absolute index.
     stats: a dict that gets the largest carries ('resample_carry', 'limit_carry'), the resampler's read range per push
     ('reads': [(E, min, max)]) and the blocks' lengths ('lens')."""
-    x48 = np.asarray(x48, dtype=F32).reshape(-1)
+    x48, flat = _rows(x48, plan)
+    C, T = x48.shape
     cuts = [int(c) for c in cuts]
-    assert cuts == sorted(cuts) and (not cuts or cuts[-1] == x48.size)
+    assert cuts == sorted(cuts) and (not cuts or cuts[-1] == T)
     rate, tp, key = plan["rate"], plan["true_peak"], plan["key"]
     flt = ResampleFilter(rate) if rate is not None else None
     H = _truepeak.half_window(rate or 48000) if tp is not None else None
     rs, ls, es = (ResampleStage(flt) if flt else None), (LimitStage(H) if tp is not None else None), EncodeStage(first)
-    carry_r, carry_l = np.zeros(0, F32), np.zeros(0, F32)
+    carry_r, carry_l = np.zeros((C, 0), F32), np.zeros((C, 0), F32)
     stats = {} if stats is None else stats
     stats.update(resample_carry=0, limit_carry=0, reads=[], lens=[])
     out, prev = [], 0
-    for c, ended in [(c, False) for c in cuts] + [(x48.size, True)]:
-        block, prev = x48[prev:c], c
+    for c, ended in [(c, False) for c in cuts] + [(T, True)]:
+        block, prev = x48[:, prev:c], c
         if rs is not None:
-            job = rs.step(block.size, ended)
-            src = np.concatenate([carry_r, block])
+            job = rs.step(block.shape[1], ended)                  # (one set of counters for all the rows)
+            src = np.concatenate([carry_r, block], 1)
             reads = {}
-            block = resample_span(flt, src, job["base"], job["base"] + src.size, job["first"], job["n_out"], reads)
+            block = resample_span(flt, src, job["base"], job["base"] + src.shape[1], job["first"], job["n_out"], reads)
             if reads:
-                stats["reads"].append((job["base"] + src.size, reads["min"], reads["max"]))
-            carry_r = src[src.size - job["n_keep"]:]
-            stats["resample_carry"] = max(stats["resample_carry"], carry_r.size)
+                stats["reads"].append((job["base"] + src.shape[1], reads["min"], reads["max"]))
+            carry_r = src[:, src.shape[1] - job["n_keep"]:]
+            stats["resample_carry"] = max(stats["resample_carry"], carry_r.shape[1])
         if ls is not None:
-            job = ls.step(block.size, ended)
-            src = np.concatenate([carry_l, block])
-            block = limit_span(src, job["base"], job["base"] + src.size, job["first"], job["n_out"], ended, H, tp)
-            carry_l = src[src.size - job["n_keep"]:]
-            stats["limit_carry"] = max(stats["limit_carry"], carry_l.size)
+            job = ls.step(block.shape[1], ended)
+            src = np.concatenate([carry_l, block], 1)
+            block = limit_span(src, job["base"], job["base"] + src.shape[1], job["first"], job["n_out"], ended, H, tp)
+            carry_l = src[:, src.shape[1] - job["n_keep"]:]
+            stats["limit_carry"] = max(stats["limit_carry"], carry_l.shape[1])
         if plan["pcm"] is not None:
-            job = es.step(block.size, ended)
-            d = _pcm.tpdf_dither(key[0], key[1], 0, block.size, first=job["first"]) if key is not None else None
+            job = es.step(block.shape[1], ended)
+            d = None
+            if key is not None:
+                d = np.stack([_pcm.tpdf_dither(key[0], key[1], ch, block.shape[1], first=job["first"]) for ch in range(C)])
             block = _pcm.quantize(block, d)
-        stats["lens"].append(block.size)
+        stats["lens"].append(block.shape[1])
         out.append(block)
-    return np.concatenate(out)
+    y = np.concatenate(out, 1)
+    if flat:
+        return y[0]
+    return np.ascontiguousarray(y.T) if plan.get("interleaved") else y
 
 
 def whole(x48, plan):
     """The one-shot delivery of the whole stream at level='input': what `chunked` has to give."""
-    y = np.asarray(x48, dtype=F32).reshape(-1)
+    x48, flat = _rows(x48, plan)
+    y = x48
     if plan["rate"] is not None:
-        y = resample_whole(y, plan["rate"])
+        y = np.stack([resample_whole(row, plan["rate"]) for row in y])
     if plan["true_peak"] is not None:
-        y = _truepeak.limit(y, plan["rate"] or 48000, plan["true_peak"])[0][0] if y.size else y
+        y = _truepeak.limit(y, plan["rate"] or 48000, plan["true_peak"])[0] if y.shape[1] else y
     if plan["pcm"] is not None:
-        y = _pcm.encode(y, plan["key"])[0]
-    return y
+        y = _pcm.encode(y, plan["key"], bool(plan.get("interleaved")) and not flat)
+    return y[0] if flat else y

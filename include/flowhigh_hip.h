@@ -835,6 +835,25 @@ int fh_stream_limit_f32(const fh_stream_job* jobs, int n_jobs, int max_out, cons
 /* fh_pcm_i16_f32's encoding of one channel: output o of a job encodes the source's sample first + o with the dither of channel 0
  * at the 64-bit sample index first + o under the job's key.  keys: DEVICE uint64 [n_jobs][2], NULL: no dither. */
 int fh_stream_pcm_i16_f32(const fh_stream_job* jobs, int n_jobs, int max_out, const uint64_t* keys, void* stream);
+/* Streams of channels.  A stream of C channels (1 .. 8) is C consecutive jobs, one per channel row, each with its own carry,
+ * fresh, dst and carry_out and all with equal base, first, n_carry, n_fresh, n_out and n_keep (fh_stream_resample_f32 runs them
+ * as they are: a row per job).  groups: DEVICE int32 [n_groups + 1], group g = the jobs groups[g] .. groups[g + 1] of the table;
+ * n_groups <= 65535.  A group that does not lie in the table, whose size is not 1 .. 8, whose jobs differ in a counter or one of
+ * whose jobs would be left unwritten on its own (above) is left unwritten as a whole, and so is a job that no group holds.
+ *
+ * fh_stream_limit_f32, channel-linked: one envelope m[n] = the maximum over the group's channels (folded in
+ * fh_tp_envelope_f32's order) and one gain for all of them: the bits of fh_tp_envelope_f32 + fh_limit_f32 on the whole
+ * [C, T] stream, and of fh_stream_limit_f32 for C = 1.  Grid (tiles of 1024 outputs + 1, groups). */
+int fh_stream_limit_linked_f32(const fh_stream_job* jobs, int n_jobs, const int32_t* groups, int n_groups, int max_out,
+                               const float* taps4, const double* w, int H, float ceiling, void* stream);
+/* fh_pcm_i16_f32's encoding of a stream of channels: output o of the group's job c encodes its source's sample first + o with the
+ * dither of channel c at the 64-bit sample index first + o under the GROUP's key.  keys: DEVICE uint64 [n_groups][2], NULL: no
+ * dither.  Planar (interleaved 0): every job writes its own dst[0 .. n_out); a group with a dst at an odd address is left
+ * unwritten.  Interleaved: the dst of the group's FIRST job is the frame buffer int16 [n_out, C] (the other jobs' dst are
+ * checked for null like any and not written); at an odd address the group is left unwritten.  The bits of fh_pcm_i16_f32 on
+ * the whole [C, T] stream under the same key, and of fh_stream_pcm_i16_f32 for C = 1 planar. */
+int fh_stream_pcm_i16_rows_f32(const fh_stream_job* jobs, int n_jobs, const int32_t* groups, int n_groups, int max_out,
+                               const uint64_t* keys, int interleaved, void* stream);
 
 #ifdef __cplusplus
 }
