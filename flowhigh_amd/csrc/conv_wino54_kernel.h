@@ -52,6 +52,12 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // (MI355X_MICROARCH.md, "price of one filler beside MFMAs"), plain ones issue in its shadow.  What the loop's shape is worth was
 // measured on a stand-alone model of it first (tools/micro/bf54.hip, profiles/r06_bf16x6_coissue.txt).
 constexpr int V_A3 = 24;             // floats (96 bytes) per output row and 16-channel chunk of the three-piece weights
+// FR (BF only, tile_cfg | FH_WINO_FRAG_ORDER): the same bytes in fragment order (packing.pack_wino54_weight_frag): a tile's rows
+// are cut into granules of 32, [granule][3 pieces][64 lanes][8 bf16], lane 32 lh + l31 = the 16 bytes the row form keeps at
+// row * 96 + piece * 32 + lh * 16.  A granule is 32 rows x 96 bytes either way, so a tile's address and size are those of the
+// row form; a wave's load is 1 KB contiguous (8 lines) where the 96-byte rows spread it over 24.
+constexpr int V_FRAG = 32 * V_A3 * 4;                // bytes of a granule (3 KB)
+constexpr int V_FPIECE = V_FRAG / 3;                 // ... of one piece of it (64 lanes x 16 bytes)
 
 constexpr int V_CK = 16;             // input channels per chunk
 constexpr int V_THREADS = 512;       // 8 waves = 8 transform points
@@ -120,12 +126,13 @@ __device__ const VToff kB8Toff = make_vtoff();
 // 0 and 2 of a fragment are the channels e + (g & 1) of the two k-step pairs of a half.  The epilogue keeps its two 32-row rounds
 // (the second has 16 real rows).  The sum over a chunk's channels runs in another order than in the 32x32x2 form: a conv's
 // bits depend on H16, which is fixed per stage (cout_pad), never chosen per launch.
-template <int MT, bool VL, bool H16 = false, bool BF = false>
+template <int MT, bool VL, bool H16 = false, bool BF = false, bool FR = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(V_THREADS, V_THREADS), amdgpu_waves_per_eu(2, 2)))
 void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, int batch, int co_tiles, int n_tiles,
                         int run_len, int dil, int pm, const int* __restrict__ run_map, int n_runs, WinoDivs dv) {
   static_assert(!H16 || MT == 2, "the 16-row form is the 48-row block");
   static_assert(!(H16 && BF), "the bf16 x 6 form has 32-row tiles only");
+  static_assert(!FR || BF, "fragment order is a layout of the three-piece weights");
   constexpr int BM = H16 ? 48 : 32 * MT;
   constexpr int MA = H16 ? 3 : MT;                    // A fragments (row tiles) per wave
   extern __shared__ __attribute__((aligned(16))) float lds[];      // V_LDS_FLOATS
@@ -301,7 +308,7 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
   // One register set, refilled behind the group's last MFMA: a second set (request a group ahead) measured no faster on the
   // model loop and costs 12 MT registers the 96 / 128-row blocks do not have (tools/micro/bf54.hip)
   u32x4 a3[BF ? MT : 1][3];
-  const int a3_lane = (l31 * V_A3 + lh * 4) * 4;
+  const int a3_lane = FR ? lane * 16 : (l31 * V_A3 + lh * 4) * 4;
   // pieces = bit mask of the pieces to request (1 h, 2 m, 4 l)
   auto load_a3 = [&](const WinoSeg& S, int chunk, int g, bool valid, int pieces = 7) {
     const __amdgpu_buffer_rsrc_t r = make_rsrc(wino_a_tile<8, V_A3>(S, chunk, g, wts), valid ? BM * V_A3 * 4 : 0);
@@ -314,14 +321,21 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
       const int om = mt < 2 ? o : o + 2 * 32 * V_A3 * 4;
 #pragma unroll
       for (int pc = 0; pc < 3; ++pc)
-        if (pieces & (1 << pc))
-          a3[mt][pc] = __builtin_amdgcn_raw_buffer_load_b128(r, om + (mt & 1) * 32 * V_A3 * 4 + 32 * pc, 0, 0);
+        if (pieces & (1 << pc)) {
+          if constexpr (FR) {
+            // (granule mt, piece pc: immediates up to 4095, beyond that one add of 4096 or 8192 per request -- 4 adds per tap
+            // group at 96 rows against the row form's 3)
+            a3[mt][pc] = __builtin_amdgcn_raw_buffer_load_b128(r, o + mt * V_FRAG + pc * V_FPIECE, 0, 0);
+          } else {
+            a3[mt][pc] = __builtin_amdgcn_raw_buffer_load_b128(r, om + (mt & 1) * 32 * V_A3 * 4 + 32 * pc, 0, 0);
+          }
+        }
     }
   };
-  // L2 warm-up of the A tiles of the NEXT chunk (conv_wino_common.h)
+  // L2 warm-up of the A tiles of the NEXT chunk (conv_wino_common.h): the fp32 forms only (BF: see its K loop)
   unsigned pf[2] = {0u, 0u};
   auto prefetch_a = [&](const WinoSeg& S, int chunk, bool valid) {
-    wino_prefetch_a<8, BM, BF ? V_A3 : V_CK>(pf, S, chunk, valid, wts, l31, lh);
+    wino_prefetch_a<8, BM, V_CK>(pf, S, chunk, valid, wts, l31, lh);
   };
 
   // ---- K loop -----------------------------------------------------------------------------------------------------
@@ -364,7 +378,11 @@ void conv_wino54_kernel(const fh_wino_group* __restrict__ groups, int n_groups, 
         for (int g = 0; g < GC; ++g) {
           if (g == 0) {
             load_x(S, c + 1, has_next);                  // stored at the end of this chunk
-            prefetch_a(S, c + 1, has_next);
+            // (no L2 warm-up of the next chunk's weights in this form: its register prefetch runs a whole tap group -- ~2 us -- ahead,
+            // which covers a miss in L2, and the warm-up's loads are one cache line per LANE: 64 tag lookups per instruction in the
+            // L1 the weight loads go through.  Measured at the headline shape, step time against the loop with the fp32 form's
+            // warm-up: -2.5 % without it (rows), -3.0 % in fragment order; a warm-up over every line of the fragment tiles: +0.7 %.
+            // profiles/wino_weight_fragments.md)
           }
           // (one tile column at a time: both columns' samples in flight at once -- one ds_read2_b64 per sample as in the fp32 form --
           // are 24 registers more than the 96-row block has: the allocator then spills a hundred)
@@ -643,7 +661,7 @@ int wino54_n_tiles(int len, int dilation, int pm) {
   return pm ? fh_cdiv((long long)dilation * v_tile_slots(len, dilation), V_BT) : fh_cdiv(fh_cdiv(len, dilation), V_OUT) * dilation;
 }
 
-template <int MT, bool VL, bool H16 = false, bool BF = false>
+template <int MT, bool VL, bool H16 = false, bool BF = false, bool FR = false>
 int launch_wino54(const fh_wino_group* groups, int n_groups, int batch, int cout_pad, int len, int dilation, int pm,
                   hipStream_t stream, const int* run_map, int n_runs) {
   constexpr int BM = H16 ? 48 : 32 * MT;
@@ -653,8 +671,8 @@ int launch_wino54(const fh_wino_group* groups, int n_groups, int batch, int cout
   const long long panels = (long long)n_groups * batch * co_tiles;
   const WinoGeom geo = wino_geometry(n_tiles, panels, run_map, n_runs, co_tiles, batch, dilation);
   FH_CHECK_ARG(geo.blocks > 0 && geo.blocks < (1ll << 31), "fh_conv_wino54_f32: grid too large");
-  if (int rc = wino_lds_opt_in<&conv_wino54_kernel<MT, VL, H16, BF>>(V_LDS_FLOATS * 4, "fh_conv_wino54_f32")) return rc;
-  hipLaunchKernelGGL((conv_wino54_kernel<MT, VL, H16, BF>), dim3((unsigned)geo.blocks), dim3(V_THREADS), V_LDS_FLOATS * 4, stream, groups,
+  if (int rc = wino_lds_opt_in<&conv_wino54_kernel<MT, VL, H16, BF, FR>>(V_LDS_FLOATS * 4, "fh_conv_wino54_f32")) return rc;
+  hipLaunchKernelGGL((conv_wino54_kernel<MT, VL, H16, BF, FR>), dim3((unsigned)geo.blocks), dim3(V_THREADS), V_LDS_FLOATS * 4, stream, groups,
                      n_groups, batch, co_tiles, n_tiles, geo.run_len, dilation, pm, run_map, n_runs, geo.dv);
   FH_CHECK_LAUNCH("fh_conv_wino54_f32");
   return FH_OK;

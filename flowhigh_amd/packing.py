@@ -216,6 +216,26 @@ def pack_wino54_weight_any(w, cout_pad, bf):
     return split_bf3(u) if bf else u
 
 
+def frag_order(u):
+    """fp32 tensor [..., cout_pad, 16] (cout_pad % 32 == 0) -> int16 tensor [..., cout_pad / 32, 3, 64, 8] of bf16 bit patterns: the
+    pieces of split_pieces in the order the lanes of v_mfma_f32_32x32x16_bf16 take the A operand.  Lane 32 lh + r of granule q,
+    piece p holds channels 8 lh .. 8 lh + 7 of row 32 q + r of that piece: split_bf3(u)[..., 32 q + r, p, 8 lh : 8 lh + 8].  A granule
+    is 3 KB, each (granule, piece) 1 KB contiguous; the 64- / 96- / 128-row blocks are 2 / 3 / 4 consecutive granules."""
+    rows = u.shape[-2]
+    if rows % 32 or u.shape[-1] != 16:
+        raise ValueError(f"fragment order: rows of 16 channels in granules of 32, got {tuple(u.shape[-2:])}")
+    lead = u.shape[:-2]
+    p = torch.stack(split_pieces(u), dim=0).view(3, *lead, rows // 32, 32, 2, 8)           # [piece, ..., q, r, lh, e]
+    n = len(lead)
+    return p.permute(*range(1, n + 2), 0, n + 3, n + 2, n + 4).contiguous().view(torch.int16).reshape(*lead, rows // 32, 3, 64, 8)
+
+
+def pack_wino54_weight_frag(w, cout_pad):
+    """pack_wino54_weight in the three-piece bf16 form, fragment order (frag_order): [ci/16, G, 8, cout_pad / 32, 3, 64, 8] bf16 bit
+    patterns, what the F(5,4) kernel reads under FH_WINO_BF16X6 | FH_WINO_FRAG_ORDER.  Same values as pack_wino54_weight_any(.., True)."""
+    return frag_order(pack_wino54_weight(w, cout_pad))
+
+
 def wino_phase_weight(wt, taps):
     """ConvTranspose1d weight [cin, cout, k] + the taps [(j, offset)] of one output phase (transposed_conv_phases)
     -> (Conv1d-style weight [cout, cin, k_r] with taps ordered by input offset, center = -smallest offset)."""

@@ -461,7 +461,27 @@ def amp_max_center(groups, direct=False):
 WINO_BF16X6 = 16          # FH_WINO_BF16X6 of flowhigh_hip.h: tile_cfg flag, three-piece bf16 weights
 WINO_XCD_RANGES = 32      # FH_WINO_XCD_RANGES: tile_cfg flag, blocks -> XCDs by time range instead of by weight panel
 WINO_NOVL = 64            # FH_WINO_NOVL: tile_cfg flag, some row of the launch is not 16-byte aligned although len % 4 == 0
+WINO_FRAG_ORDER = 128     # FH_WINO_FRAG_ORDER: tile_cfg flag beside WINO_BF16X6, three-piece weights in fragment order
 WINO_MAX_K = 12           # the kernel instantiates 1..4 tap groups of 3
+
+
+def wino_weight_flags(wcfg, bf):
+    """tile_cfg flags that name the weight format of a Winograd launch with plan tile id `wcfg` in a model whose Winograd convs
+    are bf16 x 6 (bf) or fp32: the one decision the packers (wino_packer) and every launch of a plan, ragged or streaming, follow.
+    bf16 x 6 F(5,4) launches read fragment order (packing.frag_order); the F(4,3) kernel has 96-byte rows only."""
+    if not bf:
+        return 0
+    return WINO_BF16X6 | (WINO_FRAG_ORDER if wcfg & WINO_F54 else 0)
+
+
+def wino_packer(wcfg, bf):
+    """w, cout_pad -> the transformed weights a launch with wino_weight_flags(wcfg, bf) reads."""
+    from . import packing
+    flags = wino_weight_flags(wcfg, bf)
+    if flags & WINO_FRAG_ORDER:
+        return packing.pack_wino54_weight_frag
+    f54 = wcfg & WINO_F54
+    return lambda w, cout_pad: (packing.pack_wino54_weight_any if f54 else packing.pack_wino_weight_any)(w, cout_pad, bool(bf))
 
 
 def use_bf16x6():

@@ -8,9 +8,8 @@ import os
 import torch
 
 from . import hip
-from .packing import pack_wino54_weight_any, pack_wino_weight_any
-from .planner import (AMP_DIRECT, WINO_BF16X6, WINO_F54, WINO_NOVL, act_ragged_groups, amp_max_center, amp_tile_list, make_act_group, make_wino_group,
-                      make_wino_seg, pick_wino54_tile, pick_wino_tile, use_wino54, wino_run_map)
+from .planner import (AMP_DIRECT, WINO_BF16X6, WINO_F54, WINO_FRAG_ORDER, WINO_NOVL, act_ragged_groups, amp_max_center, amp_tile_list, make_act_group,
+                      make_wino_group, make_wino_seg, pick_wino54_tile, pick_wino_tile, use_wino54, wino_packer, wino_run_map, wino_weight_flags)
 
 def amp_actconv(groups, batch, channels, dilation, device, direct=False):
     """Upload descriptors and enqueue one narrow-stage launch (test / one-off use).  direct: the bf16 x 6 form (groups made with
@@ -28,7 +27,7 @@ def conv_wino(groups, batch, cout_pad, length, dilation, device, tile_cfg=0, pha
     # (F(5,4) kernel: the groups' weights are pack_wino54_weight, ngrp = ceil(k / 4))
     if tile_cfg & WINO_F54 and any(g.out_stride > 1 or g.out_len or g.seg[i].ngrp > 3 or g.seg[i].xlen for g in groups for i in range(g.nseg)):
         raise NotImplementedError("the F(5,4) kernel takes plain convs of at most 12 taps (no strided outputs, xlen, out_len)")
-    name, cfg = wino_entry(tile_cfg, tile_cfg & WINO_BF16X6)           # (a caller's FH_WINO_BF16X6 flag stays)
+    name, cfg = wino_entry(tile_cfg, tile_cfg & (WINO_BF16X6 | WINO_FRAG_ORDER))           # (a caller's weight-format flags stay)
     enqueue(getattr(hip.lib(), name), (d.data_ptr(), len(groups), batch, cout_pad, length, dilation, int(phase_major), cfg, hip.stream()))
     return d
 
@@ -36,7 +35,7 @@ def conv_wino(groups, batch, cout_pad, length, dilation, device, tile_cfg=0, pha
 def conv_wino_ragged(groups, lengths, cout_pad, dilation, device, tile_cfg=0, phase_major=False):
     """Upload descriptors and run map and enqueue one ragged Winograd conv launch (test / one-off use): group i is one clip's
     [C, lengths[i]] tensors (g.len = lengths[i], batch 1), the groups in launch order.  tile_cfg: plan tile id, F(4,3) or
-    WINO_F54 | id, | WINO_BF16X6 for three-piece weights; the vector loader is ruled out as planner._merge_wino does it.
+    WINO_F54 | id, | WINO_BF16X6 for three-piece weights (| WINO_FRAG_ORDER: in fragment order); the vector loader is ruled out as planner._merge_wino does it.
     -> (descriptors, run map): keep both until the launch has run."""
     if any(g.len != n for g, n in zip(groups, lengths)) or len(groups) != len(lengths):
         raise ValueError("conv_wino_ragged: lengths must be the groups' own")
@@ -46,7 +45,7 @@ def conv_wino_ragged(groups, lengths, cout_pad, dilation, device, tile_cfg=0, ph
     novl = 0 if ((phase_major or all(n % 4 == 0 for n in lengths)) and not tile_cfg & WINO_NOVL) else 2
     runs = torch.tensor(wino_run_map(list(lengths), wcfg, cout_pad, dilation, bool(phase_major)), dtype=torch.int32).to(device)
     d = hip.to_device_struct_array(groups, device)
-    name, cfg = wino_entry(wcfg, tile_cfg & WINO_BF16X6, ragged=True)
+    name, cfg = wino_entry(wcfg, tile_cfg & (WINO_BF16X6 | WINO_FRAG_ORDER), ragged=True)
     enqueue(getattr(hip.lib(), name), (d.data_ptr(), len(groups), cout_pad, max(lengths), dilation, int(bool(phase_major)) | novl, cfg,
                                        runs.data_ptr(), runs.numel(), hip.stream()))
     return d, runs
@@ -185,8 +184,8 @@ def measure_act_conv_pair(device, blocks, c=192, length=60000, warm=60, reps=100
         # pays in front of fp32-MFMA convs and costs in front of bf16 x 6 ones on the same box)
         f54 = use_wino54(c, "bf16x6" if bf else "winograd")
         wcfg, wpad = pick_wino54_tile(c, bf) if f54 else pick_wino_tile(c)
-        pack = (lambda w_, p_: pack_wino54_weight_any(w_, p_, bf)) if f54 else (lambda w_, p_: pack_wino_weight_any(w_, p_, bf))
-        name, cfg = wino_entry(wcfg, WINO_BF16X6 if bf else 0)
+        pack = wino_packer(wcfg, bf)
+        name, cfg = wino_entry(wcfg, wino_weight_flags(wcfg, bf))
         us = [pack(torch.randn(c, c, k, generator=g) * 0.02, wpad).to(dev) for k in ks]
         gw = hip.to_device_struct_array([make_wino_group([make_wino_seg(ys[i], us[i], c, k, taps=4 if f54 else 3)], bias, [],
                                                          outs[i], c, wpad, length) for i, k in enumerate(ks)], dev)
@@ -262,7 +261,8 @@ calibrate_act_occupancy.last_measurement = None
 
 def wino_entry(wcfg, flag, ragged=False):
     """(library entry's name, its tile_cfg argument) of a Winograd launch with plan tile id `wcfg` (| mapping / alignment flags): the
-    F(5,4) kernel takes the tile in the low four bits, the F(4,3) kernel the whole id; flag: FH_WINO_BF16X6 or 0."""
+    F(5,4) kernel takes the tile in the low four bits, the F(4,3) kernel the whole id; flag: the weight-format flags
+    (planner.wino_weight_flags: FH_WINO_BF16X6, FH_WINO_FRAG_ORDER) or 0."""
     f54 = wcfg & WINO_F54
     return ("fh_conv_wino54" if f54 else "fh_conv_wino") + ("_ragged_f32" if ragged else "_f32"), ((wcfg & 15) if f54 else wcfg) | flag
 
@@ -301,7 +301,7 @@ def _convt(L, voc, s, B, st, base):
     enqueue(L.fh_conv_transpose_fused_f32, (s.desc.data_ptr(), s.ng, B, s.cpad, s.n_len, s.tcfg, s.phases, st), voc.conv_timing)
 
 def _wino(L, voc, s, B, st, base):
-    name, cfg = wino_entry(s.wcfg, voc.wino_flag)
+    name, cfg = wino_entry(s.wcfg, wino_weight_flags(s.wcfg, voc.bf))
     enqueue(getattr(L, name), (s.desc.data_ptr(), s.ng, s.batch, s.wpad, s.length, s.dil, s.pm, cfg, st), voc.conv_timing)
 
 def _amp(L, voc, s, B, st, base):
@@ -322,7 +322,7 @@ def _post(L, voc, s, B, st, base):
     enqueue(L.fh_conv_post_tanh_f32, (s.x.data_ptr(), voc.post_w.data_ptr(), voc.post_b.data_ptr(), s.wav.data_ptr(), B, s.c, s.length, voc.post_k, st))
 
 def _rwino(L, voc, s, B, st, base):
-    name, cfg = wino_entry(s.wcfg, voc.wino_flag, ragged=True)
+    name, cfg = wino_entry(s.wcfg, wino_weight_flags(s.wcfg, voc.bf), ragged=True)
     enqueue(getattr(L, name), (base + s.off, s.ng, s.wpad, s.maxlen, s.dil, s.pmflag, cfg, base + s.off_map, s.n_runs, st))
 
 def _rconv(L, voc, s, B, st, base):

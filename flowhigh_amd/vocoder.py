@@ -25,16 +25,16 @@ import torch
 from . import hip
 from .packing import (  # noqa: F401
     _WINO54_G, _WINO_G, fold_weight_norm, from_phase_major, pack_amp_weight, pack_conv_bf_weight, pack_conv_weight, pack_narrow_bf_weight,
-    pack_wino54_weight, pack_wino54_weight_any, pack_wino_weight, pack_wino_weight_any, phase_len, pick_ck, split_bf3, to_phase_major,
+    frag_order, pack_wino54_weight, pack_wino54_weight_any, pack_wino54_weight_frag, pack_wino_weight, pack_wino_weight_any, phase_len, pick_ck, split_bf3, to_phase_major,
     transposed_conv_extra, transposed_conv_phases, wino_phase_weight)
 from .planner import (  # noqa: F401
-    AMP_DIRECT, AMP_MAX_D, WINO54_MIN_C, WINO_BF16X6, WINO_BM, WINO_F54, WINO_MAX_K, WINO_MIN_C, WINO_NARROW, WINO_NOVL,
+    AMP_DIRECT, AMP_MAX_D, WINO54_MIN_C, WINO_BF16X6, WINO_BM, WINO_F54, WINO_FRAG_ORDER, WINO_MAX_K, WINO_MIN_C, WINO_NARROW, WINO_NOVL,
     WINO_UPS_MIN_CIN, WINO_UPS_MIN_CIN_BF, WINO_XCD_RANGES, _PlanBuilder, _TILE_PREF, _WINO_BF_SPEED, _WINO_COST, _WINO_RUN,
     _WINO_TILES, _WINO_TILES_OFF, _WINO_WIDE_PANEL_MAX, _addr, _choose_wino_cfg, act_ragged_groups, amp_max_center,
     amp_tile_len, amp_tile_list, choose_wino_cfg, make_act_group, make_amp_group, make_amp_seg, make_conv_group,
     make_conv_seg, make_wino_group, make_wino_seg, merge_ragged, pick_tile_cfg, pick_wino54_tile,
     pick_wino_tile, plan_switches, resolve_conv_form, ups_fused_ok, use_amp, use_amp_bf16x6, use_bf16x6, use_direct_bf16x6, wino_ups_min_cin, use_wino, use_wino54, wino_block_mapping,
-    wino_conv_ok, wino_launch_cost, wino_n_tiles, wino_run_len, wino_run_map, wino_split_k, wino_split_steps, wino_taps)
+    wino_conv_ok, wino_launch_cost, wino_n_tiles, wino_packer, wino_run_len, wino_run_map, wino_split_k, wino_split_steps, wino_taps, wino_weight_flags)
 from .runtime import (  # noqa: F401
     ACT_BLOCKS_CHOICES, _act_blocks, _act_choice, act1d_grouped, act1d_ragged, amp_actconv, calibrate_act_occupancy, conv_grouped, ensure_act_blocks,
     conv_wino, conv_wino_ragged, decide_act_blocks, launch_step, measure_act_conv_pair, parse_act_blocks, pick_act_blocks,
@@ -176,7 +176,7 @@ class Vocoder:
         self.pre_u = None
         if use_wino(self.c0, 1, self.form) and self.num_mels % 16 == 0 and self.c0 % 64 == 0:
             self.pre_wcfg, self.pre_wpad = pick_wino_tile(self.c0)
-            self.pre_u = W.dev("v.conv_pre.u", lambda: pack_wino_weight_any(g("conv_pre.weight"), self.pre_wpad, self.bf))
+            self.pre_u = W.dev("v.conv_pre.u", lambda: wino_packer(self.pre_wcfg, self.bf)(g("conv_pre.weight"), self.pre_wpad))
         self.stages = []
         for i, (u, k) in enumerate(zip(self.rates, self.up_k)):
             c = self.chans[i]
@@ -202,8 +202,8 @@ class Vocoder:
             st["amp"] = use_amp(c, self.ks, self.dil, self.form)
             pack_narrow = pack_narrow_bf_weight if self.amp_direct else pack_amp_weight
             ua_key = "unb" if self.amp_direct else "ua"
-            pack_res = (lambda w_: pack_wino54_weight_any(w_, st["wpad"], self.bf)) if st["w54"] else \
-                (lambda w_: pack_wino_weight_any(w_, st["wpad"], self.bf))
+            # (the weight format of a launch follows its kernel family and the model's form: planner.wino_weight_flags)
+            pack_res = lambda w_: wino_packer(st["wcfg"], self.bf)(w_, st["wpad"])
             wt = lambda i=i: g(f"ups.{i}.0.weight")               # [cin, c, k]
             st["up_b"] = W.dev(f"v.ups.{i}.b", lambda: g(f"ups.{i}.0.bias"))
             st["up_phases"] = [dict(offs=[o for _, o in taps]) for taps in transposed_conv_phases(k, u)]
@@ -220,8 +220,8 @@ class Vocoder:
                 st["up_wino"] = []
                 for r_, taps in enumerate(transposed_conv_phases(k, u)):
                     # (taps ordered by input offset: a stride-1 correlation of len(taps) taps, center = - smallest offset)
-                    st["up_wino"].append(dict(u=W.dev(f"v.ups.{i}.phase{r_}.u", lambda taps=taps: pack_wino_weight_any(
-                        wino_phase_weight(wt(), taps)[0], st["up_wpad"], self.bf)), k=len(taps), center=-min(o for _, o in taps)))
+                    st["up_wino"].append(dict(u=W.dev(f"v.ups.{i}.phase{r_}.u", lambda taps=taps: wino_packer(st["up_wcfg"], self.bf)(
+                        wino_phase_weight(wt(), taps)[0], st["up_wpad"])), k=len(taps), center=-min(o for _, o in taps)))
             st["blocks"] = []
             for j in range(self.nk):
                 r = i * self.nk + j
@@ -269,7 +269,8 @@ class Vocoder:
         self.post_w = W.dev("v.conv_post.w", lambda: g("conv_post.weight")[0])      # [c_last, 7]
         self.post_b = W.dev("v.conv_post.b", lambda: g("conv_post.bias"))
         self.post_k = self.post_w.shape[-1]
-        self.wino_flag = WINO_BF16X6 if self.bf else 0             # (the weights above are packed accordingly)
+        # (the weights above are packed accordingly; a launch adds its family's layout bit: planner.wino_weight_flags)
+        self.wino_flag = WINO_BF16X6 if self.bf else 0
         self._plans = hip.ShapeCache()
         self._ragged = hip.ShapeCache()
         self.conv_timing = None

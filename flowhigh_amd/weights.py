@@ -29,7 +29,8 @@ def format_tag(form="winograd"):
     """Everything that decides WHICH layouts the constructors pack: a blob made under other decisions is not used.
     form: the RESOLVED conv form ('winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6', planner.resolve_conv_form); the remaining layout switches as
     normalised booleans / numbers (unset and "1" are the same setting), and a fingerprint of the packers' and the planner's source
-    (tile choices, thresholds and fragment layouts live there: a code change must not silently reuse a key with another layout)."""
+    (tile choices, thresholds and fragment layouts live there: a code change must not silently reuse a key with another layout).
+    layout: bumped by hand with every change of a packed layout (5: the bf16 x 6 F(5,4) weights in fragment order, packing.frag_order)."""
     from . import hip
     pkg = Path(__file__).resolve().parent
     fp = hashlib.blake2b(digest_size=8)
@@ -37,7 +38,7 @@ def format_tag(form="winograd"):
         fp.update((pkg / name).read_bytes())
     on = lambda k: os.environ.get(k, "1") != "0"
     sw = dict(wino54=on("FH_WINO54"), wino54_h16=on("FH_WINO54_H16"), amp=on("FH_AMP"))
-    return json.dumps(dict(abi=hip.ABI_VERSION, layout=4, form=str(form), switches=sw, packers=fp.hexdigest()), sort_keys=True)
+    return json.dumps(dict(abi=hip.ABI_VERSION, layout=5, form=str(form), switches=sw, packers=fp.hexdigest()), sort_keys=True)
 
 
 def file_digest(path):

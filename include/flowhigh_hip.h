@@ -187,6 +187,13 @@ int fh_phase_len(int len, int dilation);
 /* tile_cfg | FH_WINO_NOVL: some tensor row of the launch is not 16-byte aligned although `len` % 4 == 0 (a segment with
  * xlen % 4 != 0): the slab loader must not use 16-byte loads.  Same bits. */
 #define FH_WINO_NOVL 64
+/* tile_cfg | FH_WINO_BF16X6 | FH_WINO_FRAG_ORDER (fh_conv_wino54_f32 and its ragged entry only): the three-piece weights lie
+ * in FRAGMENT order, [C_in/16][tap group][8][cout_pad/32 granules][3 pieces][64 lanes][8 bf16]: lane 32 h + r of granule q,
+ * piece p holds channels 8 h .. 8 h + 7 of row 32 q + r of that piece, the order in which the lanes of
+ * v_mfma_f32_32x32x16_bf16 take the A operand (flowhigh_amd/packing.py: pack_wino54_weight_frag).  A wave's 16-byte load then
+ * reads 1 KB contiguous (8 cache lines) where the 96-byte rows make it 32 segments over 24 lines.  Same values, same MFMA
+ * order: same bits.  Without FH_WINO_BF16X6, or on fh_conv_wino_f32, the bit is an argument error. */
+#define FH_WINO_FRAG_ORDER 128
 int fh_conv_wino_f32(const fh_wino_group* groups, int n_groups, int batch, int cout_pad, int len,
                      int dilation, int phase_major, int tile_cfg, void* stream);
 /* Ragged form (clips of different lengths, one group per clip and AMP block, batch 1): the grid is laid out for

@@ -1,5 +1,6 @@
 """Per-launch table of the vocoder's conv launches: tile, blocks, algorithmic GFLOP, us, TFLOP/s.
-Run on the GPU box: python tools/conv_layers.py [batch] [frames] [bypanel]"""
+Run on the GPU box: python tools/conv_layers.py [batch] [frames] [bypanel | rows]
+rows: the bf16 x 6 F(5,4) launches on weights in 96-byte rows instead of fragment order (planner.wino_weight_flags): same bits."""
 import sys, torch
 sys.path.insert(0, '.')
 from flowhigh_amd import synth
@@ -12,6 +13,9 @@ TILES = {0: (128, 128), 1: (192, 128), 2: (96, 256), 3: (64, 256), 4: (32, 512),
 cfg = synth.SYNTH_CFG
 if len(sys.argv) > 3 and sys.argv[3] == 'bypanel':         # A/B: every Winograd launch with the by-weight-panel block mapping
     V.wino_block_mapping = lambda *a: 0
+if len(sys.argv) > 3 and sys.argv[3] == 'rows':            # A/B: three-piece weights in rows for every Winograd launch
+    from flowhigh_amd import planner, runtime
+    planner.wino_weight_flags = runtime.wino_weight_flags = lambda wcfg, bf: V.WINO_BF16X6 if bf else 0
 import os
 if os.environ.get("TILES_OFF"):                                # A/B: plan tile ids the launch model may not pick (e.g. 257 = F(5,4) 96 x 320)
     V._WINO_TILES_OFF.update(int(t) for t in os.environ["TILES_OFF"].split(","))

@@ -1,14 +1,17 @@
 """Winograd F(5,4) kernel (conv_wino54.hip) against the F(4,3) kernel (conv_wino.hip) on the residual-stack launch shapes
 (3 groups k = 11 / 7 / 3, bias + one residual), and both against float64 on a small case.
-python tools/wino54_bench.py [batch] [bf]      bf: the timing table in the bf16 x 6 form of both kernels (three-piece weights,
-tile_cfg | FH_WINO_BF16X6; F(5,4): its 96- / 64-row blocks)"""
+python tools/wino54_bench.py [batch] [bf | frag]      bf: the timing table in the bf16 x 6 form of both kernels (three-piece weights,
+tile_cfg | FH_WINO_BF16X6; F(5,4): its 96- / 64-row blocks); frag: the same with the F(5,4) weights in fragment order
+(| FH_WINO_FRAG_ORDER, what the planner launches; bf keeps them in 96-byte rows)"""
 import sys, torch, torch.nn.functional as F
 sys.path.insert(0, '.')
 from flowhigh_amd import hip, vocoder as V
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 1
-BF = len(sys.argv) > 2 and sys.argv[2] == "bf"
+BF = len(sys.argv) > 2 and sys.argv[2] in ("bf", "frag")
+FRAG = len(sys.argv) > 2 and sys.argv[2] == "frag"
 FLAG = V.WINO_BF16X6 if BF else 0
+FLAG54 = FLAG | (V.WINO_FRAG_ORDER if FRAG else 0)
 DEV = torch.device('cuda:0')
 KS = [11, 7, 3]
 st = hip.stream()
@@ -80,7 +83,7 @@ for c, L in ((768, 5000), (384, 20000), (192, 60000), (96, 120000)):
         cfg54 = (1 if c % 96 == 0 else 2) if BF else 0 if c % 128 == 0 else 1 if c % 96 == 0 else 2
         bm = lib.fh_wino54_tile_m(cfg54 | FLAG)
         cpad = -(-c // bm) * bm
-        u5 = [V.pack_wino54_weight_any(w, cpad, BF).to(DEV) for w in ws]
+        u5 = [(V.pack_wino54_weight_frag(w, cpad) if FRAG else V.pack_wino54_weight_any(w, cpad, BF)).to(DEV) for w in ws]
         g5 = []
         for i, k in enumerate(KS):
             seg = V.make_wino_seg(xs[i], u5[i], c, k)
@@ -88,6 +91,6 @@ for c, L in ((768, 5000), (384, 20000), (192, 60000), (96, 120000)):
             g5.append(V.make_wino_group([seg], bs[i], [rs[i]], outs[i], c, cpad, L))
         d5 = hip.to_device_struct_array(g5, DEV)
         t43 = bench(lambda: hip.check(lib.fh_conv_wino_f32(dw.data_ptr(), 3, B, wpad, L, d, int(pm), wcfg | FLAG, st)))
-        t54 = bench(lambda: hip.check(lib.fh_conv_wino54_f32(d5.data_ptr(), 3, B, cpad, L, d, int(pm), cfg54 | FLAG, st)))
+        t54 = bench(lambda: hip.check(lib.fh_conv_wino54_f32(d5.data_ptr(), 3, B, cpad, L, d, int(pm), cfg54 | FLAG54, st)))
         fl = 2.0 * c * c * sum(KS) * L * B
         print(f"{c:5d} {L:7d} {d:2d} {fl/1e9:8.2f} {t43:10.1f} {fl/t43/1e6:8.1f} {t54:10.1f} {fl/t54/1e6:8.1f} {t43/t54:6.2f}")

@@ -1,11 +1,15 @@
 """Block-time constants of the F(5,4) kernel for the launch model (vocoder._WINO_COST[WINO_F54 | t] = (a, b): block time =
 a K + b us, K = 16-channel x 4-tap-group steps): launches of ~8 blocks per CU at two depths per tile height.
-python tools/wino54_cost_fit.py [bf]      (bf: also the bf16 x 6 form of round 6)"""
+python tools/wino54_cost_fit.py [bf] [rows]      (bf: also the bf16 x 6 form of round 6, weights in fragment order as the planner
+launches it; rows: in 96-byte rows)"""
 import sys, torch
 sys.path.insert(0, '.')
 from flowhigh_amd import hip, vocoder as V
 DEV = torch.device('cuda:0')
 st = hip.stream()
+
+
+ROWS = "rows" in sys.argv[1:]
 
 
 def block_time(c, tile, k=11, bf=False):
@@ -16,10 +20,12 @@ def block_time(c, tile, k=11, bf=False):
     x = torch.randn(1, c, L, device=DEV)
     out = torch.empty(1, c, L, device=DEV)
     b = torch.randn(c, device=DEV)
-    u = V.pack_wino54_weight_any(torch.randn(c, c, k) * 0.02, wpad, bf).to(DEV)
+    flags = (V.WINO_BF16X6 if ROWS else V.wino_weight_flags(V.WINO_F54 | tile, True)) if bf else 0
+    w = torch.randn(c, c, k) * 0.02
+    u = (V.pack_wino54_weight_frag(w, wpad) if flags & V.WINO_FRAG_ORDER else V.pack_wino54_weight_any(w, wpad, bf)).to(DEV)
     g = [V.make_wino_group([V.make_wino_seg(x, u, c, k, taps=4)], b, [], out, c, wpad, L)]
     dw = hip.to_device_struct_array(g, DEV)
-    run = lambda: hip.check(hip.lib().fh_conv_wino54_f32(dw.data_ptr(), 1, 1, wpad, L, 1, 0, tile | (V.WINO_BF16X6 if bf else 0), st))
+    run = lambda: hip.check(hip.lib().fh_conv_wino54_f32(dw.data_ptr(), 1, 1, wpad, L, 1, 0, tile | flags, st))
     for _ in range(2): run()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
