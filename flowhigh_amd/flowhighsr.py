@@ -40,7 +40,8 @@ import torch
 from . import hip, ode
 from .flow import FlowNet
 from .delivery import Delivery, resolve_delivery
-from .frontend import LogMel, PostProcessor, Resampler, clip_rates
+from .frontend import LogMel, PostProcessor, Resampler, _starts, _views, clip_rates
+from .grouping import pack_ragged, plan_buckets
 from .prior import expand_seed, normalize_key
 from .tables import HOP, resample_out_len
 from .vocoder import VOC, Vocoder, fold_weight_norm
@@ -166,7 +167,7 @@ def clip_noises(noise, chans):
 
 def resolve_clips(clips, channels=None, level="peak"):
     """The clips of a call, layouts checked (resolve_channels; a ValueError before any GPU work) ->
-      (clips, None)     mono clips at level='peak': the default path takes them (as they came, or [1, T] views)
+      (clips, None)     mono clips at level='peak', a plain call (FlowHighSR._planar): as they came, or [1, T] views
       (None, planar)    anything else: float [C_i, T_i] arrays, the int16 rule (max > 1 -> / 32768) applied once per clip."""
     level = resolve_level(level)
     planar = [resolve_channels(a, channels) for a in clips]
@@ -604,35 +605,24 @@ class FlowHighSR:
             prepared.append(audio)
         return prepared
 
-    def _prepare_cond(self, clips, sr, target_sampling_rate=48000, ragged=False):
-        """list of 1-D arrays (equal length, one rate) -> cond [B, T48] float32 on device, peak-normalised per clip.
-        ragged: clips of different lengths, sr one input rate or one per clip -> (cond packed [sum T48_i], list of [T48_i]
-        views) on the device, every clip the bits of the batched form on that clip alone.  One upload for the list; 'hip': the
-        segment forms of the resampler's launches, 'scipy': the host resampling and normalisation per clip, as they are."""
-        if target_sampling_rate != 48000:
-            raise NotImplementedError("the mel codec is fixed at 48 kHz")
-        prepared = self._host_clips(clips)
-        if self.upsampling_method == 'scipy':
-            import scipy.signal
-            conds = []
-            for audio, sr_i in zip(prepared, resolve_rates(sr, len(prepared)) if ragged else [sr] * len(prepared)):
-                cond = scipy.signal.resample_poly(audio, target_sampling_rate, sr_i)
-                conds.append(cond / np.max(np.abs(cond)))
-            if ragged:
-                return self.resampler.upload_packed(conds)
-            return self._upload(torch.stack([torch.tensor(cond).float() for cond in conds]))
-        if self.upsampling_method == 'hip':
-            if ragged:
-                return self.resampler.ragged(prepared, sr, target_sampling_rate)
-            x = self._upload(torch.from_numpy(np.stack([a.astype(np.float32) for a in prepared])))
-            return self.resampler(x, sr, target_sampling_rate)
-        raise UnboundLocalError(f"cond: unsupported upsampling_method '{self.upsampling_method}'")
+    def _planar(self, clips, channels, level):
+        """The clips of a call -> (float [C_i, T_i] arrays, the int16 rule (max > 1 -> / 32768) applied once per clip; plain).
+        plain: every clip mono and level='peak' (what resolve_clips hands back as it came).  It is read by the front end
+        (_prepare_rows) and by the post-processor's level arguments (_level_args); nothing else asks whether a clip is mono."""
+        clips, planar = resolve_clips(clips, channels, level)
+        if planar is None:
+            return [a[None] for a in self._host_clips(clips)], True
+        return planar, False
 
-    def _prepare_rows(self, rows, sr, ragged=False):
-        """_prepare_cond for the rows of a channels= / level= call (1-D float arrays, one per channel, the int16 rule applied
-        already) -> (cond [R, T48], or with ragged the list of [T48_i] views; gains float32 [R] on the device: the peak p every
-        row was divided by).  A silent row is divided by 1 and has gain 0.  'hip': the peaks stay on the device
-        (fh_channel_peaks_f32); 'scipy': they are the host's np.max(np.abs(.)), uploaded with the rows."""
+    def _prepare_rows(self, rows, sr, plain, ragged=False):
+        """The front end: 1-D float rows (one per channel of every clip, the int16 rule applied already; equal lengths, one
+        rate) -> (cond [R, T48] float32 on the device, every row divided by its peak p; gains float32 [R] on the device: p).
+        ragged: rows of different lengths, sr one input rate or one per row -> (list of [T48_i] views of one packed device
+        buffer, gains), every row the bits of the batched form on that row alone.  'hip': the resampler's launches (their
+        segment forms with ragged); 'scipy': resampled and normalised on the host per row, one upload.
+        A silent row is divided by 1 and has gain 0: 'hip' keeps the peaks on the device (fh_channel_peaks_f32), 'scipy' uploads
+        the host's np.max(np.abs(.)).  plain: the default path's front end -- the peak as it is (a silent clip is 0 / 0), no
+        fh_channel_peaks_f32, gains None."""
         if self.upsampling_method == 'scipy':
             import scipy.signal
             conds, peaks = [], []
@@ -640,23 +630,27 @@ class FlowHighSR:
                 cond = scipy.signal.resample_poly(audio, 48000, sr_i)
                 p = np.max(np.abs(cond))
                 peaks.append(p)
-                conds.append(cond / p if p > 0 else cond)
-            gains = self._upload(torch.from_numpy(np.array(peaks, dtype=np.float32)))
+                conds.append(cond / p if plain or p > 0 else cond)
+            gains = None if plain else self._upload(torch.from_numpy(np.array(peaks, dtype=np.float32)))
             if ragged:
                 return self.resampler.upload_packed(conds)[1], gains
             return self._upload(torch.stack([torch.tensor(cond).float() for cond in conds])), gains
         if self.upsampling_method == 'hip':
             if ragged:
-                _, views, gains = self.resampler.ragged(rows, sr, 48000, gains=True)
-                return views, gains
+                out = self.resampler.ragged(rows, sr, 48000, gains=not plain)
+                return out[1], (None if plain else out[2])
             x = self._upload(torch.from_numpy(np.stack([np.asarray(a, dtype=np.float32) for a in rows])))
-            return self.resampler(x, sr, 48000, gains=True)
+            out = self.resampler(x, sr, 48000, gains=not plain)
+            return (out, None) if plain else out
         raise UnboundLocalError(f"cond: unsupported upsampling_method '{self.upsampling_method}'")
 
-    def _level_args(self, chans, level, gains):
-        """The post-processor's gains= and groups= for rows that are chans[i] channels per clip.  level='input': the rows'
-        gains, no groups.  level='peak': every clip is a group; a mono clip among them takes gain 1, which makes its row gain
-        and its group peak the identity (w * 1, fl(q * 1)): it keeps the bits of the default path."""
+    def _level_args(self, chans, level, gains, plain):
+        """The post-processor's gains= and groups= for rows that are chans[i] channels per clip.  plain: none, it ends with
+        the per-row 0.99 peak.  level='input': the rows' gains, no groups.  level='peak': every clip is a group; a mono clip
+        among them takes gain 1, which makes its row gain and its group peak the identity (w * 1, fl(q * 1)): it keeps the bits
+        of a plain call."""
+        if plain:
+            return {}
         if level != "peak":
             return dict(gains=gains, groups=None)
         group = np.repeat(np.arange(len(chans), dtype=np.int32), chans)
@@ -665,31 +659,33 @@ class FlowHighSR:
             gains = gains.masked_fill(mono, 1.0)
         return dict(gains=gains, groups=self._upload(torch.from_numpy(group)))
 
-    def _generate_rows(self, planar, sr, timestep, noises, keys, generator, level, return_stages=False, first_frames=None):
-        """generate_batch for clips of equal length with channels= / level=: planar = float [C_i, T] arrays (resolve_clips),
-        noises = None or one [C_i, N, n_mels] per clip (clip_noises), keys = None or one key per clip.  Every channel is a row of
-        the batch and runs as a mono clip does; the rows of a clip share its prior (first_frames, with keys: the absolute frame every clip's prior starts at, _device_prior).
-        -> [sum C_i, T48] (rows in clip order),
-        with return_stages also the stages of the rows (and their gains)."""
+    def _prior_scale(self):
+        """std_2 = 1 of independent_cfm_adaptive as _sample's keyword (flowhighsr.py:88-96 of the reference)."""
+        return dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
+
+    def _generate_rows(self, planar, sr, timestep, noises, keys, generator, level, plain, return_stages=False, first_frames=None):
+        """The batch body of every entry: clips of equal length and one rate as planar float [C_i, T] arrays with their plain
+        flag (_planar), noises = None or one [C_i, N, n_mels] per clip (clip_noises), keys = None or one key per clip.  Every
+        channel is a row of the batch and runs as a mono clip does; the rows of a clip share its prior (first_frames, with
+        keys: the absolute frame every clip's prior starts at, _device_prior).  -> [sum C_i, T48] (rows in clip order; a fresh
+        tensor), with return_stages also the stages of the rows (and, unless plain, their gains)."""
         chans = [a.shape[0] for a in planar]
-        row_keys = None
+        noise = row_keys = None
         if keys is not None:
-            noise = None
             row_keys = [k for k, c in zip(keys, chans) for _ in range(c)]
             if first_frames is not None:
                 first_frames = [f for f, c in zip(first_frames, chans) for _ in range(c)]
         else:
-            if noises is None:                               # one draw per CLIP: the generator moves as for mono clips
+            if noises is None:                               # one draw per CLIP, in clip order, whatever its channels
                 n = resample_out_len(planar[0].shape[1], 48000, sr) // 480
                 noises = [channel_noise(self._draw_noise(1, n, generator), c) for c in chans]
             noise = torch.cat(list(noises), 0)
-        cond, gains = self._prepare_rows([row for a in planar for row in a], sr)
-        kw = dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
+        cond, gains = self._prepare_rows([row for a in planar for row in a], sr, plain)
         wav = self._sample(cond=cond, time_steps=timestep, cfm_method=self.cfm_method, noise=noise, keys=row_keys,
-                           first_frames=first_frames if keys is not None else None, **kw).squeeze(1)
-        out = self.postproc(wav, cond, cond.size(-1), return_cr=return_stages, **self._level_args(chans, level, gains))
-        if return_stages:
-            return out[0], dict(cond=cond, wav=wav.clone(), cr=out[1].clone(), gains=gains)
+                           first_frames=first_frames if keys is not None else None, **self._prior_scale()).squeeze(1)
+        out = self.postproc(wav, cond, cond.size(-1), return_cr=return_stages, **self._level_args(chans, level, gains, plain))
+        if return_stages:                                    # (wav and cr are plan- and workspace-owned buffers)
+            return out[0], dict(cond=cond, wav=wav.clone(), cr=out[1].clone(), **({} if gains is None else dict(gains=gains)))
         return out
 
     # ---- sampler (cfm_superresolution.py:162-284) ------------------------------------------------
@@ -765,11 +761,7 @@ class FlowHighSR:
         frames = [int(n) for n in frames]
         seg = self.flowhigh.net.ragged_workspace(frames)["seg"]
         z = self._device_prior(keys, count, max(frames), seg=seg, rows=sum(frames))
-        out, r = [], 0
-        for n in frames:
-            out.append(z[r:r + n][None])
-            r += n
-        return out
+        return [v[None] for v in _views(z, _starts(frames), frames)]
 
     def _integrate(self, y0, cond_mel, batch, n, time_steps, cond_scale=1., ragged=None):
         """Fixed-grid explicit Runge-Kutta methods (torchdiffeq semantics; ode.ODE_METHODS); y0, cond_mel [B*n, n_mels] on device.
@@ -941,10 +933,7 @@ class FlowHighSR:
                                 mel_pp, ragged=fh.net.ragged_workspace(frames))
         if packed and decode_to_audio:
             return fh.vocoder.forward_ragged_packed(mel, frames)
-        rows, out = 0, []
-        for n in frames:
-            out.append(mel[rows:rows + n])
-            rows += n
+        out = _views(mel, _starts(frames), frames)
         return fh.vocoder.forward_ragged(out) if decode_to_audio else out
 
     @torch.no_grad()
@@ -972,7 +961,7 @@ class FlowHighSR:
     @torch.no_grad()
     @hip.on_device
     def generate_batch(self, clips, sr, target_sampling_rate=48000, timestep=1, *, noise=None,
-                       generator=None, return_stages=False, seed=None, _keys=None, channels=None, level='peak',
+                       generator=None, return_stages=False, seed=None, channels=None, level='peak',
                        output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False, loudness=None,
                        true_peak=None, limiter=None):
         """B clips of equal length as one batch -> [B, T48], every clip what generate() returns for it alone.
@@ -983,43 +972,24 @@ class FlowHighSR:
         pcm=; interleaved=True gives [B, T, 1] without channels=, a list of [T, C_i] with it.  loudness= (generate): every clip
         at that many LUFS, each by its own gain.  true_peak=, limiter= (generate): every clip under that ceiling in dBTP, each by
         its own gain or its own limiter gain."""
-        clips, planar = resolve_clips(list(clips), channels, level)
-        n_clips = len(clips if planar is None else planar)
+        planar, plain = self._planar(list(clips), channels, level)
+        n_clips, chans = len(planar), [a.shape[0] for a in planar]
         opt = resolve_delivery(n_clips, output_rate, pcm, dither, dither_seed, interleaved, loudness=loudness, level=level,
                                true_peak=true_peak, limiter=limiter)
         if opt is not None and return_stages:
             raise ValueError("return_stages=True returns the 48 kHz stages: it does not go with output_rate= / pcm= / loudness= / "
                              "true_peak=")
-        keys = _keys if _keys is not None else self._prior_keys(seed, n_clips, generator, noise)
-        rows, chans, stages = self._batch_rows(clips, planar, keys, sr, target_sampling_rate, timestep, noise, generator, level,
-                                               return_stages)
+        keys = self._prior_keys(seed, n_clips, generator, noise)
+        if target_sampling_rate != 48000:
+            raise NotImplementedError("the mel codec is fixed at 48 kHz")
+        out = self._generate_rows(planar, sr, timestep, clip_noises(noise, chans), keys, generator, level, plain, return_stages)
+        rows, stages = out if return_stages else (out, None)
         if opt is not None:
             # (without channels= every clip is one row: the delivered buffer itself is the [B, T] result)
             return self.delivery.batch(rows, chans, level, opt, range(n_clips), packed=channels is None)
         if channels is not None:
             rows = list(rows.split(chans))
         return (rows, stages) if return_stages else rows
-
-    def _batch_rows(self, clips, planar, keys, sr, target_sampling_rate, timestep, noise, generator, level, return_stages=False):
-        """The 48 kHz result of a batch of equal-length clips (resolve_clips' pair) -> ([R, T48]: the clips' channels as rows,
-        in clip order; channels per clip; the stages or None).  Mono clips at level='peak' run the default path."""
-        if planar is not None:
-            if target_sampling_rate != 48000:
-                raise NotImplementedError("the mel codec is fixed at 48 kHz")
-            chans = [a.shape[0] for a in planar]
-            out = self._generate_rows(planar, sr, timestep, clip_noises(noise, chans), keys, generator, level, return_stages)
-            rows, stages = out if return_stages else (out, None)
-            return rows, chans, stages
-        cond = self._prepare_cond(clips, sr, target_sampling_rate)
-        kw = dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
-        HR_audio = self._sample(cond=cond, time_steps=timestep, cfm_method=self.cfm_method, noise=noise,
-                                generator=generator, keys=keys, **kw)
-        HR_audio = HR_audio.squeeze(1)
-        out = self.postproc(HR_audio, cond, cond.size(-1), return_cr=return_stages)
-        chans = [1] * len(clips)
-        if return_stages:
-            return out[0], chans, dict(cond=cond, wav=HR_audio.clone(), cr=out[1].clone())      # (plan-owned buffers)
-        return out, chans, None
 
     @torch.no_grad()
     @hip.on_device
@@ -1071,19 +1041,16 @@ class FlowHighSR:
         rates = resolve_rates(sr, len(clips))
         opt = resolve_delivery(len(clips), output_rate, pcm, dither, dither_seed, interleaved, loudness=loudness, level=level,
                                true_peak=true_peak, limiter=limiter)
-        clips, planar = resolve_clips(clips, channels, level)
-        chans = None
-        if planar is not None:
-            if target_sampling_rate != 48000:
-                raise NotImplementedError("the mel codec is fixed at 48 kHz")
-            clips, chans = planar, [a.shape[0] for a in planar]
-            if noise is not None:
-                for z, c in zip(noise, chans):
-                    channel_noise(z, c)                  # (a wrong leading dimension: a ValueError before any GPU work)
+        planar, plain = self._planar(clips, channels, level)
+        chans, lengths = [a.shape[0] for a in planar], [a.shape[1] for a in planar]
+        if target_sampling_rate != 48000:
+            raise NotImplementedError("the mel codec is fixed at 48 kHz")
+        if noise is not None:
+            for z, c in zip(noise, chans):
+                channel_noise(z, c)                      # (a wrong leading dimension: a ValueError before any GPU work)
         keys = self._prior_keys(seed, len(clips), generator, noise)
-        lengths = [int(np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).shape[-1]) for a in clips]
         if noise is None:
-            frames = [resample_out_len(n_in, target_sampling_rate, sr_i) // 480 for n_in, sr_i in zip(lengths, rates)]
+            frames = [resample_out_len(n_in, 48000, sr_i) // 480 for n_in, sr_i in zip(lengths, rates)]
             if keys is None:
                 noise = [self._draw_noise(1, n, generator) for n in frames]
         if noise is not None and len(noise) != len(clips):
@@ -1092,10 +1059,10 @@ class FlowHighSR:
         shapes = [tuple(z.shape) for z in noise] if noise is not None else [(1, n, self.flowhigh.n_mels) for n in frames]
         if ragged is None:
             ragged = os.environ.get("FH_RAGGED", "1") != "0"
-        if ragged and len(set(zip(lengths, rates))) > 1 and target_sampling_rate == 48000:
+        if ragged and len(set(zip(lengths, rates))) > 1:
             try:
-                return self._generate_many_ragged(clips, lengths, rates, timestep, noise, max_frames, keys=keys,
-                                                  frames=[sh[1] for sh in shapes], ends=ends, chans=chans, level=level, opt=opt)
+                return self._generate_many_ragged(planar, rates, timestep, noise, max_frames, keys, [sh[1] for sh in shapes], ends,
+                                                  level, plain, opt)
             except NotImplementedError as e:
                 # a vocoder configuration whose launch positions cannot be merged: one batch per length (said once)
                 if not getattr(self, "_ragged_fallback_logged", False):
@@ -1103,158 +1070,88 @@ class FlowHighSR:
                     import logging
                     logging.getLogger("flowhigh_amd").warning("generate_many: ragged launch sequence not available (%s); "
                                                               "running one batch per clip length", e)
-        buckets = {}
-        for i, a in enumerate(clips):
-            key = (lengths[i], rates[i], shapes[i])
-            buckets.setdefault(key, []).append(i)
-        out = [None] * len(clips)
         if streams is None:
             streams = int(os.environ.get("FH_SERVE_STREAMS", "1"))
-        frame_counts = sorted({key[2][1] for key in buckets})
-        n_streams = max(1, min(int(streams), len(frame_counts)))
+        n_streams, parts = plan_buckets(lengths, rates, shapes, streams, max_batch)
         main = torch.cuda.current_stream(self.device)
         side = self._serve_streams(n_streams) if n_streams > 1 else [main]
         for s_ in side:
             if s_ is not main:
                 s_.wait_stream(main)
-        stream_of = {n: side[i % len(side)] for i, n in enumerate(frame_counts)}
-        for key, idx in buckets.items():
-            st = stream_of[key[2][1]]
-            with torch.cuda.stream(st):
-                for k in range(0, len(idx), max_batch):
-                    part = idx[k:k + max_batch]
-                    if chans is not None:                    # (max_batch counts clips: a clip's channels stay in one batch)
-                        part_ch = [chans[i] for i in part]
-                        y = self._generate_rows([clips[i] for i in part], key[1], timestep,
-                                                clip_noises([noise[i] for i in part], part_ch) if keys is None else None,
-                                                [keys[i] for i in part] if keys is not None else None, None, level)
-                        ys = y.split(part_ch) if opt is None else self.delivery.batch(y, part_ch, level, opt, part)
-                        for i, rows in zip(part, ys):
-                            out[i] = rows.clone() if opt is None else rows
-                            if st is not main:
-                                out[i].record_stream(main)
-                        continue
-                    if keys is not None:
-                        prior = dict(_keys=[keys[i] for i in part])
-                    else:
-                        prior = dict(noise=noise[part[0]] if len(part) == 1 else torch.cat([noise[i] for i in part], 0))
-                    y = self.generate_batch([clips[i] for i in part], key[1], target_sampling_rate, timestep, **prior)
-                    ys = None if opt is None else self.delivery.batch(y, [1] * len(part), level, opt, part)
-                    for r, i in enumerate(part):
-                        out[i] = y[r:r + 1].clone() if ys is None else ys[r]
-                        if st is not main:
-                            out[i].record_stream(main)
+        out = [None] * len(clips)
+        for s_, rate, part in parts:                         # (max_batch counts clips: a clip's channels stay in one batch)
+            with torch.cuda.stream(side[s_]):
+                for i, y in zip(part, self._run_clips(planar, part, rate, timestep, noise, keys, level, plain, opt)):
+                    out[i] = y.clone() if opt is None else y
+                    if side[s_] is not main:
+                        out[i].record_stream(main)
         for s_ in side:
             if s_ is not main:
                 main.wait_stream(s_)
         return out
 
-    def _generate_many_ragged(self, clips, lengths, rates, timestep, noise, max_frames, keys=None, frames=None, ends="per_clip",
-                              chans=None, level="peak", opt=None):
-        """rates: the input rate of every clip (resolve_rates).  chans (a channels= / level= call): clips are float [C_i, T_i]
-        arrays (resolve_clips) of chans[i] channels, each C_i rows of n frames in its sequence.  opt: resolve_delivery's
+    def _run_clips(self, planar, idx, rate, timestep, noise, keys, level, plain, opt):
+        """The clips idx of a generate_many call (equal lengths, one rate) as one batch, delivered if opt says so -> one
+        [C_i, T] result per clip: views of the batch's fresh rows, or what Delivery.batch returns."""
+        chans = [planar[i].shape[0] for i in idx]
+        y = self._generate_rows([planar[i] for i in idx], rate, timestep,
+                                clip_noises([noise[i] for i in idx], chans) if keys is None else None,
+                                [keys[i] for i in idx] if keys is not None else None, None, level, plain)
+        return y.split(chans) if opt is None else self.delivery.batch(y, chans, level, opt, idx)
+
+    def _generate_many_ragged(self, planar, rates, timestep, noise, max_frames, keys, frames, ends, level, plain, opt):
+        """generate_many's ragged path.  planar, plain: _planar's pair; rates: the input rate of every clip (resolve_rates);
+        frames: every clip's frame count; clip i is C_i rows of frames[i] frames in its sequence.  opt: resolve_delivery's
         result; a clip that runs alone is delivered by the batched entries, a group by the segment forms."""
         if max_frames is None:
             max_frames = int(os.environ.get("FH_RAGGED_MAX_FRAMES", "12000"))
         chunk_limit = int(os.environ.get("FH_VOCODER_CHUNK_FRAMES", "6000"))
-        if frames is None:
-            frames = [n.shape[1] for n in noise]
-
-        def prior_of(i):              # one clip on its own: its noise, or its key
-            return dict(_keys=[keys[i]]) if keys is not None else dict(noise=noise[i])
-
-        def alone(i):
-            if chans is None:
-                y = self.generate_batch([clips[i]], rates[i], 48000, timestep, **prior_of(i))
-                return y.clone() if opt is None else self.delivery.batch(y, [1], level, opt, [i])[0]
-            y = self._generate_rows([clips[i]], rates[i], timestep, clip_noises(noise[i], [chans[i]]) if keys is None else None,
-                                    [keys[i]] if keys is not None else None, None, level)
-            return y if opt is None else self.delivery.batch(y, [chans[i]], level, opt, [i])[0]
-
-        def deliver(idx, ys):          # a group's 48 kHz results (still plan- or workspace-owned) -> the caller's own
+        # greedy packing in list order; a clip that does not fit a sequence, or has one to itself, runs as a batch of one
+        groups, alone = pack_ragged(frames, [a.shape[0] for a in planar], max_frames, chunk_limit)
+        out = [None] * len(planar)
+        for idx in [[i] for i in alone] + groups:
+            if len(idx) == 1:
+                (out[idx[0]],) = self._run_clips(planar, idx, rates[idx[0]], timestep, noise, keys, level, plain, opt)
+                continue
+            # a group's 48 kHz results are the caller's own without delivery, else still workspace-owned where delivery reads them
+            ys = self._ragged_group_rows([planar[i] for i in idx], [rates[i] for i in idx], timestep,
+                                         [noise[i] for i in idx] if keys is None else None,
+                                         [keys[i] for i in idx] if keys is not None else None, ends, level, plain, own=opt is None)
             if opt is not None:
-                ys = self.delivery.ragged([y if y.ndim == 2 else y[None] for y in ys], level, opt, idx)
+                ys = self.delivery.ragged(ys, level, opt, idx)
             for i, y in zip(idx, ys):
                 out[i] = y
-        width = chans if chans is not None else [1] * len(clips)
-        out = [None] * len(clips)
-        kw = dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
-        # greedy packing in list order; a clip that does not fit a sequence of its own runs through generate()
-        groups, cur, tot = [], [], 0
-        for i, n in enumerate(frames):
-            if n * width[i] > max_frames or (chunk_limit > 0 and n > chunk_limit):
-                out[i] = alone(i)
-                continue
-            if cur and tot + n * width[i] > max_frames:
-                groups.append(cur)
-                cur, tot = [], 0
-            cur.append(i)
-            tot += n * width[i]
-        if cur:
-            groups.append(cur)
-        for idx in groups:
-            if len(idx) == 1:
-                out[idx[0]] = alone(idx[0])
-                continue
-            if chans is not None:
-                ys = self._ragged_group_rows([clips[i] for i in idx], [rates[i] for i in idx], timestep,
-                                             [noise[i] for i in idx] if keys is None else None,
-                                             [keys[i] for i in idx] if keys is not None else None, ends, level, kw,
-                                             own=opt is None)
-                deliver(idx, ys)
-                continue
-            prior = dict(keys=[keys[i] for i in idx]) if keys is not None else dict(noises=[noise[i] for i in idx])
-            if ends == "ragged":
-                # front and back end as segment-form launches over the group: nothing below depends on the number of clips
-                _, conds = self._prepare_cond([clips[i] for i in idx], [rates[i] for i in idx], ragged=True)
-                cond_mel, mels = self.flowhigh.logmel.ragged(conds)
-                wavs = self._sample_ragged(conds, timestep, self.cfm_method, mels=mels, cond_mel=cond_mel, **prior, **kw)
-                packed, views = self.postproc.ragged(wavs, conds, [c.shape[0] for c in conds])
-                if opt is None:
-                    packed = packed.clone()                  # (the caller's own: one copy for the group, handed out as views)
-                start, ys = 0, []
-                for v in views:
-                    ys.append(packed[start:start + v.shape[0]][None])
-                    start += v.shape[0]
-                deliver(idx, ys)
-                continue
-            # (the per-clip front and back ends -- ~8 + ~12 small launches per clip -- on up to 4 side streams measured
-            # 121.5 ms against 121.3 ms on one stream for the 24-clip mix: not worth the cross-stream bookkeeping)
-            conds = [self._prepare_cond([clips[i]], rates[i], 48000)[0] for i in idx]
-            wavs = self._sample_ragged(conds, timestep, self.cfm_method, **prior, **kw)
-            deliver(idx, [self.postproc(wav, cond[None], cond.shape[0]).clone() for cond, wav in zip(conds, wavs)])
         return out
 
-    def _ragged_group_rows(self, planar, rates, timestep, noises, keys, ends, level, kw, own=True):
-        """One ragged group of a channels= / level= call: every channel of every clip is a row of the sequence, the rows of
-        a clip are adjacent and share its prior, and the post-processor gets the rows' gains and (level='peak') their clip as
-        their group.  -> list of [C_i, T48_i], each the bits of _generate_rows on that clip alone."""
+    def _ragged_group_rows(self, planar, rates, timestep, noises, keys, ends, level, plain, own=True):
+        """One ragged group: every channel of every clip is a row of the sequence, the rows of a clip are adjacent and share
+        its prior, and unless plain the post-processor gets the rows' gains and (level='peak') their clip as their group.
+        -> list of [C_i, T48_i], each the bits of _generate_rows on that clip alone.  ends='ragged': front and back end as
+        segment-form launches over the group, the results views of the post-processor's workspace (own: of one copy of it);
+        'per_clip': the batched entries once per clip (on up to 4 side streams they measured 121.5 ms against 121.3 ms on one
+        for a 24-clip mix: not worth the cross-stream bookkeeping), the results fresh tensors."""
         chans = [a.shape[0] for a in planar]
         if keys is not None:
-            prior = dict(keys=[k for k, c in zip(keys, chans) for _ in range(c)])
+            prior = dict(keys=[k for k, c in zip(keys, chans) for _ in range(c)], **self._prior_scale())
         else:
-            prior = dict(noises=[z[None] for zs, c in zip(noises, chans) for z in channel_noise(zs, c)])
+            prior = dict(noises=[z[None] for zs, c in zip(noises, chans) for z in channel_noise(zs, c)], **self._prior_scale())
         if ends == "ragged":
             rows = [row for a in planar for row in a]
-            conds, gains = self._prepare_rows(rows, [r for r, c in zip(rates, chans) for _ in range(c)], ragged=True)
+            conds, gains = self._prepare_rows(rows, [r for r, c in zip(rates, chans) for _ in range(c)], plain, ragged=True)
             cond_mel, mels = self.flowhigh.logmel.ragged(conds)
-            wavs = self._sample_ragged(conds, timestep, self.cfm_method, mels=mels, cond_mel=cond_mel, **prior, **kw)
-            packed, _ = self.postproc.ragged(wavs, conds, [c.shape[0] for c in conds], **self._level_args(chans, level, gains))
+            wavs = self._sample_ragged(conds, timestep, self.cfm_method, mels=mels, cond_mel=cond_mel, **prior)
+            packed, _ = self.postproc.ragged(wavs, conds, [c.shape[0] for c in conds], **self._level_args(chans, level, gains, plain))
             if own:
                 packed = packed.clone()                      # (the caller's own: one copy for the group, handed out as views)
-            out, start, r = [], 0, 0
-            for c in chans:                                  # (a clip's rows are adjacent and of one length)
-                t48 = conds[r].shape[0]
-                out.append(packed[start:start + c * t48].view(c, t48))
-                start, r = start + c * t48, r + c
-            return out
-        prepared = [self._prepare_rows(list(a), rate) for a, rate in zip(planar, rates)]          # (cond [C_i, T48_i], gains [C_i])
-        wavs = self._sample_ragged([row for cond, _ in prepared for row in cond], timestep, self.cfm_method, **prior, **kw)
-        out, r = [], 0
-        for (cond, gains), c in zip(prepared, chans):
-            out.append(self.postproc(torch.cat(list(wavs[r:r + c]), 0), cond, cond.shape[1], **self._level_args([c], level, gains)))
-            r += c
-        return out
+            # (a clip's rows are adjacent and of one length)
+            lens = [c * conds[r].shape[0] for c, r in zip(chans, _starts(chans))]
+            return [v.view(c, -1) for v, c in zip(_views(packed, _starts(lens), lens), chans)]
+        prepared = [self._prepare_rows(list(a), rate, plain) for a, rate in zip(planar, rates)]      # (cond [C_i, T48_i], gains [C_i])
+        wavs = self._sample_ragged([row for cond, _ in prepared for row in cond], timestep, self.cfm_method, **prior)
+        # (the vocoder's [1, Tp] buffers: one is read where it lies, a clip's several become its [C_i, Tp] rows)
+        return [self.postproc(wavs[r] if c == 1 else torch.cat(list(wavs[r:r + c]), 0), cond, cond.shape[1],
+                              **self._level_args([c], level, gains, plain))
+                for (cond, gains), c, r in zip(prepared, chans, _starts(chans))]
 
     # ---- streaming sessions (stream.py is the definition, streaming.py the host side, csrc/stream.hip the seam) ------------------
     def stream(self, sr, *, window_ms=1000, overlap_ms=200, guard_ms=50, timestep=1, seed=None, stream=0, pcm=None,
@@ -1380,8 +1277,8 @@ class FlowHighSR:
 
     def _generate_from_device(self, x, sr, timestep=1, *, noise=None, keys=None):
         cond = self.resampler(x, sr, 48000)
-        kw = dict(std_2=1.) if self.cfm_method == 'independent_cfm_adaptive' else {}
-        wav = self._sample(cond=cond, time_steps=timestep, cfm_method=self.cfm_method, noise=noise, keys=keys, **kw).squeeze(1)
+        wav = self._sample(cond=cond, time_steps=timestep, cfm_method=self.cfm_method, noise=noise, keys=keys,
+                           **self._prior_scale()).squeeze(1)
         return self.postproc(wav, cond, cond.size(-1))
 
     @torch.no_grad()

@@ -183,7 +183,7 @@ def run(model, sessions, final):
         p = sessions[items[0][0]].plan
         # (a window of C channels is one clip of C rows that share the prior: sessions of any channel counts in one batch)
         y = model._generate_rows([x for _, _, x, _ in items], p.sr, key[1], None, [sessions[si].key for si, _, _, _ in items], None,
-                                 "input", first_frames=[p.first_frame(wi) for _, wi, _, _ in items])
+                                 "input", False, first_frames=[p.first_frame(wi) for _, wi, _, _ in items])
         o, esz = p.O48, y.element_size()
         jobs, row_of, r = [], {}, 0
         for si, wi, x, _ in items:
