@@ -1,4 +1,4 @@
-"""`python -m flowhigh_amd.convert <ckpt_dir> [<blob>] [--form=winograd|bf16x6|direct|direct_bf16x6] [--probe] [--verify]`: pack the reference's checkpoint files once into the flat weight blob
+"""`python -m flowhigh_amd.convert <ckpt_dir> [<blob>] [--form=winograd|bf16x6|direct|direct_bf16x6|direct_bf16x3] [--probe] [--verify]`: pack the reference's checkpoint files once into the flat weight blob
 that `FlowHighSR.from_local` maps and uploads with one copy (flowhigh_amd/weights.py).
 
 Runs on the CPU (no GPU, no HIP library): the packers are plain torch.  The blob is tied to the content of the three source

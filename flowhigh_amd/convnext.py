@@ -70,7 +70,7 @@ class ConvNextNet:
         dev = self.device
         g = lambda name: sd[FH + name].detach().float().cpu()
         up = lambda t: t.contiguous().to(dev)
-        # bf: the linears in the bf16 x 6 form, as FlowNet's (conv_form = 'bf16x6' / 'direct_bf16x6')
+        # bf: the linears in the bf16 x 6 form, as FlowNet's (conv_form = 'bf16x6' / 'direct_bf16x6' / 'direct_bf16x3')
         self.bf = bool(bf)
         if self.bf:
             from .packing import pack_gemm_bf_weight

@@ -24,33 +24,46 @@
 //     (two register sets, requested unconditionally -- past the last step through a 0-byte descriptor -- so that every step's
 //     wait is a counted vmcnt that leaves the next step's 3 MT loads in flight); no LDS, no barrier for them;
 //   * a K step of a wave is 3 NT ds_read_b128 + 3 MT 16-byte loads for 6 MT NT MFMAs.
+//
+// The body is a template over the pieces per operand, NP.  NP = 3 is the form above.  NP = 2 (conv_form = 'direct_bf16x3',
+// fh_conv_grouped_bf16x3_f32) keeps h and m only and multiplies the three pairs of kBf16x3SmallFirst -- (m h) (h m) (h h); the
+// dropped terms are <= 3 2^-16 |a b| -- on two piece planes per slab and 64-byte weight rows [piece h, m][16]
+// (packing.pack_conv_bf3_weight): a K step of a wave is 2 NT ds_read_b128 + 2 MT 16-byte loads for 3 MT NT MFMAs, and the next
+// chunk's slab is written behind the FIRST pair's MFMAs.  Everything else -- descriptors, step order, epilogue, tiles, block
+// mapping -- is the same code.
 #include "bf16x6.h"
 #include "conv_mfma_common.h"
 #include "fh_common.h"
 
 namespace {
 
-template <int MT, int NT, int WM, int WN>
+// NP: pieces per operand -- 3: the six-pair form (fh_conv_grouped_bf16x6_f32), 2: the three-pair form (fh_conv_grouped_bf16x3_f32)
+template <int NP, int MT, int NT, int WM, int WN>
 struct ConvBfCfg {
+  static_assert(NP == 2 || NP == 3, "two or three pieces per operand");
   static constexpr int BM = 32 * MT * WM;
   static constexpr int BN = 32 * NT * WN;
   static constexpr int XW = BN + FH_CONV_MAX_HALO;       // staged samples per octet
-  static constexpr int ITEMS = 2 * XW;                   // (octet, sample) items of a chunk: 8 floats -> three 16-byte units
+  static constexpr int ITEMS = 2 * XW;                   // (octet, sample) items of a chunk: 8 floats -> NP 16-byte units
   static constexpr int XR = (ITEMS + 255) / 256;         // items per thread
   static constexpr int PLANE = 2 * XW;                   // units of a piece plane
-  static constexpr int SLAB = 3 * PLANE;                 // units of a slab
+  static constexpr int SLAB = NP * PLANE;                // units of a slab
   static constexpr int TOFF = FH_CONV_MAX_SEG * FH_CONV_MAX_TAPS / 4;      // units of the tap shift table
+  static constexpr int LDS_BYTES = 16 * (2 * SLAB + TOFF);                 // two slabs and the table
+  // blocks per CU the launch bounds promise: as many as fit the CU's 160 KB of LDS, at most 2 (three pieces: 2, except the 32 x 512
+  // tile, whose two slabs -- 108 KB -- leave room for one; two pieces: that tile's 72 KB fit twice as well)
+  static constexpr int BLOCKS_PER_CU = 2 * LDS_BYTES <= 160 * 1024 ? 2 : 1;
 };
 
-constexpr unsigned ROW_BYTES = 96;                       // a weight row: 3 pieces x 16 bf16
-
-// (blocks per CU the launch bounds promise: 2, except the 32 x 512 tile, whose two slabs -- 108 KB of LDS -- leave room for one)
-template <int MT, int NT, int WM, int WN>
-__global__ __launch_bounds__(256, (ConvBfCfg<MT, NT, WM, WN>::SLAB * 32 > 80 * 1024 ? 1 : 2)) void conv_mfma_bf_kernel(const fh_conv_group* __restrict__ groups, int n_groups, int batch, int co_tiles,
+template <int NP, int MT, int NT, int WM, int WN>
+__global__ __launch_bounds__(256, (ConvBfCfg<NP, MT, NT, WM, WN>::BLOCKS_PER_CU)) void conv_mfma_bf_kernel(const fh_conv_group* __restrict__ groups, int n_groups, int batch, int co_tiles,
                                                               int n_tiles) {
-  using Cfg = ConvBfCfg<MT, NT, WM, WN>;
+  using Cfg = ConvBfCfg<NP, MT, NT, WM, WN>;
   constexpr int BM = Cfg::BM, BN = Cfg::BN, XW = Cfg::XW, XR = Cfg::XR, PLANE = Cfg::PLANE, SLAB = Cfg::SLAB;
   constexpr int PH = 1;
+  constexpr unsigned ROW_BYTES = 32 * NP;                  // a weight row: NP pieces x 16 bf16
+  constexpr int NPAIRS = bf16_n_pairs<NP>();
+  constexpr int STAGE_PAIR = NP == 3 ? 2 : 0;              // the pair behind whose MFMAs the next chunk's slab is written
   __shared__ __attribute__((aligned(16))) u32x4 lds[2 * SLAB + Cfg::TOFF];
   int* toff = reinterpret_cast<int*>(lds + 2 * SLAB);    // [seg][tap] sample shift of each tap
 
@@ -102,11 +115,11 @@ __global__ __launch_bounds__(256, (ConvBfCfg<MT, NT, WM, WN>::SLAB * 32 > 80 * 1
   unsigned avoff[MT];                          // lane (row, half): the half's 8 channels of piece 0 of the row
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) avoff[mt] = (unsigned)((wm * MT + mt) * 32 + l31) * ROW_BYTES + (unsigned)lh * 16u;
-  auto load_a = [&](u32x4 (&a)[MT][3]) {       // the W cursor's fragments, then on to the next step
+  auto load_a = [&](u32x4 (&a)[MT][NP]) {       // the W cursor's fragments, then on to the next step
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) a[mt][p] = __builtin_amdgcn_raw_buffer_load_b128(w_r, avoff[mt] + 32u * p, w_soff, 0);
+      for (int p = 0; p < NP; ++p) a[mt][p] = __builtin_amdgcn_raw_buffer_load_b128(w_r, avoff[mt] + 32u * p, w_soff, 0);
     w_soff += wstep;
     if (--w_left == 0) w_enter();
   };
@@ -151,18 +164,26 @@ __global__ __launch_bounds__(256, (ConvBfCfg<MT, NT, WM, WN>::SLAB * 32 > 80 * 1
         float v[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) v[c] = __uint_as_float(xreg[r][c]);
-        u32x4 h, m, l;
-        bf16x6_split(v, h, m, l);
-        u32x4* const dst = lds + buf * SLAB + xo[r] * XW + xs_[r];
-        dst[0] = h;
-        dst[PLANE] = m;
-        dst[2 * PLANE] = l;
+        if constexpr (NP == 3) {
+          u32x4 h, m, l;
+          bf16x6_split(v, h, m, l);
+          u32x4* const dst = lds + buf * SLAB + xo[r] * XW + xs_[r];
+          dst[0] = h;
+          dst[PLANE] = m;
+          dst[2 * PLANE] = l;
+        } else {
+          u32x4 h, m;
+          bf16x3_split(v, h, m);
+          u32x4* const dst = lds + buf * SLAB + xo[r] * XW + xs_[r];
+          dst[0] = h;
+          dst[PLANE] = m;
+        }
       }
     }
   };
 
   // ---- prologue -----------------------------------------------------------------------------------------------------------
-  u32x4 aA[MT][3], aB[MT][3];
+  u32x4 aA[MT][NP], aB[MT][NP];
   int xbuf = 0;
   w_enter();
   x_enter();
@@ -172,10 +193,10 @@ __global__ __launch_bounds__(256, (ConvBfCfg<MT, NT, WM, WN>::SLAB * 32 > 80 * 1
   __syncthreads();
 
   // One K step: CUR holds this step's weight fragments, NXT receives the next step's.  The next chunk's slab is requested at a
-  // chunk's first tap and split into the other buffer behind the first three pair MFMAs of its second tap (of its only tap when
-  // it has one): the barrier at the chunk's end is the only one.
+  // chunk's first tap and split into the other buffer behind the first three pair MFMAs (two pieces: the first pair's) of its second tap
+  // (of its only tap when it has one): the barrier at the chunk's end is the only one.
   int xoff_cur = toff[0];
-  auto step = [&](int it, const u32x4 (&CUR)[MT][3], u32x4 (&NXT)[MT][3]) {
+  auto step = [&](int it, const u32x4 (&CUR)[MT][NP], u32x4 (&NXT)[MT][NP]) {
     const bool last_tap = K.j == K.nt - 1;
     const bool more_chunks = K.cl > 1 || K.s + 1 < nseg;
     const bool flip_x = last_tap && more_chunks;
@@ -185,21 +206,21 @@ __global__ __launch_bounds__(256, (ConvBfCfg<MT, NT, WM, WN>::SLAB * 32 > 80 * 1
     load_a(NXT);                                 // (past the last step: a 0-byte descriptor, nothing is fetched)
     if (K.j == 0 && more_chunks) load_x();
     const u32x4* const xsb = lds + xbuf * SLAB + lh * XW + xoff_cur + wn * NT * 32 + l31;
-    bf16x8 bfr[NT][3];
+    bf16x8 bfr[NT][NP];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) bfr[nt][p] = __builtin_bit_cast(bf16x8, xsb[p * PLANE + nt * 32]);
+      for (int p = 0; p < NP; ++p) bfr[nt][p] = __builtin_bit_cast(bf16x8, xsb[p * PLANE + nt * 32]);
     const int xoff_next = toff[s1 * FH_CONV_MAX_TAPS + j1];
 #pragma unroll
-    for (int pp = 0; pp < 6; ++pp) {
-      const Bf16x6Pair s = kBf16x6SmallFirst[pp];            // (weight piece, sample piece)
+    for (int pp = 0; pp < NPAIRS; ++pp) {
+      const Bf16x6Pair s = bf16_small_first<NP>(pp);         // (weight piece, sample piece)
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
           acc[0][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, CUR[mt][s.a]), bfr[nt][s.b], acc[0][mt][nt], 0, 0, 0);
-      if (pp == 2 && stage) store_x(xbuf ^ 1);
+      if (pp == STAGE_PAIR && stage) store_x(xbuf ^ 1);
     }
     if (flip_x) {
       __syncthreads();
@@ -227,21 +248,27 @@ __global__ __launch_bounds__(256, (ConvBfCfg<MT, NT, WM, WN>::SLAB * 32 > 80 * 1
 #include "conv_mfma_epilogue.h"
 }
 
-template <int MT, int NT, int WM, int WN>
+// the entry's name, for its messages
+template <int NP>
+constexpr const char* conv_bf_name() {
+  return NP == 3 ? "fh_conv_grouped_bf16x6_f32" : "fh_conv_grouped_bf16x3_f32";
+}
+
+template <int NP, int MT, int NT, int WM, int WN>
 int launch_conv_bf(const fh_conv_group* groups, int n_groups, int batch, int cout_pad, int n_len, hipStream_t stream) {
-  using Cfg = ConvBfCfg<MT, NT, WM, WN>;
+  using Cfg = ConvBfCfg<NP, MT, NT, WM, WN>;
   int co_tiles, n_tiles;
   const long long blocks = conv_grid_blocks(n_groups, batch, cout_pad, n_len, Cfg::BM, Cfg::BN, &co_tiles, &n_tiles);
-  FH_CHECK_ARG(blocks > 0 && blocks < (1ll << 31), "fh_conv_grouped_bf16x6_f32: grid too large");
-  hipLaunchKernelGGL((conv_mfma_bf_kernel<MT, NT, WM, WN>), dim3((unsigned)blocks), dim3(256), 0, stream, groups, n_groups, batch, co_tiles,
+  FH_CHECK_ARG(blocks > 0 && blocks < (1ll << 31), "%s: grid too large", conv_bf_name<NP>());
+  hipLaunchKernelGGL((conv_mfma_bf_kernel<NP, MT, NT, WM, WN>), dim3((unsigned)blocks), dim3(256), 0, stream, groups, n_groups, batch, co_tiles,
                      n_tiles);
-  FH_CHECK_LAUNCH("fh_conv_grouped_bf16x6_f32");
+  FH_CHECK_LAUNCH(conv_bf_name<NP>());
   return FH_OK;
 }
 
 // The descriptors of a launch normally live in device memory, where the launcher cannot see them (the host plan checks the shapes
 // it builds them from).  An array in pinned host memory -- which the kernel reads just as well -- is checked here.
-int check_host_groups(const fh_conv_group* groups, int n_groups) {
+int check_host_groups(const char* name, const fh_conv_group* groups, int n_groups) {
   hipPointerAttribute_t at;
   if (hipPointerGetAttributes(&at, groups) != hipSuccess) {
     (void)hipGetLastError();
@@ -251,35 +278,34 @@ int check_host_groups(const fh_conv_group* groups, int n_groups) {
   const fh_conv_group* g = static_cast<const fh_conv_group*>(at.hostPointer);
   for (int i = 0; i < n_groups; ++i) {
     FH_CHECK_ARG(g[i].nseg >= 1 && g[i].nseg <= FH_CONV_MAX_SEG && g[i].nres >= 0 && g[i].nres <= FH_CONV_MAX_SEG,
-                 "fh_conv_grouped_bf16x6_f32: group %d has %d segments, %d residuals (1 .. %d, 0 .. %d)", i, g[i].nseg, g[i].nres,
+                 "%s: group %d has %d segments, %d residuals (1 .. %d, 0 .. %d)", name, i, g[i].nseg, g[i].nres,
                  FH_CONV_MAX_SEG, FH_CONV_MAX_SEG);
     for (int s = 0; s < g[i].nseg; ++s) {
       const fh_conv_seg& sg = g[i].seg[s];
-      FH_CHECK_ARG(sg.cin > 0 && sg.cin % 16 == 0, "fh_conv_grouped_bf16x6_f32: group %d segment %d has %d input channels (a multiple of 16)",
+      FH_CHECK_ARG(sg.cin > 0 && sg.cin % 16 == 0, "%s: group %d segment %d has %d input channels (a multiple of 16)", name,
                    i, s, sg.cin);
       FH_CHECK_ARG(sg.ntaps >= 1 && sg.ntaps <= FH_CONV_MAX_TAPS && sg.off_max - sg.off_min <= FH_CONV_MAX_HALO && sg.off_max >= sg.off_min,
-                   "fh_conv_grouped_bf16x6_f32: group %d segment %d: %d taps over %d samples (at most %d over %d)", i, s, sg.ntaps,
+                   "%s: group %d segment %d: %d taps over %d samples (at most %d over %d)", name, i, s, sg.ntaps,
                    sg.off_max - sg.off_min, FH_CONV_MAX_TAPS, FH_CONV_MAX_HALO);
     }
   }
   return FH_OK;
 }
 
-}  // namespace
-
-extern "C" int fh_conv_grouped_bf16x6_f32(const fh_conv_group* groups, int n_groups, int batch, int cout_pad, int n_len, int tile_cfg,
-                                          void* stream) {
-  FH_CHECK_ARG(groups && n_groups > 0 && batch > 0 && n_len > 0, "fh_conv_grouped_bf16x6_f32: bad sizes");
+template <int NP>
+int conv_grouped_bf(const fh_conv_group* groups, int n_groups, int batch, int cout_pad, int n_len, int tile_cfg, void* stream) {
+  constexpr const char* name = conv_bf_name<NP>();
+  FH_CHECK_ARG(groups && n_groups > 0 && batch > 0 && n_len > 0, "%s: bad sizes", name);
   const int bm = fh_conv_tile_m(tile_cfg);
-  FH_CHECK_ARG(bm > 0, "fh_conv_grouped_bf16x6_f32: unknown tile_cfg %d", tile_cfg);
-  FH_CHECK_ARG(cout_pad % bm == 0, "fh_conv_grouped_bf16x6_f32: cout_pad %d not a multiple of tile %d", cout_pad, bm);
-  if (const int rc = check_host_groups(groups, n_groups)) return rc;
+  FH_CHECK_ARG(bm > 0, "%s: unknown tile_cfg %d", name, tile_cfg);
+  FH_CHECK_ARG(cout_pad % bm == 0, "%s: cout_pad %d not a multiple of tile %d", name, cout_pad, bm);
+  if (const int rc = check_host_groups(name, groups, n_groups)) return rc;
   // per-clip tensors are addressed with 32-bit byte offsets (buffer descriptors): cout * lout * 4 < 2^31 and 16 * lin * 4 < 2^32
   // are checked by the host plan (flowhigh_amd/planner.py) where the shapes are known.
   hipStream_t st = (hipStream_t)stream;
 #define FH_CONV_BF_CASE(id, MT, NT, WM, WN) \
   case id:                                  \
-    return launch_conv_bf<MT, NT, WM, WN>(groups, n_groups, batch, cout_pad, n_len, st);
+    return launch_conv_bf<NP, MT, NT, WM, WN>(groups, n_groups, batch, cout_pad, n_len, st);
   switch (tile_cfg) {          // (conv_mfma.hip's shapes: the planner's tile choice and cout_pad carry over)
     FH_CONV_BF_CASE(0, 2, 2, 2, 2)
     FH_CONV_BF_CASE(1, 3, 2, 2, 2)
@@ -291,4 +317,18 @@ extern "C" int fh_conv_grouped_bf16x6_f32(const fh_conv_group* groups, int n_gro
   }
 #undef FH_CONV_BF_CASE
   return FH_E_ARG;
+}
+
+}  // namespace
+
+extern "C" int fh_conv_grouped_bf16x6_f32(const fh_conv_group* groups, int n_groups, int batch, int cout_pad, int n_len, int tile_cfg,
+                                          void* stream) {
+  return conv_grouped_bf<3>(groups, n_groups, batch, cout_pad, n_len, tile_cfg, stream);
+}
+
+// The same launches with two pieces per operand and the three pairs of kBf16x3SmallFirst (conv_form = 'direct_bf16x3'): weights
+// [cin/16][tap][cout_pad][piece h, m][16] bf16 (packing.pack_conv_bf3_weight), 64-byte rows.
+extern "C" int fh_conv_grouped_bf16x3_f32(const fh_conv_group* groups, int n_groups, int batch, int cout_pad, int n_len, int tile_cfg,
+                                          void* stream) {
+  return conv_grouped_bf<2>(groups, n_groups, batch, cout_pad, n_len, tile_cfg, stream);
 }

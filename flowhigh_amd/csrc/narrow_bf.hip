@@ -22,6 +22,10 @@
 //     set is 18-110 KB per conv, the same for every block of the launch, and no wave waits for another inside the K loop.
 // A sample's arithmetic depends on its absolute position only (fixed K order), so a clip gives the same bits alone, in a batch, in
 // a ragged launch and in time chunks.
+//
+// The body is a template over the pieces per operand, NP.  NP = 3 is the form above.  NP = 2 (conv_form = 'direct_bf16x3',
+// fh_narrow_conv_bf16x3_f32) keeps h and m only: two piece planes in the slab, weights [k-block][N tile][piece h, m][lane][8 bf16]
+// (packing.pack_narrow_bf3_weight) and the three pairs of kBf16x3SmallFirst per fragment pair; dropped terms <= 3 2^-16 |a b|.
 #include "bf16x6.h"
 #include "fh_common.h"
 
@@ -35,11 +39,12 @@ constexpr int NB_OG = 3;                     // octets (8 channels) per slab
 constexpr int NB_PLANE = NB_OG * NB_NSP;     // units of a piece plane
 constexpr int NB_MAX_D = 6;                  // (taps: at most 11, center at most 5 -- NB_NSP; checked where the descriptors are made)
 
-// MA: N tiles (16 output channels each).  VEC: every row of every group is 16-byte aligned (len % 4 == 0).
-template <int MA, bool VEC>
+// NP: pieces per operand (3: six pairs, 2: three).  MA: N tiles (16 output channels each).  VEC: every row of every group is 16-byte
+// aligned (len % 4 == 0).
+template <int NP, int MA, bool VEC>
 __global__ __launch_bounds__(NB_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
 void narrow_bf_kernel(const fh_amp_group* __restrict__ groups, const fh_amp_tile* __restrict__ tiles, int channels, int d, int total_tiles) {
-  __shared__ __attribute__((aligned(16))) u32x4 slab[3 * NB_PLANE];
+  __shared__ __attribute__((aligned(16))) u32x4 slab[NP * NB_PLANE];
 
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lg = lane >> 4;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -88,16 +93,16 @@ void narrow_bf_kernel(const fh_amp_group* __restrict__ groups, const fh_amp_tile
       for (int cg = 0; cg < ncg; ++cg) {
         const int og = og_lo + (cg < og_rem ? 1 : 0);
         const int kog = k * og, nb = (kog + 3) >> 2;
-        const unsigned wbytes = (unsigned)(nb * MA * 3) * 1024u;
+        const unsigned wbytes = (unsigned)(nb * MA * NP) * 1024u;
         const __amdgpu_buffer_rsrc_t rw = make_rsrc(reinterpret_cast<const char*>(up) + (size_t)wbase * 1024u, wbytes);
         // ---- weights of the first k-block: requested before the slab (they are in L2; the rows may come from HBM) ------------
-        u32x4 bw[2][MA][3];
+        u32x4 bw[2][MA][NP];
         auto load_b = [&](int set, int kb) {
 #pragma unroll
           for (int na = 0; na < MA; ++na)
 #pragma unroll
-            for (int p = 0; p < 3; ++p)
-              bw[set][na][p] = __builtin_amdgcn_raw_buffer_load_b128(rw, (unsigned)lane * 16u, (unsigned)((kb * MA + na) * 3 + p) * 1024u, 0);
+            for (int p = 0; p < NP; ++p)
+              bw[set][na][p] = __builtin_amdgcn_raw_buffer_load_b128(rw, (unsigned)lane * 16u, (unsigned)((kb * MA + na) * NP + p) * 1024u, 0);
         };
         load_b(0, 0);
         // ---- slab: the samples of the group's octets, split, as [piece][octet][sample]; slab sample s is t = t0 - Ha + s ----------
@@ -105,6 +110,20 @@ void narrow_bf_kernel(const fh_amp_group* __restrict__ groups, const fh_amp_tile
         // VEC: Ha = H rounded up to 4 (16-byte loads; the taps then start Ha - H samples into the slab); else Ha = H
         const int Ha = VEC ? (H + 3) & ~3 : H;
         const int ns = NB_OUT + Ha + H;                            // samples the K loop reads
+        auto split_store = [&](const float (&v)[8], u32x4* dst) {  // 8 channels of a sample -> its unit in every piece plane
+          if constexpr (NP == 3) {
+            u32x4 h, m, l;
+            bf16x6_split(v, h, m, l);
+            dst[0] = h;
+            dst[NB_PLANE] = m;
+            dst[2 * NB_PLANE] = l;
+          } else {
+            u32x4 h, m;
+            bf16x3_split(v, h, m);
+            dst[0] = h;
+            dst[NB_PLANE] = m;
+          }
+        };
         if (VEC) {
           // item = (octet, 4 consecutive samples): 8 x 16 bytes from the octet's 8 rows (a wave-load is 1 KB of one row)
           const int o = tid / (NB_NSP / 4), qd = tid - o * (NB_NSP / 4);
@@ -121,11 +140,7 @@ void narrow_bf_kernel(const fh_amp_group* __restrict__ groups, const fh_amp_tile
               float v[8];
 #pragma unroll
               for (int c = 0; c < 8; ++c) v[c] = __uint_as_float(xq[c][e]);
-              u32x4 h, m, l;
-              bf16x6_split(v, h, m, l);
-              dst[e] = h;
-              dst[NB_PLANE + e] = m;
-              dst[2 * NB_PLANE + e] = l;
+              split_store(v, dst + e);
             }
           }
         } else {
@@ -136,12 +151,7 @@ void narrow_bf_kernel(const fh_amp_group* __restrict__ groups, const fh_amp_tile
 #pragma unroll
             for (int c = 0; c < 8; ++c)
               v[c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, in ? (unsigned)((8 * (ob + o) + c) * len + t) * 4u : 0x80000000u, 0, 0));
-            u32x4 h, m, l;
-            bf16x6_split(v, h, m, l);
-            u32x4* const dst = slab + o * NB_NSP + s;
-            dst[0] = h;
-            dst[NB_PLANE] = m;
-            dst[2 * NB_PLANE] = l;
+            split_store(v, slab + o * NB_NSP + s);
           };
           for (int o = 0; o < og; ++o) {
             stage(o, tid);
@@ -161,14 +171,14 @@ void narrow_bf_kernel(const fh_amp_group* __restrict__ groups, const fh_amp_tile
           const u32x4* const ap = slab + o * NB_NSP + (Ha - H) + tap * d + wv * (16 * NB_NM) + li;
 #pragma unroll
           for (int mp = 0; mp < NB_NM; mp += 2) {
-            bf16x8 a[2][3];
+            bf16x8 a[2][NP];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-              for (int p = 0; p < 3; ++p) a[i][p] = __builtin_bit_cast(bf16x8, ap[(mp + i) * 16 + p * NB_PLANE]);
+              for (int p = 0; p < NP; ++p) a[i][p] = __builtin_bit_cast(bf16x8, ap[(mp + i) * 16 + p * NB_PLANE]);
 #pragma unroll
-            for (int pp = 0; pp < 6; ++pp) {
-              const Bf16x6Pair s = kBf16x6SmallFirst[pp];            // (sample piece, weight piece)
+            for (int pp = 0; pp < bf16_n_pairs<NP>(); ++pp) {
+              const Bf16x6Pair s = bf16_small_first<NP>(pp);         // (sample piece, weight piece)
 #pragma unroll
               for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -182,7 +192,7 @@ void narrow_bf_kernel(const fh_amp_group* __restrict__ groups, const fh_amp_tile
           step(0, kb);
           if (kb + 1 < nb) step(1, kb + 1);
         }
-        wbase += nb * MA * 3;
+        wbase += nb * MA * NP;
         ob += og;
       }
     }
@@ -237,31 +247,61 @@ void narrow_bf_kernel(const fh_amp_group* __restrict__ groups, const fh_amp_tile
   }
 }
 
-template <int MA, bool VEC>
+// the entry's name, for its messages
+template <int NP>
+constexpr const char* narrow_name() {
+  return NP == 3 ? "fh_narrow_conv_bf16x6_f32" : "fh_narrow_conv_bf16x3_f32";
+}
+
+template <int NP, int MA, bool VEC>
 int launch_narrow(const fh_amp_group* groups, const fh_amp_tile* tiles, int channels, int dilation, int total_tiles, hipStream_t stream) {
   static std::atomic<int> blocks_per_launch[FH_MAX_DEVICES];      // 0 = not asked yet; else resident blocks of the device
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= FH_MAX_DEVICES) {
-    fh_set_error("fh_narrow_conv_bf16x6_f32: no current HIP device (or ordinal >= %d)", FH_MAX_DEVICES);
+    fh_set_error("%s: no current HIP device (or ordinal >= %d)", narrow_name<NP>(), FH_MAX_DEVICES);
     return FH_E_LAUNCH;
   }
   int resident = blocks_per_launch[dev].load(std::memory_order_acquire);
   if (!resident) {
     int per_cu = 0, cus = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)narrow_bf_kernel<MA, VEC>, NB_THREADS, 0);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)narrow_bf_kernel<NP, MA, VEC>, NB_THREADS, 0);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess || cus <= 0 || per_cu <= 0) {
-      fh_set_error("fh_narrow_conv_bf16x6_f32: occupancy query failed on device %d: %s", dev, hipGetErrorString(e));
+      fh_set_error("%s: occupancy query failed on device %d: %s", narrow_name<NP>(), dev, hipGetErrorString(e));
       return FH_E_LAUNCH;
     }
     resident = per_cu * cus;
     blocks_per_launch[dev].store(resident, std::memory_order_release);
   }
   const int grid = total_tiles < resident ? total_tiles : resident;
-  hipLaunchKernelGGL((narrow_bf_kernel<MA, VEC>), dim3((unsigned)grid), dim3(NB_THREADS), 0, stream, groups, tiles, channels, dilation,
+  hipLaunchKernelGGL((narrow_bf_kernel<NP, MA, VEC>), dim3((unsigned)grid), dim3(NB_THREADS), 0, stream, groups, tiles, channels, dilation,
                      total_tiles);
-  FH_CHECK_LAUNCH("fh_narrow_conv_bf16x6_f32");
+  FH_CHECK_LAUNCH(narrow_name<NP>());
   return FH_OK;
+}
+
+template <int NP>
+int narrow_conv_bf(const fh_amp_group* groups, int n_groups, const fh_amp_tile* tiles, int total_tiles, int channels, int dilation, int flags,
+                   void* stream) {
+  constexpr const char* name = narrow_name<NP>();
+  FH_CHECK_ARG(groups && n_groups > 0 && tiles && total_tiles > 0, "%s: bad sizes", name);
+  FH_CHECK_ARG(channels >= 8 && channels <= 48 && channels % 8 == 0, "%s: %d channels (8 .. 48, a multiple of 8)", name, channels);
+  FH_CHECK_ARG(dilation >= 1 && dilation <= NB_MAX_D, "%s: dilation %d (1 .. %d)", name, dilation, NB_MAX_D);
+  FH_CHECK_ARG(flags == 0 || flags == 1, "%s: flags %d (bit 0: rows 16-byte aligned)", name, flags);
+  const int ma = (channels + 15) / 16;
+  const bool vec = flags & 1;
+  hipStream_t st = (hipStream_t)stream;
+#define FH_NB_CASE(MA)                                                                                  \
+  case MA:                                                                                              \
+    return vec ? launch_narrow<NP, MA, true>(groups, tiles, channels, dilation, total_tiles, st)        \
+               : launch_narrow<NP, MA, false>(groups, tiles, channels, dilation, total_tiles, st);
+  switch (ma) {
+    FH_NB_CASE(1)
+    FH_NB_CASE(2)
+    FH_NB_CASE(3)
+  }
+#undef FH_NB_CASE
+  return FH_E_ARG;
 }
 
 }  // namespace
@@ -270,23 +310,11 @@ extern "C" int fh_narrow_tile_len(void) { return NB_OUT; }
 
 extern "C" int fh_narrow_conv_bf16x6_f32(const fh_amp_group* groups, int n_groups, const fh_amp_tile* tiles, int total_tiles, int channels,
                                          int dilation, int flags, void* stream) {
-  FH_CHECK_ARG(groups && n_groups > 0 && tiles && total_tiles > 0, "fh_narrow_conv_bf16x6_f32: bad sizes");
-  FH_CHECK_ARG(channels >= 8 && channels <= 48 && channels % 8 == 0, "fh_narrow_conv_bf16x6_f32: %d channels (8 .. 48, a multiple of 8)",
-               channels);
-  FH_CHECK_ARG(dilation >= 1 && dilation <= NB_MAX_D, "fh_narrow_conv_bf16x6_f32: dilation %d (1 .. %d)", dilation, NB_MAX_D);
-  FH_CHECK_ARG(flags == 0 || flags == 1, "fh_narrow_conv_bf16x6_f32: flags %d (bit 0: rows 16-byte aligned)", flags);
-  const int ma = (channels + 15) / 16;
-  const bool vec = flags & 1;
-  hipStream_t st = (hipStream_t)stream;
-#define FH_NB_CASE(MA)                                                                              \
-  case MA:                                                                                          \
-    return vec ? launch_narrow<MA, true>(groups, tiles, channels, dilation, total_tiles, st)        \
-               : launch_narrow<MA, false>(groups, tiles, channels, dilation, total_tiles, st);
-  switch (ma) {
-    FH_NB_CASE(1)
-    FH_NB_CASE(2)
-    FH_NB_CASE(3)
-  }
-#undef FH_NB_CASE
-  return FH_E_ARG;
+  return narrow_conv_bf<3>(groups, n_groups, tiles, total_tiles, channels, dilation, flags, stream);
+}
+
+// The same launches with two pieces per operand and three pairs (conv_form = 'direct_bf16x3'; weights: packing.pack_narrow_bf3_weight)
+extern "C" int fh_narrow_conv_bf16x3_f32(const fh_amp_group* groups, int n_groups, const fh_amp_tile* tiles, int total_tiles, int channels,
+                                         int dilation, int flags, void* stream) {
+  return narrow_conv_bf<2>(groups, n_groups, tiles, total_tiles, channels, dilation, flags, stream);
 }

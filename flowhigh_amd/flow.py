@@ -63,7 +63,7 @@ class FlowNet:
         g = lambda name: sd[FH + name].detach().float().cpu()
         self.depth, self.heads = depth, heads
         # bf: the linears run in the bf16 x 6 form (gemm_bf.hip: six bf16 MFMAs per product over exact three-piece splits,
-        # fp32-grade; the model's conv_form = 'bf16x6' or 'direct_bf16x6'): their weights are stored split (6 bytes per weight)
+        # fp32-grade; the model's conv_form = 'bf16x6', 'direct_bf16x6' or 'direct_bf16x3'): their weights are stored split (6 bytes per weight)
         self.bf = bool(bf)
         # attn_form: 'f32' (attention.hip) | 'bf16x6' (attention_bf.hip: the two products of attention in the same six-MFMA form,
         # the softmax unchanged).  The entry pair is picked here, once; a missing entry is an error at the first forward.

@@ -348,7 +348,9 @@ class GraphedGenerate:
 
 class FLowHigh:
     """Device-resident weights of the vector-field net + its mel codec (the reference's
-    `FLowHigh` with `audio_enc_dec = MelVoco`, models/flow.py:54-142, models/melvoco.py:16-46)."""
+    `FLowHigh` with `audio_enc_dec = MelVoco`, models/flow.py:54-142, models/melvoco.py:16-46).
+    conv_form: 'auto' | 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6' | 'direct_bf16x3' (planner.resolve_conv_form; the last one
+    is the Winograd-free plan on two bf16 pieces per operand: at most 3 2^-16 per product, not fp32-grade, never chosen by 'auto')."""
 
     def __init__(self, state_dict, vocoder_config, device="cuda", depth=2, conv_bf16x6=None, store=None, conv_form=None,
                  attn_form=None, attn_window=None, architecture=None):
@@ -401,7 +403,7 @@ class FLowHigh:
                 self.net = ConvNextNet(state_dict, device, bf=bf)
             else:
                 self.net = FlowNet(state_dict, device, depth=depth, store=store, bf=bf, attn_form=attn_form, attn_window=attn_window)
-            # conv_form: the arithmetic form of the vocoder's convs, 'auto' | 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6'
+            # conv_form: the arithmetic form of the vocoder's convs, 'auto' | 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6' | 'direct_bf16x3'
             # (planner.resolve_conv_form; None: FH_CONV_FORM / the older switches, else 'auto'.  conv_bf16x6: the boolean keyword
             # of rounds 2-5.)  'auto' = the default form, checked once against the direct form through THESE weights when the
             # checkpoint is at hand (probe_conv_form below): a model whose weights amplify the Winograd transforms' rounding is
@@ -517,7 +519,7 @@ class FlowHighSR:
     @classmethod
     def from_local(cls, ckpt_dir, device='cuda', conv_form=None, attn_form=None, attn_window=None, architecture=None,
                    **kwargs) -> 'FlowHighSR':
-        """from_local of the reference (flowhighsr.py:110-137) + conv_form = 'auto' (default) | 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6': the
+        """from_local of the reference (flowhighsr.py:110-137) + conv_form = 'auto' (default) | 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6' | 'direct_bf16x3': the
         arithmetic form of the vocoder's convs (planner.resolve_conv_form; the environment's
         FH_CONV_FORM overrides nothing a caller passes here); attn_form = None | 'f32' (default) | 'bf16x6': the form of the two
         products of attention (planner.resolve_attn_form; no part of a weight blob); attn_window = None (default: full attention, as
@@ -572,7 +574,8 @@ class FlowHighSR:
     @classmethod
     def from_pretrained(cls, device='cuda', conv_form=None, attn_form=None, attn_window=None, architecture=None,
                         **kwargs) -> 'FlowHighSR':
-        """from_local on the published checkpoint.  attn_window = None (full attention) | W >= 0 frames of 10 ms (from_local)."""
+        """from_local on the published checkpoint.  conv_form = 'auto' (default) | 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6' |
+        'direct_bf16x3' (from_local).  attn_window = None (full attention) | W >= 0 frames of 10 ms (from_local)."""
         from .planner import resolve_attn_window
         attn_window = resolve_attn_window(attn_window)          # (a wrong keyword is a ValueError before anything is fetched)
         from huggingface_hub import hf_hub_download

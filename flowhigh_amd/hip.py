@@ -110,6 +110,7 @@ _SIGS = {
     "fh_conv_grouped_f32": [_P, _I, _I, _I, _I, _I, _I, _P],
     "fh_conv_transpose_fused_f32": [_P, _I, _I, _I, _I, _I, _I, _P],
     "fh_conv_grouped_bf16x6_f32": [_P, _I, _I, _I, _I, _I, _P],
+    "fh_conv_grouped_bf16x3_f32": [_P, _I, _I, _I, _I, _I, _P],
     "fh_sizeof_wino_group": [],
     "fh_wino_tile_m": [_I],
     "fh_phase_len": [_I, _I],
@@ -139,6 +140,7 @@ _SIGS = {
     "fh_amp_actconv_f32": [_P, _I, _P, _I, _I, _I, _I, _I, _P],
     "fh_narrow_tile_len": [],
     "fh_narrow_conv_bf16x6_f32": [_P, _I, _P, _I, _I, _I, _I, _P],
+    "fh_narrow_conv_bf16x3_f32": [_P, _I, _P, _I, _I, _I, _I, _P],
     "fh_sizeof_sum_job": [],
     "fh_sum_multi_f32": [_P, _I, C.c_longlong, _P],
     "fh_attention_seg_f32": [_P, _P, _P, _I, _I, _I, _F, _P],

@@ -165,11 +165,12 @@ def narrow_slabs(channels):
     return out
 
 
-def pack_narrow_bf_weight(w, channels=None):
+def pack_narrow_bf_weight(w, channels=None, pieces=3):
     """Conv1d weight [co, ci, k] (co, ci <= channels <= 48, channels % 8 == 0, k <= 11) -> the bf16 x 6 narrow-stage kernel's
     weights (narrow_bf.hip, flowhigh_hip.h: fh_narrow_conv_bf16x6_f32): float32 container of bf16 bit patterns,
     per slab (narrow_slabs) ceil(k og / 4) k-blocks x [N tile][piece h, m, l][64 lanes][8 bf16]; lane l of k-block kb holds
-    w[16 n + (l & 15), 8 (ob + o) + 0 .. 7, tap] for the pair q = 4 kb + (l >> 4) = tap og + o, zero past k og / past the channels."""
+    w[16 n + (l & 15), 8 (ob + o) + 0 .. 7, tap] for the pair q = 4 kb + (l >> 4) = tap og + o, zero past k og / past the channels.
+    pieces: how many of the split's pieces are stored (2: pack_narrow_bf3_weight)."""
     co, ci, k = w.shape
     c = max(co, ci) if channels is None else channels
     if c % 8 or c > 48 or co > c or ci > c or k > 11:
@@ -186,9 +187,14 @@ def pack_narrow_bf_weight(w, channels=None):
         full[:, :k * og] = blk
         # [na, n, kb, lg, e] -> [kb, na, lane = 16 lg + n, e]
         full = full.view(ma, 16, nb, 4, 8).permute(2, 0, 3, 1, 4).reshape(nb, ma, 64, 8)
-        h, m, l = split_pieces(full)
-        parts.append(torch.stack([h, m, l], dim=2).contiguous().view(torch.int16).reshape(-1))      # [kb, na, piece, lane, 8]
+        parts.append(torch.stack(split_pieces(full)[:pieces], dim=2).contiguous().view(torch.int16).reshape(-1))      # [kb, na, piece, lane, 8]
     return torch.cat(parts).contiguous().view(torch.float32)
+
+
+def pack_narrow_bf3_weight(w, channels=None):
+    """pack_narrow_bf_weight with the first two pieces only, [k-block][N tile][piece h, m][64 lanes][8 bf16]: the bf16 x 3
+    narrow-stage weights (narrow_bf.hip with two pieces, flowhigh_hip.h: fh_narrow_conv_bf16x3_f32; conv_form = 'direct_bf16x3')."""
+    return pack_narrow_bf_weight(w, channels, pieces=2)
 
 
 def split_bf3(u):
@@ -202,6 +208,15 @@ def pack_conv_bf_weight(w, cout_pad):
     fh_conv_grouped_bf16x6_f32): int16 bf16 bit patterns [ci/16, k, cout_pad, piece h, m, l, 16] -- pack_conv_weight(w, cout_pad, 16)
     with every row of 16 channels split into its three pieces (the row format of the Winograd bf16 x 6 weights)."""
     return split_bf3(pack_conv_weight(w, cout_pad, 16))
+
+
+def pack_conv_bf3_weight(w, cout_pad):
+    """Conv1d weight [co, ci, k] (ci % 16 == 0) -> the bf16 x 3 direct kernel's weights (conv_mfma_bf.hip with two pieces,
+    flowhigh_hip.h: fh_conv_grouped_bf16x3_f32; conv_form = 'direct_bf16x3'): int16 bf16 bit patterns [ci/16, k, cout_pad, piece h, m, 16]
+    -- the first two pieces of pack_conv_bf_weight's rows (split_pieces(.)[:2]: the second piece of a two-piece split is the
+    three-piece split's m), as 64-byte rows: the kernel fetches no third piece it would not use."""
+    h, m = split_pieces(pack_conv_weight(w, cout_pad, 16))[:2]
+    return torch.stack([h, m], dim=-2).contiguous().view(torch.int16)
 
 
 def pack_wino_weight_any(w, cout_pad, bf):

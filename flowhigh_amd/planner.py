@@ -46,17 +46,24 @@ def wino_ups_min_cin(form):
 #               'bf16x6' (conv_mfma_bf.hip: every conv / closing-conv / unfused-upsampler launch whose segments have cin % 16 == 0),
 #               the narrow stages on narrow_bf.hip and the transformer's linears on gemm_bf.hip as in 'bf16x6'; no Winograd
 #               rounding anywhere; the phase-fused stride-2 upsamplers (0.6 % of the FLOPs) and 8-channel chunks stay on fp32 MFMA
+#   'direct_bf16x3'  the launch plan of 'direct_bf16x6', position for position, with TWO bf16 pieces per operand (h = bf16(x),
+#               m = bf16(x - h)) and the THREE pairs m h, h m, h h per product (fh_conv_grouped_bf16x3_f32 / fh_narrow_conv_bf16x3_f32:
+#               the same kernel bodies): half the MFMAs, two thirds of the LDS reads, weight bytes and slab.  NOT fp32-grade: the
+#               dropped terms are <= 3 2^-16 of a product (csrc/bf16x6.h), 2-3e-5 on the waveform (inside the 1e-4 bar; profiles/direct_bf16x3.md).
+#               The phase-fused upsamplers, 8-channel chunks, activations and the transformer's linears (six-pair gemm_bf.hip) run as
+#               in 'direct_bf16x6'.  Never chosen by 'auto'.
 #   'auto'      DEFAULT_CONV_FORM, unless a load-time probe through the loaded weights (Vocoder.probe_conv_form: the default
 #               form against the direct form on a 20-frame random mel) differs by more than PROBE_LIMIT: then 'direct'
 # Keyword > environment (FH_CONV_FORM; the older switches FH_WINO=0 -> direct, FH_CONV_BF16X6=1 / 0 -> bf16x6 / winograd) > 'auto'.
-CONV_FORMS = ("auto", "winograd", "bf16x6", "direct", "direct_bf16x6")
-DIRECT_FORMS = ("direct", "direct_bf16x6")          # the forms without Winograd kernels
+CONV_FORMS = ("auto", "winograd", "bf16x6", "direct", "direct_bf16x6", "direct_bf16x3")
+DIRECT_FORMS = ("direct", "direct_bf16x6", "direct_bf16x3")          # the forms without Winograd kernels
+DIRECT_BF_FORMS = ("direct_bf16x6", "direct_bf16x3")                # ... whose direct convs run on the BF16 matrix cores
 DEFAULT_CONV_FORM = "bf16x6"
 PROBE_LIMIT = 3e-5
 
 
 def resolve_conv_form(conv_form=None, bf16x6=None):
-    """-> (form, from_auto): one of 'winograd' / 'bf16x6' / 'direct' / 'direct_bf16x6', and whether it came from 'auto' (a probe may still change
+    """-> (form, from_auto): one of 'winograd' / 'bf16x6' / 'direct' / 'direct_bf16x6' / 'direct_bf16x3', and whether it came from 'auto' (a probe may still change
     it).  conv_form: the keyword (None: ask the environment); bf16x6: the older boolean keyword (True / False / None)."""
     form = conv_form
     if form is None and bf16x6 is not None:
@@ -108,7 +115,7 @@ def resolve_attn_window(attn_window=None):
 
 
 def _wino_on(form):
-    """Winograd kernels allowed?  form None: the environment (FH_WINO=0 / FH_CONV_FORM=direct / direct_bf16x6 switch them off)."""
+    """Winograd kernels allowed?  form None: the environment (FH_WINO=0 / FH_CONV_FORM=direct / direct_bf16x6 / direct_bf16x3 switch them off)."""
     return (resolve_conv_form()[0] if form is None else form) not in DIRECT_FORMS
 
 
@@ -117,6 +124,18 @@ def use_direct_bf16x6(form=None):
     segment's input channels are a multiple of 16: conv_form='direct_bf16x6'.  Per conv POSITION (channel counts), never per length
     or batch: a clip gets the same bits alone, batched, ragged, chunked."""
     return (resolve_conv_form()[0] if form is None else form) == "direct_bf16x6"
+
+
+def use_direct_bf16x3(form=None):
+    """... in the bf16 x 3 form (the same kernel with two pieces per operand, fh_conv_grouped_bf16x3_f32) at the same positions:
+    conv_form='direct_bf16x3'.  The narrow stages of such a model run fh_narrow_conv_bf16x3_f32."""
+    return (resolve_conv_form()[0] if form is None else form) == "direct_bf16x3"
+
+
+def direct_bf_pieces(form=None):
+    """What a conv step record's `bf` field holds for the 16-channel-chunk direct convs of a model of `form`: 0 = the fp32 entry,
+    1 = fh_conv_grouped_bf16x6_f32 (three pieces, six pairs), 2 = fh_conv_grouped_bf16x3_f32 (two pieces, three pairs)."""
+    return 1 if use_direct_bf16x6(form) else 2 if use_direct_bf16x3(form) else 0
 
 
 def use_wino(c, d, form=None):
@@ -337,7 +356,8 @@ def use_amp(c, ks, dils, form=None):
     a launch of its own): at most 48 channels (a multiple of 8), odd kernels of at most 11 taps, dilations of at most 6.
     A property of the STAGE (channel count and checkpoint configuration), never of the length or the batch.  FH_AMP=0 switches
     it off (those stages then run as in round 4: F(5,4) 48-row blocks / the direct kernel).  conv_form='direct' has no narrow-stage
-    kernel (amp_fused.hip is a Winograd kernel); 'direct_bf16x6' runs these stages on narrow_bf.hip, a direct conv (use_amp_bf16x6)."""
+    kernel (amp_fused.hip is a Winograd kernel); 'direct_bf16x6' and 'direct_bf16x3' run these stages on narrow_bf.hip, a direct conv
+    (use_amp_bf16x6)."""
     form = resolve_conv_form()[0] if form is None else form
     if os.environ.get("FH_AMP", "1") == "0" or form == "direct":
         return False
@@ -372,8 +392,8 @@ def use_gemm_bf16x6(form=None):
     """The transformer's linears of a bf16 x 6 model run in the bf16 x 6 form too (gemm_bf.hip; flow.FlowNet(bf=)).  (The A/B
     against the fp32 GEMM inside a bf16 x 6 model -- 12.89 against 13.02 ms per step, configs[4] 632 against 593 x real time --
     was run with an environment switch that left with the measurement; conv_form='winograd' is the fp32 path.)  So do those of a
-    'direct_bf16x6' model."""
-    return (resolve_conv_form()[0] if form is None else form) in ("bf16x6", "direct_bf16x6")
+    'direct_bf16x6' or 'direct_bf16x3' model (both in the six-pair form: the two-piece form is for the vocoder's direct convs only)."""
+    return (resolve_conv_form()[0] if form is None else form) in ("bf16x6",) + DIRECT_BF_FORMS
 
 
 def amp_tile_len(d):
@@ -383,6 +403,7 @@ def amp_tile_len(d):
 
 AMP_MAX_D = 6             # F_MAX_D of amp_fused.hip
 AMP_DIRECT = 4            # plan flag of a narrow-stage launch: the direct bf16 x 6 form (fh_narrow_conv_bf16x6_f32, narrow_bf.hip)
+AMP_BF16X3 = 8            # ... beside AMP_DIRECT: its two-piece form (fh_narrow_conv_bf16x3_f32; conv_form='direct_bf16x3')
 NARROW_TILE = 256         # fh_narrow_tile_len(): outputs per block and row of that form, any dilation
 
 
@@ -390,8 +411,8 @@ def use_amp_bf16x6(form=None):
     """Narrow stages of a bf16 x 6 model run the direct bf16 x 6 kernel (narrow_bf.hip) instead of the fp32-MFMA Winograd one
     (amp_fused.hip, the narrow-stage kernel of conv_form='winograd').  (A/B inside a bf16 x 6 model: same speed, five times
     closer to float64 -- profiles/r06_narrow_bf16x6.txt; the switch it was run with left with the measurement.)  The narrow stages
-    of a 'direct_bf16x6' model run the same kernel."""
-    return (resolve_conv_form()[0] if form is None else form) in ("bf16x6", "direct_bf16x6")
+    of a 'direct_bf16x6' model run the same kernel, those of a 'direct_bf16x3' model its two-piece form (plan flag AMP_BF16X3)."""
+    return (resolve_conv_form()[0] if form is None else form) in ("bf16x6",) + DIRECT_BF_FORMS
 
 
 def make_amp_seg(x, u, k, center=None, direct=False):
@@ -585,7 +606,8 @@ def make_wino_group(segs, bias, res, out, cout, cpad, length, scale=1.0, stride=
 # the launch's arguments in the order below (desc: the uploaded descriptor array, its host structs are in meta; flops: algorithmic).
 # They stay tuples: hip.ShapeCache sizes a plan by walking tuples / lists / dicts (a slotted object's tensors would not be counted) ---
 STEP_TYPES = {kind: NamedTuple(kind.capitalize() + "Step", [(f, object) for f in ["kind"] + fields.split()]) for kind, fields in dict(
-    # (bf: the bf16 x 6 entry, fh_conv_grouped_bf16x6_f32, on three-piece weights; ck is 16 then)
+    # (bf: 1 = the bf16 x 6 entry, fh_conv_grouped_bf16x6_f32, on three-piece weights; 2 = the bf16 x 3 entry, fh_conv_grouped_bf16x3_f32,
+    # on two-piece weights; ck is 16 then -- direct_bf_pieces)
     conv="desc ng cpad n_len tcfg ck flops bf",
     convt="desc ng cpad n_len tcfg phases flops",
     # (wcfg: plan tile id | WINO_XCD_RANGES | WINO_NOVL; pm: phase-major rows; batch: 1 where the groups are per batch item)
@@ -660,8 +682,9 @@ class _PlanBuilder:
     # ---- one launch each ----------------------------------------------------------------------------------------
     def conv(self, groups, cpad, n_len, tcfg, ck, bf=False):
         """Direct-kernel launch.  Few-block launches (first-stage upsampler, fused stage-closing conv at short
-        sequence lengths) switch from the 128 x 128 to the 128 x 64 tile to fill the 256 CUs.  bf: the groups' weights are
-        pack_conv_bf_weight's, the launch runs the bf16 x 6 entry (same tiles, same descriptors)."""
+        sequence lengths) switch from the 128 x 128 to the 128 x 64 tile to fill the 256 CUs.  bf = 1: the groups' weights are
+        pack_conv_bf_weight's, the launch runs the bf16 x 6 entry (same tiles, same descriptors); bf = 2: pack_conv_bf3_weight's and
+        the bf16 x 3 entry."""
         if tcfg == 0 and len(groups) * self.B * (cpad // 128) * -(-n_len // 128) < 512:
             tcfg = 5
         if bf and (ck != 16 or any(s.cin % 16 for _, s in _segs(*groups))):
@@ -678,7 +701,7 @@ class _PlanBuilder:
         flops = sum(2.0 * g.cout * s.cin * s.ntaps * n_len * self.B for g, s in _segs(*groups))
         self.executed += flops
         self.direct += flops
-        self.conv_launches.append(("direct_bf16x6" if bf else "direct", flops, flops))
+        self.conv_launches.append((("direct", "direct_bf16x6", "direct_bf16x3")[int(bf)], flops, flops))
         tail = (int(bf),) if kind == "conv" else ()
         self.add(make_step(kind, self.upload(groups), len(groups), cpad, n_len, tcfg, ck_or_phases, flops, *tail), groups)
 
@@ -706,9 +729,10 @@ class _PlanBuilder:
 
     def amp(self, groups, c, length, dil):
         """Narrow-stage launch: the groups' convs (fh_amp_actconv_f32; the model's narrow stages in the direct bf16 x 6 form:
-        fh_narrow_conv_bf16x6_f32, plan flag AMP_DIRECT)."""
+        fh_narrow_conv_bf16x6_f32, plan flag AMP_DIRECT; its two-piece form, fh_narrow_conv_bf16x3_f32: AMP_DIRECT | AMP_BF16X3)."""
         B = self.B
         direct = self.v.amp_direct
+        bf3 = AMP_BF16X3 if direct and self.v.direct_bf == 2 else 0
         d = self.upload(groups)
         tiles = amp_tile_list([g.len for g in groups], B, dil, direct=direct).to(self.v.device)
         self.keep.append(tiles)
@@ -716,8 +740,8 @@ class _PlanBuilder:
         # executed: Winograd F(5,4) 1.6 ceil(k / 4) multiply-adds per output; direct: the taps themselves
         ex = flops if direct else sum(2.0 * c * c * 1.6 * s.ngrp * length * B for _, s in _segs(*groups))
         self.executed += ex
-        self.conv_launches.append(("narrow_bf16x6" if direct else "amp", ex, flops))
-        flags = int(all(g.len % 4 == 0 for g in groups)) | (AMP_DIRECT if direct else 2)
+        self.conv_launches.append((("narrow_bf16x3" if bf3 else "narrow_bf16x6") if direct else "amp", ex, flops))
+        flags = int(all(g.len % 4 == 0 for g in groups)) | (AMP_DIRECT if direct else 2) | bf3
         self.add(make_step("amp", d, len(groups), tiles, tiles.shape[0], c, dil, amp_max_center(groups, direct), flags, flops), groups)
 
     def act(self, groups, c, length, din=1, dout=1):
@@ -1086,7 +1110,7 @@ def _merge_convt(voc, items, blobs):
 
 
 def _merge_amp(voc, items, blobs):
-    for (c, dil, form_bits), lst in _classes(items, lambda s: (s.c, s.dil, s.flags & (2 | AMP_DIRECT))):
+    for (c, dil, form_bits), lst in _classes(items, lambda s: (s.c, s.dil, s.flags & (2 | AMP_DIRECT | AMP_BF16X3))):
         allg = [g for _, groups in lst for g in groups]
         direct = bool(form_bits & AMP_DIRECT)
         # heavy groups first (the persistent blocks walk the tile list in order), then long ones

@@ -8,15 +8,17 @@ import os
 import torch
 
 from . import hip
-from .planner import (AMP_DIRECT, WINO_BF16X6, WINO_F54, WINO_FRAG_ORDER, WINO_NOVL, act_ragged_groups, amp_max_center, amp_tile_list, make_act_group,
+from .planner import (AMP_BF16X3, AMP_DIRECT, WINO_BF16X6, WINO_F54, WINO_FRAG_ORDER, WINO_NOVL, act_ragged_groups, amp_max_center, amp_tile_list, make_act_group,
                       make_wino_group, make_wino_seg, pick_wino54_tile, pick_wino_tile, use_wino54, wino_packer, wino_run_map, wino_weight_flags)
 
-def amp_actconv(groups, batch, channels, dilation, device, direct=False):
+def amp_actconv(groups, batch, channels, dilation, device, direct=False, bf3=False):
     """Upload descriptors and enqueue one narrow-stage launch (test / one-off use).  direct: the bf16 x 6 form (groups made with
-    make_amp_seg / make_amp_group(..., direct=True), weights from pack_narrow_bf_weight)."""
+    make_amp_seg / make_amp_group(..., direct=True), weights from pack_narrow_bf_weight); bf3 beside it: the bf16 x 3 form
+    (fh_narrow_conv_bf16x3_f32, weights from pack_narrow_bf3_weight)."""
     tiles = amp_tile_list([g.len for g in groups], batch, dilation, direct=direct).to(device)
     d = hip.to_device_struct_array(groups, device)
-    name, tail = narrow_entry(int(all(g.len % 4 == 0 for g in groups)) | (AMP_DIRECT if direct else 2), amp_max_center(groups, direct))
+    name, tail = narrow_entry(int(all(g.len % 4 == 0 for g in groups)) | (AMP_DIRECT if direct else 2) | (AMP_BF16X3 if direct and bf3 else 0),
+                              amp_max_center(groups, direct))
     enqueue(getattr(hip.lib(), name), (d.data_ptr(), len(groups), tiles.data_ptr(), tiles.shape[0], channels, dilation, *tail, hip.stream()))
     return d, tiles
 
@@ -52,8 +54,8 @@ def conv_wino_ragged(groups, lengths, cout_pad, dilation, device, tile_cfg=0, ph
 
 
 def conv_grouped(groups, batch, cout_pad, n_len, tile_cfg, device, ck=8, bf=False):
-    """Upload descriptors and enqueue one grouped conv launch (test / one-off use).  bf: the bf16 x 6 entry (the groups' weights
-    are pack_conv_bf_weight's; every cin a multiple of 16)."""
+    """Upload descriptors and enqueue one grouped conv launch (test / one-off use).  bf: 1 / True = the bf16 x 6 entry (the groups' weights
+    are pack_conv_bf_weight's; every cin a multiple of 16), 2 = the bf16 x 3 entry (pack_conv_bf3_weight's)."""
     d = hip.to_device_struct_array(groups, device)
     name, tail = conv_entry(bf, ck)
     enqueue(getattr(hip.lib(), name), (d.data_ptr(), len(groups), batch, cout_pad, n_len, tile_cfg, *tail, hip.stream()))
@@ -268,13 +270,16 @@ def wino_entry(wcfg, flag, ragged=False):
 
 
 def conv_entry(bf, ck):
-    """(library entry's name, its arguments behind tile_cfg) of a direct-kernel launch: the bf16 x 6 entry takes no channel chunk."""
-    return ("fh_conv_grouped_bf16x6_f32", ()) if bf else ("fh_conv_grouped_f32", (ck,))
+    """(library entry's name, its arguments behind tile_cfg) of a direct-kernel launch whose record has `bf` (planner.direct_bf_pieces:
+    0 fp32, 1 bf16 x 6, 2 bf16 x 3): the bf16 entries take no channel chunk."""
+    return (("fh_conv_grouped_bf16x3_f32" if bf == 2 else "fh_conv_grouped_bf16x6_f32"), ()) if bf else ("fh_conv_grouped_f32", (ck,))
 
 
 def narrow_entry(flags, cmax):
     """(library entry's name, its arguments behind the dilation) of a narrow-stage launch with plan flags `flags`."""
-    return ("fh_narrow_conv_bf16x6_f32", (flags & 1,)) if flags & AMP_DIRECT else ("fh_amp_actconv_f32", (cmax, flags))
+    if flags & AMP_DIRECT:
+        return ("fh_narrow_conv_bf16x3_f32" if flags & AMP_BF16X3 else "fh_narrow_conv_bf16x6_f32"), (flags & 1,)
+    return "fh_amp_actconv_f32", (cmax, flags)
 
 
 def enqueue(fn, args, timing=None):

@@ -24,7 +24,7 @@ import torch
 
 from . import hip
 from .packing import (  # noqa: F401
-    _WINO54_G, _WINO_G, fold_weight_norm, from_phase_major, pack_amp_weight, pack_conv_bf_weight, pack_conv_weight, pack_narrow_bf_weight,
+    _WINO54_G, _WINO_G, fold_weight_norm, from_phase_major, pack_amp_weight, pack_conv_bf3_weight, pack_conv_bf_weight, pack_conv_weight, pack_narrow_bf3_weight, pack_narrow_bf_weight,
     frag_order, pack_wino54_weight, pack_wino54_weight_any, pack_wino54_weight_frag, pack_wino_weight, pack_wino_weight_any, phase_len, pick_ck, split_bf3, to_phase_major,
     transposed_conv_extra, transposed_conv_phases, wino_phase_weight)
 from .planner import (  # noqa: F401
@@ -33,7 +33,7 @@ from .planner import (  # noqa: F401
     _WINO_TILES, _WINO_TILES_OFF, _WINO_WIDE_PANEL_MAX, _addr, _choose_wino_cfg, act_ragged_groups, amp_max_center,
     amp_tile_len, amp_tile_list, choose_wino_cfg, make_act_group, make_amp_group, make_amp_seg, make_conv_group,
     make_conv_seg, make_wino_group, make_wino_seg, merge_ragged, pick_tile_cfg, pick_wino54_tile,
-    pick_wino_tile, plan_switches, resolve_conv_form, ups_fused_ok, use_amp, use_amp_bf16x6, use_bf16x6, use_direct_bf16x6, wino_ups_min_cin, use_wino, use_wino54, wino_block_mapping,
+    direct_bf_pieces, pick_wino_tile, plan_switches, resolve_conv_form, ups_fused_ok, use_amp, use_amp_bf16x6, use_bf16x6, use_direct_bf16x6, wino_ups_min_cin, use_wino, use_wino54, wino_block_mapping,
     wino_conv_ok, wino_launch_cost, wino_n_tiles, wino_packer, wino_run_len, wino_run_map, wino_split_k, wino_split_steps, wino_taps, wino_weight_flags)
 from .runtime import (  # noqa: F401
     ACT_BLOCKS_CHOICES, _act_blocks, _act_choice, act1d_grouped, act1d_ragged, amp_actconv, calibrate_act_occupancy, conv_grouped, ensure_act_blocks,
@@ -56,7 +56,7 @@ class Vocoder:
         if cfg["activation"] not in ("snake", "snakebeta"):
             raise NotImplementedError(cfg["activation"])
         self.device = hip.norm_device(device)
-        # conv_form: 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6' | 'auto' (planner.resolve_conv_form: keyword > FH_CONV_FORM and the older
+        # conv_form: 'winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6' | 'direct_bf16x3' | 'auto' (planner.resolve_conv_form: keyword > FH_CONV_FORM and the older
         # switches > 'auto' = the default form; bf16x6 = the boolean keyword of rounds 2-5).  'auto' is resolved HERE to the default
         # form; a caller that holds the checkpoint may then probe it against the direct form (FLowHigh, probe_conv_form).
         self.form, self.form_auto = resolve_conv_form(conv_form, bf16x6)
@@ -64,11 +64,14 @@ class Vocoder:
         self.bf = self.form == "bf16x6"
         # ... and the narrow stages (<= 48 channels) run the direct bf16 x 6 kernel (narrow_bf.hip) instead of the fp32 Winograd one
         self.amp_direct = use_amp_bf16x6(self.form)
-        # direct_bf: the direct convs run the bf16 x 6 entry (conv_mfma_bf.hip) wherever their channel chunk is 16 ('direct_bf16x6')
-        self.direct_bf = use_direct_bf16x6(self.form)
-        # a direct conv's weights for chunk `ck`: three-piece bf16 rows where the bf16 x 6 entry runs it (store key suffix .wb), else fp32
-        conv_w = lambda bf, w, cpad_, ck: pack_conv_bf_weight(w, cpad_) if bf else pack_conv_weight(w, cpad_, ck)
-        wkey = lambda bf: "wb" if bf else "w"
+        # direct_bf: the direct convs run a bf16 entry (conv_mfma_bf.hip) wherever their channel chunk is 16 -- 1: the bf16 x 6 entry
+        # ('direct_bf16x6'), 2: the bf16 x 3 entry ('direct_bf16x3'; the narrow stages then run narrow_bf.hip's two-piece form), 0: none
+        # (planner.direct_bf_pieces: the value a conv step record carries)
+        self.direct_bf = direct_bf_pieces(self.form)
+        # a direct conv's weights for chunk `ck`: three-piece bf16 rows where the bf16 x 6 entry runs it (store key suffix .wb), two-piece
+        # rows where the bf16 x 3 entry does (.wb3), else fp32
+        conv_w = lambda bf, w, cpad_, ck: (pack_conv_bf3_weight if bf == 2 else pack_conv_bf_weight)(w, cpad_) if bf else pack_conv_weight(w, cpad_, ck)
+        wkey = lambda bf: ("w", "wb", "wb3")[int(bf)]
         # plan-shaping environment switches, read once: every plan of this model uses this snapshot (planner.plan_switches)
         self.sw = plan_switches()
         self.rates = list(cfg["upsample_rates"])
@@ -167,7 +170,7 @@ class Vocoder:
         # conv_pre
         self.pre_cfg, _, self.pre_cpad = pick_tile_cfg(self.c0)
         self.pre_ck = pick_ck(self.num_mels)
-        self.pre_bf = self.direct_bf and self.pre_ck == 16
+        self.pre_bf = self.direct_bf if self.pre_ck == 16 else 0
         self.pre_w = W.dev("v.conv_pre." + wkey(self.pre_bf), lambda: conv_w(self.pre_bf, g("conv_pre.weight"), self.pre_cpad, self.pre_ck))
         self.pre_b = W.dev("v.conv_pre.b", lambda: g("conv_pre.bias"))
         # conv_pre (num_mels -> c0, 7 taps) in Winograd form as well when the shapes fit
@@ -184,7 +187,7 @@ class Vocoder:
             tcfg, bm, cpad = pick_tile_cfg(c)
             st = dict(c=c, cin=cin, u=u, k=k, extra=self.extra[i], tile_cfg=tcfg, cpad=cpad,
                       ck=pick_ck(c), up_ck=pick_ck(cin))
-            st["conv_bf"] = self.direct_bf and st["ck"] == 16
+            st["conv_bf"] = self.direct_bf if st["ck"] == 16 else 0
             # Winograd residual stack only if every block's kernel fits its 4 tap groups (one launch per position)
             wino_k = max(self.ks) <= WINO_MAX_K
             for kk, dl in zip(self.ks, self.dil):
@@ -200,15 +203,17 @@ class Vocoder:
             # narrow stages (<= 48 channels): the residual-stack convs run on the narrow-stage kernel (planner.use_amp)
             # (a bf16 x 6 model: in the direct bf16 x 6 form, narrow_bf.hip -- self.amp_direct)
             st["amp"] = use_amp(c, self.ks, self.dil, self.form)
-            pack_narrow = pack_narrow_bf_weight if self.amp_direct else pack_amp_weight
-            ua_key = "unb" if self.amp_direct else "ua"
+            # ('direct_bf16x3': its two-piece form)
+            narrow_bf3 = self.amp_direct and self.direct_bf == 2
+            pack_narrow = pack_narrow_bf3_weight if narrow_bf3 else pack_narrow_bf_weight if self.amp_direct else pack_amp_weight
+            ua_key = "unb3" if narrow_bf3 else "unb" if self.amp_direct else "ua"
             # (the weight format of a launch follows its kernel family and the model's form: planner.wino_weight_flags)
             pack_res = lambda w_: wino_packer(st["wcfg"], self.bf)(w_, st["wpad"])
             wt = lambda i=i: g(f"ups.{i}.0.weight")               # [cin, c, k]
             st["up_b"] = W.dev(f"v.ups.{i}.b", lambda: g(f"ups.{i}.0.bias"))
             st["up_phases"] = [dict(offs=[o for _, o in taps]) for taps in transposed_conv_phases(k, u)]
             # (the phase-fused form -- fh_conv_transpose_fused_f32, ups_fused_ok -- has no bf16 x 6 twin: its stages keep fp32 weights)
-            st["up_bf"] = self.direct_bf and st["up_ck"] == 16 and not ups_fused_ok(st, self.sw["ups_fuse"])
+            st["up_bf"] = self.direct_bf if st["up_ck"] == 16 and not ups_fused_ok(st, self.sw["ups_fuse"]) else 0
             for r_, taps in enumerate(transposed_conv_phases(k, u)):
                 def phase_w(taps=taps):
                     wsel = torch.stack([wt()[:, :, j] for j, _ in taps], dim=-1)        # [cin, c, nt]

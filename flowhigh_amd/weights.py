@@ -27,7 +27,7 @@ _DTYPES = {"float32": torch.float32, "float64": torch.float64, "int16": torch.in
 
 def format_tag(form="winograd"):
     """Everything that decides WHICH layouts the constructors pack: a blob made under other decisions is not used.
-    form: the RESOLVED conv form ('winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6', planner.resolve_conv_form); the remaining layout switches as
+    form: the RESOLVED conv form ('winograd' | 'bf16x6' | 'direct' | 'direct_bf16x6' | 'direct_bf16x3', planner.resolve_conv_form); the remaining layout switches as
     normalised booleans / numbers (unset and "1" are the same setting), and a fingerprint of the packers' and the planner's source
     (tile choices, thresholds and fragment layouts live there: a code change must not silently reuse a key with another layout).
     layout: bumped by hand with every change of a packed layout (5: the bf16 x 6 F(5,4) weights in fragment order, packing.frag_order)."""

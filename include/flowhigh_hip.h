@@ -112,6 +112,17 @@ int fh_conv_transpose_fused_f32(const fh_conv_group* groups, int n_groups, int b
 int fh_conv_grouped_bf16x6_f32(const fh_conv_group* groups, int n_groups, int batch, int cout_pad, int n_len, int tile_cfg,
                                void* stream);
 
+/* fh_conv_grouped_bf16x6_f32 in the bf16 x 3 form (conv_form = 'direct_bf16x3'; the same kernel body with two pieces per operand):
+ * the same call sites, descriptors, tile_cfg ids, cout_pad, block mapping, step order and argument checks.  Every operand keeps
+ * the first two pieces of the exact split, h = bf16(x) and m = bf16(x - h), and a product w x is the three piece-pair MFMAs
+ * (m h), (h m), (h h) -- small terms first -- into one fp32 accumulator: half the MFMAs and two thirds of the slab, LDS reads and
+ * weight bytes of the six-pair form.  The dropped terms (w_m x_m and both remainders) are <= 3 2^-16 |w x| per product (bf16x6.h):
+ * NOT fp32-grade, ~2-3e-5 on the waveform (profiles/direct_bf16x3.md).  seg.w points at two-piece weights, bf16 bit patterns
+ * [cin/16][ntaps][cout_pad][piece h, m][16] (packing.pack_conv_bf3_weight: the first two pieces of pack_conv_bf_weight's rows;
+ * 64-byte rows, 4 bytes per weight); x is split on the device. */
+int fh_conv_grouped_bf16x3_f32(const fh_conv_group* groups, int n_groups, int batch, int cout_pad, int n_len, int tile_cfg,
+                               void* stream);
+
 /* ------------------------------------------------------------------------------------
  * The same Conv1d call sites (models/bigvgan/models.py:63-72, "same"-padded, stride 1, square
  * cin x cout residual-stack convs) evaluated with the Winograd minimal-filtering identity
@@ -385,6 +396,12 @@ int fh_amp_actconv_f32(const fh_amp_group* groups, int n_groups, const fh_amp_ti
  * --------------------------------------------------------------------------------- */
 int fh_narrow_tile_len(void);          /* 256 */
 int fh_narrow_conv_bf16x6_f32(const fh_amp_group* groups, int n_groups, const fh_amp_tile* tiles, int total_tiles, int channels,
+                              int dilation, int flags, void* stream);
+/* ... and in the bf16 x 3 form (conv_form = 'direct_bf16x3'; the same kernel body with two pieces per operand: h and m of the
+ * split, the three pairs (m h), (h m), (h h), dropped terms <= 3 2^-16 |a b|).  Same descriptors, tiles, flags and
+ * argument checks; fh_amp_seg.u = packing.pack_narrow_bf3_weight: the layout above with two pieces per N tile,
+ * [k-block][N tile][piece h, m][lane][8 bf16], ceil(C / 16) x 2 KB per k-block. */
+int fh_narrow_conv_bf16x3_f32(const fh_amp_group* groups, int n_groups, const fh_amp_tile* tiles, int total_tiles, int channels,
                               int dilation, int flags, void* stream);
 
 /* ------------------------------------------------------------------------------------
