@@ -9,7 +9,7 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "lib" / "libflowhigh_hip.so"
 SOURCES = ["api_common.hip", "conv_mfma.hip", "conv_mfma_bf.hip", "conv_wino.hip", "conv_wino54.hip", "conv_wino54_bf.hip", "amp_fused.hip", "narrow_bf.hip", "act1d.hip", "gemm_mfma.hip", "gemm_bf.hip", "flow_ops.hip", "convnext.hip", "sum_ops.hip",
-           "attention.hip", "attention_bf.hip", "attention_band.hip", "attention_bf_band.hip", "frontend.hip", "fft.hip", "prior.hip", "ode.hip", "level.hip", "pcm.hip", "loudness.hip", "truepeak.hip", "stream.hip", "stream_delivery.hip"]
+           "attention.hip", "attention_bf.hip", "attention_band.hip", "attention_bf_band.hip", "frontend.hip", "fft.hip", "prior.hip", "ode.hip", "steps.hip", "level.hip", "pcm.hip", "loudness.hip", "truepeak.hip", "stream.hip", "stream_delivery.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-source extra flags.  The bf16 x 6 kernels keep everything beside their MFMAs one result per lane: the SLP vectoriser
 # would re-pack it into v_pk_*_f32, which stall a bf16 MFMA (conv_wino54_kernel.h)

@@ -13,6 +13,8 @@ calls).  Fusions:
   * all eight adaptive-norm gamma/beta projections of a forward in one GEMV (the time embedding
     is identical for every clip, flow.py:208-211).
 """
+import ctypes
+
 import torch
 
 from . import hip
@@ -141,6 +143,7 @@ class FlowNet:
         self.w_pred = dev_w("f.w_pred", lambda: _pad_rows(g("to_pred.weight")))
         self.inv_freq = W.host("f.inv_freq", lambda: g("transformer.rotary_emb.inv_freq"))
         self._ws = hip.ShapeCache()
+        self._group_ws = {}
 
     def gemm(self, A, W, C_out, M, N, K, **kw):
         return hip.gemm(A, W, C_out, M, N, K, bf=self.bf, **kw)
@@ -195,19 +198,48 @@ class FlowNet:
         self.gemm(cond, self.w_c, ws["e_cond"], M, self.dim, self.dim_in, bias=self.b_embed)
 
     @hip.on_device
-    def forward(self, x, t, out, batch, n, alpha=1.0, res=None, null_cond=False, ragged=None):
+    def _group_buffers(self, n_groups):
+        """four [G, D], temb [G, D], gb [G, depth*4*D] of the grouped forward: a few KB to a few hundred KB, kept per G."""
+        bufs = self._group_ws.get(n_groups)
+        if bufs is None:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            bufs = self._group_ws[n_groups] = dict(four=torch.empty(n_groups, self.dim, **f32), temb=torch.empty(n_groups, self.dim, **f32),
+                                                   gb=torch.empty(n_groups, self.depth * 4 * self.dim, **f32))
+        return bufs
+
+    @hip.on_device
+    def forward(self, x, t, out, batch, n, alpha=1.0, res=None, null_cond=False, ragged=None, groups=None, n_seg=None):
         """out = alpha * v(x, t) + res  with v the vector field; x/out/res [B*n, dim_in].
         null_cond=True evaluates v with every frame's condition replaced by `null_cond`
         (the cond_drop_prob = 1 pass of forward_with_cond_scale, flow.py:174-178,222-230).
         ragged: a ragged_workspace -- the rows are clips of different lengths packed back to back; everything
         row-wise runs as for one long clip, the three operators that look across rows (ConvPositionEmbed, rotary
         positions, attention) take the segment table: the reference's mask paths (transformer.py:35-44,
-        attend.py:127-128) without the padding rows."""
+        attend.py:127-128) without the padding rows.
+        groups = (row_ends, times) with ragged, n_seg = k: a time per GROUP of rows (csrc/steps.hip; ode.mixed_schedule).  The
+        first k segments of the workspace run, row_ends[-1] rows in all; group g is the rows row_ends[g - 1] .. row_ends[g] - 1
+        and is evaluated at times[g] (at most 8 groups).  The time path is three grouped launches, the five norms take a gamma /
+        beta per group, the segment kernels take the prefix of the table.  The field is written raw in this form (t, alpha and
+        res are not read: the caller applies the update, fh_axpy_groups_f32); a row has the bits of a ragged forward of its
+        group's clips alone at that group's time."""
+        if groups is not None and ragged is None:
+            raise ValueError("groups= goes with a ragged workspace")
         L, st = hip.lib(), hip.stream()
         ws = ragged if ragged is not None else self.workspace(batch, n)
         M, D = (ragged["rows"] if ragged is not None else batch * n), self.dim
         seg = ragged["seg"].data_ptr() if ragged is not None else None
-        n_seg, max_n = (len(ragged["frames"]), ragged["max_n"]) if ragged is not None else (0, 0)
+        n_seg_all, max_n = (len(ragged["frames"]), ragged["max_n"]) if ragged is not None else (0, 0)
+        grp = None
+        if groups is not None:
+            row_ends, times = groups
+            n_seg = n_seg_all if n_seg is None else int(n_seg)
+            if not 1 <= n_seg <= n_seg_all or sum(ragged["frames"][:n_seg]) != row_ends[-1] or len(times) != len(row_ends):
+                raise ValueError(f"groups ending at rows {tuple(row_ends)} with {len(times)} times do not fit the first {n_seg} "
+                                 f"segments of frames {ragged['frames']}")
+            grp, M, max_n = hip.row_groups(row_ends), int(row_ends[-1]), max(ragged["frames"][:n_seg])
+            alpha, res = 1.0, None
+        else:
+            n_seg = n_seg_all
         h, h2, a, att, qkv = ws["h"], ws["h2"], ws["a"], ws["att"], ws["qkv"]
         if null_cond:
             if self._e_null is None:            # null_cond @ W_c^T + b: one row, broadcast with ldr = 0
@@ -222,19 +254,36 @@ class FlowNet:
         else:
             hip.check(L.fh_dwconv_gelu_res_seg_f32(h.data_ptr(), self.dw_w.data_ptr(), self.dw_b.data_ptr(), h2.data_ptr(),
                                                    seg, n_seg, max_n, D, self.dw_k, st), "fh_dwconv_gelu_res_seg_f32")
-        hip.check(L.fh_time_fourier_f32(self.sinu_w.data_ptr(), float(t), ws["four"].data_ptr(), D // 2, st),
-                  "fh_time_fourier_f32")
-        hip.check(L.fh_gemv_f32(self.t_w.data_ptr(), ws["four"].data_ptr(), self.t_b.data_ptr(),
-                                ws["temb"].data_ptr(), D, D, 1, st), "fh_gemv_f32")
-        hip.check(L.fh_gemv_f32(self.gb_w.data_ptr(), ws["temb"].data_ptr(), self.gb_b.data_ptr(),
-                                ws["gb"].data_ptr(), self.gb_w.shape[0], D, 0, st), "fh_gemv_f32")
-        gb = ws["gb"]
+        if grp is None:
+            hip.check(L.fh_time_fourier_f32(self.sinu_w.data_ptr(), float(t), ws["four"].data_ptr(), D // 2, st),
+                      "fh_time_fourier_f32")
+            hip.check(L.fh_gemv_f32(self.t_w.data_ptr(), ws["four"].data_ptr(), self.t_b.data_ptr(),
+                                    ws["temb"].data_ptr(), D, D, 1, st), "fh_gemv_f32")
+            hip.check(L.fh_gemv_f32(self.gb_w.data_ptr(), ws["temb"].data_ptr(), self.gb_b.data_ptr(),
+                                    ws["gb"].data_ptr(), self.gb_w.shape[0], D, 0, st), "fh_gemv_f32")
+            gb = ws["gb"]
+
+            def norm(x_, gamma, beta):
+                hip.check(L.fh_rmsnorm_f32(x_.data_ptr(), gamma.data_ptr(), hip.ptr(beta), a.data_ptr(), M, D, st), "fh_rmsnorm_f32")
+        else:
+            G, gw = grp.n, self._group_buffers(grp.n)
+            gb = gw["gb"][0]                      # (group 0's vector: group g's lies g * gb_stride floats behind it)
+            gb_stride = gw["gb"].shape[1]
+            hip.check(L.fh_time_fourier_groups_f32(self.sinu_w.data_ptr(), hip.group_floats(times), gw["four"].data_ptr(), D // 2, G, st),
+                      "fh_time_fourier_groups_f32")
+            hip.check(L.fh_gemv_rows_f32(self.t_w.data_ptr(), gw["four"].data_ptr(), D, self.t_b.data_ptr(), gw["temb"].data_ptr(), D,
+                                         D, D, G, 1, st), "fh_gemv_rows_f32")
+            hip.check(L.fh_gemv_rows_f32(self.gb_w.data_ptr(), gw["temb"].data_ptr(), D, self.gb_b.data_ptr(), gw["gb"].data_ptr(),
+                                         gb_stride, self.gb_w.shape[0], D, G, 0, st), "fh_gemv_rows_f32")
+
+            def norm(x_, gamma, beta):            # (the final norm's gamma is a weight, the same for every group: stride 0)
+                hip.check(L.fh_rmsnorm_groups_f32(x_.data_ptr(), gamma.data_ptr(), hip.ptr(beta), gb_stride if beta is not None else 0,
+                                                  a.data_ptr(), M, D, ctypes.byref(grp), st), "fh_rmsnorm_groups_f32")
         cur, other = h2, h
         for li, lay in enumerate(self.layers):
             o = li * 4 * D
             g1, b1, g2, b2 = (gb[o + i * D: o + (i + 1) * D] for i in range(4))
-            hip.check(L.fh_rmsnorm_f32(cur.data_ptr(), g1.data_ptr(), b1.data_ptr(), a.data_ptr(), M, D, st),
-                      "fh_rmsnorm_f32")
+            norm(cur, g1, b1)
             self.gemm(a, lay["w_qkv"], qkv, M, 3 * D, D)
             if seg is None:
                 hip.check(L.fh_qknorm_rope_f32(qkv.data_ptr(), lay["gq"].data_ptr(), lay["gk"].data_ptr(),
@@ -257,13 +306,11 @@ class FlowNet:
                                                               self._radius, 10.0, st), self._attn_band_seg)
             self.gemm(att, lay["w_out"], other, M, D, D, R=cur)
             cur, other = other, cur
-            hip.check(L.fh_rmsnorm_f32(cur.data_ptr(), g2.data_ptr(), b2.data_ptr(), a.data_ptr(), M, D, st),
-                      "fh_rmsnorm_f32")
+            norm(cur, g2, b2)
             ip = lay["inner_pad"]
             self.gemm(a, lay["w1"], ws["g"], M, 2 * ip, D, bias=lay["b1"], epilogue=hip.EPI_GEGLU, ldc=ws["g"].shape[1])
             self.gemm(ws["g"], lay["w2"], other, M, D, ip, bias=lay["b2"], R=cur, lda=ws["g"].shape[1])
             cur, other = other, cur
-        hip.check(L.fh_rmsnorm_f32(cur.data_ptr(), self.final_gamma.data_ptr(), 0, a.data_ptr(), M, D, st),
-                  "fh_rmsnorm_f32")
+        norm(cur, self.final_gamma, None)
         self.gemm(a, self.w_pred, out, M, self.dim_in, D, R=res, alpha=alpha)
         return out

@@ -772,6 +772,8 @@ class FlowHighSR:
         last GEMM of the vector field (eval_fused; a raw k is the same with alpha = 1 and no base: eval); with classifier-free
         guidance v = null + s (cond - null) it is two chained epilogues.  The stage arithmetic between the evaluations of heun2,
         heun3 and rk4 is fh_rk_combine_f32 (combine).  euler and midpoint are one and two eval_fused and nothing else."""
+        if isinstance(time_steps, (list, tuple)):
+            return self._integrate_mixed(y0, cond_mel, time_steps, cond_scale, ragged)
         net = self.flowhigh.net
         plan = ode.step_plan(self.odeint_kwargs['method'])          # (NotImplementedError for a name outside ODE_METHODS)
         net.set_cond(cond_mel, batch, n, ragged=ragged)
@@ -808,6 +810,78 @@ class FlowHighSR:
                     axpy_field(stage[r.src], tt, stage[r.dst], float(r.weight * dt), stage[r.base])
             y = stage["out"]
         return y
+
+    def _integrate_mixed(self, y0, cond_mel, steps, cond_scale, ragged):
+        """_integrate for a ragged sequence whose segments take different step counts: steps = the count of every segment of
+        `ragged`, sorted descending.  The segments of one count are a group of rows; pass p runs the records of the step plan
+        over the groups that still have a step p (a prefix of the rows), every group at its own time and step size
+        (ode.mixed_schedule), and a group's rows go into the result when its own last step is done.  The field is always
+        written raw and the update out = base + (weight h_g) v is fh_axpy_groups_f32, the bits of the GEMM epilogue that applies
+        it in _integrate; under guidance it is two raw fields and two chained updates with alphas h_g (1 - s) and h_g s; combine
+        is fh_rk_combine_groups_f32.  A segment's rows are the bits of _integrate on that segment alone at its count."""
+        net = self.flowhigh.net
+        plan = ode.step_plan(self.odeint_kwargs['method'])
+        sched = ode.mixed_schedule(steps)
+        frames = ragged["frames"]
+        # per group: segments and rows up to its end
+        seg_end, row_end = [], []
+        for _, n_segs in sched.groups:
+            seg_end.append((seg_end[-1] if seg_end else 0) + n_segs)
+            row_end.append(sum(frames[:seg_end[-1]]))
+        net.set_cond(cond_mel, len(frames), ragged["max_n"], ragged=ragged)
+        d = y0.shape[-1]
+        y, result = y0, torch.empty_like(y0)
+        bufs = [torch.empty_like(y0) for _ in range(5)]
+        names = {d_ for r in plan for d_ in (r[-1], getattr(r, "dst_a", None)) if d_ not in (None, "out", "x")}
+        stage = {"x": bufs[2], **{name: torch.empty_like(y0) for name in sorted(names)}}
+        L, st = hip.lib(), hip.stream()
+        field = bufs[4]
+
+        def axpy(v, alphas, base, out, rows, grp):
+            hip.check(L.fh_axpy_groups_f32(v.data_ptr(), hip.group_floats(alphas), hip.ptr(base), out.data_ptr(), rows, d,
+                                           ctypes.byref(grp), st), "fh_axpy_groups_f32")
+
+        for p, active in enumerate(sched.passes):
+            G = len(active)
+            rows, n_seg, ends = row_end[G - 1], seg_end[G - 1], row_end[:G]
+            grp = hip.row_groups(ends)
+            stage["y"], stage["out"] = y, bufs[p % 2]
+
+            def axpy_field(x, times, out, hs, base):           # out = base + h_g * v(x, times_g)
+                kw = dict(ragged=ragged, groups=(ends, times), n_seg=n_seg)
+                if cond_scale == 1.:
+                    if base is None and all(h == 1. for h in hs):          # (a raw k)
+                        net.forward(x, None, out, 0, 0, **kw)
+                        return
+                    net.forward(x, None, field, 0, 0, **kw)
+                    axpy(field, hs, base, out, rows, grp)
+                else:
+                    net.forward(x, None, field, 0, 0, null_cond=True, **kw)
+                    axpy(field, [h * (1. - cond_scale) for h in hs], base, bufs[3], rows, grp)
+                    net.forward(x, None, field, 0, 0, **kw)
+                    axpy(field, [h * cond_scale for h in hs], bufs[3], out, rows, grp)
+
+            for r in plan:
+                if isinstance(r, ode.Combine):
+                    ks = (ctypes.c_void_p * len(r.ks))(*[stage[k].data_ptr() for k in r.ks])
+                    wa = (ctypes.c_float * len(r.ks))(*r.wa)
+                    wb = None if r.wb is None else (ctypes.c_float * len(r.ks))(*r.wb)
+                    hip.check(L.fh_rk_combine_groups_f32(y.data_ptr(), ks, len(r.ks), hip.group_floats([float(dt) for _, dt in active]), wa,
+                                                         stage[r.dst_a].data_ptr(), wb, hip.ptr(None if r.dst_b is None else stage[r.dst_b]),
+                                                         rows, d, ctypes.byref(grp), st), "fh_rk_combine_groups_f32")
+                    continue
+                times = [ode.stage_time(t0, dt, r.c) for t0, dt in active]
+                if isinstance(r, ode.Eval):
+                    axpy_field(stage[r.src], times, stage[r.dst], [1.] * G, None)
+                else:
+                    axpy_field(stage[r.src], times, stage[r.dst], [ode.fused_weight(r.weight, dt) for _, dt in active], stage[r.base])
+            y = stage["out"]
+            # the groups whose last step this was (one count: one contiguous range of rows): one device copy
+            done = [g for g, (s, _) in enumerate(sched.groups[:G]) if s == p + 1]
+            if done:
+                r0 = row_end[done[0] - 1] if done[0] else 0
+                result[r0:row_end[done[-1]]].copy_(y[r0:row_end[done[-1]]])
+        return result
 
     def _cutoff_bins(self, cond_mel, n_seg, n, seg=None):
         """int32 [n_seg] cutoff bin of every clip, two launches: n_seg clips of n rows, or (seg: the device segment table)
@@ -914,6 +988,7 @@ class FlowHighSR:
         lengths as one launch sequence.
         conds: list of [T48_i] device tensors (peak-normalised), noises: list of [1, N_i, n_mels] host tensors, or None and
         keys = the clips' (seed, stream) keys: the prior is then drawn on the device, one launch over the segment table.
+        time_steps: one count, or a list of one count per clip, sorted descending (at most 8 distinct: _integrate_mixed).
         Returns the vocoder's waveforms, a list of [1, 480 N_i] (plan-owned buffers; decode_to_audio=False: the mels,
         a list of [N_i, n_mels]), each what _sample gives for that clip alone: the log-mels are made per clip, every
         row-wise operator runs on the packed rows, the operators that look across rows take the clip boundaries (the
@@ -948,18 +1023,34 @@ class FlowHighSR:
         guidance against null_cond, mel_pp: low-band replacement with per-clip cutoff bins, std_1 / std_2: prior scales of the
         independent_cfm_* paths, both reset unless both are given; cfm:162-183,278-279).
         Every result is bit-identical to `sample(cond=clip[None], ...)` on that clip alone.  Returns a list of
-        [1, 1, 480 N_i] waveforms (or [1, N_i, n_mels] mels)."""
+        [1, 1, 480 N_i] waveforms (or [1, N_i, n_mels] mels).
+        time_steps: one count, or one count per clip (generate_many's timestep=): clip i is then `sample(..., time_steps=steps[i])`."""
         if cfm_method not in _CFM_METHODS:
             cfm_method = self.cfm_method
         conds = list(conds)
+        time_steps = ode.check_steps(time_steps, len(conds), "time_steps")
         keys = self._prior_keys(seed, len(conds), generator, noise)
         conds = [c.to(self.device, torch.float32).reshape(-1) for c in conds]
         frames = [c.shape[0] // 480 for c in conds]
         if noise is None and keys is None:
             noise = [self._draw_noise(1, n, generator) for n in frames]
-        outs = self._sample_ragged(conds, time_steps, cfm_method, noises=noise, std_1=std_1, std_2=std_2, cond_scale=cond_scale,
-                                   mel_pp=mel_pp, decode_to_audio=decode_to_audio, keys=keys)
-        return [o.clone().unsqueeze(1) if decode_to_audio else o.clone()[None] for o in outs]
+        if isinstance(time_steps, list):
+            # one step count per clip: the clips sorted by count (descending, stable) into sequences of at most 8 distinct counts
+            # (one count each on the convnext backbone, which has no grouped form), the results put back in list order
+            limit = ode.MAX_STEP_GROUPS if getattr(self.flowhigh, "architecture", "transformer") != "convnext" else 1
+            seqs = [(part, [time_steps[i] for i in part]) for part in ode.split_by_steps(ode.order_by_steps(time_steps), time_steps, limit)]
+        else:
+            seqs = [(list(range(len(conds))), time_steps)]
+        result = [None] * len(conds)
+        for idx, steps in seqs:
+            if isinstance(steps, list) and len(set(steps)) == 1:
+                steps = steps[0]
+            outs = self._sample_ragged([conds[i] for i in idx], steps, cfm_method, noises=None if noise is None else [noise[i] for i in idx],
+                                       std_1=std_1, std_2=std_2, cond_scale=cond_scale, mel_pp=mel_pp, decode_to_audio=decode_to_audio,
+                                       keys=None if keys is None else [keys[i] for i in idx])
+            for i, o in zip(idx, outs):
+                result[i] = o.clone().unsqueeze(1) if decode_to_audio else o.clone()[None]
+        return result
 
     @torch.no_grad()
     @hip.on_device
@@ -968,6 +1059,7 @@ class FlowHighSR:
                        output_rate=None, pcm=None, dither=None, dither_seed=0, interleaved=False, loudness=None,
                        true_peak=None, limiter=None):
         """B clips of equal length as one batch -> [B, T48], every clip what generate() returns for it alone.
+        timestep: one step count, or one per clip (generate_many); mixed counts run one batch per distinct count.
         channels=, level= (generate): with channels= every clip may have its own number of channels and the result is a list
         of [C_i, T48]; noise= is then one tensor per clip in a list ([1, N, n_mels] shared by the clip's channels, or
         [C_i, N, n_mels]), or [B, N, n_mels]: one shared draw per clip.
@@ -982,10 +1074,29 @@ class FlowHighSR:
         if opt is not None and return_stages:
             raise ValueError("return_stages=True returns the 48 kHz stages: it does not go with output_rate= / pcm= / loudness= / "
                              "true_peak=")
+        timestep = ode.check_steps(timestep, n_clips)
+        if isinstance(timestep, list) and return_stages:
+            raise ValueError("return_stages=True returns the stages of one batch: it does not go with one step count per clip")
         keys = self._prior_keys(seed, n_clips, generator, noise)
         if target_sampling_rate != 48000:
             raise NotImplementedError("the mel codec is fixed at 48 kHz")
-        out = self._generate_rows(planar, sr, timestep, clip_noises(noise, chans), keys, generator, level, plain, return_stages)
+        if isinstance(timestep, list):
+            # one step count per clip: one batch per distinct count (the clips are of one shape), the rows put back in clip
+            # order; the host prior is drawn first, in clip order, as the one batch draws it
+            noises = clip_noises(noise, chans)
+            if noises is None and keys is None:
+                n = resample_out_len(planar[0].shape[1], 48000, sr) // 480
+                noises = [channel_noise(self._draw_noise(1, n, generator), c) for c in chans]
+            parts = [None] * n_clips
+            for count in sorted(set(timestep)):
+                idx = [i for i, s in enumerate(timestep) if s == count]
+                y = self._generate_rows([planar[i] for i in idx], sr, count, None if noises is None else [noises[i] for i in idx],
+                                        None if keys is None else [keys[i] for i in idx], None, level, plain)
+                for i, rows_i in zip(idx, y.split([chans[i] for i in idx])):
+                    parts[i] = rows_i
+            out = torch.cat(parts, 0)
+        else:
+            out = self._generate_rows(planar, sr, timestep, clip_noises(noise, chans), keys, generator, level, plain, return_stages)
         rows, stages = out if return_stages else (out, None)
         if opt is not None:
             # (without channels= every clip is one row: the delivered buffer itself is the [B, T] result)
@@ -1038,9 +1149,20 @@ class FlowHighSR:
         loudness= (generate): every clip at that many LUFS at the delivered rate, each by its own gain; a batch of equal clips
         through the batched entries of csrc/loudness.hip, a ragged group through their segment forms, the same bits either way.
         true_peak=, limiter= (generate): every clip under that ceiling in dBTP, through the batched entries of csrc/truepeak.hip or
-        their segment forms, the same bits either way."""
+        their segment forms, the same bits either way.
+        timestep: one step count for the list, or ONE COUNT PER CLIP -- generate_many(clips, sr, 48000, [1, 4, 2, ...]); a list of
+        another length than `clips`, or an entry that is no int >= 1 (a bool, a float, 0) is a ValueError before any GPU work
+        (ode.check_steps).  A list of equal counts is the int, and an int runs what it always ran.  Mixed counts run as ragged
+        sequences with a time and a step size per clip (_integrate_mixed, csrc/steps.hip): the clips of a ragged group sorted by
+        count, descending and stable, max(steps) passes over a shrinking prefix of the rows, at most 8 distinct counts per
+        sequence (a group with more is cut into several), the results back in list order; priors, keys and dither keys stay
+        tied to a clip's place in the list.  Clip i is bit for bit generate(clip_i, sr_i, timestep=steps[i]), with every option
+        above.  One batch per (length, rate, noise shape, step count) instead: ragged=False / FH_RAGGED=0, the convnext
+        backbone, a vocoder configuration whose plan cannot be merged.  profiles/mixed_steps.md has the measurement."""
         clips = list(clips)
         ends = resolve_ends(ends)
+        timestep = ode.check_steps(timestep, len(clips))      # (an int, or a list of one count per clip that are not all equal)
+        mixed = isinstance(timestep, list)
         rates = resolve_rates(sr, len(clips))
         opt = resolve_delivery(len(clips), output_rate, pcm, dither, dither_seed, interleaved, loudness=loudness, level=level,
                                true_peak=true_peak, limiter=limiter)
@@ -1062,7 +1184,11 @@ class FlowHighSR:
         shapes = [tuple(z.shape) for z in noise] if noise is not None else [(1, n, self.flowhigh.n_mels) for n in frames]
         if ragged is None:
             ragged = os.environ.get("FH_RAGGED", "1") != "0"
-        if ragged and len(set(zip(lengths, rates))) > 1:
+        # mixed step counts run as ragged sequences with a time per clip (_integrate_mixed) -- clips of one shape included -- where
+        # the vector field has the grouped form; the convnext backbone (its time-conditioned LayerNorm takes one time), ragged
+        # off and an unmergeable vocoder plan run one batch per (shape, step count) below
+        grouped_field = getattr(self.flowhigh, "architecture", "transformer") != "convnext"
+        if ragged and (len(set(zip(lengths, rates))) > 1 if not mixed else grouped_field):
             try:
                 return self._generate_many_ragged(planar, rates, timestep, noise, max_frames, keys, [sh[1] for sh in shapes], ends,
                                                   level, plain, opt)
@@ -1075,7 +1201,7 @@ class FlowHighSR:
                                                               "running one batch per clip length", e)
         if streams is None:
             streams = int(os.environ.get("FH_SERVE_STREAMS", "1"))
-        n_streams, parts = plan_buckets(lengths, rates, shapes, streams, max_batch)
+        n_streams, parts = plan_buckets(lengths, rates, shapes, streams, max_batch, steps=timestep if mixed else None)
         main = torch.cuda.current_stream(self.device)
         side = self._serve_streams(n_streams) if n_streams > 1 else [main]
         for s_ in side:
@@ -1084,7 +1210,8 @@ class FlowHighSR:
         out = [None] * len(clips)
         for s_, rate, part in parts:                         # (max_batch counts clips: a clip's channels stay in one batch)
             with torch.cuda.stream(side[s_]):
-                for i, y in zip(part, self._run_clips(planar, part, rate, timestep, noise, keys, level, plain, opt)):
+                steps = timestep[part[0]] if mixed else timestep          # (a bucket holds one step count)
+                for i, y in zip(part, self._run_clips(planar, part, rate, steps, noise, keys, level, plain, opt)):
                     out[i] = y.clone() if opt is None else y
                     if side[s_] is not main:
                         out[i].record_stream(main)
@@ -1111,13 +1238,26 @@ class FlowHighSR:
         chunk_limit = int(os.environ.get("FH_VOCODER_CHUNK_FRAMES", "6000"))
         # greedy packing in list order; a clip that does not fit a sequence, or has one to itself, runs as a batch of one
         groups, alone = pack_ragged(frames, [a.shape[0] for a in planar], max_frames, chunk_limit)
+        steps_of = (lambda i: timestep[i]) if isinstance(timestep, list) else (lambda i: timestep)
+        # mixed step counts in a group: its clips sorted by count, descending and stable, cut into sequences of at most 8 distinct
+        # counts (one launch of csrc/steps.hip takes 8 groups).  idx carries the clips' places in the caller's list through the
+        # run and the delivery: priors, keys and dither keys stay tied to them, the results go back by them
+        seqs = []
+        for idx in groups:
+            counts = [steps_of(i) for i in idx]
+            if len(set(counts)) == 1:
+                seqs.append((idx, counts[0]))
+            else:
+                for part in ode.split_by_steps(ode.order_by_steps(counts), counts):
+                    part_counts = [counts[k] for k in part]
+                    seqs.append(([idx[k] for k in part], part_counts[0] if len(set(part_counts)) == 1 else part_counts))
         out = [None] * len(planar)
-        for idx in [[i] for i in alone] + groups:
+        for idx, steps in [([i], steps_of(i)) for i in alone] + seqs:
             if len(idx) == 1:
-                (out[idx[0]],) = self._run_clips(planar, idx, rates[idx[0]], timestep, noise, keys, level, plain, opt)
+                (out[idx[0]],) = self._run_clips(planar, idx, rates[idx[0]], steps, noise, keys, level, plain, opt)
                 continue
             # a group's 48 kHz results are the caller's own without delivery, else still workspace-owned where delivery reads them
-            ys = self._ragged_group_rows([planar[i] for i in idx], [rates[i] for i in idx], timestep,
+            ys = self._ragged_group_rows([planar[i] for i in idx], [rates[i] for i in idx], steps,
                                          [noise[i] for i in idx] if keys is None else None,
                                          [keys[i] for i in idx] if keys is not None else None, ends, level, plain, own=opt is None)
             if opt is not None:
@@ -1134,6 +1274,8 @@ class FlowHighSR:
         'per_clip': the batched entries once per clip (on up to 4 side streams they measured 121.5 ms against 121.3 ms on one
         for a 24-clip mix: not worth the cross-stream bookkeeping), the results fresh tensors."""
         chans = [a.shape[0] for a in planar]
+        if isinstance(timestep, (list, tuple)):              # (one count per clip, sorted descending: a clip's rows share its count)
+            timestep = [s for s, c in zip(timestep, chans) for _ in range(c)]
         if keys is not None:
             prior = dict(keys=[k for k, c in zip(keys, chans) for _ in range(c)], **self._prior_scale())
         else:

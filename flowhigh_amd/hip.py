@@ -96,6 +96,26 @@ class StreamJob(C.Structure):
                 ("n_out", C.c_int32), ("n_keep", C.c_int32), ("ended", C.c_int32), ("pad_", C.c_int32)]
 
 
+MAX_GROUPS = 8              # FH_MAX_GROUPS of include/flowhigh_hip.h
+
+
+class RowGroups(C.Structure):
+    """fh_row_groups: the step groups of a ragged sequence as contiguous row ranges (csrc/steps.hip)."""
+    _fields_ = [("n", C.c_int32), ("row_end", C.c_int32 * MAX_GROUPS)]
+
+
+def row_groups(row_ends):
+    """fh_row_groups of the groups' cumulative row ends.  Nothing is checked here: the entries refuse what is not 1..8 groups
+    with strictly increasing ends."""
+    ends = [int(e) for e in row_ends]
+    return RowGroups(len(ends), (C.c_int32 * MAX_GROUPS)(*ends[:MAX_GROUPS]))
+
+
+def group_floats(values):
+    """One float per group as the host array the grouped entries read at call time."""
+    return (C.c_float * len(values))(*[float(v) for v in values])
+
+
 class HipError(RuntimeError):
     pass
 
@@ -174,6 +194,12 @@ _SIGS = {
     "fh_mel_splice_seg_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "fh_axpby_f32": [_P, _F, _P, _F, _P, C.c_longlong, _P],
     "fh_rk_combine_f32": [_P, _P, _I, _F, _P, _P, _P, _P, C.c_longlong, _P],
+    "fh_sizeof_row_groups": [],
+    "fh_time_fourier_groups_f32": [_P, _P, _P, _I, _I, _P],
+    "fh_gemv_rows_f32": [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
+    "fh_rmsnorm_groups_f32": [_P, _P, _P, C.c_longlong, _P, _I, _I, _P, _P],
+    "fh_axpy_groups_f32": [_P, _P, _P, _P, _I, _I, _P, _P],
+    "fh_rk_combine_groups_f32": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P],
     "fh_prior_normal_f32": [_P, _P, _P, _I, _I, _I, _P],
     "fh_prior_normal_at_f32": [_P, _P, _P, _P, _I, _I, _I, _P],
     "fh_spec_splice_f32": [_P, _P, _P, _P, _I, _I, _P],
@@ -251,7 +277,8 @@ def lib():
             or L.fh_sizeof_wino_group() != C.sizeof(WinoGroup) or L.fh_sizeof_sum_job() != C.sizeof(SumJob) \
             or L.fh_sizeof_amp_group() != C.sizeof(AmpGroup) or L.fh_sizeof_clip() != C.sizeof(Clip) \
             or L.fh_sizeof_rate() != C.sizeof(Rate) or L.fh_sizeof_pcm_clip() != C.sizeof(PcmClip) \
-            or L.fh_sizeof_xfade_job() != C.sizeof(XfadeJob) or L.fh_sizeof_stream_job() != C.sizeof(StreamJob):
+            or L.fh_sizeof_xfade_job() != C.sizeof(XfadeJob) or L.fh_sizeof_stream_job() != C.sizeof(StreamJob) \
+            or L.fh_sizeof_row_groups() != C.sizeof(RowGroups):
         raise HipError("descriptor struct layout mismatch between hip.py and flowhigh_hip.h")
     _lib = L
     return L

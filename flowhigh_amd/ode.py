@@ -15,6 +15,7 @@ y + h sum_{i<s} b_i k_i, 'k1', 'k2', ... the stages' fields.
 """
 from collections import namedtuple
 from fractions import Fraction as Fr
+from numbers import Integral
 
 ODE_METHODS = ("euler", "midpoint", "heun2", "heun3", "rk4")
 
@@ -55,6 +56,82 @@ def stages(method):
 def evaluations(method, time_steps, cond_scale=1.):
     """Passes of the vector field in one call: stages x steps, twice that under classifier-free guidance."""
     return stages(method) * int(time_steps) * (1 if float(cond_scale) == 1. else 2)
+
+
+MAX_STEP_GROUPS = 8            # FH_MAX_GROUPS of include/flowhigh_hip.h: the groups of one launch of csrc/steps.hip
+
+# groups: ((step count, number of segments), ...) in the segments' order, counts strictly descending.
+# passes[p]: ((t0_g, dt_g), ...) of the groups still active in pass p (those of count > p: a prefix of `groups`), as 0-d float32
+# tensors taken from torch.linspace(0, 1, count + 1)
+MixedSchedule = namedtuple("mixed_schedule", "groups passes")
+
+
+def check_steps(steps, n_clips, what="timestep"):
+    """A step count argument -> an int (one count for every clip; a list of equal counts is that int) or a list of one int per
+    clip.  Anything else is a ValueError: a bool, a float, a count below 1, a list of another length than n_clips."""
+    def one(s):
+        if isinstance(s, bool) or not isinstance(s, Integral) or int(s) < 1:
+            raise ValueError(f"{what}: a step count is an int >= 1, got {s!r}")
+        return int(s)
+    if isinstance(steps, (list, tuple)):
+        if len(steps) != n_clips:
+            raise ValueError(f"{what}: {len(steps)} step counts for {n_clips} clips")
+        steps = [one(s) for s in steps]
+        return steps[0] if len(set(steps)) == 1 else steps
+    return one(steps)
+
+
+def order_by_steps(steps):
+    """The positions 0 .. len(steps) - 1 sorted by step count, descending and stable (equal counts keep their order)."""
+    return sorted(range(len(steps)), key=lambda i: -steps[i])
+
+
+def split_by_steps(order, steps, max_groups=MAX_STEP_GROUPS):
+    """`order` (order_by_steps) cut into consecutive sequences of at most max_groups distinct counts each."""
+    out, cur, seen = [], [], []
+    for i in order:
+        if steps[i] not in seen:
+            if len(seen) == max_groups:
+                out.append(cur)
+                cur, seen = [], []
+            seen.append(steps[i])
+        cur.append(i)
+    if cur:
+        out.append(cur)
+    return out
+
+
+def mixed_schedule(steps):
+    """The time grid of one ragged sequence whose segments take different step counts: steps = the count of every segment,
+    sorted descending (order_by_steps).  Segments of one count are a group (at most MAX_STEP_GROUPS); pass p = 0 .. max(steps) - 1
+    runs the groups whose count is above p -- after the sort always a prefix of the segments -- and group g takes
+    t0_g = linspace(0, 1, s_g + 1)[p] and dt_g = linspace[p + 1] - linspace[p] in float32, the expressions
+    FlowHighSR._integrate uses for a sequence of one count.  stage_time and fused_weight are that method's too."""
+    import torch
+    steps = [int(s) for s in steps]
+    if not steps or min(steps) < 1 or any(a < b for a, b in zip(steps, steps[1:])):
+        raise ValueError(f"mixed_schedule: step counts >= 1 sorted descending, got {steps}")
+    groups = []
+    for s in steps:
+        if groups and groups[-1][0] == s:
+            groups[-1][1] += 1
+        else:
+            groups.append([s, 1])
+    if len(groups) > MAX_STEP_GROUPS:
+        raise ValueError(f"mixed_schedule: {len(groups)} distinct step counts, at most {MAX_STEP_GROUPS} in one sequence (split_by_steps)")
+    grids = [torch.linspace(0, 1, s + 1) for s, _ in groups]
+    passes = tuple(tuple((t[p], t[p + 1] - t[p]) for (s, _), t in zip(groups, grids) if s > p) for p in range(steps[0]))
+    return MixedSchedule(tuple((s, n) for s, n in groups), passes)
+
+
+def stage_time(t0, dt, c):
+    """The time of a stage at c of a step from t0 of size dt (float32 tensors from the linspace grid) as the float the kernels take."""
+    return float(t0) if c == 0. else float(t0 + c * dt)
+
+
+def fused_weight(weight, dt):
+    """weight * h of an eval_fused record, rounded as the float32 product it is."""
+    return float(weight * dt)
 
 
 def step_plan(method):

@@ -2,7 +2,8 @@
 `generate((sr_in, audio), sr_out, timestep)` per HTTP request, one clip at a time).
 
 Requests from any number of caller threads are collected for a few milliseconds, grouped by (input rate,
-steps) -- by steps alone with mix_rates=True, the clips' rates going on as a list -- and pushed through `FlowHighSR.generate_many`: clips of ANY lengths then run as one ragged launch
+steps) -- by steps alone with mix_rates=True, the clips' rates going on as a list; without the steps with mix_steps=True, the
+requests' step counts going on as a list -- and pushed through `FlowHighSR.generate_many`: clips of ANY lengths then run as one ragged launch
 sequence on the GPU (equal lengths as one batch) while every caller still gets exactly what `generate()` would
 have returned for its clip alone (same per-clip noise draw when a seed is given; on a prior='device' model the seed is the
 clip's key (seed, 0) and the noise is drawn on the device).  Host logic only: no gradio,
@@ -32,8 +33,21 @@ def resolve_mix_rates(mix_rates=None):
     return bool(mix_rates)
 
 
+MIX_STEPS_DEFAULT = False
+
+
+def resolve_mix_steps(mix_steps=None):
+    """mix_steps= of BatchingServer: the keyword, else FH_SERVE_MIX_STEPS (1 / 0), else MIX_STEPS_DEFAULT."""
+    if mix_steps is None:
+        env = os.environ.get("FH_SERVE_MIX_STEPS")
+        if env not in (None, "", "0", "1"):
+            raise ValueError(f"FH_SERVE_MIX_STEPS must be 0 or 1, got {env!r}")
+        return MIX_STEPS_DEFAULT if not env else env == "1"
+    return bool(mix_steps)
+
+
 class BatchingServer:
-    def __init__(self, model, max_batch=32, max_wait_ms=5.0, ends=None, mix_rates=None):
+    def __init__(self, model, max_batch=32, max_wait_ms=5.0, ends=None, mix_rates=None, mix_steps=None):
         """ends: 'per_clip' | 'ragged' | None (FH_RAGGED_ENDS, else 'per_clip'), handed to generate_many: how the front and back
         end of a ragged group run (flowhighsr.resolve_ends); a wrong value is a ValueError here, not in the worker.
         mix_rates: True | False | None (FH_SERVE_MIX_RATES = 1 / 0, else MIX_RATES_DEFAULT).  True: a collected batch is
@@ -41,10 +55,17 @@ class BatchingServer:
         one call per (input rate, steps), the grouping before generate_many took a rate list.  The results are the same bits
         either way.  Measured (profiles/mixed_rates.md, 24 clips over four rates): the one mixed call is 2.2-2.6 ms of ~86-90 ms
         faster than the four per-rate calls; the default is False all the same, because a default server is pinned never to
-        hand two input rates to one call (tests/test_parallel_cpu.py) and models whose generate_many takes one rate stay usable."""
+        hand two input rates to one call (tests/test_parallel_cpu.py) and models whose generate_many takes one rate stay usable.
+        mix_steps: True | False | None (FH_SERVE_MIX_STEPS = 1 / 0, else MIX_STEPS_DEFAULT).  True: the step count leaves the
+        group key and a group is ONE generate_many call with the requests' step counts as a list (timestep=[s_0, ...]: one ragged
+        sequence with a time per clip, flowhighsr._integrate_mixed); a window of one count hands over the int it always did.
+        False: one call per step count.  The same bits either way; profiles/mixed_steps.md has the measurement.  The default is
+        False: a default server's grouping is pinned (tests/test_parallel_cpu.py), and a model whose generate_many takes one
+        count stays usable."""
         from .flowhighsr import resolve_ends
         self.ends = resolve_ends(ends)
         self.mix_rates = resolve_mix_rates(mix_rates)
+        self.mix_steps = resolve_mix_steps(mix_steps)
         # (handed on only when something asked for a form: a model whose generate_many predates ends= keeps working)
         self._ends_kw = dict(ends=self.ends) if (ends is not None or os.environ.get("FH_RAGGED_ENDS")) else {}
         self.model = model
@@ -151,7 +172,9 @@ class BatchingServer:
                 # same step count and level; mix_rates off: same input rate too
                 # ... and the same delivery (output rate, sample format, dither, layout, loudness, true peak, limiter; the dither seed
                 # is the request's own)
-                groups.setdefault((None if self.mix_rates else item[1], item[2], item[5], item[6] and item[6][:7]), []).append(item)
+                # (mix_steps on: any step counts, going on as a list)
+                groups.setdefault((None if self.mix_rates else item[1], None if self.mix_steps else item[2], item[5],
+                                   item[6] and item[6][:7]), []).append(item)
             for (sr_in, steps, level, deliv), items in groups.items():
                 try:
                     # (handed on only where a request asked: a model whose generate_many predates the keywords keeps working.
@@ -173,6 +196,10 @@ class BatchingServer:
                         sr_in = [it[1] for it in items]
                         if len(set(sr_in)) == 1:          # (one rate in the window: the call it has always been)
                             sr_in = sr_in[0]
+                    if steps is None:
+                        steps = [it[2] for it in items]
+                        if len(set(steps)) == 1:          # (one count in the window: the call it has always been)
+                            steps = steps[0]
                     noise, prior = None, {}
                     if getattr(self.model, "prior", "reference") == "device":
                         # the device prior: a request's seed is its key (seed, 0); nothing is drawn on the host
