@@ -65,6 +65,8 @@ def fold_gamma(w2, b2, gamma):
 
 
 class ConvNextNet:
+    grouped_field = False          # (the time-conditioned LayerNorm takes one time: no forward(groups=))
+
     def __init__(self, sd, device, bf=False):
         self.device = hip.norm_device(device)
         dev = self.device

@@ -54,6 +54,8 @@ def pack_geglu(w, b):
 
 
 class FlowNet:
+    grouped_field = True           # forward(groups=): a time per group of rows, for clips of different step counts in one sequence
+
     def __init__(self, sd, device, depth=2, heads=16, dim_head=64, store=None, bf=False, attn_form="f32", attn_window=None):
         if dim_head != 64:
             raise NotImplementedError("dim_head must be 64")

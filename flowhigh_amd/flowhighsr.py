@@ -4,7 +4,7 @@ Mirrors flowhighsr.py:21-149 of the reference's src/flowhigh/ (`FlowHighSR`: cto
 `generate`, `set_cfm_method`, `from_local`, `from_pretrained`) and the inference half of
 cfm_superresolution.py:94-284 (`ConditionalFlowMatcherWrapper`:
 `sample`, `load`, `device`, `odeint_kwargs`, `sigma`, `cfm_method`).  torchdiffeq's fixed-grid
-steppers (call site cfm:243; euler, midpoint, heun2, heun3, rk4) are tableaus in ode.py, run by `_integrate`.
+steppers (call site cfm:243; euler, midpoint, heun2, heun3, rk4) are tableaus in ode.py, run by integrate.py.
 
 Everything numerical runs in the HIP kernels of libflowhigh_hip.so; this file only moves
 tensors, picks shapes and sequences launches.  There is no CPU path: constructing the model on
@@ -28,7 +28,6 @@ Extensions over the reference (all keyword-only, defaults keep reference behavio
                                      windows that share one keyed prior at their absolute frames, cross-faded on the device
                                      (stream.py is the definition, streaming.py the host side, csrc/stream.hip the seam; DESIGN.md "Streaming")
 """
-import ctypes
 import json
 from pathlib import Path
 
@@ -37,7 +36,7 @@ import os
 import numpy as np
 import torch
 
-from . import hip, ode
+from . import hip, integrate, ode
 from .flow import FlowNet
 from .delivery import Delivery, resolve_delivery
 from .frontend import LogMel, PostProcessor, Resampler, _starts, _views, clip_rates
@@ -766,123 +765,6 @@ class FlowHighSR:
         z = self._device_prior(keys, count, max(frames), seg=seg, rows=sum(frames))
         return [v[None] for v in _views(z, _starts(frames), frames)]
 
-    def _integrate(self, y0, cond_mel, batch, n, time_steps, cond_scale=1., ragged=None):
-        """Fixed-grid explicit Runge-Kutta methods (torchdiffeq semantics; ode.ODE_METHODS); y0, cond_mel [B*n, n_mels] on device.
-        One time step is the records of ode.step_plan(method).  Every update `out = base + h * v(x, t)` is the epilogue of the
-        last GEMM of the vector field (eval_fused; a raw k is the same with alpha = 1 and no base: eval); with classifier-free
-        guidance v = null + s (cond - null) it is two chained epilogues.  The stage arithmetic between the evaluations of heun2,
-        heun3 and rk4 is fh_rk_combine_f32 (combine).  euler and midpoint are one and two eval_fused and nothing else."""
-        if isinstance(time_steps, (list, tuple)):
-            return self._integrate_mixed(y0, cond_mel, time_steps, cond_scale, ragged)
-        net = self.flowhigh.net
-        plan = ode.step_plan(self.odeint_kwargs['method'])          # (NotImplementedError for a name outside ODE_METHODS)
-        net.set_cond(cond_mel, batch, n, ragged=ragged)
-        t = torch.linspace(0, 1, time_steps + 1)
-        y = y0
-        bufs = [torch.empty_like(y0) for _ in range(4)]
-        names = {d for r in plan for d in (r[-1], getattr(r, "dst_a", None)) if d not in (None, "out", "x")}
-        stage = {"x": bufs[2], **{name: torch.empty_like(y0) for name in sorted(names)}}
-        L, st, n_el = hip.lib(), hip.stream(), y0.numel()
-
-        def axpy_field(x, tt, out, h, base):           # out = base + h * v(x, tt)
-            if cond_scale == 1.:
-                net.forward(x, tt, out, batch, n, alpha=h, res=base, ragged=ragged)
-            else:
-                net.forward(x, tt, bufs[3], batch, n, alpha=h * (1. - cond_scale), res=base, null_cond=True, ragged=ragged)
-                net.forward(x, tt, out, batch, n, alpha=h * cond_scale, res=bufs[3], ragged=ragged)
-
-        for i in range(time_steps):
-            t0, dt = t[i], t[i + 1] - t[i]
-            stage["y"], stage["out"] = y, bufs[i % 2]
-            for r in plan:
-                if isinstance(r, ode.Combine):
-                    ks = (ctypes.c_void_p * len(r.ks))(*[stage[k].data_ptr() for k in r.ks])
-                    wa = (ctypes.c_float * len(r.ks))(*r.wa)
-                    wb = None if r.wb is None else (ctypes.c_float * len(r.ks))(*r.wb)
-                    hip.check(L.fh_rk_combine_f32(y.data_ptr(), ks, len(r.ks), float(dt), wa, stage[r.dst_a].data_ptr(), wb,
-                                                  hip.ptr(None if r.dst_b is None else stage[r.dst_b]), n_el, st),
-                              "fh_rk_combine_f32")
-                    continue
-                tt = float(t0) if r.c == 0. else float(t0 + r.c * dt)          # float32, from the linspace grid
-                if isinstance(r, ode.Eval):
-                    axpy_field(stage[r.src], tt, stage[r.dst], 1., None)
-                else:
-                    axpy_field(stage[r.src], tt, stage[r.dst], float(r.weight * dt), stage[r.base])
-            y = stage["out"]
-        return y
-
-    def _integrate_mixed(self, y0, cond_mel, steps, cond_scale, ragged):
-        """_integrate for a ragged sequence whose segments take different step counts: steps = the count of every segment of
-        `ragged`, sorted descending.  The segments of one count are a group of rows; pass p runs the records of the step plan
-        over the groups that still have a step p (a prefix of the rows), every group at its own time and step size
-        (ode.mixed_schedule), and a group's rows go into the result when its own last step is done.  The field is always
-        written raw and the update out = base + (weight h_g) v is fh_axpy_groups_f32, the bits of the GEMM epilogue that applies
-        it in _integrate; under guidance it is two raw fields and two chained updates with alphas h_g (1 - s) and h_g s; combine
-        is fh_rk_combine_groups_f32.  A segment's rows are the bits of _integrate on that segment alone at its count."""
-        net = self.flowhigh.net
-        plan = ode.step_plan(self.odeint_kwargs['method'])
-        sched = ode.mixed_schedule(steps)
-        frames = ragged["frames"]
-        # per group: segments and rows up to its end
-        seg_end, row_end = [], []
-        for _, n_segs in sched.groups:
-            seg_end.append((seg_end[-1] if seg_end else 0) + n_segs)
-            row_end.append(sum(frames[:seg_end[-1]]))
-        net.set_cond(cond_mel, len(frames), ragged["max_n"], ragged=ragged)
-        d = y0.shape[-1]
-        y, result = y0, torch.empty_like(y0)
-        bufs = [torch.empty_like(y0) for _ in range(5)]
-        names = {d_ for r in plan for d_ in (r[-1], getattr(r, "dst_a", None)) if d_ not in (None, "out", "x")}
-        stage = {"x": bufs[2], **{name: torch.empty_like(y0) for name in sorted(names)}}
-        L, st = hip.lib(), hip.stream()
-        field = bufs[4]
-
-        def axpy(v, alphas, base, out, rows, grp):
-            hip.check(L.fh_axpy_groups_f32(v.data_ptr(), hip.group_floats(alphas), hip.ptr(base), out.data_ptr(), rows, d,
-                                           ctypes.byref(grp), st), "fh_axpy_groups_f32")
-
-        for p, active in enumerate(sched.passes):
-            G = len(active)
-            rows, n_seg, ends = row_end[G - 1], seg_end[G - 1], row_end[:G]
-            grp = hip.row_groups(ends)
-            stage["y"], stage["out"] = y, bufs[p % 2]
-
-            def axpy_field(x, times, out, hs, base):           # out = base + h_g * v(x, times_g)
-                kw = dict(ragged=ragged, groups=(ends, times), n_seg=n_seg)
-                if cond_scale == 1.:
-                    if base is None and all(h == 1. for h in hs):          # (a raw k)
-                        net.forward(x, None, out, 0, 0, **kw)
-                        return
-                    net.forward(x, None, field, 0, 0, **kw)
-                    axpy(field, hs, base, out, rows, grp)
-                else:
-                    net.forward(x, None, field, 0, 0, null_cond=True, **kw)
-                    axpy(field, [h * (1. - cond_scale) for h in hs], base, bufs[3], rows, grp)
-                    net.forward(x, None, field, 0, 0, **kw)
-                    axpy(field, [h * cond_scale for h in hs], bufs[3], out, rows, grp)
-
-            for r in plan:
-                if isinstance(r, ode.Combine):
-                    ks = (ctypes.c_void_p * len(r.ks))(*[stage[k].data_ptr() for k in r.ks])
-                    wa = (ctypes.c_float * len(r.ks))(*r.wa)
-                    wb = None if r.wb is None else (ctypes.c_float * len(r.ks))(*r.wb)
-                    hip.check(L.fh_rk_combine_groups_f32(y.data_ptr(), ks, len(r.ks), hip.group_floats([float(dt) for _, dt in active]), wa,
-                                                         stage[r.dst_a].data_ptr(), wb, hip.ptr(None if r.dst_b is None else stage[r.dst_b]),
-                                                         rows, d, ctypes.byref(grp), st), "fh_rk_combine_groups_f32")
-                    continue
-                times = [ode.stage_time(t0, dt, r.c) for t0, dt in active]
-                if isinstance(r, ode.Eval):
-                    axpy_field(stage[r.src], times, stage[r.dst], [1.] * G, None)
-                else:
-                    axpy_field(stage[r.src], times, stage[r.dst], [ode.fused_weight(r.weight, dt) for _, dt in active], stage[r.base])
-            y = stage["out"]
-            # the groups whose last step this was (one count: one contiguous range of rows): one device copy
-            done = [g for g, (s, _) in enumerate(sched.groups[:G]) if s == p + 1]
-            if done:
-                r0 = row_end[done[0] - 1] if done[0] else 0
-                result[r0:row_end[done[-1]]].copy_(y[r0:row_end[done[-1]]])
-        return result
-
     def _cutoff_bins(self, cond_mel, n_seg, n, seg=None):
         """int32 [n_seg] cutoff bin of every clip, two launches: n_seg clips of n rows, or (seg: the device segment table)
         clips of different lengths packed back to back."""
@@ -935,7 +817,8 @@ class FlowHighSR:
             if cfm_method == 'independent_cfm_mix':     # cfm:231-237, cutoff bins per clip
                 cut = self._cutoff_bins(cond_mel, n_seg, n, seg)
                 y0 = self._mel_replace(noise, y0, cut, n_seg, n, seg)
-        mel = self._integrate(y0, cond_mel, n_seg, n, time_steps, float(cond_scale), ragged=ragged)
+        mel = integrate.solve(self.flowhigh.net, self.odeint_kwargs['method'], y0, cond_mel, n_seg, n, time_steps, float(cond_scale),
+                              ragged=ragged)
         if mel_pp:                                      # cfm:278-279, per clip
             cut = cut if cut is not None else self._cutoff_bins(cond_mel, n_seg, n, seg)
             mel = self._mel_replace(mel, cond_mel, cut, n_seg, n, seg)
@@ -988,7 +871,7 @@ class FlowHighSR:
         lengths as one launch sequence.
         conds: list of [T48_i] device tensors (peak-normalised), noises: list of [1, N_i, n_mels] host tensors, or None and
         keys = the clips' (seed, stream) keys: the prior is then drawn on the device, one launch over the segment table.
-        time_steps: one count, or a list of one count per clip, sorted descending (at most 8 distinct: _integrate_mixed).
+        time_steps: one count, or a list of one count per clip, sorted descending (at most 8 distinct: integrate.solve).
         Returns the vocoder's waveforms, a list of [1, 480 N_i] (plan-owned buffers; decode_to_audio=False: the mels,
         a list of [N_i, n_mels]), each what _sample gives for that clip alone: the log-mels are made per clip, every
         row-wise operator runs on the packed rows, the operators that look across rows take the clip boundaries (the
@@ -1037,14 +920,12 @@ class FlowHighSR:
         if isinstance(time_steps, list):
             # one step count per clip: the clips sorted by count (descending, stable) into sequences of at most 8 distinct counts
             # (one count each on the convnext backbone, which has no grouped form), the results put back in list order
-            limit = ode.MAX_STEP_GROUPS if getattr(self.flowhigh, "architecture", "transformer") != "convnext" else 1
-            seqs = [(part, [time_steps[i] for i in part]) for part in ode.split_by_steps(ode.order_by_steps(time_steps), time_steps, limit)]
+            limit = ode.MAX_STEP_GROUPS if self.flowhigh.net.grouped_field else 1
+            seqs = ode.step_sequences(list(range(len(conds))), time_steps, limit)
         else:
             seqs = [(list(range(len(conds))), time_steps)]
         result = [None] * len(conds)
         for idx, steps in seqs:
-            if isinstance(steps, list) and len(set(steps)) == 1:
-                steps = steps[0]
             outs = self._sample_ragged([conds[i] for i in idx], steps, cfm_method, noises=None if noise is None else [noise[i] for i in idx],
                                        std_1=std_1, std_2=std_2, cond_scale=cond_scale, mel_pp=mel_pp, decode_to_audio=decode_to_audio,
                                        keys=None if keys is None else [keys[i] for i in idx])
@@ -1153,7 +1034,7 @@ class FlowHighSR:
         timestep: one step count for the list, or ONE COUNT PER CLIP -- generate_many(clips, sr, 48000, [1, 4, 2, ...]); a list of
         another length than `clips`, or an entry that is no int >= 1 (a bool, a float, 0) is a ValueError before any GPU work
         (ode.check_steps).  A list of equal counts is the int, and an int runs what it always ran.  Mixed counts run as ragged
-        sequences with a time and a step size per clip (_integrate_mixed, csrc/steps.hip): the clips of a ragged group sorted by
+        sequences with a time and a step size per clip (integrate.py, csrc/steps.hip): the clips of a ragged group sorted by
         count, descending and stable, max(steps) passes over a shrinking prefix of the rows, at most 8 distinct counts per
         sequence (a group with more is cut into several), the results back in list order; priors, keys and dither keys stay
         tied to a clip's place in the list.  Clip i is bit for bit generate(clip_i, sr_i, timestep=steps[i]), with every option
@@ -1184,11 +1065,10 @@ class FlowHighSR:
         shapes = [tuple(z.shape) for z in noise] if noise is not None else [(1, n, self.flowhigh.n_mels) for n in frames]
         if ragged is None:
             ragged = os.environ.get("FH_RAGGED", "1") != "0"
-        # mixed step counts run as ragged sequences with a time per clip (_integrate_mixed) -- clips of one shape included -- where
+        # mixed step counts run as ragged sequences with a time per clip (integrate.py) -- clips of one shape included -- where
         # the vector field has the grouped form; the convnext backbone (its time-conditioned LayerNorm takes one time), ragged
         # off and an unmergeable vocoder plan run one batch per (shape, step count) below
-        grouped_field = getattr(self.flowhigh, "architecture", "transformer") != "convnext"
-        if ragged and (len(set(zip(lengths, rates))) > 1 if not mixed else grouped_field):
+        if ragged and (len(set(zip(lengths, rates))) > 1 if not mixed else self.flowhigh.net.grouped_field):
             try:
                 return self._generate_many_ragged(planar, rates, timestep, noise, max_frames, keys, [sh[1] for sh in shapes], ends,
                                                   level, plain, opt)
@@ -1242,15 +1122,7 @@ class FlowHighSR:
         # mixed step counts in a group: its clips sorted by count, descending and stable, cut into sequences of at most 8 distinct
         # counts (one launch of csrc/steps.hip takes 8 groups).  idx carries the clips' places in the caller's list through the
         # run and the delivery: priors, keys and dither keys stay tied to them, the results go back by them
-        seqs = []
-        for idx in groups:
-            counts = [steps_of(i) for i in idx]
-            if len(set(counts)) == 1:
-                seqs.append((idx, counts[0]))
-            else:
-                for part in ode.split_by_steps(ode.order_by_steps(counts), counts):
-                    part_counts = [counts[k] for k in part]
-                    seqs.append(([idx[k] for k in part], part_counts[0] if len(set(part_counts)) == 1 else part_counts))
+        seqs = [seq for idx in groups for seq in ode.step_sequences(idx, [steps_of(i) for i in idx])]
         out = [None] * len(planar)
         for idx, steps in [([i], steps_of(i)) for i in alone] + seqs:
             if len(idx) == 1:

@@ -2,8 +2,9 @@
 
 The reference hands `torchdiffeq_ode_method` to torchdiffeq.odeint (cfm_superresolution.py:115-119,243); the fixed-grid solvers of
 that library are restated here as tableaus (c, A, b):  k_j = v(y + h sum_i a_ji k_i, t0 + c_j h),  y' = y + h sum_j b_j k_j.
-`step_plan` turns a tableau into named records, in the style of the vocoder's launch records; FlowHighSR._integrate runs them.
-No GPU import: the plans are plain data and are checked on the CPU (tests/test_ode_cpu.py).
+`step_plan` turns a tableau into named records, in the style of the vocoder's launch records; `run_step` is the one loop over them,
+over two callables: integrate.py hands it the launches, the CPU tests their models.  No GPU import: the plans are plain data and the
+loop is checked on the CPU (tests/test_ode_cpu.py).
 
     eval(src, c, dst)                      dst = v(src, t0 + c h)                    the field written raw (alpha = 1, res = None)
     eval_fused(src, c, base, weight, dst)  dst = base + (weight h) v(src, t0 + c h)  the update in the last GEMM's epilogue
@@ -101,12 +102,20 @@ def split_by_steps(order, steps, max_groups=MAX_STEP_GROUPS):
     return out
 
 
+def step_sequences(idx, counts, max_groups=MAX_STEP_GROUPS):
+    """The clips idx, of step counts `counts`, as the ragged sequences they run in: [(clips, their counts), ...], sorted by count
+    (descending, stable), cut at max_groups distinct counts; counts that are all one count are that int."""
+    parts = split_by_steps(order_by_steps(counts), counts, max_groups)
+    steps = [[counts[k] for k in part] for part in parts]
+    return [([idx[k] for k in part], s[0] if len(set(s)) == 1 else s) for part, s in zip(parts, steps)]
+
+
 def mixed_schedule(steps):
     """The time grid of one ragged sequence whose segments take different step counts: steps = the count of every segment,
     sorted descending (order_by_steps).  Segments of one count are a group (at most MAX_STEP_GROUPS); pass p = 0 .. max(steps) - 1
     runs the groups whose count is above p -- after the sort always a prefix of the segments -- and group g takes
     t0_g = linspace(0, 1, s_g + 1)[p] and dt_g = linspace[p + 1] - linspace[p] in float32, the expressions
-    FlowHighSR._integrate uses for a sequence of one count.  stage_time and fused_weight are that method's too."""
+    integrate.solve uses for a sequence of one count.  stage_time and fused_weight are its uniform form's too."""
     import torch
     steps = [int(s) for s in steps]
     if not steps or min(steps) < 1 or any(a < b for a, b in zip(steps, steps[1:])):
@@ -175,3 +184,25 @@ def step_plan(method):
     base = "base" if any(isinstance(r, Combine) and "base" in (r.dst_a, r.dst_b) for r in plan) else "y"
     plan.append(EvalFused(src, c[s - 1], base, b[s - 1], "out"))
     return plan
+
+
+def stage_names(plan):
+    """The buffers a plan writes besides 'out' and 'x' (and 'y', which it only reads), sorted: 'base', 'k1', ..."""
+    return sorted({d for r in plan for d in (r[-1], getattr(r, "dst_a", None)) if d not in (None, "out", "x")})
+
+
+def run_step(plan, stage, field, combine):
+    """One time step, the only loop over the records: `stage` maps names to buffers ('y' and 'out' set by the caller), the backend
+    owns t0, h, guidance and rounding.  Its two callables return what they made and are handed the buffer of that name to write
+    into (None where `stage` has none: then they return fresh values): field(src, c, base, weight, dst) -> base + (weight h)
+    v(src, t0 + c h), or v raw with weight = base = None; combine(y, ks, wa, dst_a, wb, dst_b) -> the record's pair."""
+    for r in plan:
+        if isinstance(r, Combine):
+            stage[r.dst_a], b = combine(stage["y"], [stage[k] for k in r.ks], r.wa, stage.get(r.dst_a), r.wb, stage.get(r.dst_b))
+            if r.dst_b is not None:
+                stage[r.dst_b] = b
+        elif isinstance(r, Eval):
+            stage[r.dst] = field(stage[r.src], r.c, None, None, stage.get(r.dst))
+        else:
+            stage[r.dst] = field(stage[r.src], r.c, stage[r.base], r.weight, stage.get(r.dst))
+    return stage["out"]

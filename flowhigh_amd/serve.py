@@ -58,7 +58,7 @@ class BatchingServer:
         hand two input rates to one call (tests/test_parallel_cpu.py) and models whose generate_many takes one rate stay usable.
         mix_steps: True | False | None (FH_SERVE_MIX_STEPS = 1 / 0, else MIX_STEPS_DEFAULT).  True: the step count leaves the
         group key and a group is ONE generate_many call with the requests' step counts as a list (timestep=[s_0, ...]: one ragged
-        sequence with a time per clip, flowhighsr._integrate_mixed); a window of one count hands over the int it always did.
+        sequence with a time per clip, integrate.py's grouped form); a window of one count hands over the int it always did.
         False: one call per step count.  The same bits either way; profiles/mixed_steps.md has the measurement.  The default is
         False: a default server's grouping is pinned (tests/test_parallel_cpu.py), and a model whose generate_many takes one
         count stays usable."""

@@ -23,7 +23,9 @@ pytestmark = pytest.mark.gpu
 
 if __name__ == "__main__":                                                # (--record: no conftest has put the package on the path)
     sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from test_hip_ragged_ends import clip_list, count_calls, model_for       # noqa: E402
+from flowhigh_amd import FlowHighSR                                       # noqa: E402
+from oracle import ref_cpu                                                # noqa: E402
+from test_hip_ragged_ends import clip_list, count_calls, model_for, net_for       # noqa: E402
 
 FIXTURE = Path(__file__).resolve().parent / "golden" / "generate_launch_names.json"
 SR = 12000
@@ -37,6 +39,14 @@ def models():
     if "models" not in _STATE:
         _STATE["models"] = model_for(), model_for(prior="device")
     return _STATE["models"]
+
+
+def method_model(method):
+    """model_for() with another ODE method (the forms that pin the steppers beyond euler x 1)."""
+    if method not in _STATE:
+        _STATE[method] = FlowHighSR(net_for("TINY_CFG"), sigma=0.0, cfm_method="basic_cfm", torchdiffeq_ode_method=method,
+                                    upsampling_method="hip", prior="reference")
+    return _STATE[method]
 
 
 def inputs():
@@ -68,7 +78,14 @@ def forms():
 
     mono, mixed, buckets = (0, 1, 2), (0, "st", 2), (0, 2, 3, 0)
     long_clip = c[1][:3600]
+    # the steppers beyond euler x 1: the clips' 48 kHz conditionings for sample / sample_many, the other methods' models
+    conds, (xs, zs) = [ref_cpu.preprocess(c[i], SR)[0] for i in mono], pick(*mono)
+    rk4, heun3 = method_model("rk4"), method_model("heun3")
     return {
+        "sample_rk4_guided": (True, lambda: rk4.sample(cond=conds[0][None], time_steps=2, cond_scale=1.3, noise=zs[0])),
+        "many_heun3_ragged": (True, lambda: heun3.generate_many(xs, SR, 48000, 2, noise=zs, ends="ragged")),
+        "many_rk4_mixed_steps": (True, lambda: rk4.generate_many(xs, SR, 48000, [1, 3, 2], noise=zs, ends="ragged")),
+        "sample_many_mixed_guided": (True, lambda: m.sample_many(conds, time_steps=[1, 3, 2], cond_scale=1.3, mel_pp=True, noise=zs)),
         "generate": (True, lambda: m.generate(c[0], SR, 48000, 1, noise=z[0])),
         "generate_level_input": (False, lambda: m.generate(c[0], SR, 48000, 1, noise=z[0], level="input")),
         "generate_stereo": (False, lambda: m.generate(c["st"], SR, 48000, 1, noise=z["st"], channels="first")),

@@ -1,5 +1,5 @@
 """GPU: the ODE methods heun2 / heun3 / rk4 -- fh_rk_combine_f32 (csrc/ode.hip) at its edges against a float64 evaluation, and the
-tableau stepper of FlowHighSR._integrate through sample / generate_batch / generate_many / sample_many / capture on both backbones,
+tableau stepper of integrate.solve through sample / generate_batch / generate_many / sample_many / capture on both backbones,
 against the textbook stepper (tests/ref_odeint.py) over the oracle's vector field.
 
 Bars.  Kernel: per element 2^-21 (|y| + |h| sum |w_j k_j|) -- at most 5 roundings of half an ulp (2^-24 relative each, of partial

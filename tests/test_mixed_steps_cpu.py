@@ -33,18 +33,17 @@ def test_schedule_is_the_linspace_grid_of_every_count(steps):
             assert s > p and t0.dtype == dt.dtype == torch.float32
             seen[s].append((t0, dt))
     for s in counts:
-        t = torch.linspace(0, 1, s + 1)                      # what _integrate takes for a sequence of that count alone
+        t = torch.linspace(0, 1, s + 1)                      # what integrate.solve takes for a sequence of that count alone
         assert len(seen[s]) == s
         for i, (t0, dt) in enumerate(seen[s]):
             assert torch.equal(t0, t[i]) and torch.equal(dt, t[i + 1] - t[i])
+
+            def field(src, c, base, weight, dst):            # every evaluation of a step: its time and its weight
+                assert ode.stage_time(t0, dt, c) == (float(t[i]) if c == 0. else float(t[i] + c * (t[i + 1] - t[i])))
+                if weight is not None:
+                    assert ode.fused_weight(weight, dt) == float(weight * (t[i + 1] - t[i]))
             for method in ode.ODE_METHODS:
-                for r in ode.step_plan(method):
-                    if isinstance(r, ode.Combine):
-                        continue
-                    want = float(t[i]) if r.c == 0. else float(t[i] + r.c * (t[i + 1] - t[i]))
-                    assert ode.stage_time(t0, dt, r.c) == want
-                    if isinstance(r, ode.EvalFused):
-                        assert ode.fused_weight(r.weight, dt) == float(r.weight * (t[i + 1] - t[i]))
+                ode.run_step(ode.step_plan(method), {"y": None}, field, lambda *args: (None, None))
 
 
 def test_schedule_refuses_what_is_not_sorted_or_too_many_counts():
@@ -67,9 +66,9 @@ def coeff_b(t):
 
 
 def integrate_lockstep(method, steps, y0):
-    """The records of step_plan(method) over mixed_schedule(steps) in numpy float64, as _integrate_mixed sequences them: pass p
-    over the rows of the active prefix, every row at its group's time and step, a group's rows copied out after its last step.
-    y0 [len(steps), d]; dy/dt = a(t) y + b(t)."""
+    """The records of step_plan(method) over mixed_schedule(steps) in numpy float64, as integrate.solve sequences its grouped
+    form: pass p is ode.run_step over the rows of the active prefix, every row at its group's time and step, a group's rows
+    copied out after its last step.  y0 [len(steps), d]; dy/dt = a(t) y + b(t)."""
     sched, plan = ode.mixed_schedule(steps), ode.step_plan(method)
     seg_end = np.cumsum([n for _, n in sched.groups])
     y, result = y0.copy(), np.full_like(y0, np.nan)
@@ -79,18 +78,18 @@ def integrate_lockstep(method, steps, y0):
         per_row = np.repeat(np.arange(G), [n for _, n in sched.groups[:G]])
         t0 = np.array([float(a[0]) for a in active])[per_row][:, None]
         dt = np.array([float(a[1]) for a in active])[per_row][:, None]
-        stage = {"y": y[:rows]}
-        for r in plan:
-            if isinstance(r, ode.Combine):
-                for w, dst in ((r.wa, r.dst_a), (r.wb, r.dst_b)):
-                    if dst is not None:
-                        stage[dst] = stage["y"] + dt * sum(wj * stage[k] for wj, k in zip(w, r.ks) if wj != 0.)
-                continue
-            tt = t0 + r.c * dt
-            v = coeff_a(tt) * stage[r.src] + coeff_b(tt)
-            stage[r.dst] = v if isinstance(r, ode.Eval) else stage[r.base] + (r.weight * dt) * v
+
+        def field(src, c, base, weight, dst):
+            tt = t0 + c * dt
+            v = coeff_a(tt) * src + coeff_b(tt)
+            return v if weight is None else base + (weight * dt) * v
+
+        def combine(y_, ks, wa, dst_a, wb, dst_b):
+            return tuple(None if w is None else y_ + dt * sum(wj * k for wj, k in zip(w, ks) if wj != 0.) for w in (wa, wb))
+
+        out = ode.run_step(plan, {"y": y[:rows]}, field, combine)
         y = y.copy()
-        y[:rows] = stage["out"]
+        y[:rows] = out
         for g, (s, _) in enumerate(sched.groups[:G]):
             if s == p + 1:
                 r0 = int(seg_end[g - 1]) if g else 0
@@ -150,6 +149,25 @@ def test_nine_distinct_counts_split_into_two_sequences():
         ode.mixed_schedule([steps[i] for i in part])               # (each is a schedule of at most 8 groups)
     assert ode.split_by_steps(ode.order_by_steps([2, 1, 2]), [2, 1, 2]) == [[0, 2, 1]]
     assert ode.split_by_steps(ode.order_by_steps([2, 1, 2]), [2, 1, 2], 1) == [[0, 2], [1]]
+
+
+def test_step_sequences_sort_cut_and_collapse_one_count_to_an_int():
+    """The clips of a group -> (clips, an int or a descending list of counts) per ragged sequence, the clips by their own ids."""
+    idx = [10, 11, 12, 13, 14, 15, 16]
+    assert ode.step_sequences(idx, [1, 4, 2, 4, 1, 2, 4]) == [([11, 13, 16, 12, 15, 10, 14], [4, 4, 4, 2, 2, 1, 1])]
+    assert ode.step_sequences(idx[:3], [3, 3, 3]) == [([10, 11, 12], 3)]                  # one count: the int, the order kept
+    assert ode.step_sequences(idx[:1], [5]) == [([10], 5)] and ode.step_sequences([], []) == []
+    # one distinct count per sequence (a backbone without the grouped field): every sequence an int
+    assert ode.step_sequences(idx[:4], [2, 1, 2, 3], 1) == [([13], 3), ([10, 12], 2), ([11], 1)]
+    # nine distinct counts: eight in the first sequence, the last count alone and therefore an int
+    steps = [5, 1, 9, 3, 3, 7, 2, 8, 6, 4, 9, 1]
+    seqs = ode.step_sequences(list(range(100, 112)), steps)
+    assert [c for c, _ in seqs] == [[102, 110, 107, 105, 108, 100, 109, 103, 104, 106], [101, 111]]
+    assert [s for _, s in seqs] == [[9, 9, 8, 7, 6, 5, 4, 3, 3, 2], 1]
+    for clips, counts in seqs:                                                           # (what split_by_steps gives, by ids)
+        assert isinstance(counts, int) or counts == [steps[i - 100] for i in clips]
+    order = ode.order_by_steps(steps)
+    assert [[100 + k for k in part] for part in ode.split_by_steps(order, steps)] == [c for c, _ in seqs]
 
 
 def test_buckets_take_the_step_count_into_their_key():

@@ -1,5 +1,6 @@
 """CPU: the ODE methods' host side -- the tableaus of flowhigh_amd/ode.py (consistency, order of accuracy), step_plan against the
-textbook stepper (tests/ref_odeint.py), evaluations(), the C ABI's new entry and its argument checks, the unknown-method error."""
+textbook stepper (tests/ref_odeint.py) through ode.run_step, the loop the product runs, the product's uniform driver
+(integrate.solve) on a recording net, evaluations(), the C ABI's new entry and its argument checks, the unknown-method error."""
 import ctypes
 import math
 import re
@@ -9,7 +10,7 @@ import pytest
 import torch
 
 import ref_odeint
-from flowhigh_amd import FlowHighSR, hip, ode
+from flowhigh_amd import hip, integrate, ode
 from oracle import ref_cpu
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -44,24 +45,21 @@ def _linear_problem_error(method, steps, stepper):
 
 
 def run_plan(f, y0, t, method):
-    """step_plan(method) interpreted on CPU tensors: what FlowHighSR._integrate does with launches."""
+    """step_plan(method) on CPU tensors: ode.run_step, the loop integrate.solve runs with launches, over fresh tensors."""
     plan = ode.step_plan(method)
     y = y0
     for i in range(len(t) - 1):
         t0, h = t[i], t[i + 1] - t[i]
-        buf = {"y": y}
-        for r in plan:
-            if isinstance(r, ode.Eval):
-                buf[r.dst] = f(t0 + r.c * h, buf[r.src])
-            elif isinstance(r, ode.EvalFused):
-                buf[r.dst] = buf[r.base] + (r.weight * h) * f(t0 + r.c * h, buf[r.src])
-            else:
-                assert isinstance(r, ode.Combine) and 1 <= len(r.ks) == len(r.wa) <= ode.MAX_COMBINE_TERMS
-                assert (r.wb is None) == (r.dst_b is None) and any(r.wa) and (r.wb is None or (any(r.wb) and len(r.wb) == len(r.ks)))
-                for w, dst in ((r.wa, r.dst_a), (r.wb, r.dst_b)):
-                    if w is not None:
-                        buf[dst] = buf["y"] + h * ref_odeint.weighted([buf[k] for k in r.ks], w)
-        y = buf["out"]
+
+        def field(src, c, base, weight, dst):
+            v = f(t0 + c * h, src)
+            return v if weight is None else base + (weight * h) * v
+
+        def combine(y_, ks, wa, dst_a, wb, dst_b):
+            assert 1 <= len(ks) == len(wa) <= ode.MAX_COMBINE_TERMS and any(wa) and (wb is None or (any(wb) and len(wb) == len(ks)))
+            return tuple(None if w is None else y_ + h * ref_odeint.weighted(ks, w) for w in (wa, wb))
+
+        y = ode.run_step(plan, {"y": y}, field, combine)
     return y
 
 
@@ -113,6 +111,13 @@ def test_plans_launches_per_step():
         assert sum(not isinstance(r, ode.Combine) for r in plan) == ode.stages(m)
         assert isinstance(plan[-1], ode.EvalFused) and plan[-1].dst == "out" and plan[-1].weight == ode.tableau(m)[2][-1]
         assert sum(r.wb is not None for r in plan if isinstance(r, ode.Combine)) == (m in NEW)      # one two-output combine
+        for r in plan:
+            if isinstance(r, ode.Combine):
+                assert 1 <= len(r.ks) == len(r.wa) <= ode.MAX_COMBINE_TERMS
+                assert (r.wb is None) == (r.dst_b is None) and any(r.wa) and (r.wb is None or (any(r.wb) and len(r.wb) == len(r.ks)))
+    # the buffers a stepper allocates besides 'y', 'out' and 'x'
+    assert [ode.stage_names(ode.step_plan(m)) for m in ode.ODE_METHODS] == \
+        [[], [], ["base", "k1"], ["base", "k1", "k2"], ["base", "k1", "k2", "k3"]]
     last = ode.step_plan("rk4")[-2]
     assert last == ode.Combine(("k1", "k2", "k3"), (1., -1., 1.), "x", (1 / 8, 3 / 8, 3 / 8), "base")
     assert ode.step_plan("heun3")[3] == ode.Combine(("k1", "k2"), (0., 2 / 3), "x", (.25, 0.), "base")
@@ -131,14 +136,60 @@ def test_unknown_and_adaptive_methods_name_the_supported_set():
                 call()
             assert repr(name) in str(e.value)
 
-    class Net:                                                # _integrate asks for the plan before it touches the net
+    class Net:                                                # integrate.solve asks for the plan before it touches the net
         def set_cond(self, *a, **k):
             raise AssertionError("the method was not checked first")
-    m = FlowHighSR.__new__(FlowHighSR)
-    m.flowhigh = type("F", (), {"net": Net()})()
-    m.odeint_kwargs = dict(method="dopri5")
     with pytest.raises(NotImplementedError, match=r"heun3.*adaptive"):
-        m._integrate(torch.zeros(4, 4), torch.zeros(4, 4), 1, 4, 1)
+        integrate.solve(Net(), "dopri5", torch.zeros(4, 4), torch.zeros(4, 4), 1, 4, 1)
+
+
+class _RecordingNet:
+    """The two methods integrate.solve calls on a net, recorded; nothing is computed."""
+    def __init__(self):
+        self.calls = []
+
+    def set_cond(self, cond, batch, n, ragged=None):
+        self.calls.append(("set_cond", cond, batch, n, ragged))
+
+    def forward(self, x, t, out, batch, n, alpha=1., res=None, null_cond=False, ragged=None):
+        self.calls.append(("forward", x, t, out, batch, n, alpha, res, null_cond, ragged))
+
+
+@pytest.mark.parametrize("cond_scale", [1.0, 1.3])
+@pytest.mark.parametrize("steps", [1, 2, 4])
+@pytest.mark.parametrize("method", ["euler", "midpoint"])
+def test_uniform_backend_sequences_forward_calls(method, steps, cond_scale):
+    """The product's uniform driver on CPU tensors (euler and midpoint launch no library entry of their own): every record is
+    one net.forward at the record's time and weight from the linspace grid, onto the record's base, or under guidance two
+    chained calls through one scratch buffer; set_cond comes once, first; the steps' results alternate between two buffers."""
+    net, y0, cond = _RecordingNet(), torch.zeros(6, 4), torch.ones(6, 4)
+    got = integrate.solve(net, method, y0, cond, 2, 3, steps, cond_scale)
+    assert net.calls[0][0] == "set_cond" and net.calls[0][1] is cond and net.calls[0][2:] == (2, 3, None)
+    calls = net.calls[1:]
+    assert all(c[0] == "forward" and c[4:6] == (2, 3) and c[9] is None for c in calls)
+    plan, t = ode.step_plan(method), torch.linspace(0, 1, steps + 1)
+    assert len(calls) == len(plan) * steps * (1 if cond_scale == 1. else 2)
+    calls, y, outs, scratch = iter(calls), y0, [], None
+    for i in range(steps):
+        t0, dt = t[i], t[i + 1] - t[i]
+        named = {"y": y}
+        for r in plan:                                        # (eval_fused records only: test_plans_launches_per_step)
+            tt, h = ode.stage_time(t0, dt, r.c), ode.fused_weight(r.weight, dt)
+            _, x, t_a, out, _, _, alpha, res, null, _ = next(calls)
+            if cond_scale != 1.:
+                assert (t_a, alpha, null) == (tt, h * (1. - 1.3), True) and x is named[r.src] and res is named[r.base]
+                scratch = out if scratch is None else scratch
+                assert out is scratch
+                _, x, t_a, out, _, _, alpha, res, null, _ = next(calls)
+                assert (t_a, alpha, null) == (tt, h * 1.3, False) and x is named[r.src] and res is scratch
+            else:
+                assert (t_a, alpha, null) == (tt, h, False) and x is named[r.src] and res is named[r.base]
+            assert all(out is not b for b in (scratch, y0, cond, *named.values()))
+            named[r.dst] = out
+        y = named["out"]
+        outs.append(y)
+    assert got is y and next(calls, None) is None
+    assert all(a is not b for a, b in zip(outs, outs[1:])) and all(a is b for a, b in zip(outs, outs[2:]))
 
 
 def test_header_exports_and_abi_are_consistent():
