@@ -1,12 +1,12 @@
 // Streaming delivery (FlowHighSR.stream(delivery=), FlowHighSR.delivery_stream; flowhigh_amd/stream_delivery.py is the schedule
 // and the definition): the delivery of a stream block by block, with the bits of the one-shot delivery of the whole stream.
 //   fh_stream_resample_f32   the polyphase resampler (frontend.hip: resample_poly_kernel's loop and order) on absolute indices
-//   fh_stream_limit_f32      the oversampled envelope and the look-ahead limiter of a mono stream in one launch
+//   fh_stream_limit_f32      the oversampled envelope and the look-ahead limiter of mono streams in one launch
 //                            (truepeak.hip: tp_envelope_kernel + limit_kernel, their arithmetic and order)
 //   fh_stream_pcm_i16_f32    pcm.hip's encoder with the dither at the sample's absolute index
 //   fh_stream_limit_linked_f32   the limiter of streams of 1 .. 8 channels: one envelope and one gain for a stream's channels
 //   fh_stream_pcm_i16_rows_f32   the encoder of such streams: channel c's dither, planar rows or interleaved sample frames
-// One fh_stream_job per stream and launch.  A job's source is TWO spans, the carry the stream kept and the fresh block, read as
+// One fh_stream_job per row and launch.  A job's source is TWO spans, the carry the stream kept and the fresh block, read as
 // one run of samples whose first has the absolute index `base`; nothing is concatenated.  The last block column of a launch
 // copies the last n_keep source samples into the stream's other carry buffer (the two ping-pong, so the copy never writes
 // what the launch reads).
@@ -14,32 +14,27 @@
 // The job table lives on the device: a kernel returns at once on a job with a negative count or a null pointer it would use,
 // reads the source only through sd_src::at (0 outside the two spans) and writes only dst[0 .. n_out) and carry_out[0 .. n_keep).
 //
-// Limiter: a workgroup owns TILE outputs from `first` on.  The samples of tile +- (2 H + HALO) go to LDS (0 before the stream's
-// sample 0, and past its last one when it has ended), m and r over tile +- 2 H are computed from there (r = 1 outside the
-// stream), then the sliding minimum by doubling and the float64 Hann sum in ascending k as limit_kernel has them.  The
-// envelope work is (TILE + 4 H) / TILE of that of the two launches on a clip: the price of one launch and no m round trip.
+// Groups: a stream of C channels is a group of C consecutive jobs, one per channel row, with equal base, first and counts.  The
+// limiter and the encoder are ONE kernel body each, instantiated with a group locator: OneJob for the mono entries (job g alone is
+// group g: C = 1, no table is read), GroupTable for the other two (a device table `groups` of int32 [n_groups + 1] gives every
+// stream's first job; a group whose size is not 1 .. 8, whose jobs differ in a counter or one of whose jobs fails job_ok is left
+// unwritten).  So a mono stream has the bits of a stream of one channel.  The resampler runs a row per job as it is.
 //
-// Channels: a stream of C channels is C consecutive jobs, one per channel row, with equal base, first and counts; a device table
-// `groups` of int32 [n_groups + 1] gives every stream's first job.  The resampler runs a row per job as it is.  The linked limiter's
-// workgroup owns one tile of one STREAM: it stages each channel in turn through the one xs buffer and folds the channels' peaks
-// with fmaxf in tp_envelope_kernel's order (best = 0, then channel 0, 1, ...) into one m per sample; r, the sliding minimum and
-// the Hann sum then run once per tile, and every channel's x (read again from its source) takes the one g.  LDS is the mono
-// kernel's.  A group whose size is not 1 .. 8, whose jobs differ in a counter or one of whose jobs fails job_ok is left unwritten.
+// Limiter: a workgroup owns TILE outputs of one group from `first` on.  Channel by channel, the samples of tile +- (2 H + HALO) go
+// to the one xs buffer in LDS (0 before the stream's sample 0, and past its last one when it has ended) and the channel's peaks
+// are folded with fmaxf in tp_envelope_kernel's order (best = 0, then channel 0, 1, ...) into one m per sample of tile +- 2 H; the
+// last channel's pass turns m into r (1 outside the stream).  Then the sliding minimum and the float64 Hann sum run once per tile
+// (gain_tile, which limit_kernel calls too), and every channel's x takes the one g: the last channel's from xs, which still holds
+// it, the others' read again from their source.  The envelope work is (TILE + 4 H) / TILE of that of the two launches on a clip:
+// the price of one launch and no m round trip.
 #include "fh_common.h"
 #include "pcm_common.h"
 #include "truepeak_common.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int TILE = 1024;                      // outputs per workgroup of the limiter
-constexpr int PER = TILE / THREADS;
-constexpr int HALO = tp::HALO, PHASE_TAPS = tp::PHASE_TAPS, MAX_H = tp::MAX_H;
-constexpr int LIM_N = TILE + 4 * MAX_H;
+using namespace tp;                             // (truepeak_common.h: THREADS, the limiter's TILE outputs per workgroup, ...)
 constexpr int MAX_CH = 8;                       // channels of a stream
-using tp::limit_sample;
-using tp::load_taps;
-using tp::tp_phase;
 
 struct sd_src {                                 // the two spans as one run of samples
   const float* carry;
@@ -98,114 +93,67 @@ __global__ __launch_bounds__(THREADS) void stream_resample_kernel(const fh_strea
   ((float*)J.dst)[o] = acc;
 }
 
-// max(|x[n]|, |x4[4 n + p]|, p = 0 .. 3) of the sample staged at xs[j + HALO]: tp_tile's chain
-__device__ __forceinline__ float peak_at(const float* __restrict__ xs, const float (*hs)[PHASE_TAPS], int j) {
-  float mv = fabsf(xs[j + HALO]);
-  mv = fmaxf(mv, tp_phase<0>(xs, hs, j));
-  mv = fmaxf(mv, tp_phase<1>(xs, hs, j));
-  mv = fmaxf(mv, tp_phase<2>(xs, hs, j));
-  mv = fmaxf(mv, tp_phase<3>(xs, hs, j));
-  return mv;
-}
-
-// a[0][j] = r[tile0 - 2 H + j], j < N = TILE + 4 H (behind a barrier) -> acc[k] = g[tile0 + t + k THREADS] in float64: the sliding
-// minimum by doubling and the Hann sum in ascending k, as limit_kernel has them
-__device__ __forceinline__ void gain_tile(float (*a)[LIM_N], const double* __restrict__ ws, int H, double (&acc)[PER]) {
-  const int t = threadIdx.x, W = 2 * H + 1, N = TILE + 4 * H;
-  int cur = 0, P = 1;
-  for (; 2 * P <= W; P *= 2) {                                      // a[cur][j] = min r[j .. j + P) -> ... + 2 P)
-    for (int j = t; j < N; j += THREADS) a[cur ^ 1][j] = j + P < N ? fminf(a[cur][j], a[cur][j + P]) : a[cur][j];
-    cur ^= 1;
-    __syncthreads();
-  }
-  // q[i] = min r[i .. i + W): the sample tile0 - H + i, i < TILE + 2 H (i + W - 1 <= N - 1)
-  float* __restrict__ q = a[cur ^ 1];
-  for (int i = t; i < TILE + 2 * H; i += THREADS) q[i] = fminf(a[cur][i], a[cur][i + W - P]);
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < PER; ++k) acc[k] = 0.0;
-  for (int kk = 0; kk < W; ++kk) {                                  // g[tile0 + i] = sum_kk w[kk] q[i + kk], ascending
-    const double wv = ws[kk];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) acc[k] = fma(wv, (double)q[t + k * THREADS + kk], acc[k]);
-  }
-}
-
-__global__ __launch_bounds__(THREADS) void stream_limit_kernel(const fh_stream_job* __restrict__ jobs, const float* __restrict__ taps,
-                                                               const double* __restrict__ w, int H, float c32) {
-  __shared__ float xs[LIM_N + 2 * HALO];
-  __shared__ float hs[4][PHASE_TAPS];
-  __shared__ float a[2][LIM_N];
-  __shared__ double ws[2 * MAX_H + 1];
-  const fh_stream_job J = jobs[blockIdx.y];
-  if (!job_ok(J)) return;
-  const sd_src S = source(J);
-  if (blockIdx.x == gridDim.x - 1) {
-    keep_tail(J, S);
-    return;
-  }
-  const long long rel0 = (long long)blockIdx.x * TILE;               // the tile's first output in dst
-  if (rel0 >= J.n_out) return;
-  const long long tile0 = J.first + rel0, end = S.end();
-  const int t = threadIdx.x, W = 2 * H + 1, N = TILE + 4 * H;
-  load_taps(taps, hs);
-  for (int j = t; j < N + 2 * HALO; j += THREADS) xs[j] = S.at(tile0 - 2 * H - HALO + j);      // (0 before sample 0 and past `end`)
-  for (int j = t; j < W; j += THREADS) ws[j] = w[j];
-  __syncthreads();
-  for (int j = t; j < N; j += THREADS) {                            // a[0][j] = r[tile0 - 2 H + j]
-    const long long n = tile0 - 2 * H + j;
-    float r = 1.f;
-    if (n >= 0 && n < end) {
-      const float mv = peak_at(xs, hs, j);
-      if (mv > c32) r = __fdiv_rn(c32, mv);
-    }
-    a[0][j] = r;
-  }
-  __syncthreads();
-  double acc[PER];
-  gain_tile(a, ws, H, acc);
-  float* __restrict__ dst = (float*)J.dst + rel0;
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int i = t + k * THREADS;
-    if (rel0 + i < J.n_out) dst[i] = limit_sample(xs[i + 2 * H + HALO], (float)acc[k], c32);
-  }
-}
-
 // The jobs [j0, j0 + n) of one stream: one per channel row
 struct sd_group {
   int j0, n;
 };
 
-// group g of the table, checked (the tables live on the device): 1 .. 8 jobs inside the job table, each job_ok, all with the
-// counters of the first
-__device__ __forceinline__ bool group_ok(const fh_stream_job* __restrict__ jobs, int n_jobs, const int32_t* __restrict__ groups, int g,
-                                         sd_group& G) {
-  const int j0 = groups[g], j1 = groups[g + 1];
-  if (j0 < 0 || j1 > n_jobs || j1 <= j0 || j1 - j0 > MAX_CH) return false;
-  const fh_stream_job A = jobs[j0];
-  for (int j = j0; j < j1; ++j) {
-    const fh_stream_job J = jobs[j];
-    if (!job_ok(J) || J.base != A.base || J.first != A.first || J.n_carry != A.n_carry || J.n_fresh != A.n_fresh ||
-        J.n_out != A.n_out || J.n_keep != A.n_keep)
-      return false;
+// The group locators: group(g, G) gives group g, checked (false: it is left unwritten), group_of(j) the group that may hold job j,
+// and `interleaved` says whether the encoder writes sample frames (a constant 0 where none can occur).
+struct OneJob {                                 // job g alone is group g
+  const fh_stream_job* jobs;
+  static constexpr int interleaved = 0;
+  __device__ bool group(int g, sd_group& G) const {
+    G = {g, 1};
+    const fh_stream_job J = jobs[g];            // (the whole record in one read, not field by field as job_ok asks)
+    return job_ok(J);
   }
-  G = {j0, j1 - j0};
-  return true;
-}
+  __device__ int group_of(int job) const { return job; }
+};
+struct GroupTable {                             // groups[g] .. groups[g + 1] of the device table
+  const fh_stream_job* jobs;
+  int n_jobs;
+  const int32_t* groups;
+  int n_groups, interleaved;
+  // 1 .. 8 jobs inside the job table, each job_ok, all with the counters of the first (the tables live on the device)
+  __device__ bool group(int g, sd_group& G) const {
+    const int j0 = groups[g], j1 = groups[g + 1];
+    if (j0 < 0 || j1 > n_jobs || j1 <= j0 || j1 - j0 > MAX_CH) return false;
+    const fh_stream_job A = jobs[j0];
+    for (int j = j0; j < j1; ++j) {
+      const fh_stream_job J = jobs[j];
+      if (!job_ok(J) || J.base != A.base || J.first != A.first || J.n_carry != A.n_carry || J.n_fresh != A.n_fresh ||
+          J.n_out != A.n_out || J.n_keep != A.n_keep)
+        return false;
+    }
+    G = {j0, j1 - j0};
+    return true;
+  }
+  __device__ int group_of(int job) const {      // the last group that starts at or below the job, by bisection
+    int g = 0, hi = n_groups;
+    while (hi - g > 1) {
+      const int mid = (g + hi) >> 1;
+      if (groups[mid] <= job)
+        g = mid;
+      else
+        hi = mid;
+    }
+    return g;
+  }
+};
 
-// stream_limit_kernel for streams of channels: a workgroup owns one tile of one group.  a[0][j] collects m over the channels (the
-// thread that owns j is the same for every channel), then becomes r; from there on the tile is the mono kernel's.
-__global__ __launch_bounds__(THREADS) void stream_limit_linked_kernel(const fh_stream_job* __restrict__ jobs, int n_jobs,
-                                                                      const int32_t* __restrict__ groups, const float* __restrict__ taps,
-                                                                      const double* __restrict__ w, int H, float c32) {
+// A workgroup owns one tile of one group.  a[0][j] collects m over the channels (the thread that owns j is the same in every
+// pass) and becomes r in the last channel's pass.
+template <class Groups>
+__global__ __launch_bounds__(THREADS) void stream_limit_kernel(Groups groups, const float* __restrict__ taps, const double* __restrict__ w,
+                                                               int H, float c32) {
   __shared__ float xs[LIM_N + 2 * HALO];
   __shared__ float hs[4][PHASE_TAPS];
   __shared__ float a[2][LIM_N];
   __shared__ double ws[2 * MAX_H + 1];
   sd_group G;
-  if (!group_ok(jobs, n_jobs, groups, blockIdx.y, G)) return;
-  jobs += G.j0;
+  if (!groups.group(blockIdx.y, G)) return;
+  const fh_stream_job* __restrict__ jobs = groups.jobs + G.j0;
   if (blockIdx.x == gridDim.x - 1) {
     for (int c = 0; c < G.n; ++c) {
       const fh_stream_job J = jobs[c];
@@ -217,36 +165,35 @@ __global__ __launch_bounds__(THREADS) void stream_limit_linked_kernel(const fh_s
   const long long rel0 = (long long)blockIdx.x * TILE;               // the tile's first output in every dst
   if (rel0 >= J0.n_out) return;
   const long long tile0 = J0.first + rel0, end = source(J0).end();
-  const int t = threadIdx.x, W = 2 * H + 1, N = TILE + 4 * H;
+  const int t = threadIdx.x, N = TILE + 4 * H;
   load_taps(taps, hs);
-  for (int j = t; j < W; j += THREADS) ws[j] = w[j];
+  for (int j = t; j < 2 * H + 1; j += THREADS) ws[j] = w[j];
   for (int c = 0; c < G.n; ++c) {                                    // a[0][j] = m[tile0 - 2 H + j]: best = 0, then channel by channel
     const sd_src S = source(jobs[c]);
-    for (int j = t; j < N + 2 * HALO; j += THREADS) xs[j] = S.at(tile0 - 2 * H - HALO + j);
+    for (int j = t; j < N + 2 * HALO; j += THREADS) xs[j] = S.at(tile0 - 2 * H - HALO + j);      // (0 before sample 0 and past `end`)
     __syncthreads();
     for (int j = t; j < N; j += THREADS) {
       const long long n = tile0 - 2 * H + j;
-      const float best = c ? a[0][j] : 0.f;
-      a[0][j] = (n >= 0 && n < end) ? fmaxf(best, peak_at(xs, hs, j)) : best;
+      const bool last = c == G.n - 1;
+      float mv = c ? a[0][j] : 0.f, r = 1.f;                           // r[tile0 - 2 H + j]; 1 outside the stream
+      if (n >= 0 && n < end) {
+        mv = fmaxf(mv, peak_at(xs, hs, j));
+        if (last && mv > c32) r = __fdiv_rn(c32, mv);                  // (a branch: few samples are over the ceiling)
+      }
+      a[0][j] = last ? r : mv;
     }
-    __syncthreads();                                                 // (xs is staged again)
+    __syncthreads();                                                 // (xs is staged again, or a[0] is read)
   }
-  for (int j = t; j < N; j += THREADS) {                             // a[0][j] = r[tile0 - 2 H + j]; 1 outside the stream
-    const long long n = tile0 - 2 * H + j;
-    const float mv = a[0][j];
-    a[0][j] = (n >= 0 && n < end && mv > c32) ? __fdiv_rn(c32, mv) : 1.f;
-  }
-  __syncthreads();
   double acc[PER];
   gain_tile(a, ws, H, acc);
-  for (int c = 0; c < G.n; ++c) {                                    // (x is read again from the source: LDS holds one channel)
+  for (int c = 0; c < G.n; ++c) {                                    // (xs holds the last channel, the others are read again)
     const fh_stream_job J = jobs[c];
     const sd_src S = source(J);
     float* __restrict__ dst = (float*)J.dst + rel0;
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
       const int i = t + k * THREADS;
-      if (rel0 + i < J.n_out) dst[i] = limit_sample(S.at(tile0 + i), (float)acc[k], c32);
+      if (rel0 + i < J.n_out) dst[i] = limit_sample(c == G.n - 1 ? xs[i + 2 * H + HALO] : S.at(tile0 + i), (float)acc[k], c32);
     }
   }
 }
@@ -287,13 +234,6 @@ __device__ __forceinline__ void pcm_row(const fh_stream_job& J, const unsigned l
   }
 }
 
-__global__ __launch_bounds__(THREADS) void stream_pcm_kernel(const fh_stream_job* __restrict__ jobs,
-                                                             const unsigned long long* __restrict__ keys) {
-  const fh_stream_job J = jobs[blockIdx.y];
-  if (!job_ok(J) || (((size_t)J.dst) & 1)) return;                  // (an odd dst would misalign every 16-byte store)
-  pcm_row(J, keys ? keys + 2 * blockIdx.y : nullptr, 0);
-}
-
 // Interleaved output of a stream of C = 2, 4 or 8 channels whose frame buffer is aligned to a frame (2 C bytes): the thread
 // encodes its run of every channel and stores each sample frame as ONE 4-, 8- or 16-byte word, as pcm.hip's pcm_frames does.
 template <int C>
@@ -317,35 +257,28 @@ __device__ __forceinline__ void stream_frames(const fh_stream_job* __restrict__ 
     if (first + k < n_out) frames[first + k] = o[k];
 }
 
-// The encoder of streams of channels.  Grid (blocks of 256 runs, jobs): job j is channel j - groups[g] of the group g that
-// holds it, found by bisection (a job no group holds, or whose group fails group_ok, is left unwritten).  Planar: every job
-// writes its own dst as stream_pcm_kernel does.  Interleaved: the group's first dst is the frame buffer int16 [n_out, C]; with
-// whole-frame stores the blocks of channel 0 write for the group, otherwise every job stores its samples at their places.
-__global__ __launch_bounds__(THREADS) void stream_pcm_rows_kernel(const fh_stream_job* __restrict__ jobs, int n_jobs,
-                                                                  const int32_t* __restrict__ groups, int n_groups,
-                                                                  const unsigned long long* __restrict__ keys, int interleaved) {
-  const int job = blockIdx.y;
-  int g = 0, hi = n_groups;
-  while (hi - g > 1) {                                               // the last group that starts at or below the job
-    const int mid = (g + hi) >> 1;
-    if (groups[mid] <= job)
-      g = mid;
-    else
-      hi = mid;
-  }
+// The encoder.  Grid (blocks of 256 runs, jobs): job j is channel j - G.j0 of the group that holds it (a job no group holds, or
+// whose group is refused, is left unwritten) and takes the group's key.  Planar: every job writes its own dst, none if a dst of
+// the group is odd (it would misalign every 16-byte store).  Interleaved: the group's first dst is the frame buffer int16
+// [n_out, C]; with whole-frame stores the blocks of channel 0 write for the group, otherwise every job stores its samples at
+// their places.
+template <class Groups>
+__global__ __launch_bounds__(THREADS) void stream_pcm_kernel(Groups groups, const unsigned long long* __restrict__ keys) {
+  const int job = blockIdx.y, g = groups.group_of(job);
   sd_group G;
-  if (!group_ok(jobs, n_jobs, groups, g, G) || job < G.j0 || job >= G.j0 + G.n) return;
+  if (!groups.group(g, G) || job < G.j0 || job >= G.j0 + G.n) return;
+  const fh_stream_job* __restrict__ jobs = groups.jobs;
   const int ch = job - G.j0;
   const unsigned long long* __restrict__ key = keys ? keys + 2 * g : nullptr;
-  if (!interleaved) {
+  if (!groups.interleaved) {
     for (int c = 0; c < G.n; ++c)
-      if (((size_t)jobs[G.j0 + c].dst) & 1) return;                  // (an odd dst anywhere: the group is left unwritten)
+      if (((size_t)jobs[G.j0 + c].dst) & 1) return;
     pcm_row(jobs[job], key, ch);
     return;
   }
-  int16_t* __restrict__ frames = (int16_t*)jobs[G.j0].dst;
-  if (((size_t)frames) & 1) return;
-  if ((G.n == 2 || G.n == 4 || G.n == 8) && (((size_t)frames) & (2 * G.n - 1)) == 0) {
+  int16_t* __restrict__ out = (int16_t*)jobs[G.j0].dst;
+  if (((size_t)out) & 1) return;
+  if ((G.n == 2 || G.n == 4 || G.n == 8) && (((size_t)out) & (2 * G.n - 1)) == 0) {
     if (ch != 0) return;                                             // (the blocks of channel 0 write whole frames)
     if (G.n == 2)
       stream_frames<2>(jobs + G.j0, key);
@@ -362,7 +295,7 @@ __global__ __launch_bounds__(THREADS) void stream_pcm_rows_kernel(const fh_strea
   pcm_run(J, key, ch, first, x, d);
 #pragma unroll
   for (int k = 0; k < RUN; ++k)
-    if (first + k < J.n_out) frames[(size_t)(first + k) * G.n + ch] = encode(x[k], d[k]);
+    if (first + k < J.n_out) out[(size_t)(first + k) * G.n + ch] = encode(x[k], d[k]);
 }
 
 }  // namespace
@@ -386,43 +319,44 @@ extern "C" int fh_stream_resample_f32(const fh_stream_job* jobs, int n_jobs, int
   return FH_OK;
 }
 
-extern "C" int fh_stream_limit_f32(const fh_stream_job* jobs, int n_jobs, int max_out, const float* taps4, const double* w, int H,
-                                   float ceiling, void* stream) {
-  FH_CHECK_STREAM_JOBS("fh_stream_limit_f32");
-  FH_CHECK_ARG(taps4 && w, "fh_stream_limit_f32: null pointer (taps4 %p, w %p)", (const void*)taps4, (const void*)w);
-  FH_CHECK_ARG(H >= 1 && H <= MAX_H, "fh_stream_limit_f32: H %d (1 .. %d)", H, MAX_H);
-  FH_CHECK_ARG(ceiling > 0.f && ceiling <= 1.f, "fh_stream_limit_f32: ceiling %g (0 < c <= 1)", (double)ceiling);
-  FH_CHECK_ARG((((size_t)taps4) & 3) == 0 && (((size_t)w) & 7) == 0, "fh_stream_limit_f32: taps4 must be 4-byte, w 8-byte aligned");
-  hipLaunchKernelGGL(stream_limit_kernel, dim3(fh_cdiv(max_out, TILE) + 1, n_jobs), dim3(THREADS), 0, (hipStream_t)stream, jobs, taps4,
-                     w, H, ceiling);
-  FH_CHECK_LAUNCH("fh_stream_limit_f32");
-  return FH_OK;
-}
-
-extern "C" int fh_stream_pcm_i16_f32(const fh_stream_job* jobs, int n_jobs, int max_out, const uint64_t* keys, void* stream) {
-  FH_CHECK_STREAM_JOBS("fh_stream_pcm_i16_f32");
-  hipLaunchKernelGGL(stream_pcm_kernel, dim3(fh_cdiv(((long long)max_out + RUN - 1) / RUN + 1, THREADS), n_jobs), dim3(THREADS), 0,
-                     (hipStream_t)stream, jobs, (const unsigned long long*)keys);
-  FH_CHECK_LAUNCH("fh_stream_pcm_i16_f32");
-  return FH_OK;
-}
+#define FH_CHECK_STREAM_LIMIT(name)                                                                                        \
+  FH_CHECK_ARG(taps4 && w, name ": null pointer (taps4 %p, w %p)", (const void*)taps4, (const void*)w);                    \
+  FH_CHECK_ARG(H >= 1 && H <= MAX_H, name ": H %d (1 .. %d)", H, MAX_H);                                                   \
+  FH_CHECK_ARG(ceiling > 0.f && ceiling <= 1.f, name ": ceiling %g (0 < c <= 1)", (double)ceiling);                       \
+  FH_CHECK_ARG((((size_t)taps4) & 3) == 0 && (((size_t)w) & 7) == 0, name ": taps4 must be 4-byte, w 8-byte aligned")
 
 #define FH_CHECK_STREAM_GROUPS(name)                                                                                       \
   FH_CHECK_ARG(groups, name ": null group table");                                                                        \
   FH_CHECK_ARG(n_groups > 0 && n_groups < 65536, name ": %d groups (1 .. 65535)", n_groups);                              \
   FH_CHECK_ARG((((size_t)groups) & 3) == 0, name ": groups must be 4-byte aligned")
 
+static int pcm_blocks(int max_out) { return fh_cdiv(((long long)max_out + RUN - 1) / RUN + 1, THREADS); }      // runs of a row at any alignment
+
+extern "C" int fh_stream_limit_f32(const fh_stream_job* jobs, int n_jobs, int max_out, const float* taps4, const double* w, int H,
+                                   float ceiling, void* stream) {
+  FH_CHECK_STREAM_JOBS("fh_stream_limit_f32");
+  FH_CHECK_STREAM_LIMIT("fh_stream_limit_f32");
+  hipLaunchKernelGGL(stream_limit_kernel<OneJob>, dim3(fh_cdiv(max_out, TILE) + 1, n_jobs), dim3(THREADS), 0, (hipStream_t)stream,
+                     OneJob{jobs}, taps4, w, H, ceiling);
+  FH_CHECK_LAUNCH("fh_stream_limit_f32");
+  return FH_OK;
+}
+
+extern "C" int fh_stream_pcm_i16_f32(const fh_stream_job* jobs, int n_jobs, int max_out, const uint64_t* keys, void* stream) {
+  FH_CHECK_STREAM_JOBS("fh_stream_pcm_i16_f32");
+  hipLaunchKernelGGL(stream_pcm_kernel<OneJob>, dim3(pcm_blocks(max_out), n_jobs), dim3(THREADS), 0, (hipStream_t)stream, OneJob{jobs},
+                     (const unsigned long long*)keys);
+  FH_CHECK_LAUNCH("fh_stream_pcm_i16_f32");
+  return FH_OK;
+}
+
 extern "C" int fh_stream_limit_linked_f32(const fh_stream_job* jobs, int n_jobs, const int32_t* groups, int n_groups, int max_out,
                                           const float* taps4, const double* w, int H, float ceiling, void* stream) {
   FH_CHECK_STREAM_JOBS("fh_stream_limit_linked_f32");
   FH_CHECK_STREAM_GROUPS("fh_stream_limit_linked_f32");
-  FH_CHECK_ARG(taps4 && w, "fh_stream_limit_linked_f32: null pointer (taps4 %p, w %p)", (const void*)taps4, (const void*)w);
-  FH_CHECK_ARG(H >= 1 && H <= MAX_H, "fh_stream_limit_linked_f32: H %d (1 .. %d)", H, MAX_H);
-  FH_CHECK_ARG(ceiling > 0.f && ceiling <= 1.f, "fh_stream_limit_linked_f32: ceiling %g (0 < c <= 1)", (double)ceiling);
-  FH_CHECK_ARG((((size_t)taps4) & 3) == 0 && (((size_t)w) & 7) == 0,
-               "fh_stream_limit_linked_f32: taps4 must be 4-byte, w 8-byte aligned");
-  hipLaunchKernelGGL(stream_limit_linked_kernel, dim3(fh_cdiv(max_out, TILE) + 1, n_groups), dim3(THREADS), 0, (hipStream_t)stream,
-                     jobs, n_jobs, groups, taps4, w, H, ceiling);
+  FH_CHECK_STREAM_LIMIT("fh_stream_limit_linked_f32");
+  hipLaunchKernelGGL(stream_limit_kernel<GroupTable>, dim3(fh_cdiv(max_out, TILE) + 1, n_groups), dim3(THREADS), 0, (hipStream_t)stream,
+                     GroupTable{jobs, n_jobs, groups, n_groups, 0}, taps4, w, H, ceiling);
   FH_CHECK_LAUNCH("fh_stream_limit_linked_f32");
   return FH_OK;
 }
@@ -431,8 +365,8 @@ extern "C" int fh_stream_pcm_i16_rows_f32(const fh_stream_job* jobs, int n_jobs,
                                           const uint64_t* keys, int interleaved, void* stream) {
   FH_CHECK_STREAM_JOBS("fh_stream_pcm_i16_rows_f32");
   FH_CHECK_STREAM_GROUPS("fh_stream_pcm_i16_rows_f32");
-  hipLaunchKernelGGL(stream_pcm_rows_kernel, dim3(fh_cdiv(((long long)max_out + RUN - 1) / RUN + 1, THREADS), n_jobs), dim3(THREADS), 0,
-                     (hipStream_t)stream, jobs, n_jobs, groups, n_groups, (const unsigned long long*)keys, interleaved ? 1 : 0);
+  hipLaunchKernelGGL(stream_pcm_kernel<GroupTable>, dim3(pcm_blocks(max_out), n_jobs), dim3(THREADS), 0, (hipStream_t)stream,
+                     GroupTable{jobs, n_jobs, groups, n_groups, interleaved ? 1 : 0}, (const unsigned long long*)keys);
   FH_CHECK_LAUNCH("fh_stream_pcm_i16_rows_f32");
   return FH_OK;
 }

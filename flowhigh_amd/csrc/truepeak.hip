@@ -13,7 +13,7 @@
 //
 // Limiter (limit_kernel): grid (tile, clip), TILE frames each.  r over the tile +- 2 H goes to LDS (1 outside the clip), the
 // sliding minimum over 2 H + 1 is made by doubling (a[j] = min r[j .. j + P), P the largest power of two <= 2 H + 1, then two
-// overlapping windows), the Hann FIR runs in float64 in ascending k from the host's double table, and the rows are written with
+// overlapping windows), the Hann FIR runs in float64 in ascending k from the host's double table (gain_tile), and the rows are written with
 // level.hip's slots: a 16-byte word wholly inside the tile's part of the row is one store, the ends go element by element.
 #include <math.h>
 
@@ -22,20 +22,8 @@
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int TILE = 1024;                      // frames per workgroup
-constexpr int PER = TILE / THREADS;
-constexpr int HALO = 10;                        // input samples either side of n that x4[4 n + p] reads
-constexpr int PHASE_TAPS = 2 * HALO + 1;        // phase 0; the others have one fewer
-constexpr int PLAN_TAPS = 8 * HALO + 2;         // tables.resample_poly_plan(4, 1): one leading pad, then the 81 taps
-constexpr int MAX_H = 512;
+using namespace tp;                             // (truepeak_common.h: what stream_delivery.hip shares, the tile's constants too)
 constexpr int MAX_LEN = 1 << 30;
-constexpr int LIM_N = TILE + 4 * MAX_H;
-// (load_taps, tp_phase and limit_sample are in truepeak_common.h, shared with stream_delivery.hip; the constants are one statement)
-static_assert(HALO == tp::HALO && PHASE_TAPS == tp::PHASE_TAPS && PLAN_TAPS == tp::PLAN_TAPS && MAX_H == tp::MAX_H, "truepeak_common.h");
-using tp::limit_sample;
-using tp::load_taps;
-using tp::tp_phase;
 
 struct tp_row {                                 // one row as the true-peak body sees it
   const float* x;
@@ -100,11 +88,7 @@ __device__ __forceinline__ void tp_tile(const float* __restrict__ x, int len, in
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     const int i = threadIdx.x + k * THREADS;
-    float best = fabsf(xs[i + HALO]);
-    best = fmaxf(best, tp_phase<0>(xs, hs, i));
-    best = fmaxf(best, tp_phase<1>(xs, hs, i));
-    best = fmaxf(best, tp_phase<2>(xs, hs, i));
-    best = fmaxf(best, tp_phase<3>(xs, hs, i));
+    const float best = peak_at(xs, hs, i);
     v[k] = (tile0 + i < len) ? best : 0.f;
   }
   __syncthreads();
@@ -169,7 +153,7 @@ __global__ __launch_bounds__(THREADS) void limit_kernel(Loc loc, const float* __
   const tp_view c = loc(blockIdx.y);
   const long long tile0 = (long long)blockIdx.x * TILE;
   if (c.channels < 1 || c.channels > 8 || c.len < 1 || c.len > m_pitch || tile0 >= c.len) return;
-  const int t = threadIdx.x, W = 2 * H + 1, N = TILE + 4 * H;
+  const int t = threadIdx.x, N = TILE + 4 * H;
   const float* __restrict__ mc = m + (size_t)blockIdx.y * m_pitch;
   for (int j = t; j < N; j += THREADS) {                            // a[0][j] = r[tile0 - 2 H + j]
     const long long n = tile0 - 2 * H + j;
@@ -180,26 +164,10 @@ __global__ __launch_bounds__(THREADS) void limit_kernel(Loc loc, const float* __
     }
     a[0][j] = r;
   }
-  for (int j = t; j < W; j += THREADS) ws[j] = w[j];
-  __syncthreads();
-  int cur = 0, P = 1;
-  for (; 2 * P <= W; P *= 2) {                                      // a[cur][j] = min r[j .. j + P) -> ... + 2 P)
-    for (int j = t; j < N; j += THREADS) a[cur ^ 1][j] = j + P < N ? fminf(a[cur][j], a[cur][j + P]) : a[cur][j];
-    cur ^= 1;
-    __syncthreads();
-  }
-  // q[i] = min r[i .. i + W): the frame tile0 - H + i, i < TILE + 2 H (i + W - 1 <= N - 1)
-  float* __restrict__ q = a[cur ^ 1];
-  for (int i = t; i < TILE + 2 * H; i += THREADS) q[i] = fminf(a[cur][i], a[cur][i + W - P]);
+  for (int j = t; j < 2 * H + 1; j += THREADS) ws[j] = w[j];
   __syncthreads();
   double acc[PER];
-#pragma unroll
-  for (int k = 0; k < PER; ++k) acc[k] = 0.0;
-  for (int kk = 0; kk < W; ++kk) {                                  // g[tile0 + i] = sum_kk w[kk] q[i + kk], ascending
-    const double wv = ws[kk];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) acc[k] = fma(wv, (double)q[t + k * THREADS + kk], acc[k]);
-  }
+  gain_tile(a, ws, H, acc);
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     const int i = t + k * THREADS;

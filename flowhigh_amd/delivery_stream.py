@@ -173,15 +173,16 @@ def _push(delivery, streams, blocks, final):
     for i, s in enumerate(streams):
         groups.setdefault(s.key, []).append(i)
     for key, idx in groups.items():
-        rate, ceiling_db, pcm, dithered = key[:4]
-        linked, frames = len(key) > 4, len(key) > 4 and key[5]
+        s0 = streams[idx[0]]                     # (what the key names is the same for all of them; the key itself is not taken apart)
+        rate, ceiling_db, dithered = s0.plan["rate"], s0.plan["true_peak"], s0.plan["key"] is not None
+        linked, frames = s0.channels is not None, s0.interleaved
         # What every stage emits follows from the blocks' lengths, so the jobs of all stages are made first and go up as ONE
         # buffer; a stage's outputs are one buffer too, a stream's part of it ([rows, n_out], contiguous) the next stage's fresh block.
         n_in = {i: cur[i].shape[1] for i in idx}
         src = {i: [cur[i].data_ptr() + 4 * r * n_in[i] for r in range(streams[i].rows)] for i in idx}
         stages, tables_ = [], []
         for name in ("resample", "limit", "encode"):
-            if name not in streams[idx[0]].stages:
+            if name not in s0.stages:
                 continue
             # (a stream with nothing new and nothing to end stays as it is: its job would write and move nothing)
             live = [i for i in idx if final or n_in[i]]
@@ -204,36 +205,32 @@ def _push(delivery, streams, blocks, final):
                 assert n_out == room
                 jobs += js
                 cur[i], src[i], n_in[i] = part, dst, room
-            table = [(hip.StreamJob * len(jobs))(*jobs)]
-            if linked and name != "resample":            # (the resampler runs a row per job as it is)
-                table.append(np.cumsum([0] + [streams[i].rows for i in live]).astype(np.int32))
-            stages.append((name, live, max(rooms), len(jobs), len(tables_), buf))      # (buf: alive until its launches are queued)
-            tables_ += table
+            grouped = linked and name != "resample"      # (the resampler runs a row per job as it is)
+            stages.append((name, live, max(rooms), len(jobs), len(tables_), grouped, buf))      # (buf: alive until its launches are queued)
+            tables_.append((hip.StreamJob * len(jobs))(*jobs))
+            if grouped:
+                tables_.append(np.cumsum([0] + [streams[i].rows for i in live]).astype(np.int32))
         if not stages:
             continue
         if dithered and stages[-1][0] == "encode":
             tables_.append(np.array([streams[i].plan["key"] for i in stages[-1][1]], dtype=np.uint64).view(np.int64))
         keep, ptrs = upload_tables(tables_, dev)
         L = hip.lib()
-        for name, live, max_out, n_jobs, at, _ in stages:
-            jp = ptrs[at]
+        for name, live, max_out, n_jobs, at, grouped, _ in stages:      # one launch per stage: the mono entry, or the one that takes groups
+            tables = (ptrs[at], n_jobs) + ((ptrs[at + 1], len(live)) if grouped else ())
             if name == "resample":
                 taps, n_taps, pre, up, down = delivery.resampler._filter(rate, 48000)
-                hip.check(L.fh_stream_resample_f32(jp, n_jobs, max_out, taps, up, down, n_taps, pre, hip.stream()), "fh_stream_resample_f32")
+                entry, args = "fh_stream_resample_f32", (taps, up, down, n_taps, pre)
             elif name == "limit":
                 H = streams[live[0]].stages[name].counters.H
                 c32 = float(np.float32(_truepeak.ceiling(ceiling_db)))
-                if linked:
-                    hip.check(L.fh_stream_limit_linked_f32(jp, n_jobs, ptrs[at + 1], len(live), max_out, delivery._tp_taps(),
-                                                           delivery._window(H), H, c32, hip.stream()), "fh_stream_limit_linked_f32")
-                else:
-                    hip.check(L.fh_stream_limit_f32(jp, n_jobs, max_out, delivery._tp_taps(), delivery._window(H), H, c32, hip.stream()),
-                              "fh_stream_limit_f32")
-            elif max_out and linked:
-                hip.check(L.fh_stream_pcm_i16_rows_f32(jp, n_jobs, ptrs[at + 1], len(live), max_out, ptrs[-1] if dithered else 0,
-                                                       int(frames), hip.stream()), "fh_stream_pcm_i16_rows_f32")
+                entry, args = f"fh_stream_limit{'_linked' if linked else ''}_f32", (delivery._tp_taps(), delivery._window(H), H, c32)
             elif max_out:
-                hip.check(L.fh_stream_pcm_i16_f32(jp, n_jobs, max_out, ptrs[-1] if dithered else 0, hip.stream()), "fh_stream_pcm_i16_f32")
+                entry = f"fh_stream_pcm_i16{'_rows' if linked else ''}_f32"
+                args = (ptrs[-1] if dithered else 0,) + ((int(frames),) if linked else ())
+            else:
+                continue
+            hip.check(getattr(L, entry)(*tables, max_out, *args, hip.stream()), entry)
     del fresh
     out = []
     for s, c in zip(streams, cur):                       # (what stood still at some stage emits an empty block of the result's type)

@@ -104,6 +104,30 @@ def test_linked_limiter_alone_at_48000(C, cuts):
     assert same_bits(one_shot(x[1:], **LIMIT), x[1:])
 
 
+@pytest.mark.parametrize("C", [1, 2])
+def test_non_finite_samples_give_the_same_bits_in_every_limiter(C):
+    """A NaN at 700 and a +Inf at 2300 of the last channel of [C, 3000] (three tiles; H = 240, so they are further apart than
+    4 H + 20 and do not interact).  A NaN peak folds to m = 0 in the envelope (fmaxf(0, NaN)), which the limiter of a stream of
+    channels does too; both give r = 1 there, as a compare of the NaN itself with the ceiling does.  The stream without
+    n_channels, the stream with n_channels=C and fh_tp_envelope_f32 + fh_limit_f32 on the whole rows: the same bits."""
+    n, cuts = 3000, [1, 7, 300, 301, 1500, 2222, 2999, 3000]
+    host = (0.3 * np.random.default_rng(30).uniform(-1.0, 1.0, (C, n))).astype(np.float32)
+    host[C - 1, 700], host[C - 1, 2300] = np.nan, np.inf
+    x = torch.from_numpy(host).cuda()
+    D, L = delivery(), hip.lib()
+    H, c32 = truepeak.half_window(48000), float(np.float32(truepeak.ceiling(LIMIT["true_peak"])))
+    assert H == 240
+    m, want = torch.empty(1, n, dtype=torch.float32, device="cuda"), torch.empty(C, n, dtype=torch.float32, device="cuda")
+    hip.check(L.fh_tp_envelope_f32(x.data_ptr(), D._tp_taps(), m.data_ptr(), 1, C, n, hip.stream()), "envelope")
+    hip.check(L.fh_limit_f32(x.data_ptr(), want.data_ptr(), m.data_ptr(), D._window(H), 0, 1, C, n, H, c32, hip.stream()), "limit")
+    # the NaN does not reach m (what is left at 700 is the other channel's peak, 0 where there is none); the Inf does
+    assert bool(torch.isfinite(m[0, 700])) and (C > 1 or float(m[0, 700]) == 0.0) and float(m[0, 2300]) == float("inf")
+    assert not same_bits(want[0, 2100:2290], x[0, 2100:2290])            # the gain comes down before the Inf, in every channel
+    assert same_bits(pushed(stream_of(C, **LIMIT), x, cuts), want)
+    if C == 1:
+        assert same_bits(pushed(stream_of(**LIMIT), x, cuts), want)
+
+
 @pytest.mark.parametrize("cuts", sorted(CUTS))
 def test_linked_limiter_at_8000_through_the_chain(cuts):
     x = linked_clip(2, CUTS[cuts], seed=3)
@@ -283,6 +307,55 @@ def test_nothing_past_the_end_is_written_and_bad_groups_are_left_alone(entry):
     for k in (0, 1):
         assert untouched(keeps[k], PAD, PAD + n_keep) and same_bits(keeps[k][PAD:PAD + n_keep], src[k, -n_keep:])
     assert all(untouched(k) for k in keeps[2:])
+
+
+@pytest.mark.parametrize("entry", ["limit", "encode"])
+def test_jobs_of_one_mono_launch_are_groups_of_one(entry):
+    """Three jobs of other sizes, bases and dither keys in ONE launch of a mono entry, each with a carry and a fresh span and a
+    dst at an odd element offset of a sentinel buffer, against the entry of streams of channels on the groups [0, 1, 2, 3] of the
+    same jobs, planar, with the same key table: the same bits, nothing written outside dst[0 .. n_out) and carry_out[0 .. n_keep)."""
+    n_outs, n_carry, n_keep, H = [1, 1025, 2500], 700, 600, 240
+    rng = np.random.default_rng(31)
+    carry = [torch.from_numpy(rng.uniform(-0.9, 0.9, n_carry).astype(np.float32)).cuda() for _ in n_outs]
+    fresh = [torch.from_numpy(rng.uniform(-0.9, 0.9, n + 300).astype(np.float32)).cuda() for n in n_outs]
+    bases = [40000, 2 ** 33 + 7, 123457]
+    lead = 2 * H + 10 if entry == "limit" else 3                         # (the limiter's outputs trail its source by 2 H + 10)
+    odt, esz = (torch.float32, 4) if entry == "limit" else (torch.int16, 2)
+    keys = np.array([[77, 0], [78, 5], [2 ** 40 + 3, 1]], dtype=np.uint64)
+    kp = torch.from_numpy(keys.view(np.int64)).cuda()
+    D, L = delivery(), hip.lib()
+
+    def launch(linked):
+        dsts = [sentinel_buffer(PAD + 1 + n + PAD, odt) for n in n_outs]
+        keeps = [sentinel_buffer(PAD + 1 + n_keep + PAD) for _ in n_outs]
+        jobs = [hip.StreamJob(carry[j].data_ptr(), fresh[j].data_ptr(), dsts[j].data_ptr() + esz * (PAD + 1),
+                              keeps[j].data_ptr() + 4 * (PAD + 1), bases[j], bases[j] + lead, n_carry, fresh[j].numel(), n,
+                              n_keep if entry == "limit" else 0, 0, 0) for j, n in enumerate(n_outs)]
+        keep, (jp, gp) = upload_tables([(hip.StreamJob * 3)(*jobs), np.arange(4, dtype=np.int32)], torch.device("cuda"))
+        tables = (jp, 3, gp, 3) if linked else (jp, 3)
+        if entry == "limit":
+            rc = getattr(L, "fh_stream_limit_linked_f32" if linked else "fh_stream_limit_f32")(
+                *tables, max(n_outs), D._tp_taps(), D._window(H), H, 0.5, hip.stream())
+        else:
+            rc = getattr(L, "fh_stream_pcm_i16_rows_f32" if linked else "fh_stream_pcm_i16_f32")(
+                *tables, max(n_outs), kp.data_ptr(), *((0,) if linked else ()), hip.stream())
+        torch.cuda.synchronize()
+        assert rc == 0
+        return dsts, keeps
+
+    (dm, km), (dl, kl) = launch(False), launch(True)
+    ints = torch.int32 if entry == "limit" else torch.int16
+    for j, n in enumerate(n_outs):
+        assert torch.equal(dm[j].view(ints), dl[j].view(ints)) and same_bits(km[j], kl[j])
+        assert untouched(dm[j], PAD + 1, PAD + 1 + n) and not untouched(dm[j])
+        src = torch.cat([carry[j], fresh[j]])
+        if entry == "limit":
+            assert untouched(km[j], PAD + 1, PAD + 1 + n_keep) and same_bits(km[j][PAD + 1:PAD + 1 + n_keep], src[-n_keep:])
+            assert float(dm[j][PAD + 1:PAD + 1 + n].abs().max()) <= 0.5
+        else:                                                             # job j under its own key, at its absolute indices
+            assert untouched(km[j])
+            d = pcm.tpdf_dither(int(keys[j, 0]), int(keys[j, 1]), 0, n, first=bases[j] + lead)
+            assert np.array_equal(dm[j][PAD + 1:PAD + 1 + n].cpu().numpy(), pcm.quantize(src[lead:lead + n].cpu().numpy(), d))
 
 
 def test_a_group_with_an_odd_dst_is_left_unwritten():

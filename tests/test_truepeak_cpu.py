@@ -271,7 +271,9 @@ def test_header_exports_and_abi_are_consistent():
             assert ctype is want, (name, p)
     build = __import__("flowhigh_amd.build", fromlist=["SOURCES"])
     assert "truepeak.hip" in build.SOURCES
-    text = (ROOT / "flowhigh_amd" / "csrc" / "truepeak.hip").read_text()
+    text = (ROOT / "flowhigh_amd" / "csrc" / "truepeak.hip").read_text()            # (its constants are truepeak_common.h's, stated once)
+    assert '#include "truepeak_common.h"' in text and "MAX_H =" not in text and "HALO =" not in text
+    text = (ROOT / "flowhigh_amd" / "csrc" / "truepeak_common.h").read_text()
     assert f"MAX_H = {truepeak.MAX_H};" in text and f"HALO = {truepeak.HALF};" in text
 
 
