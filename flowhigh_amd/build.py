@@ -24,7 +24,7 @@ EXTRA_FLAGS = {"conv_wino54_bf.hip": ["-fno-slp-vectorize"], "conv_wino.hip": ["
 # fixed at the source, conv_wino_common.h: wino_prefetch_a; the limit here is about speed.)
 RESOURCE_FLAGS = ["-Rpass-analysis=kernel-resource-usage"]
 MAX_SCRATCH_BYTES = 16          # per lane: up to 4 spilled registers (prologue / epilogue values) are tolerated and reported
-HEADERS = ["fh_common.h", "bf16x6.h", "conv_mfma_common.h", "conv_mfma_epilogue.h", "conv_wino_common.h", "conv_wino54_kernel.h", "attention_softmax.h", "attention_kernel.h", "attention_bf_kernel.h", "gemm_common.h", "philox.h", "pcm_common.h", "truepeak_common.h"]
+HEADERS = ["fh_common.h", "row_groups.h", "bf16x6.h", "conv_mfma_common.h", "conv_mfma_epilogue.h", "conv_wino_common.h", "conv_wino54_kernel.h", "attention_softmax.h", "attention_kernel.h", "attention_bf_kernel.h", "gemm_common.h", "philox.h", "pcm_common.h", "truepeak_common.h"]
 
 
 def _deps():

@@ -26,6 +26,7 @@ import re
 import torch
 
 from . import hip
+from .field import FieldNet, across
 from .flow import FH, _pad_rows
 
 DWLN_ROWS = 16          # rows of one clip a block of fh_dwconv_ln_f32 owns (csrc/convnext.hip: LN_ROWS)
@@ -64,7 +65,7 @@ def fold_gamma(w2, b2, gamma):
     return w.float(), b.float()
 
 
-class ConvNextNet:
+class ConvNextNet(FieldNet):
     grouped_field = False          # (the time-conditioned LayerNorm takes one time: no forward(groups=))
 
     def __init__(self, sd, device, bf=False):
@@ -121,9 +122,6 @@ class ConvNextNet:
             raise NotImplementedError("convnext blocks of different inner widths")
         self._ws = hip.ShapeCache()
 
-    def gemm(self, A, W, C_out, M, N, K, **kw):
-        return hip.gemm(A, W, C_out, M, N, K, bf=self.bf, **kw)
-
     @hip.on_device
     def workspace(self, batch, n):
         key = (batch, n)
@@ -138,41 +136,9 @@ class ConvNextNet:
         self._ws[key] = ws
         return ws
 
-    @hip.on_device
-    def ragged_workspace(self, frames):
-        """Workspace for a ragged batch, as FlowNet.ragged_workspace: clips of `frames` frames packed back to back, with the
-        device segment table [n_seg][2] = (first row, rows) the two operators that look across rows take."""
-        frames = tuple(int(n) for n in frames)
-        key = ("ragged",) + frames
-        M, max_n = sum(frames), max(frames)
-        if key in self._ws:
-            small = self._ws[key]
-        else:
-            starts = [0]
-            for n in frames[:-1]:
-                starts.append(starts[-1] + n)
-            small = dict(seg=torch.tensor([[s_, n] for s_, n in zip(starts, frames)], dtype=torch.int32).to(self.device),
-                         frames=frames, rows=M, max_n=max_n)
-            self._ws[key] = small
-        ws = dict(self.workspace(1, -(-M // 256) * 256))      # (the row buffers of one clip of >= M frames, never held by the entry)
-        ws.update(small)
-        return ws
-
-    @hip.on_device
-    def set_cond(self, cond, batch, n, ragged=None):
-        """cond [B*n, dim_in] (log-mel of the low-res clip): e_cond = cond @ W_c^T + b."""
-        ws = ragged if ragged is not None else self.workspace(batch, n)
-        M = ragged["rows"] if ragged is not None else batch * n
-        self.gemm(cond, self.w_c, ws["e_cond"], M, self.dim, self.dim_in, bias=self.b_embed)
-
-    def _dwconv_ln(self, x, w, b, ksz, scale, shift, y, batch, n, seg, n_seg, max_n):
-        L, st = hip.lib(), hip.stream()
-        if seg is None:
-            hip.check(L.fh_dwconv_ln_f32(x.data_ptr(), hip.ptr(w), hip.ptr(b), scale.data_ptr(), shift.data_ptr(), y.data_ptr(),
-                                         batch, n, self.dim, ksz, LN_EPS, st), "fh_dwconv_ln_f32")
-        else:
-            hip.check(L.fh_dwconv_ln_seg_f32(x.data_ptr(), hip.ptr(w), hip.ptr(b), scale.data_ptr(), shift.data_ptr(),
-                                             y.data_ptr(), seg, n_seg, max_n, self.dim, ksz, LN_EPS, st), "fh_dwconv_ln_seg_f32")
+    def _dwconv_ln(self, x, w, b, ksz, scale, shift, y, rows):
+        across("fh_dwconv_ln", (x.data_ptr(), hip.ptr(w), hip.ptr(b), scale.data_ptr(), shift.data_ptr(), y.data_ptr()), rows,
+               (self.dim, ksz, LN_EPS))
 
     @hip.on_device
     def forward(self, x, t, out, batch, n, alpha=1.0, res=None, null_cond=False, ragged=None):
@@ -181,38 +147,18 @@ class ConvNextNet:
         L, st = hip.lib(), hip.stream()
         ws = ragged if ragged is not None else self.workspace(batch, n)
         M, D = (ragged["rows"] if ragged is not None else batch * n), self.dim
-        seg = ragged["seg"].data_ptr() if ragged is not None else None
-        n_seg, max_n = (len(ragged["frames"]), ragged["max_n"]) if ragged is not None else (0, 0)
-        h, h2, a, gbuf = ws["h"], ws["h2"], ws["a"], ws["g"]
-        if null_cond:
-            if self._e_null is None:            # null_cond @ W_c^T + b: one row, broadcast with ldr = 0
-                self._e_null = torch.empty(1, D, dtype=torch.float32, device=self.device)
-                self.gemm(self.null_cond, self.w_c, self._e_null, 1, D, self.dim_in, bias=self.b_embed)
-            self.gemm(x, self.w_x, h, M, D, self.dim_in, R=self._e_null, ldr=0)
-        else:
-            self.gemm(x, self.w_x, h, M, D, self.dim_in, R=ws["e_cond"])
-        if seg is None:
-            hip.check(L.fh_dwconv_gelu_res_f32(h.data_ptr(), self.dw_w.data_ptr(), self.dw_b.data_ptr(),
-                                               h2.data_ptr(), batch, n, D, self.dw_k, st), "fh_dwconv_gelu_res_f32")
-        else:
-            hip.check(L.fh_dwconv_gelu_res_seg_f32(h.data_ptr(), self.dw_w.data_ptr(), self.dw_b.data_ptr(), h2.data_ptr(),
-                                                   seg, n_seg, max_n, D, self.dw_k, st), "fh_dwconv_gelu_res_seg_f32")
-        hip.check(L.fh_time_fourier_f32(self.sinu_w.data_ptr(), float(t), ws["four"].data_ptr(), self.sinu_w.shape[0], st),
-                  "fh_time_fourier_f32")
-        hip.check(L.fh_gemv_f32(self.t_w.data_ptr(), ws["four"].data_ptr(), self.t_b.data_ptr(),
-                                ws["temb"].data_ptr(), self.hidden, self.t_w.shape[1], 1, st), "fh_gemv_f32")
-        hip.check(L.fh_gemv_f32(self.ss_w.data_ptr(), ws["temb"].data_ptr(), self.ss_b.data_ptr(),
-                                ws["ss"].data_ptr(), self.ss_w.shape[0], self.hidden, 0, st), "fh_gemv_f32")
-        ss = ws["ss"]
+        rows = (batch, n) if ragged is None else (ragged["seg"].data_ptr(), len(ragged["frames"]), ragged["max_n"])
+        h, h2, a, gbuf, ss = ws["h"], ws["h2"], ws["a"], ws["g"], ws["ss"]
+        self._embed(x, ws, M, rows, null_cond)
+        self._time_path(t, ws, self.sinu_w.shape[0], self.hidden, self.ss_w, self.ss_b, ss)
         cur, other = h2, h
         for i, lay in enumerate(self.layers):
             o = 2 * i * D
-            self._dwconv_ln(cur, lay["cw"], lay["cb"], lay["ksz"], ss[o:o + D], ss[o + D:o + 2 * D], a, batch, n, seg, n_seg, max_n)
+            self._dwconv_ln(cur, lay["cw"], lay["cb"], lay["ksz"], ss[o:o + D], ss[o + D:o + 2 * D], a, rows)
             inner = lay["inner"]
             self.gemm(a, lay["w1"], gbuf, M, inner, D, bias=lay["b1"])
             hip.check(L.fh_gelu_f32(gbuf.data_ptr(), gbuf.data_ptr(), M * inner, st), "fh_gelu_f32")
             self.gemm(gbuf, lay["w2"], other, M, D, inner, bias=lay["b2"], R=cur)
             cur, other = other, cur
-        self._dwconv_ln(cur, None, None, 1, self.ln_w, self.ln_b, a, batch, n, seg, n_seg, max_n)
-        self.gemm(a, self.w_pred, out, M, self.dim_in, D, R=res, alpha=alpha)
-        return out
+        self._dwconv_ln(cur, None, None, 1, self.ln_w, self.ln_b, a, rows)
+        return self._predict(a, out, M, alpha, res)

@@ -1,10 +1,10 @@
 // HBM-bound pointwise / reduction kernels of the FLowHigh transformer.
 //   fh_dwconv_gelu_res_f32 : ConvPositionEmbed + residual   models/transformer.py:16-46, flow.py:240
-//   fh_rmsnorm_f32         : AdaptiveRMSNorm / RMSNorm      models/transformer.py:49-88
+//   fh_rmsnorm_f32         : AdaptiveRMSNorm / RMSNorm      models/transformer.py:49-88 (fh_rmsnorm_groups_f32: gamma / beta per group of rows)
 //   fh_qknorm_rope_f32     : MultiheadRMSNorm + RoPE        models/attend.py:144-151,179-184, pos_emb.py:53-59
 // All tensors are token-major [B*n, dim]; consecutive lanes touch consecutive features
 // (16-byte vector accesses), row reductions are 64-lane butterflies, no LDS.
-#include "fh_common.h"
+#include "row_groups.h"
 
 namespace {
 
@@ -71,15 +71,18 @@ __global__ __launch_bounds__(256) void dwconv_gelu_res_kernel(const float* __res
   }
 }
 
-// one wave per row; dim % 256 == 0, dim <= 4096
-__global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ x,
-                                                      const float* __restrict__ gamma,
-                                                      const float* __restrict__ beta,
-                                                      float* __restrict__ y, int rows, int dim,
-                                                      float scale) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+// one wave per row; dim % 256 == 0, dim <= 4096.  The one body of fh_rmsnorm_f32 (Sel = OneGroup: gamma0 / beta0 as they are)
+// and fh_rmsnorm_groups_f32 (Sel = RowGroups: the row's group g reads gamma0 / beta0 + g * g_stride).
+template <class Sel>
+__global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma0,
+                                                      const float* __restrict__ beta0, long long g_stride,
+                                                      float* __restrict__ y, int rows, int dim, float scale, Sel sel) {
+  const int row = sel.row();
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
+  const int gi = sel.group(row);
+  const float* gamma = gamma0 + (size_t)gi * g_stride;
+  const float* beta = beta0 ? beta0 + (size_t)gi * g_stride : nullptr;
   const float* xr = x + (size_t)row * dim;
   float* yr = y + (size_t)row * dim;
   f32x4 v[16];
@@ -176,9 +179,23 @@ extern "C" int fh_rmsnorm_f32(const float* x, const float* gamma, const float* b
                               int rows, int dim, void* stream) {
   FH_CHECK_ARG(x && gamma && y && rows > 0, "fh_rmsnorm_f32: bad args");
   FH_CHECK_ARG(dim % 256 == 0 && dim <= 4096, "fh_rmsnorm_f32: dim %d unsupported", dim);
-  hipLaunchKernelGGL(rmsnorm_kernel, dim3(fh_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma,
-                     beta, y, rows, dim, sqrtf((float)dim));
+  hipLaunchKernelGGL(rmsnorm_kernel<OneGroup>, dim3(fh_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, 0LL, y,
+                     rows, dim, sqrtf((float)dim), OneGroup{});
   FH_CHECK_LAUNCH("fh_rmsnorm_f32");
+  return FH_OK;
+}
+
+extern "C" int fh_rmsnorm_groups_f32(const float* x, const float* gamma, const float* beta, long long g_stride, float* y, int rows,
+                                     int dim, const fh_row_groups* groups, void* stream) {
+  FH_CHECK_ARG(x && gamma && y && rows > 0, "fh_rmsnorm_groups_f32: bad args");
+  FH_CHECK_ARG(dim % 256 == 0 && dim > 0 && dim <= 4096, "fh_rmsnorm_groups_f32: dim %d unsupported", dim);
+  FH_CHECK_GROUPS("fh_rmsnorm_groups_f32", groups, rows);
+  FH_CHECK_ARG(g_stride >= 0 && g_stride % 4 == 0, "fh_rmsnorm_groups_f32: g_stride %lld must be a non-negative multiple of 4", g_stride);
+  FH_CHECK_ARG(((((size_t)x) | ((size_t)gamma) | ((size_t)beta) | ((size_t)y)) & 15) == 0,
+               "fh_rmsnorm_groups_f32: x, gamma, beta and y must be 16-byte aligned");
+  hipLaunchKernelGGL(rmsnorm_kernel<RowGroups>, dim3(fh_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, g_stride,
+                     y, rows, dim, sqrtf((float)dim), RowGroups{groups_arg(groups)});
+  FH_CHECK_LAUNCH("fh_rmsnorm_groups_f32");
   return FH_OK;
 }
 

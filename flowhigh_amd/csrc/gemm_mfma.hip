@@ -98,44 +98,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(const float* __restrict__ A, 
   gemm_epilogue(acc, g, bias, R, ldr, C, ldc, M, N, alpha, mode);
 }
 
-// ---- y = act(W x + b), one wave per output row ------------------------------------------
-__global__ __launch_bounds__(256) void gemv_kernel(const float* __restrict__ W,
-                                                   const float* __restrict__ x,
-                                                   const float* __restrict__ bias,
-                                                   float* __restrict__ y, int N, int K, int act) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= N) return;
-  const float* w = W + (size_t)row * K;
-  float s = 0.f;
-  for (int k = lane * 4; k < K; k += 256) {
-    f32x4 wv = *reinterpret_cast<const f32x4*>(w + k);
-    f32x4 xv = *reinterpret_cast<const f32x4*>(x + k);
-    s = fmaf(wv[0], xv[0], s);
-    s = fmaf(wv[1], xv[1], s);
-    s = fmaf(wv[2], xv[2], s);
-    s = fmaf(wv[3], xv[3], s);
-  }
-  s = wave_sum(s);
-  if (lane == 0) {
-    s += bias ? bias[row] : 0.f;
-    if (act == 1) s = s / (1.f + expf(-s));
-    y[row] = s;
-  }
-}
-
-__global__ void time_fourier_kernel(const float* __restrict__ w, float t, float* __restrict__ out,
-                                    int half) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= half) return;
-  // pos_emb.py:24: freqs = x * weights * 2 * math.pi, evaluated left to right in fp32
-  float f = t * w[i];
-  f = f * 2.0f;
-  f = f * 3.14159265358979323846f;
-  out[i] = sinf(f);
-  out[half + i] = cosf(f);
-}
-
 }  // namespace
 
 extern "C" int fh_gemm_f32(const float* A, int lda, const float* W, const float* bias,
@@ -143,21 +105,4 @@ extern "C" int fh_gemm_f32(const float* A, int lda, const float* W, const float*
                            float alpha, int epilogue, void* stream) {
   return launch_gemm<float>("fh_gemm_f32", BK, gemm_kernel<1, 1>, gemm_kernel<1, 2>, gemm_kernel<2, 2>, A, lda, W, bias, R, ldr, C,
                             ldc, M, N, K, alpha, epilogue, stream);
-}
-
-extern "C" int fh_gemv_f32(const float* W, const float* x, const float* bias, float* y, int N,
-                           int K, int act, void* stream) {
-  FH_CHECK_ARG(W && x && y && N > 0 && K > 0 && K % 4 == 0, "fh_gemv_f32: bad args");
-  hipLaunchKernelGGL(gemv_kernel, dim3(fh_cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream, W, x, bias, y,
-                     N, K, act);
-  FH_CHECK_LAUNCH("fh_gemv_f32");
-  return FH_OK;
-}
-
-extern "C" int fh_time_fourier_f32(const float* w, float t, float* out, int half_dim, void* stream) {
-  FH_CHECK_ARG(w && out && half_dim > 0, "fh_time_fourier_f32: bad args");
-  hipLaunchKernelGGL(time_fourier_kernel, dim3(fh_cdiv(half_dim, 256)), dim3(256), 0,
-                     (hipStream_t)stream, w, t, out, half_dim);
-  FH_CHECK_LAUNCH("fh_time_fourier_f32");
-  return FH_OK;
 }

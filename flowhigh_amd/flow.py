@@ -18,6 +18,7 @@ import ctypes
 import torch
 
 from . import hip
+from .field import FieldNet, across, entry_pair
 from .tables import rotary_tables
 
 FH = "flowhigh."
@@ -53,7 +54,7 @@ def pack_geglu(w, b):
     return _pad_rows(wp.view(nblk * 64, k)), bp.view(-1).contiguous(), nblk * 32
 
 
-class FlowNet:
+class FlowNet(FieldNet):
     grouped_field = True           # forward(groups=): a time per group of rows, for clips of different step counts in one sequence
 
     def __init__(self, sd, device, depth=2, heads=16, dim_head=64, store=None, bf=False, attn_form="f32", attn_window=None):
@@ -73,14 +74,15 @@ class FlowNet:
         # the softmax unchanged).  The entry pair is picked here, once; a missing entry is an error at the first forward.
         from .planner import resolve_attn_form
         self.attn_form = resolve_attn_form(attn_form)
-        self._attn, self._attn_seg = (("fh_attention_bf16x6_f32", "fh_attention_bf16x6_seg_f32") if self.attn_form == "bf16x6"
-                                      else ("fh_attention_f32", "fh_attention_seg_f32"))
+        stem = "fh_attention_bf16x6" if self.attn_form == "bf16x6" else "fh_attention"
+        self._attn, self._attn_seg = entry_pair(stem)
         # attn_window: None (full attention: the pair above, as always) | W >= 0: frame i attends to the frames j of its clip with
         # |i - j| <= W (frames of 10 ms: 500 = +-5 s) -- the banded pair of the same form, with W as their radius
         from .planner import resolve_attn_window
         self.attn_window = resolve_attn_window(attn_window)
-        self._attn_band, self._attn_band_seg = (self._attn.replace("_f32", "_band_f32"), self._attn_seg.replace("_seg_f32", "_band_seg_f32"))
+        self._attn_band, self._attn_band_seg = entry_pair(stem + "_band")
         self._radius = None if self.attn_window is None else min(self.attn_window, 2 ** 31 - 1)      # (the entries take a C int)
+        self._attn_stem, self._attn_tail = (stem, (10.0,)) if self._radius is None else (stem + "_band", (self._radius, 10.0))
         from .planner import use_gemm_bf16x6
         if getattr(W, "form", None) is not None and use_gemm_bf16x6(W.form) != self.bf:
             # (a blob holds the linears in ONE form: asking it for the other would fail on the first missing key)
@@ -147,9 +149,6 @@ class FlowNet:
         self._ws = hip.ShapeCache()
         self._group_ws = {}
 
-    def gemm(self, A, W, C_out, M, N, K, **kw):
-        return hip.gemm(A, W, C_out, M, N, K, bf=self.bf, **kw)
-
     @hip.on_device
     def workspace(self, batch, n):
         key = (batch, n)
@@ -167,37 +166,9 @@ class FlowNet:
         self._ws[key] = ws
         return ws
 
-    @hip.on_device
-    def ragged_workspace(self, frames):
-        """Workspace for a ragged batch: clips of `frames` frames each packed back to back (M = sum rows, no padding).
-        Carries the device segment table [n_seg][2] = (first row, rows) the seg kernels take."""
-        frames = tuple(int(n) for n in frames)
-        key = ("ragged",) + frames
-        M, max_n = sum(frames), max(frames)
-        if key in self._ws:
-            small = self._ws[key]
-        else:
-            cos_t, sin_t = rotary_tables(self.inv_freq, max_n)      # positions restart in every clip
-            starts = [0]
-            for n in frames[:-1]:
-                starts.append(starts[-1] + n)
-            small = dict(cos=cos_t.to(self.device), sin=sin_t.to(self.device),
-                         seg=torch.tensor([[s_, n] for s_, n in zip(starts, frames)], dtype=torch.int32).to(self.device),
-                         frames=frames, rows=M, max_n=max_n)
-            self._ws[key] = small           # (accounted with what it owns: the tables)
-        # The row buffers are the ones of ONE clip of >= M frames, looked up on every call and never held by the
-        # cached entry (an entry that kept them would pin workspace(1, M) for every mix of lengths, outside the byte
-        # bound of the cache); M is rounded up so that mixes of similar total length share them.
-        ws = dict(self.workspace(1, -(-M // 256) * 256))
-        ws.update(small)
-        return ws
-
-    @hip.on_device
-    def set_cond(self, cond, batch, n, ragged=None):
-        """cond [B*n, dim_in] (log-mel of the low-res clip): e_cond = cond @ W_c^T + b."""
-        ws = ragged if ragged is not None else self.workspace(batch, n)
-        M = ragged["rows"] if ragged is not None else batch * n
-        self.gemm(cond, self.w_c, ws["e_cond"], M, self.dim, self.dim_in, bias=self.b_embed)
+    def _ragged_tables(self, max_n):
+        cos_t, sin_t = rotary_tables(self.inv_freq, max_n)      # positions restart in every clip
+        return dict(cos=cos_t.to(self.device), sin=sin_t.to(self.device))
 
     @hip.on_device
     def _group_buffers(self, n_groups):
@@ -229,7 +200,6 @@ class FlowNet:
         L, st = hip.lib(), hip.stream()
         ws = ragged if ragged is not None else self.workspace(batch, n)
         M, D = (ragged["rows"] if ragged is not None else batch * n), self.dim
-        seg = ragged["seg"].data_ptr() if ragged is not None else None
         n_seg_all, max_n = (len(ragged["frames"]), ragged["max_n"]) if ragged is not None else (0, 0)
         grp = None
         if groups is not None:
@@ -242,28 +212,12 @@ class FlowNet:
             alpha, res = 1.0, None
         else:
             n_seg = n_seg_all
+        rows = (batch, n) if ragged is None else (ragged["seg"].data_ptr(), n_seg, max_n)
         h, h2, a, att, qkv = ws["h"], ws["h2"], ws["a"], ws["att"], ws["qkv"]
-        if null_cond:
-            if self._e_null is None:            # null_cond @ W_c^T + b: one row, broadcast with ldr = 0
-                self._e_null = torch.empty(1, D, dtype=torch.float32, device=self.device)
-                self.gemm(self.null_cond, self.w_c, self._e_null, 1, D, self.dim_in, bias=self.b_embed)
-            self.gemm(x, self.w_x, h, M, D, self.dim_in, R=self._e_null, ldr=0)
-        else:
-            self.gemm(x, self.w_x, h, M, D, self.dim_in, R=ws["e_cond"])
-        if seg is None:
-            hip.check(L.fh_dwconv_gelu_res_f32(h.data_ptr(), self.dw_w.data_ptr(), self.dw_b.data_ptr(),
-                                               h2.data_ptr(), batch, n, D, self.dw_k, st), "fh_dwconv_gelu_res_f32")
-        else:
-            hip.check(L.fh_dwconv_gelu_res_seg_f32(h.data_ptr(), self.dw_w.data_ptr(), self.dw_b.data_ptr(), h2.data_ptr(),
-                                                   seg, n_seg, max_n, D, self.dw_k, st), "fh_dwconv_gelu_res_seg_f32")
+        self._embed(x, ws, M, rows, null_cond)
         if grp is None:
-            hip.check(L.fh_time_fourier_f32(self.sinu_w.data_ptr(), float(t), ws["four"].data_ptr(), D // 2, st),
-                      "fh_time_fourier_f32")
-            hip.check(L.fh_gemv_f32(self.t_w.data_ptr(), ws["four"].data_ptr(), self.t_b.data_ptr(),
-                                    ws["temb"].data_ptr(), D, D, 1, st), "fh_gemv_f32")
-            hip.check(L.fh_gemv_f32(self.gb_w.data_ptr(), ws["temb"].data_ptr(), self.gb_b.data_ptr(),
-                                    ws["gb"].data_ptr(), self.gb_w.shape[0], D, 0, st), "fh_gemv_f32")
             gb = ws["gb"]
+            self._time_path(t, ws, D // 2, D, self.gb_w, self.gb_b, gb)
 
             def norm(x_, gamma, beta):
                 hip.check(L.fh_rmsnorm_f32(x_.data_ptr(), gamma.data_ptr(), hip.ptr(beta), a.data_ptr(), M, D, st), "fh_rmsnorm_f32")
@@ -287,25 +241,9 @@ class FlowNet:
             g1, b1, g2, b2 = (gb[o + i * D: o + (i + 1) * D] for i in range(4))
             norm(cur, g1, b1)
             self.gemm(a, lay["w_qkv"], qkv, M, 3 * D, D)
-            if seg is None:
-                hip.check(L.fh_qknorm_rope_f32(qkv.data_ptr(), lay["gq"].data_ptr(), lay["gk"].data_ptr(),
-                                               ws["cos"].data_ptr(), ws["sin"].data_ptr(), batch, n, self.heads, st),
-                          "fh_qknorm_rope_f32")
-                if self._radius is None:
-                    hip.check(getattr(L, self._attn)(qkv.data_ptr(), att.data_ptr(), batch, n, self.heads, 10.0, st), self._attn)
-                else:
-                    hip.check(getattr(L, self._attn_band)(qkv.data_ptr(), att.data_ptr(), batch, n, self.heads, self._radius, 10.0, st),
-                              self._attn_band)
-            else:
-                hip.check(L.fh_qknorm_rope_seg_f32(qkv.data_ptr(), lay["gq"].data_ptr(), lay["gk"].data_ptr(),
-                                                   ws["cos"].data_ptr(), ws["sin"].data_ptr(), seg, n_seg, max_n,
-                                                   self.heads, st), "fh_qknorm_rope_seg_f32")
-                if self._radius is None:
-                    hip.check(getattr(L, self._attn_seg)(qkv.data_ptr(), att.data_ptr(), seg, n_seg, max_n, self.heads, 10.0, st),
-                              self._attn_seg)
-                else:
-                    hip.check(getattr(L, self._attn_band_seg)(qkv.data_ptr(), att.data_ptr(), seg, n_seg, max_n, self.heads,
-                                                              self._radius, 10.0, st), self._attn_band_seg)
+            across("fh_qknorm_rope", (qkv.data_ptr(), lay["gq"].data_ptr(), lay["gk"].data_ptr(), ws["cos"].data_ptr(), ws["sin"].data_ptr()),
+                   rows, (self.heads,))
+            across(self._attn_stem, (qkv.data_ptr(), att.data_ptr()), rows, (self.heads, *self._attn_tail))
             self.gemm(att, lay["w_out"], other, M, D, D, R=cur)
             cur, other = other, cur
             norm(cur, g2, b2)
@@ -314,5 +252,4 @@ class FlowNet:
             self.gemm(ws["g"], lay["w2"], other, M, D, ip, bias=lay["b2"], R=cur, lda=ws["g"].shape[1])
             cur, other = other, cur
         norm(cur, self.final_gamma, None)
-        self.gemm(a, self.w_pred, out, M, self.dim_in, D, R=res, alpha=alpha)
-        return out
+        return self._predict(a, out, M, alpha, res)

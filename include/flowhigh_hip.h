@@ -576,27 +576,30 @@ int fh_axpby_f32(const float* x, float a, const float* y, float b, float* out, l
 int fh_rk_combine_f32(const float* y, const float* const* ks, int n_k, float h, const float* wa, float* out_a,
                       const float* wb, float* out_b, long long n, void* stream);
 
-/* A time and a step size per clip (flowhigh_amd/ode.py: mixed_schedule; csrc/steps.hip): the clips of a ragged sequence are
+/* A time and a step size per clip (flowhigh_amd/ode.py: mixed_schedule; csrc/row_groups.h): the clips of a ragged sequence are
  * sorted by step count, so the clips of one count are one contiguous range of rows, a GROUP.  Group g is the rows
  * row_end[g - 1] .. row_end[g] - 1 (row_end[-1] = 0); n = 1 .. FH_MAX_GROUPS, row_end strictly increasing from a first entry >= 1.
  * Every entry below reads the groups and its per-group scalars (HOST pointers, n entries) at call time into kernel
  * arguments: no device table, no upload, graph-capturable; a wave finds its row's group by at most eight scalar compares.
- * An entry that takes rows refuses row_end[n - 1] != rows. */
+ * An entry that takes rows refuses row_end[n - 1] != rows.  Each grouped entry launches the kernel body of its one-time entry (the
+ * one-time entry is the case of one group, or one vector), which is why a group's rows have that entry's bits. */
 #define FH_MAX_GROUPS 8
 typedef struct {
   int32_t n;
   int32_t row_end[FH_MAX_GROUPS];
 } fh_row_groups;
 int fh_sizeof_row_groups(void);
-/* fh_time_fourier_f32 for n_groups times: out [n_groups][2 half_dim], row g the embedding of t[g], the bits of the one-time entry. */
+/* fh_time_fourier_f32 for n_groups times: out [n_groups][2 half_dim], row g the embedding of t[g]: the one-time entry is this
+ * kernel with one group. */
 int fh_time_fourier_groups_f32(const float* w, const float* t, float* out, int half_dim, int n_groups, void* stream);
 /* Y[j] = act(W X[j] + bias) for T = 1 .. 8 vectors X[j] = X + j ldx (K floats each), Y[j] = Y + j ldy (N floats each); K % 4 == 0,
- * ldx % 4 == 0, W and X 16-byte aligned.  One wave per row of W, which is read once for all T; every sum is accumulated in
- * fh_gemv_f32's order, so every Y[j] has that entry's bits. */
+ * ldx % 4 == 0, W and X 16-byte aligned.  One wave per row of W, which is read once for all T; fh_gemv_f32 is this kernel at
+ * T = 1, ldx = K, ldy = N, so every Y[j] has that entry's bits. */
 int fh_gemv_rows_f32(const float* W, const float* X, int ldx, const float* bias, float* Y, int ldy, int N, int K, int T, int act,
                      void* stream);
 /* fh_rmsnorm_f32 with a gamma / beta per group: a row of group g reads gamma + g g_stride and beta + g g_stride (beta may be
- * NULL); g_stride % 4 == 0.  dim % 256 == 0, dim <= 4096; the bits of fh_rmsnorm_f32 on the group's rows with its vectors. */
+ * NULL); g_stride % 4 == 0.  dim % 256 == 0, dim <= 4096; one kernel body with fh_rmsnorm_f32 (which is group 0
+ * for every row), hence its bits on the group's rows with its vectors. */
 int fh_rmsnorm_groups_f32(const float* x, const float* gamma, const float* beta, long long g_stride, float* y, int rows, int dim,
                           const fh_row_groups* groups, void* stream);
 /* out = alpha[g] v + res over [rows, dim] floats (res may be NULL: out = alpha[g] v), dim % 4 == 0, 16-byte aligned pointers: the
@@ -606,7 +609,8 @@ int fh_rmsnorm_groups_f32(const float* x, const float* gamma, const float* beta,
 int fh_axpy_groups_f32(const float* v, const float* alpha, const float* res, float* out, int rows, int dim,
                        const fh_row_groups* groups, void* stream);
 /* fh_rk_combine_f32 with a step h[g] per group over [rows, dim] floats (dim % 4 == 0): the same term order, skipped zero weights,
- * one- and two-output forms and aliasing rules; a row of group g has the bits of that entry called with h[g]. */
+ * one- and two-output forms and aliasing rules, because both kernels run one element body; a row of group g has the bits of
+ * that entry called with h[g]. */
 int fh_rk_combine_groups_f32(const float* y, const float* const* ks, int n_k, const float* h, const float* wa, float* out_a,
                              const float* wb, float* out_b, int rows, int dim, const fh_row_groups* groups, void* stream);
 
