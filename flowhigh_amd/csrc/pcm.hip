@@ -16,6 +16,8 @@
 // every sample is a 2-byte store at its place in its frame.  Loads are two 16-byte reads where the run's first float is 16-byte
 // aligned, else eight 4-byte reads.  Which stores are used never changes a value.
 // encode() and dither_run() are in pcm_common.h: the encoder of a stream's blocks (stream_delivery.hip) uses the same two.
+//   fh_pcm_s24_f32, fh_pcm_s24_seg_f32   the same two forms in 24 bits (pcm='s24': 3 bytes a sample at any byte address,
+//                        pcm='s24in32': an int32): pcm_s24_kernel below; encode24() and the stores of a run are in pcm_common.h
 #include "fh_common.h"
 #include "pcm_common.h"
 #include "philox.h"
@@ -143,6 +145,83 @@ __global__ __launch_bounds__(256) void pcm_i16_kernel(Loc loc, const unsigned lo
 
 int pcm_blocks(int len) { return fh_cdiv(((long long)len + RUN - 1) / RUN + 1, 256); }      // runs of a row at any alignment
 
+// ---- 24 bits: pcm='s24' (container 3: packed, 3 bytes a sample) and 's24in32' (container 4: int32) ---------------------------
+// The locators of the int16 kernel with dst as a byte address.
+struct pcm24_view {
+  const float* src;
+  unsigned char* dst;
+  long long pitch;
+  int channels, len;
+};
+struct BatchedPcm24 {
+  const float* x;
+  unsigned char* y;
+  int channels, len, container;
+  __device__ pcm24_view operator()(int b) const {
+    const size_t per = (size_t)channels * len;
+    return {x + b * per, y + b * per * container, (long long)len, channels, len};
+  }
+};
+struct PcmTable24 {
+  const fh_pcm_clip* clips;
+  __device__ pcm24_view operator()(int b) const {
+    const fh_pcm_clip c = clips[b];
+    return {c.src, reinterpret_cast<unsigned char*>(c.dst), (long long)c.pitch, c.channels, c.len};
+  }
+};
+
+// Grid as pcm_i16_kernel's.  Planar: the blocks of channel ch own the row of that channel, N = len samples.  Interleaved: the
+// clip is ONE flat row of N = len * C samples, flat sample s = sample s / C of channel s % C, and the blocks (x, z) with z < C
+// share its runs: run (z * gridDim.x + x) * 256 + thread (C * gridDim.x * 256 >= C * (ceil(len / 8) + 1) runs, enough at any
+// alignment); a run's 8 samples lie in up to 8 channels, so each takes its own Philox block (dither_at).  Every C takes that
+// path.  The stores are store_run24's (pcm_common.h) either way; which ones are used never changes a value.
+template <class Loc>
+__global__ __launch_bounds__(256) void pcm_s24_kernel(Loc loc, const unsigned long long* __restrict__ keys, int interleaved,
+                                                      int container) {
+  const pcm24_view c = loc(blockIdx.y);
+  const int ch = blockIdx.z;
+  if (c.channels < 1 || c.channels > 8 || c.len < 1 || ch >= c.channels) return;      // (a table lives on the device: checked)
+  if (container == 4 && ((size_t)c.dst & 3)) return;                                  // (the batched entry refused it already)
+  unsigned long long seed = 0, strm = 0;
+  if (keys) {
+    seed = keys[2 * blockIdx.y];
+    strm = keys[2 * blockIdx.y + 1];
+  }
+  int q[RUN];
+  if (!interleaved) {
+    unsigned char* __restrict__ row = c.dst + (size_t)ch * c.len * container;
+    const long long first = ((long long)blockIdx.x * 256 + threadIdx.x) * RUN - lead24(row, container);
+    if (first >= c.len) return;
+    float x[RUN], d[RUN];
+    load_run(c.src + (long long)ch * c.pitch, first, c.len, first >= 0 && first + RUN <= c.len, x);
+#pragma unroll
+    for (int k = 0; k < RUN; ++k) d[k] = 0.f;
+    if (keys) dither_run(seed, strm, ch, first, d);
+#pragma unroll
+    for (int k = 0; k < RUN; ++k) q[k] = encode24(x[k], d[k]);
+    store_run24(row, first, c.len, q, container);
+    return;
+  }
+  const long long N = (long long)c.len * c.channels;
+  const long long first = (((long long)ch * gridDim.x + blockIdx.x) * 256 + threadIdx.x) * RUN - lead24(c.dst, container);
+  if (first >= N) return;
+  const long long s0 = first < 0 ? 0 : first;
+  long long t = N <= 0xFFFFFFFFll ? (long long)((unsigned)s0 / (unsigned)c.channels) : s0 / c.channels;
+  int cc = (int)(s0 - t * c.channels);
+#pragma unroll
+  for (int k = 0; k < RUN; ++k) {
+    const long long s = first + k;
+    q[k] = 0;
+    if (s < 0 || s >= N) continue;
+    q[k] = encode24(c.src[(long long)cc * c.pitch + t], keys ? dither_at(seed, strm, cc, t) : 0.f);
+    if (++cc == c.channels) {
+      cc = 0;
+      ++t;
+    }
+  }
+  store_run24(c.dst, first, N, q, container);
+}
+
 }  // namespace
 
 extern "C" int fh_sizeof_pcm_clip(void) { return (int)sizeof(fh_pcm_clip); }
@@ -169,5 +248,34 @@ extern "C" int fh_pcm_i16_seg_f32(const fh_pcm_clip* clips, int n_clips, int max
   hipLaunchKernelGGL(pcm_i16_kernel<PcmTable>, dim3(pcm_blocks(max_len), n_clips, max_channels), dim3(256), 0,
                      (hipStream_t)stream, PcmTable{clips}, (const unsigned long long*)keys, interleaved ? 1 : 0);
   FH_CHECK_LAUNCH("fh_pcm_i16_seg_f32");
+  return FH_OK;
+}
+
+extern "C" int fh_pcm_s24_f32(const float* x, void* y, const uint64_t* keys, int n_clips, int channels, int len, int interleaved,
+                              int container, void* stream) {
+  FH_CHECK_ARG(x && y, "fh_pcm_s24_f32: null pointer (x %p, y %p)", (const void*)x, y);
+  FH_CHECK_ARG(n_clips > 0 && n_clips < 65536, "fh_pcm_s24_f32: %d clips (1 .. 65535)", n_clips);
+  FH_CHECK_ARG(channels >= 1 && channels <= 8, "fh_pcm_s24_f32: %d channels (1 .. 8)", channels);
+  FH_CHECK_ARG(len > 0, "fh_pcm_s24_f32: len %d must be positive", len);
+  FH_CHECK_ARG(container == 3 || container == 4, "fh_pcm_s24_f32: container %d (3: packed bytes, 4: int32)", container);
+  FH_CHECK_ARG((((size_t)x) & 3) == 0, "fh_pcm_s24_f32: x must be 4-byte aligned");
+  FH_CHECK_ARG(container == 3 || (((size_t)y) & 3) == 0, "fh_pcm_s24_f32: an int32 y must be 4-byte aligned");
+  hipLaunchKernelGGL(pcm_s24_kernel<BatchedPcm24>, dim3(pcm_blocks(len), n_clips, channels), dim3(256), 0, (hipStream_t)stream,
+                     BatchedPcm24{x, (unsigned char*)y, channels, len, container}, (const unsigned long long*)keys,
+                     interleaved ? 1 : 0, container);
+  FH_CHECK_LAUNCH("fh_pcm_s24_f32");
+  return FH_OK;
+}
+
+extern "C" int fh_pcm_s24_seg_f32(const fh_pcm_clip* clips, int n_clips, int max_channels, int max_len, const uint64_t* keys,
+                                  int interleaved, int container, void* stream) {
+  FH_CHECK_ARG(clips, "fh_pcm_s24_seg_f32: null clip table");
+  FH_CHECK_ARG(n_clips > 0 && n_clips < 65536, "fh_pcm_s24_seg_f32: %d clips (1 .. 65535)", n_clips);
+  FH_CHECK_ARG(max_channels >= 1 && max_channels <= 8, "fh_pcm_s24_seg_f32: %d channels (1 .. 8)", max_channels);
+  FH_CHECK_ARG(max_len > 0, "fh_pcm_s24_seg_f32: max_len %d must be positive", max_len);
+  FH_CHECK_ARG(container == 3 || container == 4, "fh_pcm_s24_seg_f32: container %d (3: packed bytes, 4: int32)", container);
+  hipLaunchKernelGGL(pcm_s24_kernel<PcmTable24>, dim3(pcm_blocks(max_len), n_clips, max_channels), dim3(256), 0,
+                     (hipStream_t)stream, PcmTable24{clips}, (const unsigned long long*)keys, interleaved ? 1 : 0, container);
+  FH_CHECK_LAUNCH("fh_pcm_s24_seg_f32");
   return FH_OK;
 }

@@ -6,6 +6,7 @@
 //   fh_stream_pcm_i16_f32    pcm.hip's encoder with the dither at the sample's absolute index
 //   fh_stream_limit_linked_f32   the limiter of streams of 1 .. 8 channels: one envelope and one gain for a stream's channels
 //   fh_stream_pcm_i16_rows_f32   the encoder of such streams: channel c's dither, planar rows or interleaved sample frames
+//   fh_stream_pcm_s24_rows_f32   its 24-bit twin (packed in 3 bytes or in an int32), for mono streams too: a group of one job
 // One fh_stream_job per row and launch.  A job's source is TWO spans, the carry the stream kept and the fresh block, read as
 // one run of samples whose first has the absolute index `base`; nothing is concatenated.  The last block column of a launch
 // copies the last n_keep source samples into the stream's other carry buffer (the two ping-pong, so the copy never writes
@@ -298,6 +299,64 @@ __global__ __launch_bounds__(THREADS) void stream_pcm_kernel(Groups groups, cons
     if (first + k < J.n_out) out[(size_t)(first + k) * G.n + ch] = encode(x[k], d[k]);
 }
 
+// The 24-bit encoder (pcm.hip's pcm_s24_kernel on a stream's blocks; container 3: packed bytes, 4: int32).  Grid and groups as
+// stream_pcm_kernel's; a mono stream is a group of one job.  Planar: job j writes its own dst, n_out samples from any byte
+// address (container 4: none of the group if a dst is not 4-byte aligned).  Interleaved: the group's first dst is the frame
+// buffer, ONE flat row of n_out * C samples whose runs the blocks of the group's C jobs share (run (ch * gridDim.x + x) * THREADS
+// + thread); flat sample s is output s / C of job s % C, with that channel's dither at the absolute index first + s / C.
+__global__ __launch_bounds__(THREADS) void stream_pcm24_kernel(GroupTable groups, const unsigned long long* __restrict__ keys,
+                                                               int container) {
+  const int job = blockIdx.y, g = groups.group_of(job);
+  sd_group G;
+  if (!groups.group(g, G) || job < G.j0 || job >= G.j0 + G.n) return;
+  const fh_stream_job* __restrict__ jobs = groups.jobs + G.j0;
+  const int ch = job - G.j0;
+  const unsigned long long* __restrict__ key = keys ? keys + 2 * g : nullptr;
+  int q[RUN];
+  if (!groups.interleaved) {
+    if (container == 4)
+      for (int c = 0; c < G.n; ++c)
+        if (((size_t)jobs[c].dst) & 3) return;
+    const fh_stream_job J = jobs[ch];
+    if (J.n_out == 0) return;
+    unsigned char* __restrict__ row = (unsigned char*)J.dst;
+    const long long first = ((long long)blockIdx.x * THREADS + threadIdx.x) * RUN - lead24(row, container);
+    if (first >= J.n_out) return;
+    float x[RUN], d[RUN];
+    pcm_run(J, key, ch, first, x, d);
+#pragma unroll
+    for (int k = 0; k < RUN; ++k) q[k] = encode24(x[k], d[k]);
+    store_run24(row, first, J.n_out, q, container);
+    return;
+  }
+  unsigned char* __restrict__ out = (unsigned char*)jobs[0].dst;
+  if (container == 4 && (((size_t)out) & 3)) return;
+  const long long abs0 = jobs[0].first, N = (long long)jobs[0].n_out * G.n;      // (the counters are the group's)
+  if (N == 0) return;
+  const long long first = (((long long)ch * gridDim.x + blockIdx.x) * THREADS + threadIdx.x) * RUN - lead24(out, container);
+  if (first >= N) return;
+  const long long s0 = first < 0 ? 0 : first;
+  long long o = N <= 0xFFFFFFFFll ? (long long)((unsigned)s0 / (unsigned)G.n) : s0 / G.n;
+  int cc = (int)(s0 - o * G.n);
+  unsigned long long seed = 0, strm = 0;
+  if (key) {
+    seed = key[0];
+    strm = key[1];
+  }
+#pragma unroll
+  for (int k = 0; k < RUN; ++k) {
+    const long long s = first + k;
+    q[k] = 0;
+    if (s < 0 || s >= N) continue;
+    q[k] = encode24(source(jobs[cc]).at(abs0 + o), key ? dither_at(seed, strm, cc, abs0 + o) : 0.f);
+    if (++cc == G.n) {
+      cc = 0;
+      ++o;
+    }
+  }
+  store_run24(out, first, N, q, container);
+}
+
 }  // namespace
 
 extern "C" int fh_sizeof_stream_job(void) { return (int)sizeof(fh_stream_job); }
@@ -368,5 +427,16 @@ extern "C" int fh_stream_pcm_i16_rows_f32(const fh_stream_job* jobs, int n_jobs,
   hipLaunchKernelGGL(stream_pcm_kernel<GroupTable>, dim3(pcm_blocks(max_out), n_jobs), dim3(THREADS), 0, (hipStream_t)stream,
                      GroupTable{jobs, n_jobs, groups, n_groups, interleaved ? 1 : 0}, (const unsigned long long*)keys);
   FH_CHECK_LAUNCH("fh_stream_pcm_i16_rows_f32");
+  return FH_OK;
+}
+
+extern "C" int fh_stream_pcm_s24_rows_f32(const fh_stream_job* jobs, int n_jobs, const int32_t* groups, int n_groups, int max_out,
+                                          const uint64_t* keys, int interleaved, int container, void* stream) {
+  FH_CHECK_STREAM_JOBS("fh_stream_pcm_s24_rows_f32");
+  FH_CHECK_STREAM_GROUPS("fh_stream_pcm_s24_rows_f32");
+  FH_CHECK_ARG(container == 3 || container == 4, "fh_stream_pcm_s24_rows_f32: container %d (3: packed bytes, 4: int32)", container);
+  hipLaunchKernelGGL(stream_pcm24_kernel, dim3(pcm_blocks(max_out), n_jobs), dim3(THREADS), 0, (hipStream_t)stream,
+                     GroupTable{jobs, n_jobs, groups, n_groups, interleaved ? 1 : 0}, (const unsigned long long*)keys, container);
+  FH_CHECK_LAUNCH("fh_stream_pcm_s24_rows_f32");
   return FH_OK;
 }

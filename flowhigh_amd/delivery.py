@@ -8,6 +8,8 @@
                               4x oversampled peak, or with limiter='lookahead' the oversampled envelope and the look-ahead
                               limiter (behind the UNCAPPED loudness gain where loudness= is given as well)
               -> pcm='int16': one launch of fh_pcm_i16_f32 / fh_pcm_i16_seg_f32 (csrc/pcm.hip; pcm.py is the definition)
+                 pcm='s24', 's24in32': one launch of fh_pcm_s24_f32 / fh_pcm_s24_seg_f32: 24-bit samples packed in 3 bytes
+                              (uint8 [..., 3], the pcm_s24le layout) or sign-extended in an int32
 
 `batch` runs the batched entries over clips of one length, `ragged` the segment forms over a group of clips of different
 lengths; rows are read where the post-processor left them, and a clip gets the same bits from either.  With every keyword at
@@ -26,7 +28,20 @@ from .frontend import _launch, _ptr, clip_array, upload_tables
 from .prior import expand_seed
 
 MAX_RATE_FACTOR = 640             # max(up, down) of the reduced output_rate / 48000: the filter has 20 * that + 1 taps
-_PCM = (None, "int16")
+_PCM = (None, "int16", "s24", "s24in32")
+# pcm -> (the result's dtype, bytes per sample, the entries' stem); the 24-bit entries take the bytes per sample as `container`
+PCM_FORMATS = {"int16": (torch.int16, 2, "i16"), "s24": (torch.uint8, 3, "s24"), "s24in32": (torch.int32, 4, "s24")}
+
+
+def pcm_buffer(pcm, samples, device):
+    """The encoder's output buffer for `samples` samples: int16 / int32 [samples], or uint8 [3 * samples]."""
+    dtype, size, _ = PCM_FORMATS[pcm]
+    return torch.empty(samples * size // dtype.itemsize, dtype=dtype, device=device)
+
+
+def pcm_shape(pcm, *shape):
+    """The shape of an encoded block of `shape` samples: 's24' holds a sample as a last axis of 3 bytes."""
+    return tuple(shape) + ((3,) if pcm == "s24" else ())
 _DITHER = (None, "tpdf")
 
 
@@ -117,7 +132,8 @@ class Delivery:
     def batch(self, rows, chans, level, opt, which, packed=False):
         """rows [R, T48]: the channels of len(chans) clips of one length, in clip order; which: the clips' indices in the
         call (their dither keys).  -> list of the clips' results, [C_i, T] float32 / int16, or [T, C_i] int16 interleaved:
-        views of one buffer in clip order.  packed (mono clips only): that buffer instead, [R, T], or [R, T, 1] interleaved."""
+        views of one buffer in clip order.  packed (mono clips only): that buffer instead, [R, T], or [R, T, 1] interleaved.
+        pcm='s24in32': int32 in the int16 shapes; pcm='s24': uint8 with a last axis of 3 bytes ([C_i, T, 3], [T, C_i, 3])."""
         rows = self._rows(rows).contiguous()
         R, n = rows.shape[0], len(chans)
         if sum(chans) != R or (packed and R != n):
@@ -171,15 +187,17 @@ class Delivery:
                     _launch("fh_limit_seg_f32", clips, n, T, _ptr(m), self._window(H), 0, H, c32)
         if opt["pcm"] is None:
             return y if packed else list(y.split(chans))
-        out = torch.empty(R * T, dtype=torch.int16, device=self.device)
+        out = pcm_buffer(opt["pcm"], R * T, self.device)
         keys = self._keys(opt, which)
         if len(set(chans)) == 1:
-            _launch("fh_pcm_i16_f32", _ptr(y), _ptr(out), hip.ptr(keys), n, chans[0], T, int(opt["interleaved"]))
+            _, size, stem = PCM_FORMATS[opt["pcm"]]
+            _launch(f"fh_pcm_{stem}_f32", _ptr(y), _ptr(out), hip.ptr(keys), n, chans[0], T, int(opt["interleaved"]),
+                    *((size,) if stem == "s24" else ()))
         else:                      # clips of different channel counts: the segment form, the rows still where they are
             self._pcm_seg([y.data_ptr() + 4 * T * r for r in _starts(chans)], [T] * n, chans, [T] * n, out, keys, opt)
         if packed:
-            return out.view(R, T, 1) if opt["interleaved"] else out.view(R, T)
-        return _clip_views(out, chans, [T] * n, opt["interleaved"])
+            return out.view(pcm_shape(opt["pcm"], R, T, 1) if opt["interleaved"] else pcm_shape(opt["pcm"], R, T))
+        return _clip_views(out, chans, [T] * n, opt["interleaved"], opt["pcm"])
 
     def _group_peak(self, peak, chans):
         """The rows' peak slots -> the joint peak of every clip in all of its rows' slots; a silent clip's becomes 1.0, so the
@@ -316,11 +334,13 @@ class Delivery:
         return dbtp
 
     def _pcm_seg(self, srcs, pitches, chans, lens, out, keys, opt):
+        _, size, stem = PCM_FORMATS[opt["pcm"]]
         off = _starts([c * t for c, t in zip(chans, lens)])
-        table = (hip.PcmClip * len(chans))(*[hip.PcmClip(int(s), out.data_ptr() + 2 * o, int(p), int(c), int(t))
+        table = (hip.PcmClip * len(chans))(*[hip.PcmClip(int(s), out.data_ptr() + size * o, int(p), int(c), int(t))
                                             for s, o, p, c, t in zip(srcs, off, pitches, chans, lens)])
         desc, (clips,) = upload_tables([table], self.device)
-        _launch("fh_pcm_i16_seg_f32", clips, len(chans), max(chans), max(lens), hip.ptr(keys), int(opt["interleaved"]))
+        _launch(f"fh_pcm_{stem}_seg_f32", clips, len(chans), max(chans), max(lens), hip.ptr(keys), int(opt["interleaved"]),
+                *((size,) if stem == "s24" else ()))
 
     @hip.on_device
     def ragged(self, clips, level, opt, which):
@@ -380,9 +400,9 @@ class Delivery:
         if opt["rate"] is not None or target is not None or ceiling is not None:
             if opt["pcm"] is None:
                 return [y[row_off[r]:row_off[r] + c * t].view(c, t) for r, c, t in zip(first, chans, lens)]
-        out = torch.empty(sum(c * t for c, t in zip(chans, lens)), dtype=torch.int16, device=self.device)
+        out = pcm_buffer(opt["pcm"], sum(c * t for c, t in zip(chans, lens)), self.device)
         self._pcm_seg(srcs, pitches, chans, lens, out, self._keys(opt, which), opt)
-        return _clip_views(out, chans, lens, opt["interleaved"])
+        return _clip_views(out, chans, lens, opt["interleaved"], opt["pcm"])
 
 
 _COEF = {}
@@ -399,11 +419,11 @@ def _starts(lens):
     return [int(x) for x in np.cumsum([0] + list(lens[:-1]))]
 
 
-def _clip_views(out, chans, lens, interleaved):
-    """The clips of a packed int16 buffer: [C, T] planar, [T, C] interleaved."""
-    views, o = [], 0
+def _clip_views(out, chans, lens, interleaved, pcm="int16"):
+    """The clips of a packed result buffer: [C, T] planar, [T, C] interleaved; 's24' (uint8, 3 bytes a sample): [C, T, 3], [T, C, 3]."""
+    views, o, k = [], 0, 3 if pcm == "s24" else 1
     for c, t in zip(chans, lens):
-        v = out[o:o + c * t]
-        views.append(v.view(t, c) if interleaved else v.view(c, t))
-        o += c * t
+        v = out[o:o + k * c * t]
+        views.append(v.view(pcm_shape(pcm, t, c) if interleaved else pcm_shape(pcm, c, t)))
+        o += k * c * t
     return views

@@ -14,6 +14,9 @@ with one set of counters per stage and carry buffers of [C, capacity], the resam
 channel-linked (fh_stream_limit_linked_f32: one envelope, one gain) and the encoder gives channel c its own dither, planar [C, m]
 or sample frames [m, C] (fh_stream_pcm_i16_rows_f32).  Streams of any channel counts that share a plan share its launches.
 A stream without n_channels calls the three mono entries exactly as before.
+pcm='s24' / 's24in32' (24 bits: uint8 with a last axis of 3 bytes, or int32): the encode stage is fh_stream_pcm_s24_rows_f32 for
+every stream, a mono one as a group of one job; the plan key holds the format, so streams of different formats never share an
+encode launch.
 """
 import numpy as np
 import torch
@@ -176,6 +179,8 @@ def _push(delivery, streams, blocks, final):
         s0 = streams[idx[0]]                     # (what the key names is the same for all of them; the key itself is not taken apart)
         rate, ceiling_db, dithered = s0.plan["rate"], s0.plan["true_peak"], s0.plan["key"] is not None
         linked, frames = s0.channels is not None, s0.interleaved
+        pcm = s0.plan["pcm"]
+        wide = pcm in ("s24", "s24in32")
         # What every stage emits follows from the blocks' lengths, so the jobs of all stages are made first and go up as ONE
         # buffer; a stage's outputs are one buffer too, a stream's part of it ([rows, n_out], contiguous) the next stage's fresh block.
         n_in = {i: cur[i].shape[1] for i in idx}
@@ -191,21 +196,27 @@ def _push(delivery, streams, blocks, final):
             rooms = [streams[i].stages[name].counters.peek(n_in[i], final) for i in live]
             sizes = [r * streams[i].rows for i, r in zip(live, rooms)]
             offs = [int(o) for o in np.cumsum([0] + [-(-n // 8) * 8 for n in sizes[:-1]])]          # (16-byte aligned parts)
-            buf = torch.empty(offs[-1] + sizes[-1], dtype=torch.int16 if name == "encode" else torch.float32, device=dev)
-            jobs, esz = [], buf.element_size()
+            # (esz: bytes per sample; per: the buffer's elements per sample -- 3 uint8 for 's24', else 1)
+            if name == "encode":
+                buf = _delivery.pcm_buffer(pcm, offs[-1] + sizes[-1], dev)
+                esz, shape = _delivery.PCM_FORMATS[pcm][1], (lambda *s: _delivery.pcm_shape(pcm, *s))
+            else:
+                buf, esz, shape = torch.empty(offs[-1] + sizes[-1], dtype=torch.float32, device=dev), 4, (lambda *s: s)
+            jobs, per = [], esz // buf.element_size()
             for i, off, room in zip(live, offs, rooms):
                 rows = streams[i].rows
                 base = buf.data_ptr() + off * esz
-                part = buf[off:off + room * rows]
+                part = buf[off * per:(off + room * rows) * per]
                 if name == "encode" and frames:          # sample frames [n_out, C]: the first job's dst is the frame buffer
-                    dst, part = [base] * rows, part.view(room, rows)
+                    dst, part = [base] * rows, part.view(shape(room, rows))
                 else:
-                    dst, part = [base + r * room * esz for r in range(rows)], part.view(rows, room)
+                    dst, part = [base + r * room * esz for r in range(rows)], part.view(shape(rows, room))
                 js, n_out = streams[i].stages[name].jobs(src[i], n_in[i], dst, final, dev)
                 assert n_out == room
                 jobs += js
                 cur[i], src[i], n_in[i] = part, dst, room
-            grouped = linked and name != "resample"      # (the resampler runs a row per job as it is)
+            # (the resampler runs a row per job as it is; the 24-bit encoder has no mono entry: a mono stream is a group of one job)
+            grouped = (linked and name != "resample") or (name == "encode" and wide)
             stages.append((name, live, max(rooms), len(jobs), len(tables_), grouped, buf))      # (buf: alive until its launches are queued)
             tables_.append((hip.StreamJob * len(jobs))(*jobs))
             if grouped:
@@ -225,6 +236,9 @@ def _push(delivery, streams, blocks, final):
                 H = streams[live[0]].stages[name].counters.H
                 c32 = float(np.float32(_truepeak.ceiling(ceiling_db)))
                 entry, args = f"fh_stream_limit{'_linked' if linked else ''}_f32", (delivery._tp_taps(), delivery._window(H), H, c32)
+            elif max_out and wide:
+                entry = "fh_stream_pcm_s24_rows_f32"
+                args = (ptrs[-1] if dithered else 0, int(frames), _delivery.PCM_FORMATS[pcm][1])
             elif max_out:
                 entry = f"fh_stream_pcm_i16{'_rows' if linked else ''}_f32"
                 args = (ptrs[-1] if dithered else 0,) + ((int(frames),) if linked else ())
@@ -234,9 +248,12 @@ def _push(delivery, streams, blocks, final):
     del fresh
     out = []
     for s, c in zip(streams, cur):                       # (what stood still at some stage emits an empty block of the result's type)
-        want = torch.float32 if s.plan["pcm"] is None else torch.int16
+        fmt = s.plan["pcm"]
         if c.numel():
             out.append(c)
+        elif fmt is None:
+            out.append(torch.empty((s.rows, 0), dtype=torch.float32, device=dev))
         else:
-            out.append(torch.empty((0, s.rows) if s.interleaved and want == torch.int16 else (s.rows, 0), dtype=want, device=dev))
+            out.append(torch.empty(_delivery.pcm_shape(fmt, *((0, s.rows) if s.interleaved else (s.rows, 0))),
+                                   dtype=_delivery.PCM_FORMATS[fmt][0], device=dev))
     return out

@@ -1182,7 +1182,8 @@ class FlowHighSR:
         their prior where they overlap and are cross-faded there (fh_xfade_seg_f32).  seed=None draws one from torch's generator.
         Latency: a sample is final once the window that holds it left of its right overlap has arrived, at most window_ms after it
         came in, plus one batched run.  The sample format is fixed by the session's first block: an integer dtype is divided by
-        32768, a float dtype taken as it is.  pcm='int16' encodes every emitted block (no dither: the encoding is stateless).
+        32768, a float dtype taken as it is.  pcm='int16' | 's24' | 's24in32' encodes every emitted block (no dither: the encoding is
+        stateless; 's24' blocks are uint8 [1, n, 3]).
         delivery=dict(output_rate=, pcm=, dither=, dither_seed=, true_peak=, limiter='lookahead'): what the session emits goes
         through a DeliveryStream (delivery_stream()): the keywords mean what they mean to generate(level='input'), and the blocks
         of the stream add up to the bits of that delivery of the whole 48 kHz stream, delivery.delivered_len(T48, output_rate)
@@ -1331,6 +1332,9 @@ class FlowHighSR:
         it is put at 0.99 of its own peak (over the clip's channels) again, at level='input' it is left as resampled.
         target_sampling_rate keeps its meaning (the rate of the mel codec: 48000 or NotImplementedError).
         pcm = None | 'int16': torch.int16 in the float result's shape, pcm.py's encoding of it (round to nearest even, clamp).
+        pcm = 's24': packed signed 24-bit little-endian (a WAV's pcm_s24le layout) as torch.uint8 with a last axis of 3 bytes,
+        [C, T, 3] ([1, T, 3] mono), [T, C, 3] interleaved -- .reshape(-1) of that is the data chunk of a 24-bit WAV file;
+        pcm = 's24in32': the same integer sign-extended in a torch.int32, shaped like the int16 result (pcm.py: encode24).
         dither = None | 'tpdf' (pcm only): +-1 LSB triangular dither from the key (dither_seed, 0) -- dither_seed an int, or
         [(seed, stream)]; a function of the key, the channel and the sample index alone.
         interleaved = True (pcm only): [T, C] ([T, 1] for a mono clip), written in that order by the kernel.

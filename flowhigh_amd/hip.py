@@ -225,6 +225,8 @@ _SIGS = {
     "fh_pcm_i16_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
     "fh_sizeof_pcm_clip": [],
     "fh_pcm_i16_seg_f32": [_P, _I, _I, _I, _P, _I, _P],
+    "fh_pcm_s24_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "fh_pcm_s24_seg_f32": [_P, _I, _I, _I, _P, _I, _I, _P],
     "fh_loudness_span_len": [],
     "fh_kweight_energy_f32": [_P, _P, _P, _I, _I, _I, _P],
     "fh_kweight_energy_seg_f32": [_P, _P, _I, _I, _I, _P, _P, _I, _P],
@@ -245,6 +247,7 @@ _SIGS = {
     "fh_stream_pcm_i16_f32": [_P, _I, _I, _P, _P],
     "fh_stream_limit_linked_f32": [_P, _I, _P, _I, _I, _P, _P, _I, _F, _P],
     "fh_stream_pcm_i16_rows_f32": [_P, _I, _P, _I, _I, _P, _I, _P],
+    "fh_stream_pcm_s24_rows_f32": [_P, _I, _P, _I, _I, _P, _I, _I, _P],
 }
 EXPORTS = sorted(_SIGS) + ["fh_last_error"]
 

@@ -14,6 +14,16 @@ the difference of two uniforms on [0, 1): triangular on (-1, 1) LSB with varianc
 float32.  It depends on (seed, stream, c, t) only -- not on the batch, the layout, the number of channels or the clip's length --
 and the key's tag keeps its Philox blocks apart from the prior's under the same (seed, stream).
 
+
+The 24-bit encodings (pcm='s24': packed signed 24-bit little-endian, 3 bytes a sample; pcm='s24in32': the same integer in an
+int32; fh_pcm_s24_f32, fh_pcm_s24_seg_f32, fh_stream_pcm_s24_rows_f32).  A sample x (float32):
+  v = float64(x) * 2^23                exact
+  v = v + float64(d)                   when dithering: ONE float64 add, round to nearest even
+  q = rint(v), ties to even, clamped to [-8388608, 8388607]; NaN encodes as 0, +-inf saturates.
+d is the dither above, unchanged: the 24-bit dither of a sample is its 16-bit one, one LSB being 256 times smaller.  The add is
+in float64 because x * 2^23 fills the float32 significand: fl32(x * 2^23 + d) rounds on a grid of 0.5 and throws the dither away
+(constant float32(0.7), key (7, 0), 2^20 samples: a DC bias of +0.187 LSB against -0.0004; DESIGN.md "Delivery").
+
 numpy only: nothing here touches torch or the GPU.
 """
 import numpy as np
@@ -22,6 +32,20 @@ from .prior import _MASK32, normalize_key, philox4x32_10
 
 KEY_TAG = 0x50434D31            # 'PCM1'
 FULL_SCALE = 32768.0
+FULL_SCALE24 = 8388608.0
+# the values of pcm=.  The 24-bit names are the sample-format names of ffmpeg and ALSA: the result is a byte layout, not a dtype.
+FORMATS = ("int16", "s24", "s24in32")
+
+
+def encoder(pcm):
+    """pcm -> the format's (quantize, encode): functions of (x, d) and of (x, key, interleaved)."""
+    if pcm == "int16":
+        return quantize, encode
+    if pcm not in FORMATS:
+        raise ValueError(f"pcm must be one of {FORMATS}, got {pcm!r}")
+    packed = pcm == "s24"
+    return ((lambda x, d=None: pack24(quantize24(x, d))) if packed else quantize24,
+            lambda x, key=None, interleaved=False: encode24(x, key, interleaved, packed))
 
 
 def dither_uniforms(seed, stream, channel, n, first=0):
@@ -77,3 +101,42 @@ def encode(x, key=None, interleaved=False):
         d = np.stack([tpdf_dither(key[0], key[1], c, x.shape[1]) for c in range(x.shape[0])])
     q = quantize(x, d)
     return np.ascontiguousarray(q.T) if interleaved else q
+
+
+def quantize24(x, d=None):
+    """float32 samples (any shape) -> the 24-bit integer in an int32, d: the dither in LSB (same shape) or None."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = np.asarray(x, dtype=np.float32).astype(np.float64) * FULL_SCALE24
+        if d is not None:
+            v = v + np.asarray(d, dtype=np.float32).astype(np.float64)
+        q = np.where(np.isnan(v), 0.0, np.clip(np.rint(v), -8388608.0, 8388607.0))
+    return q.astype(np.int32)
+
+
+def pack24(q):
+    """int32 [...] -> uint8 [..., 3]: the low three bytes of every sample, least significant first (pcm_s24le)."""
+    u = np.asarray(q, dtype=np.int32).astype(np.uint32)
+    return np.stack([u & 0xFF, (u >> 8) & 0xFF, (u >> 16) & 0xFF], -1).astype(np.uint8)
+
+
+def unpack24(b):
+    """uint8 [..., 3] -> int32 [...]: pack24's inverse, sign-extended."""
+    b = np.asarray(b, dtype=np.uint8).astype(np.int32)
+    u = b[..., 0] | (b[..., 1] << 8) | (b[..., 2] << 16)
+    return (u ^ 0x800000) - 0x800000
+
+
+def encode24(x, key=None, interleaved=False, packed=True):
+    """One clip, planar float32 [C, T] (or [T]: one channel) -> packed: uint8 [C, T, 3], or [T, C, 3] with interleaved
+    ('s24'); not packed: int32 [C, T] / [T, C] ('s24in32').  key: None (no dither) or the clip's (seed, stream)."""
+    x = np.asarray(x, dtype=np.float32)
+    if x.ndim == 1:
+        x = x[None]
+    if x.ndim != 2:
+        raise ValueError(f"a clip is [C, T], got shape {x.shape}")
+    d = None
+    if key is not None:
+        d = np.stack([tpdf_dither(key[0], key[1], c, x.shape[1]) for c in range(x.shape[0])])
+    q = quantize24(x, d)
+    q = np.ascontiguousarray(q.T) if interleaved else q
+    return pack24(q) if packed else q

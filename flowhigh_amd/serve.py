@@ -84,7 +84,8 @@ class BatchingServer:
         [C, T48].  level = 'peak' | 'input' as in generate.  A shape that fits no layout is a ValueError here.
         output_rate=, pcm=, dither=, dither_seed= as in generate (dither_seed: an int s = the key (s, 0), or a (seed, stream)
         pair), checked here; requests are grouped by them too.  With pcm= the Future's array is int16, and a channels='last'
-        request gets it in its own layout, [T, C], written that way on the device.
+        request gets it in its own layout, [T, C], written that way on the device.  pcm='s24in32': int32 in the same shapes;
+        pcm='s24': uint8 with a last axis of 3 bytes, [T, C, 3] for a channels='last' request, [C, T, 3] or [1, T, 3] otherwise.
         loudness = None | a target in LUFS as in generate: requests are grouped by it, and it is handed to generate_many only
         where a request gave it.  true_peak = None | a ceiling in dBTP, limiter = None | 'lookahead' as in generate: the same."""
         if self._closed:
@@ -219,7 +220,8 @@ class BatchingServer:
                         if deliv is not None and deliv[3]:          # [T, C] from the device; a 1-D request's is [T, 1]
                             it[4].set_result((y if it[0].ndim == 2 else y.squeeze(1)).numpy())
                             continue
-                        it[4].set_result((y if it[0].ndim == 2 else y.squeeze(0)).numpy())
+                        # (pcm='s24' is a byte layout: a 1-D request's stays the planar uint8 [1, T, 3])
+                        it[4].set_result((y if it[0].ndim == 2 or y.ndim == 3 else y.squeeze(0)).numpy())
                 except Exception as e:            # noqa: BLE001  (every waiting caller must be released)
                     for it in items:
                         if not it[4].done():

@@ -14,7 +14,9 @@ the past in a carry and gives the bits of the one-shot delivery of the whole str
               samples final, max(0, F - D) outputs are final while the stream is open and F at its end; the carry is the samples
               from max(0, first unemitted - D) on: at most 2 D.  The edge rules of truepeak.py (zeros outside for the
               oversampling, r = 1 outside, q extended by H) hold at the stream's first and last sample and nowhere else.
-  encoder     sample t of the stream takes pcm.py's dither of channel 0 at the absolute index t: no carry, one counter.
+  encoder     sample t of the stream takes pcm.py's dither of channel 0 at the absolute index t: no carry, one counter.  The
+              format is the plan's pcm: 'int16', or 24 bits as 's24' (3 bytes a sample: blocks [C, n, 3] / [n, C, 3]) or
+              's24in32' (int32): pcm.quantize24 / pcm.pack24.
 
 A stream of C channels (1 <= C <= 8, fixed when it opens) is C rows [C, T] that move together: ONE set of counters per stage, the
 resampler per row, the limiter channel-linked as truepeak.limit is on a [C, T] clip (m is the maximum over the rows of what a
@@ -227,8 +229,10 @@ MAX_CHANNELS = 8
 
 def make_plan(rate=None, true_peak=None, pcm=None, key=None, channels=None, interleaved=False):
     """The stages of a delivery, as delivery_stream.resolve gives them: rate None | R, true_peak None | the ceiling in dBTP
-    (limiter='lookahead'), pcm None | 'int16', key None | the dither's (seed, stream); channels None (one mono stream: the plan
+    (limiter='lookahead'), pcm None | 'int16' | 's24' | 's24in32', key None | the dither's (seed, stream); channels None (one mono stream: the plan
     it always was) | C rows that move together, 1 .. 8; interleaved: the encoder's output as sample frames [n, C]."""
+    if pcm is not None and pcm not in _pcm.FORMATS:
+        raise ValueError(f"pcm must be None or one of {_pcm.FORMATS}, got {pcm!r}")
     plan = dict(rate=rate, true_peak=true_peak, pcm=pcm, key=key)
     if channels is None:
         if interleaved:
@@ -295,13 +299,13 @@ def chunked(x48, cuts, plan, stats=None, first=0):
             d = None
             if key is not None:
                 d = np.stack([_pcm.tpdf_dither(key[0], key[1], ch, block.shape[1], first=job["first"]) for ch in range(C)])
-            block = _pcm.quantize(block, d)
+            block = _pcm.encoder(plan["pcm"])[0](block, d)                  # ('s24': [C, n, 3])
         stats["lens"].append(block.shape[1])
         out.append(block)
     y = np.concatenate(out, 1)
     if flat:
         return y[0]
-    return np.ascontiguousarray(y.T) if plan.get("interleaved") else y
+    return np.ascontiguousarray(np.swapaxes(y, 0, 1)) if plan.get("interleaved") else y
 
 
 def whole(x48, plan):
@@ -313,5 +317,5 @@ def whole(x48, plan):
     if plan["true_peak"] is not None:
         y = _truepeak.limit(y, plan["rate"] or 48000, plan["true_peak"])[0] if y.shape[1] else y
     if plan["pcm"] is not None:
-        y = _pcm.encode(y, plan["key"], bool(plan.get("interleaved")) and not flat)
+        y = _pcm.encoder(plan["pcm"])[1](y, plan["key"], bool(plan.get("interleaved")) and not flat)
     return y[0] if flat else y

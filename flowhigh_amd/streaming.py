@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .delivery import PCM_FORMATS, pcm_shape
 from .frontend import upload_tables
 from .stream import StreamPlan
 
@@ -120,8 +121,8 @@ def open_session(model, sr, window_ms, overlap_ms, guard_ms, timestep, seed, str
     if model.prior != 'device':
         raise ValueError("a streaming session shares one keyed prior between its windows: construct the model with prior='device' "
                          "(a prior='reference' model draws from a generator, window by window)")
-    if pcm not in (None, "int16"):
-        raise ValueError(f"pcm must be None or 'int16', got {pcm!r}")
+    if pcm is not None and pcm not in PCM_FORMATS:
+        raise ValueError(f"pcm must be None or one of {tuple(PCM_FORMATS)}, got {pcm!r}")
     if isinstance(timestep, bool) or int(timestep) != timestep or timestep < 1:
         raise ValueError(f"timestep must be a positive integer, got {timestep!r}")
     plan = StreamPlan(sr, window_ms, overlap_ms, guard_ms)
@@ -143,12 +144,15 @@ def _ramp(model, plan):
     return cache[k]
 
 
-def _encode(model, block):
-    """float32 [C, n] -> int16 [C, n], planar: pcm.py's encoding without dither, which is stateless (fh_pcm_i16_f32)."""
-    out = torch.empty(block.shape, dtype=torch.int16, device=block.device)
+def _encode(model, block, pcm="int16"):
+    """float32 [C, n] -> int16 [C, n], planar: pcm.py's encoding without dither, which is stateless (fh_pcm_i16_f32);
+    pcm='s24in32': int32 [C, n], 's24': uint8 [C, n, 3] (fh_pcm_s24_f32)."""
+    dtype, size, stem = PCM_FORMATS[pcm]
+    out = torch.empty(pcm_shape(pcm, *block.shape), dtype=dtype, device=block.device)
     if block.shape[1]:
-        hip.check(hip.lib().fh_pcm_i16_f32(block.data_ptr(), out.data_ptr(), 0, 1, block.shape[0], block.shape[1], 0, hip.stream()),
-                  "fh_pcm_i16_f32")
+        entry = f"fh_pcm_{stem}_f32"
+        hip.check(getattr(hip.lib(), entry)(block.data_ptr(), out.data_ptr(), 0, 1, block.shape[0], block.shape[1], 0,
+                                            *((size,) if stem == "s24" else ()), hip.stream()), entry)
     return out
 
 
@@ -213,7 +217,7 @@ def run(model, sessions, final):
                 parts[si].append(s.tail)         # the stream ended with the last window's right overlap: it is final as it is
             s.tail = None
         block = torch.cat(parts[si], 1) if parts[si] else torch.empty(s.rows, 0, dtype=torch.float32, device=model.device)
-        out.append(_encode(model, block) if s.pcm == "int16" else block)
+        out.append(_encode(model, block, s.pcm) if s.pcm is not None else block)
     # every delivering session's block of this push through one launch sequence (delivery_stream.py)
     carried = [si for si, s in enumerate(sessions) if s.delivery is not None]
     if carried:

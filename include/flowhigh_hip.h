@@ -764,6 +764,20 @@ int fh_sizeof_pcm_clip(void);
 /* max_channels, max_len: the largest channels / len of the table. */
 int fh_pcm_i16_seg_f32(const fh_pcm_clip* clips, int n_clips, int max_channels, int max_len, const uint64_t* keys,
                        int interleaved, void* stream);
+/* 24-bit PCM (pcm='s24', pcm='s24in32'; pcm.py: quantize24, pack24):
+ *   sample x -> v = double(x) * 2^23 (exact) -> v = v + double(d) when dithering, ONE float64 add (a float32 add would round
+ *   the dither away: x * 2^23 fills the float32 significand) -> rint, ties to even -> clamp to [-8388608, 8388607]; NaN -> 0,
+ *   +-inf saturates.  d is the dither above, unchanged (one LSB is 256 times smaller).
+ * container 3: a sample is its low three bytes, least significant first (pcm_s24le), y at ANY byte address; rows, clips and
+ *   blocks may abut anywhere: no byte outside y[0 .. 3 n_clips channels len) is read or written.
+ * container 4: the integer sign-extended in an int32; y 4-byte aligned (refused otherwise).  Any other container is refused.
+ * Layouts, keys and limits as fh_pcm_i16_f32. */
+int fh_pcm_s24_f32(const float* x, void* y, const uint64_t* keys, int n_clips, int channels, int len, int interleaved,
+                   int container, void* stream);
+/* The same over a table of clips: fh_pcm_clip with dst read as a BYTE address (container 4: a clip whose dst is not 4-byte
+ * aligned is left unwritten).  Clip c gets the bits of fh_pcm_s24_f32 on that clip alone with keys[c]. */
+int fh_pcm_s24_seg_f32(const fh_pcm_clip* clips, int n_clips, int max_channels, int max_len, const uint64_t* keys,
+                       int interleaved, int container, void* stream);
 
 /* -----------------------------------------------------------------------------------
  * Integrated loudness on the device (csrc/loudness.hip; FlowHighSR.generate*(loudness=L), FlowHighSR.measure_loudness): ITU-R
@@ -916,6 +930,12 @@ int fh_stream_limit_linked_f32(const fh_stream_job* jobs, int n_jobs, const int3
  * the whole [C, T] stream under the same key, and of fh_stream_pcm_i16_f32 for C = 1 planar. */
 int fh_stream_pcm_i16_rows_f32(const fh_stream_job* jobs, int n_jobs, const int32_t* groups, int n_groups, int max_out,
                                const uint64_t* keys, int interleaved, void* stream);
+/* The 24-bit twin (fh_pcm_s24_f32's encoding and containers): dst is container * n_out bytes per job, or the frame buffer of
+ * container * n_out * C bytes behind the group's first job.  A mono stream is a group of one job.  container 3: dst at any byte
+ * address; container 4: a group with a dst (interleaved: its first dst) that is not 4-byte aligned is left unwritten.  The bits
+ * of fh_pcm_s24_f32 on the whole [C, T] stream under the same key. */
+int fh_stream_pcm_s24_rows_f32(const fh_stream_job* jobs, int n_jobs, const int32_t* groups, int n_groups, int max_out,
+                               const uint64_t* keys, int interleaved, int container, void* stream);
 
 #ifdef __cplusplus
 }
