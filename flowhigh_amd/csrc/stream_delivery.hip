@@ -3,10 +3,11 @@
 //   fh_stream_resample_f32   the polyphase resampler (frontend.hip: resample_poly_kernel's loop and order) on absolute indices
 //   fh_stream_limit_f32      the oversampled envelope and the look-ahead limiter of mono streams in one launch
 //                            (truepeak.hip: tp_envelope_kernel + limit_kernel, their arithmetic and order)
-//   fh_stream_pcm_i16_f32    pcm.hip's encoder with the dither at the sample's absolute index
+//   fh_stream_pcm_i16_f32    the PCM encoder (pcm_common.h: pcm.hip's bodies) with the dither at the sample's absolute index
 //   fh_stream_limit_linked_f32   the limiter of streams of 1 .. 8 channels: one envelope and one gain for a stream's channels
 //   fh_stream_pcm_i16_rows_f32   the encoder of such streams: channel c's dither, planar rows or interleaved sample frames
-//   fh_stream_pcm_s24_rows_f32   its 24-bit twin (packed in 3 bytes or in an int32), for mono streams too: a group of one job
+//   fh_stream_pcm_s24_rows_f32   the same kernel in 24 bits (packed in 3 bytes or in an int32), for mono streams too: a group of
+//                                one job
 // One fh_stream_job per row and launch.  A job's source is TWO spans, the carry the stream kept and the fresh block, read as
 // one run of samples whose first has the absolute index `base`; nothing is concatenated.  The last block column of a launch
 // copies the last n_keep source samples into the stream's other carry buffer (the two ping-pong, so the copy never writes
@@ -16,7 +17,8 @@
 // reads the source only through sd_src::at (0 outside the two spans) and writes only dst[0 .. n_out) and carry_out[0 .. n_keep).
 //
 // Groups: a stream of C channels is a group of C consecutive jobs, one per channel row, with equal base, first and counts.  The
-// limiter and the encoder are ONE kernel body each, instantiated with a group locator: OneJob for the mono entries (job g alone is
+// limiter and the encoder are ONE kernel each, instantiated with a group locator (the encoder with a sample format of
+// pcm_common.h as well, whose bodies do all of its arithmetic and stores): OneJob for the mono entries (job g alone is
 // group g: C = 1, no table is read), GroupTable for the other two (a device table `groups` of int32 [n_groups + 1] gives every
 // stream's first job; a group whose size is not 1 .. 8, whose jobs differ in a counter or one of whose jobs fails job_ok is left
 // unwritten).  So a mono stream has the bits of a stream of one channel.  The resampler runs a row per job as it is.
@@ -36,6 +38,7 @@ namespace {
 
 using namespace tp;                             // (truepeak_common.h: THREADS, the limiter's TILE outputs per workgroup, ...)
 constexpr int MAX_CH = 8;                       // channels of a stream
+static_assert(THREADS == PCM_THREADS, "the encoder bodies count their runs in blocks of PCM_THREADS");
 
 struct sd_src {                                 // the two spans as one run of samples
   const float* carry;
@@ -199,162 +202,47 @@ __global__ __launch_bounds__(THREADS) void stream_limit_kernel(Groups groups, co
   }
 }
 
-// x[k], d[k] = the source's sample and channel ch's dither at the output first + k of the job (the absolute index J.first + first + k)
-__device__ __forceinline__ void pcm_run(const fh_stream_job& J, const unsigned long long* __restrict__ key, int ch, long long first,
-                                        float (&x)[RUN], float (&d)[RUN]) {
-  const sd_src S = source(J);
-#pragma unroll
-  for (int k = 0; k < RUN; ++k) {
-    const long long o = first + k;
-    x[k] = (o >= 0 && o < J.n_out) ? S.at(J.first + o) : 0.f;
-    d[k] = 0.f;
-  }
-  if (key) dither_run(key[0], key[1], ch, J.first + first, d);
-}
-
-// dst[o] = pcm.hip's encode of the source's sample first + o with the dither of channel ch at the index first + o.  A thread owns
-// the 16-byte word of 8 outputs counted from the aligned address at or below dst, as pcm_i16_kernel does for a planar row.
-__device__ __forceinline__ void pcm_row(const fh_stream_job& J, const unsigned long long* __restrict__ key, int ch) {
-  int16_t* __restrict__ row = (int16_t*)J.dst;
-  const int lead = (int)(((size_t)row >> 1) & (RUN - 1));
-  const long long first = ((long long)blockIdx.x * THREADS + threadIdx.x) * RUN - lead;      // the run's first output
-  if (J.n_out == 0 || first >= J.n_out) return;
-  float x[RUN], d[RUN];
-  pcm_run(J, key, ch, first, x, d);
-  if (first >= 0 && first + RUN <= J.n_out) {
-    i16x8 v;
-#pragma unroll
-    for (int k = 0; k < RUN; ++k) v[k] = encode(x[k], d[k]);
-    *reinterpret_cast<i16x8*>(row + first) = v;
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < RUN; ++k) {
-    const long long o = first + k;
-    if (o >= 0 && o < J.n_out) row[o] = encode(x[k], d[k]);
-  }
-}
-
-// Interleaved output of a stream of C = 2, 4 or 8 channels whose frame buffer is aligned to a frame (2 C bytes): the thread
-// encodes its run of every channel and stores each sample frame as ONE 4-, 8- or 16-byte word, as pcm.hip's pcm_frames does.
-template <int C>
-__device__ __forceinline__ void stream_frames(const fh_stream_job* __restrict__ jobs, const unsigned long long* __restrict__ key) {
-  typedef short frame_t __attribute__((ext_vector_type(C)));
-  const long long first = ((long long)blockIdx.x * THREADS + threadIdx.x) * RUN;
-  const int n_out = jobs[0].n_out;
-  if (first >= n_out) return;
-  frame_t o[RUN];
-#pragma unroll
-  for (int ch = 0; ch < C; ++ch) {
+// The jobs of a checked group as the encoder bodies see them: the source of pcm_common.h over the two spans of every job.  The
+// counters are the group's (its jobs have equal ones); output o of a job is the stream's sample first + o.
+struct stream_rows {
+  const fh_stream_job* jobs;                    // channel c is jobs[c]
+  long long first;
+  int n, n_out;
+  __device__ int channels() const { return n; }
+  __device__ int len() const { return n_out; }
+  __device__ long long origin() const { return first; }
+  __device__ float at(int ch, long long o) const { return source(jobs[ch]).at(first + o); }
+  __device__ void load_run(int ch, long long o0, float (&x)[RUN]) const {
     const fh_stream_job J = jobs[ch];
-    float x[RUN], d[RUN];
-    pcm_run(J, key, ch, first, x, d);
+    const sd_src S = source(J);
 #pragma unroll
-    for (int k = 0; k < RUN; ++k) o[k][ch] = encode(x[k], d[k]);
+    for (int k = 0; k < RUN; ++k) {
+      const long long o = o0 + k;
+      x[k] = (o >= 0 && o < n_out) ? S.at(first + o) : 0.f;
+    }
   }
-  frame_t* __restrict__ frames = reinterpret_cast<frame_t*>(jobs[0].dst);
-#pragma unroll
-  for (int k = 0; k < RUN; ++k)
-    if (first + k < n_out) frames[first + k] = o[k];
-}
+};
 
-// The encoder.  Grid (blocks of 256 runs, jobs): job j is channel j - G.j0 of the group that holds it (a job no group holds, or
-// whose group is refused, is left unwritten) and takes the group's key.  Planar: every job writes its own dst, none if a dst of
-// the group is odd (it would misalign every 16-byte store).  Interleaved: the group's first dst is the frame buffer int16
-// [n_out, C]; with whole-frame stores the blocks of channel 0 write for the group, otherwise every job stores its samples at
-// their places.
-template <class Groups>
-__global__ __launch_bounds__(THREADS) void stream_pcm_kernel(Groups groups, const unsigned long long* __restrict__ keys) {
-  const int job = blockIdx.y, g = groups.group_of(job);
-  sd_group G;
-  if (!groups.group(g, G) || job < G.j0 || job >= G.j0 + G.n) return;
-  const fh_stream_job* __restrict__ jobs = groups.jobs;
-  const int ch = job - G.j0;
-  const unsigned long long* __restrict__ key = keys ? keys + 2 * g : nullptr;
-  if (!groups.interleaved) {
-    for (int c = 0; c < G.n; ++c)
-      if (((size_t)jobs[G.j0 + c].dst) & 1) return;
-    pcm_row(jobs[job], key, ch);
-    return;
-  }
-  int16_t* __restrict__ out = (int16_t*)jobs[G.j0].dst;
-  if (((size_t)out) & 1) return;
-  if ((G.n == 2 || G.n == 4 || G.n == 8) && (((size_t)out) & (2 * G.n - 1)) == 0) {
-    if (ch != 0) return;                                             // (the blocks of channel 0 write whole frames)
-    if (G.n == 2)
-      stream_frames<2>(jobs + G.j0, key);
-    else if (G.n == 4)
-      stream_frames<4>(jobs + G.j0, key);
-    else
-      stream_frames<8>(jobs + G.j0, key);
-    return;
-  }
-  const fh_stream_job J = jobs[job];
-  const long long first = ((long long)blockIdx.x * THREADS + threadIdx.x) * RUN;
-  if (first >= J.n_out) return;
-  float x[RUN], d[RUN];
-  pcm_run(J, key, ch, first, x, d);
-#pragma unroll
-  for (int k = 0; k < RUN; ++k)
-    if (first + k < J.n_out) out[(size_t)(first + k) * G.n + ch] = encode(x[k], d[k]);
-}
-
-// The 24-bit encoder (pcm.hip's pcm_s24_kernel on a stream's blocks; container 3: packed bytes, 4: int32).  Grid and groups as
-// stream_pcm_kernel's; a mono stream is a group of one job.  Planar: job j writes its own dst, n_out samples from any byte
-// address (container 4: none of the group if a dst is not 4-byte aligned).  Interleaved: the group's first dst is the frame
-// buffer, ONE flat row of n_out * C samples whose runs the blocks of the group's C jobs share (run (ch * gridDim.x + x) * THREADS
-// + thread); flat sample s is output s / C of job s % C, with that channel's dither at the absolute index first + s / C.
-__global__ __launch_bounds__(THREADS) void stream_pcm24_kernel(GroupTable groups, const unsigned long long* __restrict__ keys,
-                                                               int container) {
+// The encoder: pcm.hip's kernel on a stream's blocks, with the dither at the sample's absolute index.  Grid (blocks of 256 runs,
+// jobs): job j is channel j - G.j0 of the group that holds it (a job no group holds, or whose group is refused, is left
+// unwritten) and takes the group's key.  Planar: every job writes its own dst, none if a dst of the group is misaligned for the
+// format.  Interleaved: the group's first dst is the frame buffer [n_out, C].  The samples, the dither and the stores are the
+// bodies of pcm_common.h.
+template <class Groups, class Fmt>
+__global__ __launch_bounds__(THREADS) void stream_pcm_kernel(Groups groups, Fmt fmt, const unsigned long long* __restrict__ keys) {
   const int job = blockIdx.y, g = groups.group_of(job);
   sd_group G;
   if (!groups.group(g, G) || job < G.j0 || job >= G.j0 + G.n) return;
   const fh_stream_job* __restrict__ jobs = groups.jobs + G.j0;
   const int ch = job - G.j0;
+  for (int c = 0; c < (groups.interleaved ? 1 : G.n); ++c)
+    if (!fmt.ok(jobs[c].dst)) return;
+  const stream_rows src{jobs, jobs[0].first, G.n, jobs[0].n_out};
   const unsigned long long* __restrict__ key = keys ? keys + 2 * g : nullptr;
-  int q[RUN];
-  if (!groups.interleaved) {
-    if (container == 4)
-      for (int c = 0; c < G.n; ++c)
-        if (((size_t)jobs[c].dst) & 3) return;
-    const fh_stream_job J = jobs[ch];
-    if (J.n_out == 0) return;
-    unsigned char* __restrict__ row = (unsigned char*)J.dst;
-    const long long first = ((long long)blockIdx.x * THREADS + threadIdx.x) * RUN - lead24(row, container);
-    if (first >= J.n_out) return;
-    float x[RUN], d[RUN];
-    pcm_run(J, key, ch, first, x, d);
-#pragma unroll
-    for (int k = 0; k < RUN; ++k) q[k] = encode24(x[k], d[k]);
-    store_run24(row, first, J.n_out, q, container);
-    return;
-  }
-  unsigned char* __restrict__ out = (unsigned char*)jobs[0].dst;
-  if (container == 4 && (((size_t)out) & 3)) return;
-  const long long abs0 = jobs[0].first, N = (long long)jobs[0].n_out * G.n;      // (the counters are the group's)
-  if (N == 0) return;
-  const long long first = (((long long)ch * gridDim.x + blockIdx.x) * THREADS + threadIdx.x) * RUN - lead24(out, container);
-  if (first >= N) return;
-  const long long s0 = first < 0 ? 0 : first;
-  long long o = N <= 0xFFFFFFFFll ? (long long)((unsigned)s0 / (unsigned)G.n) : s0 / G.n;
-  int cc = (int)(s0 - o * G.n);
-  unsigned long long seed = 0, strm = 0;
-  if (key) {
-    seed = key[0];
-    strm = key[1];
-  }
-#pragma unroll
-  for (int k = 0; k < RUN; ++k) {
-    const long long s = first + k;
-    q[k] = 0;
-    if (s < 0 || s >= N) continue;
-    q[k] = encode24(source(jobs[cc]).at(abs0 + o), key ? dither_at(seed, strm, cc, abs0 + o) : 0.f);
-    if (++cc == G.n) {
-      cc = 0;
-      ++o;
-    }
-  }
-  store_run24(out, first, N, q, container);
+  if (groups.interleaved)
+    encode_interleaved(fmt, src, ch, (unsigned char*)jobs[0].dst, key);
+  else
+    encode_row(fmt, src, ch, (unsigned char*)jobs[ch].dst, key);
 }
 
 }  // namespace
@@ -389,8 +277,6 @@ extern "C" int fh_stream_resample_f32(const fh_stream_job* jobs, int n_jobs, int
   FH_CHECK_ARG(n_groups > 0 && n_groups < 65536, name ": %d groups (1 .. 65535)", n_groups);                              \
   FH_CHECK_ARG((((size_t)groups) & 3) == 0, name ": groups must be 4-byte aligned")
 
-static int pcm_blocks(int max_out) { return fh_cdiv(((long long)max_out + RUN - 1) / RUN + 1, THREADS); }      // runs of a row at any alignment
-
 extern "C" int fh_stream_limit_f32(const fh_stream_job* jobs, int n_jobs, int max_out, const float* taps4, const double* w, int H,
                                    float ceiling, void* stream) {
   FH_CHECK_STREAM_JOBS("fh_stream_limit_f32");
@@ -403,8 +289,8 @@ extern "C" int fh_stream_limit_f32(const fh_stream_job* jobs, int n_jobs, int ma
 
 extern "C" int fh_stream_pcm_i16_f32(const fh_stream_job* jobs, int n_jobs, int max_out, const uint64_t* keys, void* stream) {
   FH_CHECK_STREAM_JOBS("fh_stream_pcm_i16_f32");
-  hipLaunchKernelGGL(stream_pcm_kernel<OneJob>, dim3(pcm_blocks(max_out), n_jobs), dim3(THREADS), 0, (hipStream_t)stream, OneJob{jobs},
-                     (const unsigned long long*)keys);
+  hipLaunchKernelGGL((stream_pcm_kernel<OneJob, I16>), dim3(pcm_blocks(max_out), n_jobs), dim3(THREADS), 0, (hipStream_t)stream,
+                     OneJob{jobs}, I16{}, (const unsigned long long*)keys);
   FH_CHECK_LAUNCH("fh_stream_pcm_i16_f32");
   return FH_OK;
 }
@@ -424,8 +310,8 @@ extern "C" int fh_stream_pcm_i16_rows_f32(const fh_stream_job* jobs, int n_jobs,
                                           const uint64_t* keys, int interleaved, void* stream) {
   FH_CHECK_STREAM_JOBS("fh_stream_pcm_i16_rows_f32");
   FH_CHECK_STREAM_GROUPS("fh_stream_pcm_i16_rows_f32");
-  hipLaunchKernelGGL(stream_pcm_kernel<GroupTable>, dim3(pcm_blocks(max_out), n_jobs), dim3(THREADS), 0, (hipStream_t)stream,
-                     GroupTable{jobs, n_jobs, groups, n_groups, interleaved ? 1 : 0}, (const unsigned long long*)keys);
+  hipLaunchKernelGGL((stream_pcm_kernel<GroupTable, I16>), dim3(pcm_blocks(max_out), n_jobs), dim3(THREADS), 0, (hipStream_t)stream,
+                     GroupTable{jobs, n_jobs, groups, n_groups, interleaved ? 1 : 0}, I16{}, (const unsigned long long*)keys);
   FH_CHECK_LAUNCH("fh_stream_pcm_i16_rows_f32");
   return FH_OK;
 }
@@ -434,9 +320,9 @@ extern "C" int fh_stream_pcm_s24_rows_f32(const fh_stream_job* jobs, int n_jobs,
                                           const uint64_t* keys, int interleaved, int container, void* stream) {
   FH_CHECK_STREAM_JOBS("fh_stream_pcm_s24_rows_f32");
   FH_CHECK_STREAM_GROUPS("fh_stream_pcm_s24_rows_f32");
-  FH_CHECK_ARG(container == 3 || container == 4, "fh_stream_pcm_s24_rows_f32: container %d (3: packed bytes, 4: int32)", container);
-  hipLaunchKernelGGL(stream_pcm24_kernel, dim3(pcm_blocks(max_out), n_jobs), dim3(THREADS), 0, (hipStream_t)stream,
-                     GroupTable{jobs, n_jobs, groups, n_groups, interleaved ? 1 : 0}, (const unsigned long long*)keys, container);
+  FH_CHECK_PCM_CONTAINER("fh_stream_pcm_s24_rows_f32");
+  hipLaunchKernelGGL((stream_pcm_kernel<GroupTable, S24>), dim3(pcm_blocks(max_out), n_jobs), dim3(THREADS), 0, (hipStream_t)stream,
+                     GroupTable{jobs, n_jobs, groups, n_groups, interleaved ? 1 : 0}, S24{container}, (const unsigned long long*)keys);
   FH_CHECK_LAUNCH("fh_stream_pcm_s24_rows_f32");
   return FH_OK;
 }

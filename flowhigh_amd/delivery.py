@@ -16,6 +16,7 @@ lengths; rows are read where the post-processor left them, and a clip gets the s
 its default nothing here runs.
 """
 import ctypes
+import functools
 import math
 
 import numpy as np
@@ -23,14 +24,31 @@ import torch
 
 from . import hip, tables
 from . import loudness as _loudness
+from . import pcm as _pcm_def
 from . import truepeak as _truepeak
 from .frontend import _launch, _ptr, clip_array, upload_tables
 from .prior import expand_seed
 
 MAX_RATE_FACTOR = 640             # max(up, down) of the reduced output_rate / 48000: the filter has 20 * that + 1 taps
-_PCM = (None, "int16", "s24", "s24in32")
 # pcm -> (the result's dtype, bytes per sample, the entries' stem); the 24-bit entries take the bytes per sample as `container`
 PCM_FORMATS = {"int16": (torch.int16, 2, "i16"), "s24": (torch.uint8, 3, "s24"), "s24in32": (torch.int32, 4, "s24")}
+assert tuple(PCM_FORMATS) == _pcm_def.FORMATS
+_PCM = (None, *PCM_FORMATS)
+_DITHER = (None, "tpdf")
+_PCM_ENTRIES = {"batched": "fh_pcm_{}_f32", "segment": "fh_pcm_{}_seg_f32", "stream mono": "fh_stream_pcm_{}_f32",
+                "stream rows": "fh_stream_pcm_{}_rows_f32"}
+
+
+@functools.lru_cache(maxsize=None)
+def pcm_entry(pcm, form):
+    """The encode launch of a format in one of its forms ('batched', 'segment', 'stream mono', 'stream rows') -> (the entry's
+    name, the arguments behind `interleaved`: the 24-bit entries' container).  The 24-bit formats have no mono stream entry: a
+    mono stream is a group of one job of 'stream rows'."""
+    _, size, stem = PCM_FORMATS[pcm]
+    name = _PCM_ENTRIES[form].format(stem)
+    if name not in hip.EXPORTS:
+        raise ValueError(f"pcm={pcm!r} has no {form} entry")
+    return name, ((size,) if stem == "s24" else ())
 
 
 def pcm_buffer(pcm, samples, device):
@@ -42,7 +60,6 @@ def pcm_buffer(pcm, samples, device):
 def pcm_shape(pcm, *shape):
     """The shape of an encoded block of `shape` samples: 's24' holds a sample as a last axis of 3 bytes."""
     return tuple(shape) + ((3,) if pcm == "s24" else ())
-_DITHER = (None, "tpdf")
 
 
 def resolve_output_rate(output_rate):
@@ -190,9 +207,8 @@ class Delivery:
         out = pcm_buffer(opt["pcm"], R * T, self.device)
         keys = self._keys(opt, which)
         if len(set(chans)) == 1:
-            _, size, stem = PCM_FORMATS[opt["pcm"]]
-            _launch(f"fh_pcm_{stem}_f32", _ptr(y), _ptr(out), hip.ptr(keys), n, chans[0], T, int(opt["interleaved"]),
-                    *((size,) if stem == "s24" else ()))
+            entry, tail = pcm_entry(opt["pcm"], "batched")
+            _launch(entry, _ptr(y), _ptr(out), hip.ptr(keys), n, chans[0], T, int(opt["interleaved"]), *tail)
         else:                      # clips of different channel counts: the segment form, the rows still where they are
             self._pcm_seg([y.data_ptr() + 4 * T * r for r in _starts(chans)], [T] * n, chans, [T] * n, out, keys, opt)
         if packed:
@@ -334,13 +350,12 @@ class Delivery:
         return dbtp
 
     def _pcm_seg(self, srcs, pitches, chans, lens, out, keys, opt):
-        _, size, stem = PCM_FORMATS[opt["pcm"]]
+        size, (entry, tail) = PCM_FORMATS[opt["pcm"]][1], pcm_entry(opt["pcm"], "segment")
         off = _starts([c * t for c, t in zip(chans, lens)])
         table = (hip.PcmClip * len(chans))(*[hip.PcmClip(int(s), out.data_ptr() + size * o, int(p), int(c), int(t))
                                             for s, o, p, c, t in zip(srcs, off, pitches, chans, lens)])
         desc, (clips,) = upload_tables([table], self.device)
-        _launch(f"fh_pcm_{stem}_seg_f32", clips, len(chans), max(chans), max(lens), hip.ptr(keys), int(opt["interleaved"]),
-                *((size,) if stem == "s24" else ()))
+        _launch(entry, clips, len(chans), max(chans), max(lens), hip.ptr(keys), int(opt["interleaved"]), *tail)
 
     @hip.on_device
     def ragged(self, clips, level, opt, which):

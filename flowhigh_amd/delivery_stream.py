@@ -236,12 +236,9 @@ def _push(delivery, streams, blocks, final):
                 H = streams[live[0]].stages[name].counters.H
                 c32 = float(np.float32(_truepeak.ceiling(ceiling_db)))
                 entry, args = f"fh_stream_limit{'_linked' if linked else ''}_f32", (delivery._tp_taps(), delivery._window(H), H, c32)
-            elif max_out and wide:
-                entry = "fh_stream_pcm_s24_rows_f32"
-                args = (ptrs[-1] if dithered else 0, int(frames), _delivery.PCM_FORMATS[pcm][1])
-            elif max_out:
-                entry = f"fh_stream_pcm_i16{'_rows' if linked else ''}_f32"
-                args = (ptrs[-1] if dithered else 0,) + ((int(frames),) if linked else ())
+            elif max_out:                                # (the mono entry takes no `interleaved`: one channel has one layout)
+                entry, tail = _delivery.pcm_entry(pcm, "stream rows" if grouped else "stream mono")
+                args = (ptrs[-1] if dithered else 0,) + ((int(frames), *tail) if grouped else ())
             else:
                 continue
             hip.check(getattr(L, entry)(*tables, max_out, *args, hip.stream()), entry)

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .delivery import PCM_FORMATS, pcm_shape
+from .delivery import PCM_FORMATS, pcm_entry, pcm_shape
 from .frontend import upload_tables
 from .stream import StreamPlan
 
@@ -147,12 +147,11 @@ def _ramp(model, plan):
 def _encode(model, block, pcm="int16"):
     """float32 [C, n] -> int16 [C, n], planar: pcm.py's encoding without dither, which is stateless (fh_pcm_i16_f32);
     pcm='s24in32': int32 [C, n], 's24': uint8 [C, n, 3] (fh_pcm_s24_f32)."""
-    dtype, size, stem = PCM_FORMATS[pcm]
-    out = torch.empty(pcm_shape(pcm, *block.shape), dtype=dtype, device=block.device)
+    out = torch.empty(pcm_shape(pcm, *block.shape), dtype=PCM_FORMATS[pcm][0], device=block.device)
     if block.shape[1]:
-        entry = f"fh_pcm_{stem}_f32"
-        hip.check(getattr(hip.lib(), entry)(block.data_ptr(), out.data_ptr(), 0, 1, block.shape[0], block.shape[1], 0,
-                                            *((size,) if stem == "s24" else ()), hip.stream()), entry)
+        entry, tail = pcm_entry(pcm, "batched")
+        hip.check(getattr(hip.lib(), entry)(block.data_ptr(), out.data_ptr(), 0, 1, block.shape[0], block.shape[1], 0, *tail,
+                                            hip.stream()), entry)
     return out
 
 

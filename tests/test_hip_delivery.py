@@ -90,6 +90,34 @@ def test_pcm_kernel_gives_pcm_py_s_bits(C, n_clips):
                     assert intact16(buf, lead, n), case
 
 
+@pytest.mark.parametrize("C", [1, 3])
+def test_pcm_planar_rows_at_every_lead(C):
+    """A planar row starts 0 .. 7 int16 past a 16-byte boundary, so its first run holds 8 .. 1 of its samples: every one of the 8
+    offsets (the later rows move with T), lengths below, at and above a run and two runs, the input on the 16-byte grid and one
+    float past it, with and without dither."""
+    L = hip.lib()
+    key = (77 + 2 ** 33, 5)
+    kd = dev_keys([key])
+    for T in (1, 7, 8, 9, 17, 23):
+        x = planted(1, C, T, seed=T + 10 * C)
+        n = x.size
+        xbuf = torch.full((GUARD + 1 + n,), SENT32, dtype=torch.int32).view(torch.float32).cuda()
+        wants = {d: want_clip(x[0], key if d else None, 0) for d in (False, True)}
+        for xlead in (GUARD, GUARD + 1):
+            xd = xbuf[xlead:xlead + n]
+            xd.copy_(torch.from_numpy(x.reshape(-1)))
+            assert xd.data_ptr() % 16 == 4 * (xlead - GUARD)
+            for lead in range(GUARD, GUARD + 8):
+                for dither in (False, True):
+                    buf, y = frame16(n, lead)
+                    assert y.data_ptr() % 16 == 2 * (lead - GUARD)
+                    hip.check(L.fh_pcm_i16_f32(xd.data_ptr(), y.data_ptr(), kd.data_ptr() if dither else 0, 1, C, T, 0, st()),
+                              "fh_pcm_i16_f32")
+                    case = (T, lead, xlead, dither)
+                    assert torch.equal(y.cpu(), wants[dither]), case
+                    assert intact16(buf, lead, n), case
+
+
 def test_pcm_kernel_dither_does_not_depend_on_layout_batch_or_channel_count():
     """Channel 1 of clip 2 of a batch of 4-channel clips = channel 1 of a 2-channel clip alone under the same key, planar or
     interleaved; channel 0 is not channel 1."""

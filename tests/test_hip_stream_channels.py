@@ -198,6 +198,71 @@ def test_dither_at_indices_past_32_bits():
         assert not np.array_equal(got[1], pcm.quantize(host[1], low[1]))  # (the high word counts)
 
 
+BLOCK_CUTS = (0, 1, 9, 24, 41)
+
+
+@pytest.mark.parametrize("first", [0, 2 ** 32 + 5])
+@pytest.mark.parametrize("C", CHANNELS)
+def test_int16_blocks_add_up_to_the_batched_entry(C, first):
+    """A clip [C, 41] encoded in the blocks the cuts 0, 1, 9, 24, 41 make, each a launch of the rows entry (planar, and in frames)
+    or, for C = 1, of the mono entry, `first` running on from 0 and from past 2^32: the blocks side by side are pcm.py's
+    encoding under the dither from `first` on, and from 0 fh_pcm_i16_f32's of the whole clip.  Nothing else is written."""
+    L, T, key, lo = hip.lib(), BLOCK_CUTS[-1], (77, 5), 8
+    host = np.random.default_rng(70 + C).uniform(-1.05, 1.05, (C, T)).astype(np.float32)
+    host[:, ::3] *= np.float32(2.0 ** -13)                               # a few LSB: the dither decides
+    x = torch.from_numpy(host).cuda()
+    kd = torch.from_numpy(np.array([key], dtype=np.uint64).view(np.int64)).cuda()
+    want = pcm.quantize(host, np.stack([pcm.tpdf_dither(key[0], key[1], c, T, first=first) for c in range(C)]))
+    for entry, frames in [("rows", 0), ("rows", 1)] + ([("mono", 0)] if C == 1 else []):
+        buf = sentinel_buffer(C * T + 2 * lo, torch.int16)
+        y0 = buf.data_ptr() + 2 * lo
+        for a, b in zip(BLOCK_CUTS, BLOCK_CUTS[1:]):
+            n = b - a
+            dsts = [y0 + 2 * a * C] * C if frames else [y0 + 2 * (c * T + a) for c in range(C)]
+            jobs = [hip.StreamJob(0, x[c, a:].data_ptr(), dsts[c], 0, first + a, first + a, 0, n, n, 0, 0, 0) for c in range(C)]
+            if entry == "rows":
+                assert launch_rows(jobs, [0, C], n, kd.data_ptr(), frames) == 0
+            else:
+                keep, (jp,) = upload_tables([(hip.StreamJob * 1)(*jobs)], torch.device("cuda"))
+                hip.check(L.fh_stream_pcm_i16_f32(jp, 1, n, kd.data_ptr(), hip.stream()), "fh_stream_pcm_i16_f32")
+                torch.cuda.synchronize()
+        got = buf[lo:lo + C * T]
+        blocks = got.cpu().numpy()
+        assert np.array_equal(blocks.reshape(T, C).T if frames else blocks.reshape(C, T), want), (entry, frames)
+        assert untouched(buf, lo, lo + C * T), (entry, frames)
+        if first == 0:
+            whole = torch.empty(C * T, dtype=torch.int16, device="cuda")
+            hip.check(L.fh_pcm_i16_f32(x.data_ptr(), whole.data_ptr(), kd.data_ptr(), 1, C, T, frames, hip.stream()), "fh_pcm_i16_f32")
+            assert torch.equal(whole, got), (entry, frames)
+
+
+@pytest.mark.parametrize("C", [2, 4, 8])
+def test_whole_frames_and_scattered_frames_agree(C):
+    """Interleaved C = 2, 4, 8 from the segment entry and from the rows entry, the destination on a frame boundary (whole-frame
+    stores) and one int16 past it (2-byte stores): both pcm.py's frames, dithered, the neighbours intact."""
+    L, key, lo = hip.lib(), (77, 0), 16
+    kd = torch.from_numpy(np.array([key], dtype=np.uint64).view(np.int64)).cuda()
+    for T in (7, 9, 257):
+        host = np.random.default_rng(80 + C + T).uniform(-1.05, 1.05, (C, T)).astype(np.float32)
+        host[:, ::3] *= np.float32(2.0 ** -13)
+        x = torch.from_numpy(host).cuda()
+        want = torch.from_numpy(np.ascontiguousarray(pcm.encode(host, key, True)).reshape(-1))
+        for entry in ("seg", "rows"):
+            for shift in (0, 1):
+                buf = sentinel_buffer(C * T + 2 * lo, torch.int16)
+                at = lo + shift
+                dst = buf.data_ptr() + 2 * at
+                assert dst % (2 * C) == 2 * shift
+                if entry == "seg":
+                    keep, (clips,) = upload_tables([(hip.PcmClip * 1)(hip.PcmClip(x.data_ptr(), dst, T, C, T))], torch.device("cuda"))
+                    hip.check(L.fh_pcm_i16_seg_f32(clips, 1, C, T, kd.data_ptr(), 1, hip.stream()), "fh_pcm_i16_seg_f32")
+                    torch.cuda.synchronize()
+                else:
+                    assert launch_rows(rows_jobs(x, [dst] * C, T), [0, C], T, kd.data_ptr(), 1) == 0
+                assert torch.equal(buf[at:at + C * T].cpu(), want), (T, entry, shift)
+                assert untouched(buf, at, at + C * T), (T, entry, shift)
+
+
 @pytest.mark.parametrize("cuts", sorted(CUTS))
 def test_full_chain_in_frames(cuts):
     x = linked_clip(2, CUTS[cuts], seed=6)

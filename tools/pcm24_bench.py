@@ -20,10 +20,11 @@ import torch
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 from flowhigh_amd import FLowHigh, FlowHighSR, hip, synth                  # noqa: E402
+from flowhigh_amd.delivery import PCM_FORMATS, pcm_entry                   # noqa: E402
 from flowhigh_amd.frontend import upload_tables                            # noqa: E402
 
 T, C, SECONDS = 480000, 2, 10.0
-FORMATS = (("int16", "i16", 2), ("s24", "s24", 3), ("s24in32", "s24", 4))
+FORMATS = tuple(PCM_FORMATS)
 
 
 def quartiles(v):
@@ -33,18 +34,17 @@ def quartiles(v):
 
 def launcher(n_clips, fmt, interleaved, dither, x, keys):
     """-> a function that queues the encode launch of n_clips clips [C, T] in the format, and its output buffer."""
-    name, stem, size = fmt
-    L, tail = hip.lib(), ((size,) if stem == "s24" else ())
+    name, size = fmt, PCM_FORMATS[fmt][1]
+    entry, tail = pcm_entry(name, "batched" if n_clips == 1 else "segment")
+    call = getattr(hip.lib(), entry)
     out = torch.empty(n_clips * C * T * size, dtype=torch.uint8, device=x.device)
     kp = keys.data_ptr() if dither else 0
     if n_clips == 1:
-        return (lambda: hip.check(getattr(L, f"fh_pcm_{stem}_f32")(x.data_ptr(), out.data_ptr(), kp, 1, C, T, interleaved, *tail,
-                                                                     hip.stream()), name)), out
+        return (lambda: hip.check(call(x.data_ptr(), out.data_ptr(), kp, 1, C, T, interleaved, *tail, hip.stream()), name)), out
     table = (hip.PcmClip * n_clips)(*[hip.PcmClip(x.data_ptr() + 4 * C * T * b, out.data_ptr() + size * C * T * b, T, C, T)
                                       for b in range(n_clips)])
     keep, (clips,) = upload_tables([table], x.device)
-    return (lambda keep=keep: hip.check(getattr(L, f"fh_pcm_{stem}_seg_f32")(clips, n_clips, C, T, kp, interleaved, *tail,
-                                                                             hip.stream()), name)), out
+    return (lambda keep=keep: hip.check(call(clips, n_clips, C, T, kp, interleaved, *tail, hip.stream()), name)), out
 
 
 def launch_us(fn, reps):
@@ -80,7 +80,7 @@ def main():
         keys = torch.from_numpy(np.array([[7, b] for b in range(n_clips)], dtype=np.uint64).view(np.int64)).to(dev)
         for interleaved in (0, 1):
             for dither in (True, False):
-                fns = {fmt[0]: launcher(n_clips, fmt, interleaved, dither, x, keys) for fmt in FORMATS}
+                fns = {fmt: launcher(n_clips, fmt, interleaved, dither, x, keys) for fmt in FORMATS}
                 for fn, _ in fns.values():
                     launch_us(fn, 3)
                 # the two 24-bit containers hold one integer
