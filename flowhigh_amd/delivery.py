@@ -318,6 +318,43 @@ class Delivery:
                                          [c.shape[1] for c in clips], rate, None)
         return lufs
 
+    def _report(self, energies, row_len, chans, hop):
+        """fh_loudness_report_f32 over rows that are chans[i] per clip -> float32 [n_clips, 6] (meter.FIELDS)."""
+        R, n = len(row_len), len(chans)
+        host = np.concatenate([np.asarray(row_len, dtype=np.int32), np.repeat(np.arange(n, dtype=np.int32), chans)])
+        tab = torch.from_numpy(host).pin_memory().to(self.device, non_blocking=True)
+        report = torch.empty(n, 6, dtype=torch.float32, device=self.device)
+        _launch("fh_loudness_report_f32", _ptr(energies), energies.shape[1], _ptr(tab[:R]), _ptr(tab[R:]), R, n, hop, _ptr(report))
+        return report
+
+    @hip.on_device
+    def measure_report(self, rows, chans=None, rate=48000):
+        """FlowHighSR.measure_loudness_report: rows, chans and rate as measure() takes them -> float32 [n_clips, 6] on the device:
+        integrated, momentary maximum, short-term maximum, range, last momentary, last short-term (meter.py is the definition).
+        Column 0 has the bits of measure()."""
+        hop, _ = _loudness.geometry(rate)
+        rate = int(rate)
+        if isinstance(rows, torch.Tensor):
+            rows = self._rows(rows).contiguous()
+            R, T = rows.shape
+            chans = [1] * R if chans is None else [int(c) for c in chans]
+            if sum(chans) != R or min(chans, default=0) < 1 or T < 1:
+                raise ValueError(f"{R} rows of {T} samples for clips of {chans} channels")
+            hop, energies = self._energies(rate, R, T)
+            _launch("fh_kweight_energy_f32", _ptr(rows), _coef(rate), _ptr(energies), R, T, hop)
+            return self._report(energies, [T] * R, chans, hop)
+        if chans is not None:
+            raise ValueError("chans= goes with one [R, T] tensor: a list holds one [C_i, T_i] tensor per clip")
+        clips = [self._rows(c) for c in rows]
+        if not clips or min(min(c.shape) for c in clips) < 1:
+            raise ValueError("measure_loudness_report takes at least one clip, every clip at least one sample")
+        chans, lens = [c.shape[0] for c in clips], [c.shape[1] for c in clips]
+        seg = self._seg_tables([c.data_ptr() for c in clips], [c.stride(0) for c in clips], chans, lens, row_table=0)
+        hop, energies = self._energies(rate, sum(chans), max(lens))
+        _launch("fh_kweight_energy_seg_f32", seg["clips"], seg["group"], len(chans), sum(chans), max(lens), _coef(rate),
+                _ptr(energies), hop)
+        return self._report(energies, seg["row_len"], chans, hop)
+
     @hip.on_device
     def measure_true_peak(self, rows, chans=None, rate=48000):
         """FlowHighSR.measure_true_peak: rows as measure() takes them -> float32 [n_clips] dBTP on the device (-inf for silence):

@@ -17,18 +17,23 @@ A stream without n_channels calls the three mono entries exactly as before.
 pcm='s24' / 's24in32' (24 bits: uint8 with a last axis of 3 bytes, or int32): the encode stage is fh_stream_pcm_s24_rows_f32 for
 every stream, a mono one as a group of one job; the plan key holds the format, so streams of different formats never share an
 encode launch.
+meter=True: the stream owns a LoudnessMeter (loudness_meter.py) at the delivered rate, fed the float32 samples the stream makes
+final -- behind the resampler and the limiter, in front of the encoder -- by one more launch behind the plan's stages, its job
+table in the plan's one upload; loudness() reads it.  The delivered blocks are those of the stream without the meter; a stream
+with nothing but the meter returns its blocks as they came.
 """
 import numpy as np
 import torch
 
 from . import delivery as _delivery
 from . import hip
+from . import loudness_meter as _lm
 from . import stream_delivery as SD
 from . import truepeak as _truepeak
 from .frontend import upload_tables
 
-KEYWORDS = ("output_rate", "pcm", "dither", "dither_seed", "true_peak", "limiter")
-_REFUSED = dict(loudness="loudness is a statistic of the whole stream",
+KEYWORDS = ("output_rate", "pcm", "dither", "dither_seed", "true_peak", "limiter", "meter")
+_REFUSED = dict(loudness="loudness is a statistic of the whole stream (meter=True reads it: DeliveryStream.loudness())",
                 channels="a stream is mono unless it is opened with n_channels=C",
                 interleaved="a stream is mono: there is nothing to interleave (a stream opened with n_channels=C takes it)")
 
@@ -46,7 +51,8 @@ def check_channels(n_channels):
 def resolve(delivery, session_pcm=None, n_channels=None):
     """delivery= of stream() / the keywords of delivery_stream(), checked (ValueError, before any GPU work) -> None when every
     value is a default, else dict(rate: None | R, true_peak: None | the ceiling in dBTP, pcm, key: None | the dither's (seed, stream)),
-    with n_channels=C also channels: C and interleaved (a key of delivery that only such a stream takes)."""
+    with n_channels=C also channels: C and interleaved (a key of delivery that only such a stream takes), with meter=True also
+    meter: True (a key that counts as non-default: a plan may hold nothing else)."""
     n_channels = check_channels(n_channels)
     if delivery is None:
         return None
@@ -57,19 +63,24 @@ def resolve(delivery, session_pcm=None, n_channels=None):
             raise ValueError(f"delivery= does not take {name}=: {_REFUSED[name]}")
         if name not in KEYWORDS and name != "interleaved":
             raise ValueError(f"delivery= has no key {name!r}: it takes {', '.join(KEYWORDS)}")
-    kw = {k: delivery.get(k) for k in KEYWORDS if k != "dither_seed"}
+    kw = {k: delivery.get(k) for k in KEYWORDS if k not in ("dither_seed", "meter")}
+    meter = delivery.get("meter", False)
+    if meter not in (False, True):
+        raise ValueError(f"meter must be a bool, got {meter!r}")
     if n_channels is not None:
         kw["interleaved"] = delivery.get("interleaved", False)
     if kw["true_peak"] is not None and kw["limiter"] is None:
         raise ValueError("true_peak= without limiter='lookahead' is one gain from the whole stream's peak: a stream takes "
                          "true_peak= with limiter='lookahead'")
     opt = _delivery.resolve_delivery(1, dither_seed=delivery.get("dither_seed", 0), level="input", **kw)
-    if opt is None:
+    if opt is None and not meter:
         return None
     if session_pcm is not None:
         raise ValueError("delivery= and the session's pcm= are two encoders for one stream: give pcm in delivery=")
+    if opt is None:
+        return SD.make_plan(channels=n_channels, meter=True)
     return SD.make_plan(opt["rate"], opt.get("true_peak"), opt["pcm"], None if opt["keys"] is None else opt["keys"][0],
-                        n_channels, opt["interleaved"])
+                        n_channels, opt["interleaved"], bool(meter))
 
 
 class _StageState:
@@ -114,6 +125,10 @@ class DeliveryStream:
         self.key = (plan["rate"], plan["true_peak"], plan["pcm"], plan["key"] is not None)
         if self.channels is not None:
             self.key += ("linked", self.interleaved)
+        self.meter = None
+        if plan.get("meter"):                    # (metered streams form plans of their own: their push has one launch more)
+            self.meter = _lm.LoudnessMeter(owner, plan["rate"] or 48000, self.channels)
+            self.key += ("meter",)
         self.stages = {}
         if plan["rate"] is not None:
             flt = SD.ResampleFilter(plan["rate"])
@@ -129,6 +144,12 @@ class DeliveryStream:
 
     def flush(self):
         return self.owner.delivery_push([self], [None], final=True)[0]
+
+    def loudness(self):
+        """The meter's reading (LoudnessMeter.read) of a stream opened with meter=True: float32 [6] on the device."""
+        if self.meter is None:
+            raise RuntimeError("the stream has no meter: open it with meter=True")
+        return self.meter.read()
 
 
 def _block(b, device, channels=None):
@@ -169,6 +190,16 @@ def _push(delivery, streams, blocks, final):
     dev = delivery.device
     cur = [_block(b, dev, s.channels) for s, b in zip(streams, blocks)]             # (every block is checked before any stream moves)
     fresh = list(cur)          # (a block made contiguous is a copy of this push's own: it lives until the launches that read it are queued)
+    metered = [i for i, s in enumerate(streams) if s.meter is not None]
+    if metered:                # (what reaches a meter follows from the lengths: its log's bound is checked before any stream moves)
+        reach = []
+        for i in metered:
+            n = cur[i].shape[1]
+            for name in ("resample", "limit"):
+                if name in streams[i].stages and (final or n):
+                    n = streams[i].stages[name].counters.peek(n, final)
+            reach.append(n)
+        _lm.check([streams[i].meter for i in metered], reach, final)
     if final:
         for s in streams:
             s.closed = True
@@ -185,8 +216,10 @@ def _push(delivery, streams, blocks, final):
         # buffer; a stage's outputs are one buffer too, a stream's part of it ([rows, n_out], contiguous) the next stage's fresh block.
         n_in = {i: cur[i].shape[1] for i in idx}
         src = {i: [cur[i].data_ptr() + 4 * r * n_in[i] for r in range(streams[i].rows)] for i in idx}
-        stages, tables_ = [], []
+        stages, tables_, floats = [], [], None
         for name in ("resample", "limit", "encode"):
+            if name == "encode" and s0.meter is not None:                # the meter takes the floats in front of the encoder
+                floats = [cur[i] for i in idx]
             if name not in s0.stages:
                 continue
             # (a stream with nothing new and nothing to end stays as it is: its job would write and move nothing)
@@ -221,9 +254,12 @@ def _push(delivery, streams, blocks, final):
             tables_.append((hip.StreamJob * len(jobs))(*jobs))
             if grouped:
                 tables_.append(np.cumsum([0] + [streams[i].rows for i in live]).astype(np.int32))
-        if not stages:
+        planned = _lm.plan([streams[i].meter for i in idx], floats, final) if floats is not None else []
+        if not stages and not planned:
             continue
-        if dithered and stages[-1][0] == "encode":
+        tables_ += [table for _, table in planned]                          # (the meter's jobs go up with the plan's)
+        at_keys = len(tables_)
+        if dithered and stages and stages[-1][0] == "encode":
             tables_.append(np.array([streams[i].plan["key"] for i in stages[-1][1]], dtype=np.uint64).view(np.int64))
         keep, ptrs = upload_tables(tables_, dev)
         L = hip.lib()
@@ -238,10 +274,12 @@ def _push(delivery, streams, blocks, final):
                 entry, args = f"fh_stream_limit{'_linked' if linked else ''}_f32", (delivery._tp_taps(), delivery._window(H), H, c32)
             elif max_out:                                # (the mono entry takes no `interleaved`: one channel has one layout)
                 entry, tail = _delivery.pcm_entry(pcm, "stream rows" if grouped else "stream mono")
-                args = (ptrs[-1] if dithered else 0,) + ((int(frames), *tail) if grouped else ())
+                args = (ptrs[at_keys] if dithered else 0,) + ((int(frames), *tail) if grouped else ())
             else:
                 continue
             hip.check(getattr(L, entry)(*tables, max_out, *args, hip.stream()), entry)
+        _lm.launch(planned, ptrs[at_keys - len(planned):at_keys])           # (behind the stage that made its floats)
+        del floats
     del fresh
     out = []
     for s, c in zip(streams, cur):                       # (what stood still at some stage emits an empty block of the result's type)

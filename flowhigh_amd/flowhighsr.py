@@ -1190,7 +1190,9 @@ class FlowHighSR:
         samples.  The resampler withholds about 10 max(up, down) / up samples at 48 kHz and the limiter 2 H + 10 delivered
         samples (about 10.2 ms) until the flush.  The dither's key is (dither_seed, 0).  delivery= excludes the session's own pcm=;
         it does not take loudness= (a statistic of the whole stream), true_peak= without the limiter (the same), channels=, or,
-        in a mono session, interleaved=; a dict of defaults is None.
+        in a mono session, interleaved=; a dict of defaults is None.  meter=True in it: the DeliveryStream owns a loudness meter
+        (loudness_meter()) fed the float32 samples it makes final, session.delivery.loudness() reads it; the blocks are those of
+        the same session without the meter.
         n_channels=C (an int 1 .. 8; None: one mono stream): the stream has C channels, fixed here and never read from a block's
         shape.  Blocks are [C, n] (a block of another row count is a ValueError that leaves the session as it was), push() and
         flush() return [C, m].  Window i is what generate(window_i [C, n], sr, channels='first', level='input') returns under
@@ -1231,7 +1233,10 @@ class FlowHighSR:
         samples it made final, flush() the rest.  The blocks add up to Delivery.batch of the whole stream at level='input'.
         n_channels=C (an int 1 .. 8; None: the mono stream): push takes [C, n] and returns [C, m], the blocks add up to
         Delivery.batch of the whole [C, T] stream as one clip: the limiter's envelope and gain are one for all channels, channel c
-        takes its own dither.  interleaved=True (with n_channels and pcm): int16 sample frames [m, C].  Refused: channels= (the
+        takes its own dither.  interleaved=True (with n_channels and pcm): int16 sample frames [m, C].  meter=True: the stream owns a
+        LoudnessMeter (loudness_meter()) at the delivered rate, fed the float32 samples the stream makes final -- behind the
+        resampler and the limiter, in front of the encoder --; loudness() returns its read().  The blocks have the bits of the same
+        stream without the meter; with nothing but meter=True they are returned as they came.  Refused: channels= (the
         count goes by n_channels=), loudness=, true_peak= without limiter='lookahead', and interleaved= without n_channels."""
         from .delivery_stream import DeliveryStream, resolve
         return DeliveryStream(resolve(keywords, None, n_channels), self)
@@ -1262,6 +1267,33 @@ class FlowHighSR:
         device, -inf for a clip no block of which passes the gates.  The kernels of loudness= with no target: it reads what a
         loudness= call delivered, and whether the peak cap bound (flowhigh_amd/loudness.py is the definition)."""
         return self.delivery.measure(rows, chans, rate)
+
+    @torch.no_grad()
+    def measure_loudness_report(self, rows, chans=None, rate=48000):
+        """EBU R128's figures on the device: rows, chans and rate as measure_loudness takes them -> float32 [n_clips, 6] on the
+        device: the integrated loudness (the bits of measure_loudness), the maximum momentary (400 ms) and the maximum
+        short-term (3 s) loudness in LUFS, the loudness range (EBU Tech 3342) in LU, and the last momentary and short-term
+        value; -inf for an empty series (a clip shorter than 3 s has no short-term value) and a range of 0 when no window passes
+        its gates (flowhigh_amd/meter.py is the definition).  At most 2^20 sub-blocks of 100 ms per clip."""
+        return self.delivery.measure_report(rows, chans, rate)
+
+    def loudness_meter(self, rate=48000, n_channels=None, log_capacity=None):
+        """The meter of a stream at `rate`: push(block) takes float32 [1, n] / [n] on the model's device ([C, n] with
+        n_channels=C, an int 1 .. 8), n may be 0, and returns nothing; read() -> float32 [6] on the device, the row
+        measure_loudness_report(x[:, :m.measured]) gives for the stream x so far, bit for bit (m.measured, a host int: the
+        complete 100 ms sub-blocks among the whole spans of 4096 samples pushed; all -inf with a range of 0 while it is 0);
+        flush() processes the rest and closes the meter: read() is then the report of all of x.  read() costs one launch; nothing
+        is read back by any of them.  log_capacity: the sub-blocks the energy log holds at first (it grows by doubling, to 2^20
+        at most: a push that would begin one more is a RuntimeError that leaves the meter as it was)."""
+        from .loudness_meter import LOG_CAPACITY, LoudnessMeter
+        return LoudnessMeter(self, rate, n_channels, LOG_CAPACITY if log_capacity is None else log_capacity)
+
+    @torch.no_grad()
+    def meter_push(self, meters, blocks, final=False):
+        """One block per LoudnessMeter (None: nothing): ONE launch for all rows of all meters of one rate and one table upload.
+        final: the meters end here.  A meter's result does not depend on its company."""
+        from .loudness_meter import push
+        push(self.delivery, meters, blocks, final)
 
     @torch.no_grad()
     def measure_true_peak(self, rows, chans=None, rate=48000):

@@ -96,6 +96,17 @@ class StreamJob(C.Structure):
                 ("n_out", C.c_int32), ("n_keep", C.c_int32), ("ended", C.c_int32), ("pad_", C.c_int32)]
 
 
+class MeterState(C.Structure):
+    """fh_meter_state: the K-weighting's record of one row of a metered stream (csrc/loudness.hip)."""
+    _fields_ = [("s1", C.c_double), ("s2", C.c_double), ("t1", C.c_double), ("t2", C.c_double), ("acc", C.c_double)]
+
+
+class MeterJob(C.Structure):
+    """fh_meter_job: one row of a fh_stream_kweight_energy_f32 launch (csrc/loudness.hip)."""
+    _fields_ = [("kept", C.c_void_p), ("fresh", C.c_void_p), ("keep", C.c_void_p), ("state", C.c_void_p), ("log", C.c_void_p),
+                ("base", C.c_int64), ("n_kept", C.c_int32), ("n_fresh", C.c_int32), ("log_len", C.c_int32), ("ended", C.c_int32)]
+
+
 MAX_GROUPS = 8              # FH_MAX_GROUPS of include/flowhigh_hip.h
 
 
@@ -231,6 +242,10 @@ _SIGS = {
     "fh_kweight_energy_f32": [_P, _P, _P, _I, _I, _I, _P],
     "fh_kweight_energy_seg_f32": [_P, _P, _I, _I, _I, _P, _P, _I, _P],
     "fh_loudness_gate_f32": [_P, _I, _P, _P, _I, _I, _I, _D, _P, _P, _P, _P],
+    "fh_loudness_report_f32": [_P, _I, _P, _P, _I, _I, _I, _P, _P],
+    "fh_sizeof_meter_state": [],
+    "fh_sizeof_meter_job": [],
+    "fh_stream_kweight_energy_f32": [_P, _P, _I, _P, _I, _P],
     "fh_tp_tile_len": [],
     "fh_true_peak_f32": [_P, _P, _P, _I, _I, _P],
     "fh_true_peak_seg_f32": [_P, _P, _I, _I, _I, _P, _P, _P],
@@ -281,7 +296,8 @@ def lib():
             or L.fh_sizeof_amp_group() != C.sizeof(AmpGroup) or L.fh_sizeof_clip() != C.sizeof(Clip) \
             or L.fh_sizeof_rate() != C.sizeof(Rate) or L.fh_sizeof_pcm_clip() != C.sizeof(PcmClip) \
             or L.fh_sizeof_xfade_job() != C.sizeof(XfadeJob) or L.fh_sizeof_stream_job() != C.sizeof(StreamJob) \
-            or L.fh_sizeof_row_groups() != C.sizeof(RowGroups):
+            or L.fh_sizeof_row_groups() != C.sizeof(RowGroups) or L.fh_sizeof_meter_state() != C.sizeof(MeterState) \
+            or L.fh_sizeof_meter_job() != C.sizeof(MeterJob):
         raise HipError("descriptor struct layout mismatch between hip.py and flowhigh_hip.h")
     _lib = L
     return L

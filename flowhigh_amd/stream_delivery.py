@@ -227,13 +227,19 @@ def limit_span(src, base, E, first, n_out, ended, H, true_peak_db):
 MAX_CHANNELS = 8
 
 
-def make_plan(rate=None, true_peak=None, pcm=None, key=None, channels=None, interleaved=False):
+def make_plan(rate=None, true_peak=None, pcm=None, key=None, channels=None, interleaved=False, meter=False):
     """The stages of a delivery, as delivery_stream.resolve gives them: rate None | R, true_peak None | the ceiling in dBTP
     (limiter='lookahead'), pcm None | 'int16' | 's24' | 's24in32', key None | the dither's (seed, stream); channels None (one mono stream: the plan
-    it always was) | C rows that move together, 1 .. 8; interleaved: the encoder's output as sample frames [n, C]."""
+    it always was) | C rows that move together, 1 .. 8; interleaved: the encoder's output as sample frames [n, C]; meter: the stream
+    owns a loudness meter (meter.py) fed the float32 samples it makes final, in front of the encoder: no stage, and the plan's
+    key "meter" only when it is set."""
     if pcm is not None and pcm not in _pcm.FORMATS:
         raise ValueError(f"pcm must be None or one of {_pcm.FORMATS}, got {pcm!r}")
     plan = dict(rate=rate, true_peak=true_peak, pcm=pcm, key=key)
+    if meter not in (False, True):
+        raise ValueError(f"meter must be a bool, got {meter!r}")
+    if meter:
+        plan["meter"] = True
     if channels is None:
         if interleaved:
             raise ValueError("interleaved goes with channels: a mono stream has nothing to interleave")

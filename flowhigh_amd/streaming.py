@@ -24,7 +24,7 @@ _CARRIED = "delivery=dict(...) carries it across pushes"
 _NOT_BUILT = dict(channels="a session is one mono stream unless it is opened with n_channels=C, which takes [C, n] blocks",
                   dither=f"dither needs a sample-index offset across blocks (csrc/pcm.hip): {_CARRIED}",
                   output_rate=f"resampling a stream needs resampler state across blocks: {_CARRIED}",
-                  loudness="loudness is a statistic of a whole clip",
+                  loudness="loudness is a statistic of a whole clip (delivery=dict(meter=True) reads the stream's)",
                   true_peak=f"the true peak is a statistic of a whole clip: {_CARRIED} with limiter='lookahead'")
 
 

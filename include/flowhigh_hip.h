@@ -810,6 +810,60 @@ int fh_loudness_gate_f32(const double* energies, int n_sub, const int32_t* lens,
                          int hop, double target, const uint32_t* peak_bits, float* lufs, float* gains, void* stream);
 
 /* -----------------------------------------------------------------------------------
+ * Loudness meter (csrc/loudness.hip; FlowHighSR.measure_loudness_report, FlowHighSR.loudness_meter, delivery_stream(meter=True)):
+ * EBU R128's figures as flowhigh_amd/meter.py defines them -- the integrated loudness above, the momentary series (the 400 ms
+ * blocks), the short-term series (3 s windows of 30 sub-blocks at 100 ms hop) and the loudness range of EBU Tech 3342 (absolute
+ * gate at -70 LUFS, relative gate 20 LU below the absolute-gated mean, both strict; the 10th and 95th percentile of the survivors
+ * by the nearest-rank rule in integers).
+ * --------------------------------------------------------------------------------- */
+/* One workgroup per clip over the energies the two energy entries leave; energies, n_sub (the pitch), lens, group, rows, n_clips
+ * and hop as fh_loudness_gate_f32 takes them, and n_sub <= 2^20.  report: DEVICE float [n_clips][6] =
+ *   I        the integrated loudness: the bits of fh_loudness_gate_f32's lufs on the same energies
+ *   M_max    the largest momentary loudness -0.691 + 10 log10(z[j]) over the clip's 400 ms blocks (a clip shorter than one
+ *            block is one block of its whole length)
+ *   S_max    the largest short-term loudness over the windows zs[j] = (s[j] + ... + s[j + 29]) / (30 hop), j < K - 29,
+ *            s[i] = the sum over the clip's rows of energies[r, i], K = len / hop the complete sub-blocks
+ *   LRA      10 log10(hi / lo) in LU: of the n windows with zs > ZA and zs > 0.01 mean(zs over those with zs > ZA), sorted
+ *            ascending, lo is number (10 (n - 1) + 50) / 100 and hi number (95 (n - 1) + 50) / 100 (integer division); 0 when n = 0
+ *   M_last, S_last   the last value of either series
+ * in LUFS / LU; -inf for an empty series or a block of energy 0.  Double arithmetic, every window's 30 terms added in ascending
+ * order; the percentiles are an exact selection over the windows' bit patterns (8 passes of 8 bits, both at once), the windows
+ * made again from the energies on every pass: nothing is sorted or stored. */
+int fh_loudness_report_f32(const double* energies, int n_sub, const int32_t* lens, const int32_t* group, int rows, int n_clips,
+                           int hop, float* report, void* stream);
+/* The K-weighting of a stream, block by block, with the bits of fh_kweight_energy_f32 on the whole stream: one job per row (one
+ * channel of one stream) and launch.  A job's source is two runs read as one: the n_kept samples the row kept (fewer than a
+ * span), then the n_fresh new ones; `base` is the absolute index of the first of them, a multiple of the span length, so span
+ * boundaries stay where fh_kweight_energy_f32 has them.  The job starts from its record, walks every whole span of the source
+ * -- with `ended` also the partial one behind them, and the stream ends there --, writes every sub-block sum that it finishes, and
+ * the running sum of the one in progress, to log[] at the sub-block's absolute index (an index of log_len or more is not
+ * written), stores the record back and copies the samples behind the last whole span to keep[] (a buffer that is neither run).
+ * Nothing is read back: what was walked follows from the lengths alone. */
+typedef struct {
+  double s1, s2, t1, t2;   /* the filter's state behind the last sample walked */
+  double acc;              /* the running sum of the sub-block in progress */
+} fh_meter_state;
+typedef struct {
+  const float* kept;       /* n_kept float32 */
+  const float* fresh;      /* n_fresh float32 */
+  float* keep;             /* (n_kept + n_fresh) % span samples, when the stream has not ended */
+  fh_meter_state* state;   /* the row's record: all zero for a new stream */
+  double* log;             /* the row of the stream's energy log, log_len doubles */
+  int64_t base;            /* absolute index of the first source sample: a multiple of fh_loudness_span_len() */
+  int32_t n_kept, n_fresh;
+  int32_t log_len;         /* <= 2^20 */
+  int32_t ended;
+} fh_meter_job;
+int fh_sizeof_meter_state(void);
+int fh_sizeof_meter_job(void);
+/* jobs: DEVICE array; check: the same table on the HOST, read before the call returns: a job with a null pointer to something
+ * it would use, a negative count, n_kept of a span or more, n_fresh > 2^30 - 2 spans, log_len > 2^20 or a base that is negative or no
+ * multiple of the span length is refused here (FH_E_ARG), and the kernel leaves a job of the device table that fails the same
+ * checks unwritten.  coef and hop as fh_kweight_energy_f32 takes them; n_jobs <= 65535. */
+int fh_stream_kweight_energy_f32(const fh_meter_job* jobs, const fh_meter_job* check, int n_jobs, const double* coef, int hop,
+                                 void* stream);
+
+/* -----------------------------------------------------------------------------------
  * True peak and the look-ahead limiter on the device (csrc/truepeak.hip; FlowHighSR.generate*(true_peak=, limiter=),
  * FlowHighSR.measure_true_peak): ITU-R BS.1770-4 Annex 2 as flowhigh_amd/truepeak.py defines it.  Oversampling is by 4 at every
  * rate with the 81 taps of scipy.signal.resample_poly(x, 4, 1), zeros outside the clip, in float32 FMA chains in ascending tap order:
