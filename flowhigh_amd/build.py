@@ -9,7 +9,7 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "lib" / "libflowhigh_hip.so"
 SOURCES = ["api_common.hip", "conv_mfma.hip", "conv_mfma_bf.hip", "conv_wino.hip", "conv_wino54.hip", "conv_wino54_bf.hip", "amp_fused.hip", "narrow_bf.hip", "act1d.hip", "gemm_mfma.hip", "gemm_bf.hip", "flow_ops.hip", "convnext.hip", "sum_ops.hip",
-           "attention.hip", "attention_bf.hip", "attention_band.hip", "attention_bf_band.hip", "frontend.hip", "fft.hip", "prior.hip", "ode.hip", "steps.hip", "level.hip", "pcm.hip", "loudness.hip", "truepeak.hip", "stream.hip", "stream_delivery.hip"]
+           "attention.hip", "attention_bf.hip", "attention_band.hip", "attention_bf_band.hip", "frontend.hip", "fft.hip", "prior.hip", "ode.hip", "steps.hip", "level.hip", "pcm.hip", "loudness.hip", "quality.hip", "truepeak.hip", "stream.hip", "stream_delivery.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-source extra flags.  The bf16 x 6 kernels keep everything beside their MFMAs one result per lane: the SLP vectoriser
 # would re-pack it into v_pk_*_f32, which stall a bf16 MFMA (conv_wino54_kernel.h)
@@ -24,7 +24,7 @@ EXTRA_FLAGS = {"conv_wino54_bf.hip": ["-fno-slp-vectorize"], "conv_wino.hip": ["
 # fixed at the source, conv_wino_common.h: wino_prefetch_a; the limit here is about speed.)
 RESOURCE_FLAGS = ["-Rpass-analysis=kernel-resource-usage"]
 MAX_SCRATCH_BYTES = 16          # per lane: up to 4 spilled registers (prologue / epilogue values) are tolerated and reported
-HEADERS = ["fh_common.h", "row_groups.h", "bf16x6.h", "conv_mfma_common.h", "conv_mfma_epilogue.h", "conv_wino_common.h", "conv_wino54_kernel.h", "attention_softmax.h", "attention_kernel.h", "attention_bf_kernel.h", "gemm_common.h", "philox.h", "pcm_common.h", "truepeak_common.h"]
+HEADERS = ["fh_common.h", "row_groups.h", "bf16x6.h", "conv_mfma_common.h", "conv_mfma_epilogue.h", "conv_wino_common.h", "conv_wino54_kernel.h", "attention_softmax.h", "attention_kernel.h", "attention_bf_kernel.h", "gemm_common.h", "philox.h", "pcm_common.h", "truepeak_common.h", "fft2048.h"]
 
 
 def _deps():

@@ -17,42 +17,13 @@
 //
 // Spectrum layout ("P-layout", shared with fh_spec_energy_f32 / fh_spec_splice_f32): 33 blocks of 64
 // floats = 32 Re then 32 Im of bins 32 b .. 32 b + 31; bins >= 1025 are zero.
-#include "fh_common.h"
+// (the transform itself, fft2048_stages, is in fft2048.h: fh_quality_frames_f32 runs it as well)
+#include "fft2048.h"
 
 namespace {
 
-constexpr int FFT_N = 2048;
-constexpr int FFT_LOG = 11;
-constexpr int FFT_BINS = 1025;
 constexpr int FFT_P_WIDTH = 2112;     // 33 * 64
 constexpr int FFT_MAG_WIDTH = 1056;   // 33 * 32
-
-__device__ __forceinline__ int bitrev11(int n) { return (int)(__brev((unsigned)n) >> 21); }
-
-// 11 in-place butterfly stages over re[], im[] (bit-reversed order in, natural order out)
-__device__ __forceinline__ void fft2048_stages(double* re, double* im, const double2* __restrict__ tw, int tid) {
-#pragma unroll 1
-  for (int s = 1; s <= FFT_LOG; ++s) {
-    const int half = 1 << (s - 1);
-    const int tstep = FFT_N >> s;               // twiddle index stride: W_m^pos = W_2048^(pos * 2048 / m)
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int j = tid + 256 * q;
-      const int pos = j & (half - 1);
-      const int i0 = ((j >> (s - 1)) << s) + pos, i1 = i0 + half;
-      const double2 w = tw[pos * tstep];
-      const double xr = re[i1], xi = im[i1];
-      const double tr = w.x * xr - w.y * xi, ti = w.x * xi + w.y * xr;
-      const double ar = re[i0], ai = im[i0];
-      re[i0] = ar + tr;
-      im[i0] = ai + ti;
-      re[i1] = ar - tr;
-      im[i1] = ai - ti;
-    }
-  }
-  __syncthreads();
-}
 
 // mode 0: packed complex spectrum [rows, 2112]; mode 1: magnitudes [rows, 1056]
 __global__ __launch_bounds__(256) void rfft2048_kernel(const float* __restrict__ frames,

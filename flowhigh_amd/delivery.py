@@ -25,6 +25,7 @@ import torch
 from . import hip, tables
 from . import loudness as _loudness
 from . import pcm as _pcm_def
+from . import quality as _quality
 from . import truepeak as _truepeak
 from .frontend import _launch, _ptr, clip_array, upload_tables
 from .prior import expand_seed
@@ -132,6 +133,7 @@ class Delivery:
         self.device = hip.norm_device(device)
         self.resampler = resampler            # its tap cache holds the (R, 48000) filters beside the input side's
         self._windows = {}                    # half window H -> the limiter's device double [2 H + 1]
+        self._fft = None                      # measure_quality's window and twiddles
 
     def _keys(self, opt, which):
         """Device int64 [n, 2] of the clips `which` of the call, or None without dither."""
@@ -386,6 +388,71 @@ class Delivery:
         self._delivery_gain(None, None, None, tp, group, R, len(chans), None, False, dbtp=dbtp)
         return dbtp
 
+    def _fft_tables(self):
+        """(the device Hann window, the device twiddles) of the quality report's STFT, uploaded once."""
+        if self._fft is None:
+            self._fft = (tables.hann_window().to(self.device), tables.fft_twiddles().to(self.device))
+        return self._fft[0].data_ptr(), self._fft[1].data_ptr()
+
+    @hip.on_device
+    def measure_quality(self, rows, ref_rows, chans=None, rate=48000, cutoff_hz=None):
+        """FlowHighSR.measure_quality: an estimate and its reference, float32 [R, T] rows (chans[i] per clip; None: every row a
+        clip) or two lists of [C_i, T_i] tensors of equal shapes pair by pair -> float32 [n_clips, 4] on the device: lsd, lsd_low,
+        lsd_high, snr_db (quality.py is the definition).  cutoff_hz: None, one positive number, or one per clip.  Everything is
+        checked before the first launch.  Rows of one length and one cutoff run the batched entry, anything else the segment
+        form, read where the rows are; a clip gets the same bits from either."""
+        batched = isinstance(rows, torch.Tensor) or isinstance(ref_rows, torch.Tensor)
+        if batched:
+            if not (isinstance(rows, torch.Tensor) and isinstance(ref_rows, torch.Tensor)):
+                raise ValueError("measure_quality takes two [R, T] tensors or two lists of [C_i, T_i] tensors")
+            est, ref = [rows], [ref_rows]
+        else:
+            if chans is not None:
+                raise ValueError("chans= goes with two [R, T] tensors: a list holds one [C_i, T_i] tensor per clip")
+            est, ref = list(rows), list(ref_rows)
+            if not est or len(est) != len(ref):
+                raise ValueError(f"measure_quality takes at least one clip and a reference for every clip, got {len(est)} and {len(ref)}")
+        for e, r in zip(est, ref):
+            for t in (e, r):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.ndim != 2 or t.device != self.device:
+                    raise ValueError(f"measure_quality takes float32 [rows, T] on {self.device}, got "
+                                     f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}")
+            if e.shape != r.shape or min(e.shape) < 1:
+                raise ValueError(f"an estimate and its reference have one shape of at least one row and one sample, got "
+                                 f"{tuple(e.shape)} and {tuple(r.shape)}")
+        if batched:
+            R, T = rows.shape
+            chans = [1] * R if chans is None else [int(c) for c in chans]
+            if sum(chans) != R or min(chans, default=0) < 1:
+                raise ValueError(f"{R} rows of {T} samples for clips of {chans} channels")
+            lens = [T] * len(chans)
+        else:
+            chans, lens = [e.shape[0] for e in est], [e.shape[1] for e in est]
+        n, R, max_len = len(chans), sum(chans), max(lens)
+        if R > 65535 or max_len > 2 ** 30:
+            raise ValueError(f"measure_quality takes up to 65535 rows of up to 2^30 samples, got {R} rows, {max_len} samples")
+        kcs = _quality_bins(cutoff_hz, rate, n)
+        window, tw = self._fft_tables()
+        F = _quality.n_frames(max_len)
+        frames = torch.empty(R, F, 5, dtype=torch.float64, device=self.device)
+        row_len = np.repeat(np.asarray(lens, dtype=np.int32), chans)
+        group = np.repeat(np.arange(n, dtype=np.int32), chans)
+        if batched and len(set(kcs)) == 1:
+            e, r = rows.contiguous(), ref_rows.contiguous()
+            desc, (p_len, p_group) = upload_tables([row_len, group], self.device)
+            _launch("fh_quality_frames_f32", _ptr(e), _ptr(r), window, tw, _ptr(frames), R, max_len, kcs[0])
+        else:
+            if batched:                                # (one cutoff per clip: the clips as views of the two tensors)
+                est, ref = list(rows.split(chans)), list(ref_rows.split(chans))
+            est, ref = [self._rows(e) for e in est], [self._rows(r) for r in ref]
+            table = (hip.QualityClip * n)(*[hip.QualityClip(e.data_ptr(), r.data_ptr(), e.stride(0), r.stride(0), c, t, k, 0)
+                                            for e, r, c, t, k in zip(est, ref, chans, lens, kcs)])
+            desc, (p_clips, p_len, p_group) = upload_tables([table, row_len, group], self.device)
+            _launch("fh_quality_frames_seg_f32", p_clips, ctypes.addressof(table), p_group, n, R, max_len, window, tw, _ptr(frames))
+        report = torch.empty(n, 4, dtype=torch.float32, device=self.device)
+        _launch("fh_quality_report_f32", _ptr(frames), F, p_len, p_group, R, n, _ptr(report))
+        return report
+
     def _pcm_seg(self, srcs, pitches, chans, lens, out, keys, opt):
         size, (entry, tail) = PCM_FORMATS[opt["pcm"]][1], pcm_entry(opt["pcm"], "segment")
         off = _starts([c * t for c, t in zip(chans, lens)])
@@ -469,6 +536,20 @@ def _coef(rate):
 
 def _starts(lens):
     return [int(x) for x in np.cumsum([0] + list(lens[:-1]))]
+
+
+def _quality_bins(cutoff_hz, rate, n_clips):
+    """measure_quality's cutoff_hz (None, one number, or one per clip) -> the cutoff bin of every clip, -1 without a cutoff."""
+    if cutoff_hz is None or np.ndim(cutoff_hz) == 0:
+        cut = [cutoff_hz] * n_clips
+    else:
+        cut = list(cutoff_hz)
+        if len(cut) != n_clips:
+            raise ValueError(f"one cutoff_hz per clip: {len(cut)} for {n_clips} clips")
+    for c in cut:
+        if c is not None and (isinstance(c, (bool, str, bytes)) or not isinstance(c, (int, float, np.integer, np.floating))):
+            raise ValueError(f"cutoff_hz must be None or finite and positive, got {c!r}")
+    return [-1 if c is None else _quality.cutoff_bin(c, rate) for c in cut]
 
 
 def _clip_views(out, chans, lens, interleaved, pcm="int16"):

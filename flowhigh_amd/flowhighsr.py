@@ -1303,6 +1303,18 @@ class FlowHighSR:
         the definition)."""
         return self.delivery.measure_true_peak(rows, chans, rate)
 
+    @torch.no_grad()
+    def measure_quality(self, rows, ref_rows, chans=None, rate=48000, cutoff_hz=None):
+        """Spectral quality report on the device: an estimate against a full-band reference.  rows, ref_rows = float32 [R, T] on
+        the model's device (chans: channels per clip, summing to R; None: every row is a clip), or two lists of [C_i, T_i] tensors
+        of equal shapes pair by pair (no chans=; one launch sequence for all of them).  cutoff_hz: None, one positive number, or
+        one per clip -- for a clip generated from sr_in it is sr_in / 2; rate turns it into a bin and does nothing else
+        -> float32 [n_clips, 4] on the device, nothing is read back: the log-spectral distance over all bins, below and above the
+        cutoff (NaN for an empty band, and for both without a cutoff), and the SNR in dB (+inf for identical rows).  STFT of
+        2048 / 480 with the post-processor's window; flowhigh_amd/quality.py is the definition.  Synthetic-weight models give
+        distances between computations, not perceptual quality."""
+        return self.delivery.measure_quality(rows, ref_rows, chans, rate, cutoff_hz)
+
     def _serve_streams(self, n):
         pool = getattr(self, "_side_streams", None)
         if pool is None or len(pool) < n:

@@ -96,6 +96,12 @@ class StreamJob(C.Structure):
                 ("n_out", C.c_int32), ("n_keep", C.c_int32), ("ended", C.c_int32), ("pad_", C.c_int32)]
 
 
+class QualityClip(C.Structure):
+    """fh_quality_clip: one clip of fh_quality_frames_seg_f32 (csrc/quality.hip)."""
+    _fields_ = [("est", C.c_void_p), ("ref", C.c_void_p), ("est_pitch", C.c_int64), ("ref_pitch", C.c_int64),
+                ("channels", C.c_int32), ("len", C.c_int32), ("kc", C.c_int32), ("pad_", C.c_int32)]
+
+
 class MeterState(C.Structure):
     """fh_meter_state: the K-weighting's record of one row of a metered stream (csrc/loudness.hip)."""
     _fields_ = [("s1", C.c_double), ("s2", C.c_double), ("t1", C.c_double), ("t2", C.c_double), ("acc", C.c_double)]
@@ -246,6 +252,10 @@ _SIGS = {
     "fh_sizeof_meter_state": [],
     "fh_sizeof_meter_job": [],
     "fh_stream_kweight_energy_f32": [_P, _P, _I, _P, _I, _P],
+    "fh_sizeof_quality_clip": [],
+    "fh_quality_frames_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "fh_quality_frames_seg_f32": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "fh_quality_report_f32": [_P, _I, _P, _P, _I, _I, _P, _P],
     "fh_tp_tile_len": [],
     "fh_true_peak_f32": [_P, _P, _P, _I, _I, _P],
     "fh_true_peak_seg_f32": [_P, _P, _I, _I, _I, _P, _P, _P],
@@ -297,7 +307,7 @@ def lib():
             or L.fh_sizeof_rate() != C.sizeof(Rate) or L.fh_sizeof_pcm_clip() != C.sizeof(PcmClip) \
             or L.fh_sizeof_xfade_job() != C.sizeof(XfadeJob) or L.fh_sizeof_stream_job() != C.sizeof(StreamJob) \
             or L.fh_sizeof_row_groups() != C.sizeof(RowGroups) or L.fh_sizeof_meter_state() != C.sizeof(MeterState) \
-            or L.fh_sizeof_meter_job() != C.sizeof(MeterJob):
+            or L.fh_sizeof_meter_job() != C.sizeof(MeterJob) or L.fh_sizeof_quality_clip() != C.sizeof(QualityClip):
         raise HipError("descriptor struct layout mismatch between hip.py and flowhigh_hip.h")
     _lib = L
     return L

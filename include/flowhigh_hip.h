@@ -991,6 +991,59 @@ int fh_stream_pcm_i16_rows_f32(const fh_stream_job* jobs, int n_jobs, const int3
 int fh_stream_pcm_s24_rows_f32(const fh_stream_job* jobs, int n_jobs, const int32_t* groups, int n_groups, int max_out,
                                const uint64_t* keys, int interleaved, int container, void* stream);
 
+/* -----------------------------------------------------------------------------------
+ * Spectral quality report on the device (csrc/quality.hip; FlowHighSR.measure_quality): the log-spectral distance of an estimate
+ * e from a reference r, over all bins and below / above a cutoff bin, and their SNR, as flowhigh_amd/quality.py defines them.
+ *   STFT: n_fft 2048, hop 480, the float32 Hann window (`window`, 2048 floats) taken as double, 1024 zeros either side:
+ *   F = 1 + len / 480 frames, bins k = 0 .. 1024, P[t, k] = |X[t, k]|^2;  d = log10(max(P_r, 1e-8)) - log10(max(P_e, 1e-8));
+ *   kc = the first bin of the high band: low = [0, kc), high = [kc, 1025), kc = -1: no cutoff;
+ *   l_band[t] = sqrt(mean over the band's bins of d[t, k]^2): NaN for an empty band, and for low and high without a cutoff.
+ * Both spectra of a frame come from ONE complex transform of e + i r (the LDS FFT of fh_rfft2048_f32; `twiddles` as that entry
+ * takes them), separated as X_e[k] = (Z[k] + conj Z[2048 - k]) / 2, X_r[k] = (Z[k] - conj Z[2048 - k]) / (2 i).  Everything
+ * behind the float32 loads is float64; no frame or spectrum is stored.  No floating-point atomics: every sum is a fixed tree.
+ * --------------------------------------------------------------------------------- */
+/* One workgroup per frame of every row pair of est, ref [rows, len] (float32).  frames: DEVICE double [rows][F][5], 8-byte
+ * aligned; frame t of row r gets
+ *   l_full[t], l_low[t], l_high[t]                                    (above)
+ *   sum of r[n]^2 and sum of (r[n] - e[n])^2 over the samples n in [480 t, min(480 t + 480, len)) that the frame owns, the
+ *   difference formed per sample in double
+ * and nothing else is written.  1 <= len <= 2^30, rows <= 65535, -1 <= kc <= 1025.  A frame's five values depend on the row pair,
+ * t and kc alone. */
+int fh_quality_frames_f32(const float* est, const float* ref, const float* window, const double* twiddles, double* frames, int rows,
+                          int len, int kc, void* stream);
+/* The same over clips of different lengths and channel counts read where they are; a row gets the bits of
+ * fh_quality_frames_f32 on that row pair alone with the clip's kc. */
+typedef struct {
+  const float* est;    /* the estimate's first row */
+  const float* ref;    /* the reference's first row */
+  int64_t est_pitch;   /* floats from one row of est to the next */
+  int64_t ref_pitch;   /* the same for ref */
+  int32_t channels;    /* rows of the clip, >= 1 */
+  int32_t len;         /* samples per row, >= 1 */
+  int32_t kc;          /* -1 .. 1025 */
+  int32_t pad_;
+} fh_quality_clip;
+int fh_sizeof_quality_clip(void);
+/* clips: DEVICE array; check: the same table on the HOST, read before the call returns (a clip with a null pointer, channels < 1,
+ * len outside 1 .. max_len or kc outside -1 .. 1025 is refused; the kernel checks its own copy again and leaves such a clip
+ * unwritten).  group: DEVICE int32 [rows], non-decreasing, values in [0, n_clips): row r is channel r - (first row of its clip)
+ * of clip group[r].  frames: DEVICE double [rows][1 + max_len / 480][5], row r written up to its own 1 + len / 480 frames;
+ * max_len: the largest len of the table. */
+int fh_quality_frames_seg_f32(const fh_quality_clip* clips, const fh_quality_clip* check, const int32_t* group, int n_clips,
+                              int rows, int max_len, const float* window, const double* twiddles, double* frames, void* stream);
+/* One workgroup per clip over the frames either entry leaves (f_pitch: the frames per row of the buffer): the clip's rows are
+ * those r with group[r] == c, every one of lens[r] samples (lens, group: DEVICE int32 [rows]).  report: DEVICE float
+ * [n_clips][4] =
+ *   lsd, lsd_low, lsd_high   the mean of l_band[t] over the C F frames of the clip's C rows
+ *   snr_db                   10 log10(sum r^2 / sum (r - e)^2) over all of its samples: +inf for identical rows, -inf for a
+ *                            silent reference beside another estimate, NaN for 0 / 0
+ * each computed in double and rounded once.  Thread t adds the values of the frames i = t, t + 256, ... of the clip (i = channel
+ * * F + frame) in ascending order, the 256 partial sums are added in a fixed tree: the order depends on the clip's (C, F)
+ * alone, so a clip has the same bits whatever it is packed with.  A clip with no row, or whose frames do not fit f_pitch, reads
+ * nothing and reports NaN. */
+int fh_quality_report_f32(const double* frames, int f_pitch, const int32_t* lens, const int32_t* group, int rows, int n_clips,
+                          float* report, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
